@@ -19,7 +19,8 @@ collectives are the barriers bracketing the timed region and the max-reduce of t
 
 Prints ONE JSON line (rank 0) with `roofline` (dominant kernel = render_kernel, timed with HIP events
 on the launch stream inside the timed region) and `cpu_baseline` (the CPU oracle on a bounded sample
-of the same workload, on this host's cores).
+of the same workload, on this host's cores).  `--dump-outputs DIR` also writes what the last timed headline step returned (rgb,
+depth, weights_sum as DIR/<name>.npy, float32); its inputs and draws are the same in every run with the same arguments.
 """
 
 import argparse
@@ -876,6 +877,8 @@ def main():
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--no-secondary', action='store_true', help='skip the gen_videos frames/sec measurement')
     ap.add_argument('--no-backward', action='store_true', help='skip the renderer-backward timing behind roofline_backward')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None, help='write what the last timed headline step returned (rgb, depth, '
+                    'weights_sum) to DIR/<name>.npy as float32; rank 0 only')
     ap.add_argument('--full-line', action='store_true', help='with several ranks: every rank runs the whole line (forced arithmetics, in-kernel draws, '
                     'backward, backbone-plane step, both orbit flows); by default those run on rank 0 alone and the others go straight to the orbit')
     ap.add_argument('--stub-step', action='store_true', help=argparse.SUPPRESS)       # CPU rehearsal of the multi-rank plumbing (stub_main)
@@ -985,6 +988,7 @@ def main():
             out = step(i if n_steps == args.steps else None, mlp, nchw_input, generated)
         torch.cuda.synchronize()
         mine = time.perf_counter() - t0
+        last_out[0] = out
         if solo:
             elapsed = mine
         else:
@@ -993,6 +997,14 @@ def main():
         assert torch.isfinite(out[0]).all()
         kms = sum(ev[i][0].elapsed_time(ev[i][1]) for i in timed_steps) / len(timed_steps) if n_steps == args.steps else None
         return elapsed, mine, kms      # events sit on the launch stream around the render call
+
+    last_out = [None]                  # what the last step of the last timed region returned
+
+    def headline_region():
+        # The generator is reseeded in front of every repetition, outside the timing: the ramp and the number of repetitions depend on
+        # the clock, so without it the draws of the last step -- and the outputs --dump-outputs writes -- would differ from run to run.
+        torch.manual_seed(rank)
+        return timed_region(nchw_input=headline_nchw)
 
     def progress(what):            # one line per phase on stderr: a watchdog that kills silent runs sees the bench alive
         if rank == 0:
@@ -1012,13 +1024,18 @@ def main():
         ramp_steps += 10
     # Repetitions of the K-step region: at least --reps, and as many as cover 0.3 s of stepping (K = 20 steps are 12 ms: five of them
     # gave the driver's round-2 run a 19 % spread; the median of ~25 does not move).  Every repetition is exactly K steps.
-    chrono = [timed_region(nchw_input=headline_nchw)]
+    chrono = [headline_region()]
     n_reps = max(args.reps, min(60, int(0.3 / max(chrono[0][0], 1e-4)) + 1))
     if world > 1:
         n_reps = int(gnerf_harness.max_over_ranks(float(n_reps), dev))          # same count on every rank (the regions hold barriers)
-    chrono += [timed_region(nchw_input=headline_nchw) for _ in range(n_reps - 1)]
+    chrono += [headline_region() for _ in range(n_reps - 1)]
     regions = sorted(chrono)                                                     # by elapsed time
     elapsed, mine, kernel_ms = regions[len(regions) // 2]                        # the median repetition is the one reported
+    if args.dump_outputs and rank == 0:
+        import numpy as np
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, t in zip(('rgb', 'depth', 'weights_sum'), last_out[0]):
+            np.save(os.path.join(args.dump_outputs, name + '.npy'), t.detach().float().cpu().numpy())
     assert gnerf_hip.last_mlp_choice(dev) == 'f16x3', 'config 2 is inside the f16 hi/lo range: the device-side choice must pick it'
     # one long region (>= 100 ms of steps, whatever --steps is) as a cross-check of the K-step median
     n_long = max(args.steps, int(0.1 / (elapsed / args.steps)) + 1)

@@ -1,17 +1,34 @@
 """Drop-in API check: every public callable of the overlay modules has the reference's signature (names, order, defaults), and
-every public name the reference modules define exists in the overlay.  Needs the reference tree (build container only)."""
+every public name the reference modules define exists in the overlay; the overlay's error behaviour and CPU results equal the
+reference's.  The reference's side is tests/golden/reference_api.json.gz, which tests/golden/make_reference_runs.py records from a
+G-NeRF checkout by running the scripts below on it; the tests run the same scripts on the overlay alone."""
 
+import gzip
+import json
 import os
 import subprocess
 import sys
 
-import pytest
-
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF = '/root/reference/g_nerf'
+OURS = os.path.join(ROOT, 'g-nerf_amd')
+FIXTURE = os.path.join(ROOT, 'tests', 'golden', 'reference_api.json.gz')
+
+
+def _run_json(code, timeout=600):
+    """Run a script in a fresh interpreter (so sys.path and sys.modules stay clean) and parse the JSON of its last stdout line."""
+    r = subprocess.run([sys.executable, '-c', code], capture_output=True, text=True, env=dict(os.environ, PYTHONDONTWRITEBYTECODE='1'),
+                       cwd='/tmp', timeout=timeout)
+    assert r.returncode == 0, r.stderr[-3000:]
+    return json.loads(r.stdout.strip().splitlines()[-1])
+
+
+def _reference(key):
+    with gzip.open(FIXTURE, 'rt') as f:
+        return json.load(f)[key]
+
 
 SCRIPT = r'''
-import sys, inspect, importlib, importlib.util, json
+import sys, inspect, importlib, importlib.util, json, gzip
 sys.dont_write_bytecode = True
 MODS = ["torch_utils.ops.bias_act", "torch_utils.ops.upfirdn2d", "torch_utils.ops.filtered_lrelu", "torch_utils.ops.grid_sample_gradfix",
         "torch_utils.ops.conv2d_resample", "torch_utils.ops.fma", "torch_utils.custom_ops", "training.volumetric_rendering.renderer", "training.volumetric_rendering.ray_marcher",
@@ -44,18 +61,18 @@ def sig(f):
         s = inspect.signature(f)
     except (TypeError, ValueError):
         return None
-    return [(p.name, str(p.kind), repr(p.default) if p.default is not inspect._empty else None) for p in s.parameters.values()]
+    return [[p.name, str(p.kind), repr(p.default) if p.default is not inspect._empty else None] for p in s.parameters.values()]
 
 
+if %(record)r:                                         # the reference tree: its public API, as JSON
+    sys.path.insert(0, %(ref)r)
+    ref_mods = {n: importlib.import_module(n) for n in MODS}
+    print(json.dumps({n: {k: (sig(v) if callable(v) else "value", {mn: sig(mv) for mn, mv in vars(v).items() if callable(mv) and not mn.startswith("_")} if inspect.isclass(v) else None)
+                          for k, v in public(m).items()} for n, m in ref_mods.items()}))
+    sys.exit(0)
 report = {"missing": [], "signature": []}
-sys.path.insert(0, %(ref)r)                            # the reference alone first ...
-ref_mods = {n: importlib.import_module(n) for n in MODS}
-ref_pub = {n: {k: (sig(v) if callable(v) else "value", {mn: sig(mv) for mn, mv in vars(v).items() if callable(mv) and not mn.startswith("_")} if inspect.isclass(v) else None)
-               for k, v in public(m).items()} for n, m in ref_mods.items()}
-for n in list(sys.modules):
-    if n.split(".")[0] in ("torch_utils", "training", "dnnlib"):
-        del sys.modules[n]
-sys.path.insert(0, %(ours)r)                           # ... then the overlay in front of it
+ref_pub = json.load(gzip.open(%(fixture)r, "rt"))["signatures"]
+sys.path.insert(0, %(ours)r)                           # the overlay against the recorded reference API
 for n in MODS:
     m = importlib.import_module(n)
     assert %(ours)r in m.__file__, (n, m.__file__)
@@ -79,13 +96,8 @@ print(json.dumps(report))
 '''
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason='reference tree only exists in the build container')
 def test_overlay_matches_reference_signatures():
-    import json
-    code = SCRIPT % dict(ref=REF, ours=os.path.join(ROOT, 'g-nerf_amd'))
-    r = subprocess.run([sys.executable, '-c', code], capture_output=True, text=True, env=dict(os.environ, PYTHONDONTWRITEBYTECODE='1'), cwd='/tmp', timeout=600)
-    assert r.returncode == 0, r.stderr[-3000:]
-    report = json.loads(r.stdout.strip().splitlines()[-1])
+    report = _run_json(SCRIPT % dict(record=False, ref=None, ours=OURS, fixture=FIXTURE))
     assert report['missing'] == [], report['missing']
     assert report['signature'] == [], report['signature']
 
@@ -125,17 +137,10 @@ print(json.dumps(out))
 '''
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason='reference tree only exists in the build container')
 def test_overlay_error_behaviour_matches_reference():
     """The same misuse raises the same exception type in the overlay ops as in the reference's (and valid helper calls give the same
     shapes): the error behaviour is part of the drop-in contract."""
-    import json
-    res = {}
-    for name, paths in (('ref', [REF]), ('ours', [os.path.join(ROOT, 'g-nerf_amd'), REF])):
-        r = subprocess.run([sys.executable, '-c', ERR_SCRIPT % dict(paths=paths)], capture_output=True, text=True,
-                           env=dict(os.environ, PYTHONDONTWRITEBYTECODE='1'), cwd='/tmp', timeout=600)
-        assert r.returncode == 0, r.stderr[-3000:]
-        res[name] = json.loads(r.stdout.strip().splitlines()[-1])
+    res = {'ref': _reference('errors'), 'ours': _run_json(ERR_SCRIPT % dict(paths=[OURS]))}
     assert res['ours'] == res['ref'], {k: (res['ref'][k], res['ours'][k]) for k in res['ref'] if res['ref'][k] != res['ours'][k]}
 
 
@@ -209,20 +214,13 @@ print(json.dumps(out))
 '''
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason='reference tree only exists in the build container')
 def test_overlay_renderer_modules_match_reference_on_cpu():
     """The four renderer modules of the overlay against the reference's on the CPU, same seeds (both consume torch's generator in the
     same order): ImportanceRenderer.forward under every option the reference reads (white_back, disparity sampling, 'auto' ray limits,
     no importance pass, density noise, box_warp), run_model, sample_from_3dgrid, project_onto_planes, the math_utils helpers and
     MipRayMarcher2 incl. its refusal of other clamp modes."""
-    import json
     import numpy as np
-    res = {}
-    for name, paths in (('ref', [REF]), ('ours', [os.path.join(ROOT, 'g-nerf_amd'), REF])):
-        r = subprocess.run([sys.executable, '-c', RENDER_SCRIPT % dict(paths=paths)], capture_output=True, text=True,
-                           env=dict(os.environ, PYTHONDONTWRITEBYTECODE='1'), cwd='/tmp', timeout=600)
-        assert r.returncode == 0, r.stderr[-3000:]
-        res[name] = json.loads(r.stdout.strip().splitlines()[-1])
+    res = {'ref': _reference('renderer'), 'ours': _run_json(RENDER_SCRIPT % dict(paths=[OURS]))}
     assert res['ours'].keys() == res['ref'].keys()
     assert res['ours']['marcher_bad_mode'] == res['ref']['marcher_bad_mode']
     for k in res['ref']:
@@ -307,18 +305,11 @@ def _is_numeric(a):
         return False
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason='reference tree only exists in the build container')
 def test_overlay_ops_match_reference_on_cpu():
     """The four op modules of the overlay against the reference's on the CPU (the reference's `_ref` forms; first- and second-order
     gradients through autograd): every activation of bias_act incl. the activation table itself, upfirdn2d variants (per-axis factors,
     crops, separable 8-tap filter, no filter), filtered_lrelu, grid_sample with the flag off and on."""
-    import json
-    res = {}
-    for name, paths in (('ref', [REF]), ('ours', [os.path.join(ROOT, 'g-nerf_amd'), REF])):
-        r = subprocess.run([sys.executable, '-c', OPS_SCRIPT % dict(paths=paths)], capture_output=True, text=True,
-                           env=dict(os.environ, PYTHONDONTWRITEBYTECODE='1'), cwd='/tmp', timeout=600)
-        assert r.returncode == 0, r.stderr[-3000:]
-        res[name] = json.loads(r.stdout.strip().splitlines()[-1])
+    res = {'ref': _reference('ops'), 'ours': _run_json(OPS_SCRIPT % dict(paths=[OURS]))}
     assert res['ours']['acts'] == res['ref']['acts'] and res['ours']['act_table'] == res['ref']['act_table']
     assert res['ours']['gs_1'] is not None
     if res['ref']['gs_1'] is None:                   # the reference's flag-on path is broken under this torch: the flag-off results are the same function
@@ -328,3 +319,11 @@ def test_overlay_ops_match_reference_on_cpu():
             continue
         for x, y in zip(res['ref'][k], res['ours'][k]):
             _close(x, y, k)
+
+
+def record_reference(ref):
+    """The reference tree's side of the four tests above (tests/golden/make_reference_runs.py writes it to FIXTURE)."""
+    return {'signatures': _run_json(SCRIPT % dict(record=True, ref=ref, ours=None, fixture=None)),
+            'errors': _run_json(ERR_SCRIPT % dict(paths=[ref])),
+            'renderer': _run_json(RENDER_SCRIPT % dict(paths=[ref])),
+            'ops': _run_json(OPS_SCRIPT % dict(paths=[ref]))}

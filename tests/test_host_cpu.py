@@ -323,31 +323,64 @@ def test_custom_ops_plugin_surface():
         custom_ops.get_plugin('no_such_plugin', sources=[])
 
 
-@pytest.mark.skipif(not os.path.isdir('/root/reference/g_nerf'), reason='reference tree only exists in the build container')
-def test_overlay_resolves_reference_modules():
-    """With g-nerf_amd/ BEFORE the reference's g_nerf/ on sys.path, hot-path modules come from this repo
-    and everything else (persistence, misc, conv2d_gradfix, triplane ...) from the reference -- the
-    drop-in arrangement INTEGRATION.md describes.  Run in a child process to keep sys.path clean."""
+# A stand-in for the G-NeRF g_nerf/ directory the overlay is placed in front of: one module the overlay lacks in each package it
+# extends, the conv2d_gradfix module conv2d_resample imports from that tree (recording its calls), a triplane module that takes
+# the renderer by the reference's import, and modules the overlay provides too, which must stay shadowed.
+STAND_IN_TREE = {
+    'torch_utils/__init__.py': '',
+    'torch_utils/persistence.py': '',
+    'torch_utils/ops/__init__.py': '',
+    'torch_utils/ops/conv2d_gradfix.py': '''import torch
+calls = []
+def conv2d(input, weight, bias=None, stride=1, padding=0, dilation=1, groups=1):
+    calls.append("conv2d")
+    return torch.nn.functional.conv2d(input, weight, bias, stride, padding, dilation, groups)
+def conv_transpose2d(input, weight, bias=None, stride=1, padding=0, output_padding=0, groups=1, dilation=1):
+    calls.append("conv_transpose2d")
+    return torch.nn.functional.conv_transpose2d(input, weight, bias, stride, padding, output_padding, groups, dilation)
+''',
+    'torch_utils/ops/bias_act.py': 'raise ImportError("the overlay must shadow this module")\n',
+    'torch_utils/ops/conv2d_resample.py': 'raise ImportError("the overlay must shadow this module")\n',
+    'training/__init__.py': '',
+    'training/triplane.py': 'from training.volumetric_rendering.renderer import ImportanceRenderer\n',
+    'training/volumetric_rendering/__init__.py': '',
+    'training/volumetric_rendering/renderer.py': 'raise ImportError("the overlay must shadow this module")\n',
+}
+
+
+def test_overlay_resolves_reference_modules(tmp_path):
+    """With g-nerf_amd/ BEFORE a G-NeRF g_nerf/ tree on sys.path (here the stand-in above), hot-path modules come from this repo
+    and everything else (persistence, conv2d_gradfix, triplane ...) from the tree behind it -- the drop-in arrangement
+    INTEGRATION.md describes -- and conv2d_resample convolves through that tree's conv2d_gradfix.  Run in a child process to keep
+    sys.path clean."""
+    tree = tmp_path / 'g_nerf'
+    for rel, text in STAND_IN_TREE.items():
+        (tree / rel).parent.mkdir(parents=True, exist_ok=True)
+        (tree / rel).write_text(text)
+    ours = os.path.join(ROOT, 'g-nerf_amd')
     code = r'''
-import sys, types, torch
+import os, sys, torch
 sys.dont_write_bytecode = True
-sys.path.insert(0, "/root/reference/g_nerf"); sys.path.insert(0, %r)
-tvr = types.ModuleType("torchvision.models.resnet"); tvr.ResNet = type("ResNet", (torch.nn.Module,), {}); tvr.Bottleneck = type("B", (torch.nn.Module,), {})
-sys.modules.update({"torchvision": types.ModuleType("torchvision"), "torchvision.models": types.ModuleType("torchvision.models"), "torchvision.models.resnet": tvr})
+ours, tree = %r, %r
+sys.path.insert(0, tree); sys.path.insert(0, ours)
 import torch_utils.ops.bias_act as ba, torch_utils.persistence as pe, torch_utils.ops.conv2d_resample as cr, torch_utils.ops.conv2d_gradfix as gf, torch_utils.ops.fma as fm
 import training.volumetric_rendering.renderer as rr, training.triplane as tp
-assert "g-nerf_amd" in ba.__file__ and "g-nerf_amd" in rr.__file__, (ba.__file__, rr.__file__)
-assert "/root/reference" in pe.__file__ and "/root/reference" in gf.__file__ and "/root/reference" in tp.__file__
-assert "g-nerf_amd" in cr.__file__ and "g-nerf_amd" in fm.__file__ and cr.conv2d_gradfix is gf          # round 3: the two caller modules are overlaid too
+def inside(m, d): return os.path.realpath(m.__file__).startswith(os.path.realpath(d) + os.sep)
+assert inside(ba, ours) and inside(rr, ours), (ba.__file__, rr.__file__)
+assert inside(pe, tree) and inside(gf, tree) and inside(tp, tree), (pe.__file__, gf.__file__, tp.__file__)
+assert inside(cr, ours) and inside(fm, ours) and cr.conv2d_gradfix is gf          # the two caller modules are overlaid too
 assert tp.ImportanceRenderer is rr.ImportanceRenderer
 import torch_utils.ops.upfirdn2d as up
-assert cr.upfirdn2d is up and "g-nerf_amd" in up.__file__
-dec = tp.OSGDecoder(32, {"decoder_lr_mul": 1, "decoder_output_dim": 32})
-assert rr._osg_decoder_weights(dec) is not None
+assert cr.upfirdn2d is up and inside(up, ours)
+g = torch.Generator().manual_seed(0)
+x, w = torch.randn(1, 4, 8, 8, generator=g), torch.randn(5, 4, 3, 3, generator=g)
+y = cr.conv2d_resample(x, w, padding=1)
+assert gf.calls == ["conv2d"], gf.calls
+assert torch.allclose(y, torch.nn.functional.conv2d(x, w, padding=1), atol=1e-5)
 print("overlay ok")
-''' % os.path.join(ROOT, 'g-nerf_amd')
+''' % (ours, str(tree))
     env = dict(os.environ, PYTHONDONTWRITEBYTECODE='1')
-    out = subprocess.run([sys.executable, '-c', code], capture_output=True, text=True, env=env, cwd='/tmp')
+    out = subprocess.run([sys.executable, '-c', code], capture_output=True, text=True, env=env, cwd=str(tmp_path))
     assert out.returncode == 0 and 'overlay ok' in out.stdout, out.stderr[-2000:]
 
 
