@@ -11,8 +11,8 @@
 // leave as fp16 channels_last.
 //
 // Decomposition.  A workgroup (round 6: 8 waves, <= 128 registers per lane, 76.5 KB of LDS, so TWO workgroups share a CU: FOUR waves per
-// SIMD, and one workgroup's barriers, input-tile loads and epilogue hide under the other's MFMAs; rounds 5: 4 waves with 256 registers,
-// GNERF_CONV_WAVES=4) computes an 8 x 32 tile of output pixels for 128 output channels.  The 10 x 34 input pixels the tile's nine taps touch are staged once per 64 input channels (43.5 KB; image borders
+// SIMD, and one workgroup's barriers, input-tile loads and epilogue hide under the other's MFMAs; round 5: 4 waves with 256 registers)
+// computes an 8 x 32 tile of output pixels for 128 output channels.  The 10 x 34 input pixels the tile's nine taps touch are staged once per 64 input channels (43.5 KB; image borders
 // come in as zeros from the buffer load's range check) and every tap reads them at a shifted position; the weights of one (tap, 64
 // input channels) -- 16 KB -- stream through a double buffer while the previous tap is being multiplied.  Both are filled by LDS-DMA
 // (buffer_load / global_load ... lds: no registers, no ds_write), whose LDS image is lane-linear, so the bank swizzle is applied to
@@ -27,8 +27,7 @@
 // SIMD's, and no hand-built pipeline beat two independent workgroups.)
 // Orientation: A = weights (M = 16 output channels), B = input (N = 16 pixels of a row), K = 32 input channels per instruction; a lane's
 // four accumulator registers are then four CONSECUTIVE output channels of one pixel -- an 8-byte piece of the channels_last result.
-// A wave owns two rows of the tile and 64 of the 128 channels: 64 accumulator registers, 16 MFMAs per 8 ds_read_b128 (GNERF_CONV_WAVES=4: two
-// rows x 128 channels, 128 accumulator registers, 32 MFMAs per 12 ds_read_b128, fragment reads software-pipelined among the MFMAs).
+// A wave owns two rows of the tile and 64 of the 128 channels: 64 accumulator registers, 16 MFMAs per 8 ds_read_b128.
 
 #include "common.h"
 #include <type_traits>
@@ -45,36 +44,22 @@ constexpr int kTH = 8, kTW = 32;                    // output pixels of a tile
 constexpr int kIH = kTH + 2, kIW = kTW + 2;         // input pixels incl. the one-pixel halo
 constexpr int kCK = 64;                             // input channels resident in LDS (a chunk)
 constexpr int kCO = 128;                            // output channels per workgroup
-// GNERF_CONV_WAVES: waves of a workgroup.  4 (round 5): a wave owns two rows of the tile -- 128 accumulator registers, fragments double-buffered
-// and read among the previous k-step's MFMAs, 252 registers: two waves per SIMD.  8 (round 6, shipped): 64 accumulator registers per wave,
-// fragments single-buffered, <= 128 registers: FOUR waves per SIMD on the same 76 KB of LDS per workgroup, the latency hiding left to the
-// hardware's wave scheduler instead of the hand-built pipeline.  In-kernel clock stamps (tools/conv_clock.py, profiles/r06_conv_clock.jsonl):
-// 7-9 % fewer cycles than the four-wave form, of which the chip's power management takes most back as a lower clock (1.98 -> 1.85 GHz on
-// random operands); wall time -1.5 % (plain) ... -9 % (transposed, fp32-grade at small sizes).
-#ifndef GNERF_CONV_WAVES
-#define GNERF_CONV_WAVES 8
-#endif
-// GNERF_CONV_COSPLIT (with eight waves): 1 = a wave owns one tile row x 128 output channels (8 weight + 2 pixel fragments per 16 MFMAs), 2
-// (shipped) = two rows x 64 output channels (4 + 4 fragments per 16 MFMAs: a fifth fewer LDS bytes for the same matrix work; 1-2 % faster).
-// GNERF_CONV_COUNTED_WAITS=1 (a pair of channel blocks starts when its own fragments have landed): measured, no gain, off.
-#ifndef GNERF_CONV_COSPLIT
-#define GNERF_CONV_COSPLIT (GNERF_CONV_WAVES == 8 ? 2 : 1)
-#endif
-#ifndef GNERF_CONV_COUNTED_WAITS
-#define GNERF_CONV_COUNTED_WAITS 0
-#endif
-// GNERF_CONV_NT: 1 = the input tile's LDS-DMA loads non-temporal, 2 = the output stores non-temporal, 3 = both, 4 (shipped, round 6) = the plain
-// convolution's output stores only.  The output is streamed (written once, read by the NEXT kernel) and should not evict the weights that every
-// workgroup of an XCD re-reads from its L2: alone the kernel is 1-5 % faster with 2 (profiles/r06_conv_nt_ab.txt), in the orbit's pipeline -- the
-// next kernel reads what was stored -- 8 views per call go from 2 838-2 856 to 2 879-2 884 frames/s.  The input tile is NOT stream-once (halos,
-// the transposed form's four phases): 1 is 10-20 % slower on the transposed form; the transposed form's stores are a wash.
-#ifndef GNERF_CONV_NT
-#define GNERF_CONV_NT 4
-#endif
-constexpr int kWaves = GNERF_CONV_WAVES;
-constexpr int kCoSplit = GNERF_CONV_COSPLIT;
-static_assert(kWaves == 4 || kWaves == 8, "4 or 8 waves per workgroup");
-static_assert(kCoSplit == 1 || (kCoSplit == 2 && kWaves == 8), "the output channels are split over wave pairs in the eight-wave form only");
+// Eight waves per workgroup (round 6): 64 accumulator registers per wave, fragments single-buffered, <= 128 registers: FOUR waves per SIMD
+// on the same 76 KB of LDS per workgroup, the latency hiding left to the hardware's wave scheduler.  Round 5's four waves (two rows x 128
+// channels each, 128 accumulator registers, fragments double-buffered and read among the previous k-step's MFMAs, 252 registers: two waves
+// per SIMD) took 7-9 % more cycles by in-kernel clock stamps (tools/conv_clock.py, profiles/r06_conv_clock.jsonl), of which the chip's
+// power management gives most back as a higher clock (1.85 -> 1.98 GHz on random operands); wall time +1.5 % (plain) ... +9 % (transposed,
+// fp32-grade at small sizes).
+// The output channels are split over wave pairs: a wave owns two tile rows x 64 output channels (4 + 4 fragments per 16 MFMAs), a fifth
+// fewer LDS bytes for the same matrix work than one row x 128 channels (8 + 2): 1-2 % faster.  Each k-step's MFMAs wait for all of the
+// wave's fragments: starting a pair of channel blocks as soon as its own fragments have landed (counted waits) was measured, no gain.
+// Non-temporal stores for the plain convolution's output only.  The output is streamed (written once, read by the NEXT kernel) and should
+// not evict the weights that every workgroup of an XCD re-reads from its L2: alone the kernel is 1-5 % faster with them
+// (profiles/r06_conv_nt_ab.txt), in the orbit's pipeline -- the next kernel reads what was stored -- 8 views per call go from 2 838-2 856 to
+// 2 879-2 884 frames/s.  The input tile is NOT stream-once (halos, the transposed form's four phases): non-temporal LDS-DMA loads are 10-20 %
+// slower on the transposed form; the transposed form's non-temporal stores are a wash.
+constexpr int kWaves = 8;
+constexpr int kCoSplit = 2;
 constexpr int kConvThreads = 64 * kWaves;
 constexpr int kRowsPW = kTH / (kWaves / kCoSplit);  // tile rows of a wave
 constexpr int kPB = 2 * kRowsPW;                    // 16-pixel blocks of a wave
@@ -119,10 +104,7 @@ struct ConvArgs {
 };
 
 typedef __attribute__((address_space(3))) void* lds_ptr_t;
-typedef unsigned u4nt __attribute__((ext_vector_type(4)));     // (what __builtin_nontemporal_store takes: GNERF_CONV_NT)
-#ifndef GNERF_CONV_EPILOGUE_F32
-#define GNERF_CONV_EPILOGUE_F32 1
-#endif
+typedef unsigned u4nt __attribute__((ext_vector_type(4)));     // (what __builtin_nontemporal_store takes)
 
 // MODE 0: the 3x3 convolution (padding 1) with the epilogue.
 // MODE 1 (round 5): the stride-2 TRANSPOSED 3x3 convolution of the x2 layers (conv_transpose2d(x, w, stride 2): 2H + 1 outputs per axis; what
@@ -150,8 +132,8 @@ __device__ unsigned long long g_conv_stamps[16384][8];
 #endif
 
 template <int MODE, bool SCALE, bool NOISE, bool NEXT, bool OUT32 = false, bool RGB = false>
-__global__ __launch_bounds__(kConvThreads, kWaves == 8 ? 4 : 2) void conv3x3_epilogue_kernel(ConvArgs a) {
-    static_assert(!RGB || (MODE == 0 && !OUT32 && !NEXT && GNERF_CONV_EPILOGUE_F32), "the ToRGB tail belongs to the plain fp16 convolution of a block's last layer");
+__global__ __launch_bounds__(kConvThreads, 4) void conv3x3_epilogue_kernel(ConvArgs a) {
+    static_assert(!RGB || (MODE == 0 && !OUT32 && !NEXT), "the ToRGB tail belongs to the plain fp16 convolution of a block's last layer");
     extern __shared__ __align__(16) char lds[];
 #ifdef GNERF_CONV_STAMPS
     const unsigned long long stamp_c0 = __builtin_amdgcn_s_memtime(), stamp_r0 = __builtin_amdgcn_s_memrealtime();
@@ -226,7 +208,7 @@ __global__ __launch_bounds__(kConvThreads, kWaves == 8 ? 4 : 2) void conv3x3_epi
             const int cg = cin0 + ((slot ^ (pix & 7)) << 3);        // first of this piece's eight input channels
             const bool ok = pix < kIH * kIW && iy >= 0 && iy < H && ix >= 0 && ix < W && cg < Cin;      // (cin below a multiple of 64: the last chunk's tail reads as zeros)
             const unsigned off = ok ? unsigned(((iy * W + ix) * Cin + cg) * 2) : 0x80000000u;     // out of range: zeros
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(xrsrc, (lds_ptr_t)(xs + (it * kConvThreads + wv * 64) * 16), 16, off, 0, 0, (GNERF_CONV_NT & 1) ? 2 : 0);
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(xrsrc, (lds_ptr_t)(xs + (it * kConvThreads + wv * 64) * 16), 16, off, 0, 0, 0);
         }
     };
     // weights of (tap, 64 input channels) -> buffer `buf`.  Lane (co = (threads / 8) it + tid / 8, slot = tid % 8) of trip `it` reads 16 bytes of output
@@ -271,15 +253,9 @@ __global__ __launch_bounds__(kConvThreads, kWaves == 8 ? 4 : 2) void conv3x3_epi
                                                      (lds_ptr_t)(ep + 1536 + wv * 256), 4, 0, 0);
     }
     const int n_chunks = a.cin_pad / kCK, total = n_chunks * n_taps;
-    // ---- main loop, software-pipelined ACROSS steps.  A step (one tap of one 64-channel chunk) is two k-steps of 32 MFMAs; while
-    // the MFMAs of one k-step issue, the twelve fragments of the NEXT k-step are read -- the second k-step of this step, or the first
-    // of the next step.  The one barrier of a step sits between its two k-steps: there the next step's weights (requested a step
-    // ago) have landed, every wave has read the last of this step's weights (their buffer takes the step after next) and, at a
-    // chunk's last tap, the last of the input tile (the next chunk is requested right there and arrives under 32 MFMAs).
-    // (Round 5's first two-workgroup loop read a step's first twelve fragments at the step's top, behind the barrier: 2 % slower -- the
-    // other workgroup of the CU already covered most of that; commit b13915a has both loops and the timing-only ablation macros.)
-    h8 A[kWaves == 4 ? 2 : 1][kCB], B[kWaves == 4 ? 2 : 1][kPB];
-    // fragment f of k-step kc of step s: f = 0..3 the input fragments of the wave's four pixel blocks, f = 4..11 the eight weight fragments.
+    // ---- main loop.  A step is one tap of one 64-channel chunk: two k-steps of 16 MFMAs per wave.
+    h8 A[kCB], B[kPB];
+    // fragment f of k-step kc of step s: f = 0..3 the input fragments of the wave's four pixel blocks, f = 4..7 its four weight fragments.
     // Addresses from two lane constants and wave-uniform terms (the tap's shift, the weight buffer); pixel block f ^ 1 and the weight
     // fragments sit at constant offsets (16 pixels / 16 channels further: the swizzle's period is 8 rows), k-step 1 flips bit 6.
     const int xlane = (kRowsPW * wrow * kIW + r) * kRow;             // byte offset of this lane's pixel row (the wave's first tile row, column r) without the tap's shift
@@ -302,28 +278,6 @@ __global__ __launch_bounds__(kConvThreads, kWaves == 8 ? 4 : 2) void conv3x3_epi
 #pragma unroll
             for (int pb = 0; pb < kPB; pb++) acc[cb][pb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(Af[cb], Bf[pb], acc[cb][pb], 0, 0, 0);
     };
-    // 32 MFMAs from (Ac, Bc) with the twelve reads of (s2, kc2) into (An, Bn) among them: {8 MFMAs, six reads} twice, then 16 MFMAs --
-    // fenced so that the compiler keeps the order; the last read has 24 MFMAs to come back behind
-    auto phase = [&](const h8 (&Ac)[kCB], const h8 (&Bc)[kPB], bool reads, int tap2, int buf2, int kc2, h8 (&An)[kCB], h8 (&Bn)[kPB]) {
-        __builtin_amdgcn_sched_barrier(0);
-        mfma_group(0, Ac, Bc);
-        __builtin_amdgcn_sched_barrier(0);
-        if (reads) {
-#pragma unroll
-            for (int f = 0; f < 6; f++) load_frag(tap2, buf2, kc2, f, An, Bn);
-        }
-        __builtin_amdgcn_sched_barrier(0);
-        mfma_group(1, Ac, Bc);
-        __builtin_amdgcn_sched_barrier(0);
-        if (reads) {
-#pragma unroll
-            for (int f = 6; f < 12; f++) load_frag(tap2, buf2, kc2, f, An, Bn);
-        }
-        __builtin_amdgcn_sched_barrier(0);
-        mfma_group(2, Ac, Bc);
-        mfma_group(3, Ac, Bc);
-        __builtin_amdgcn_sched_barrier(0);
-    };
     // step s = (chunk, tap); s + 1 and s + 2 are kept alongside as running counters
     auto next_step = [&](int& tp, int& ck) { if (++tp == n_taps) { tp = 0; ck++; } };
     int tap = 0, chunk = 0, tap1 = 0, chunk1 = 0, tap2, chunk2;
@@ -338,58 +292,19 @@ __global__ __launch_bounds__(kConvThreads, kWaves == 8 ? 4 : 2) void conv3x3_epi
     asm volatile("" ::: "memory");
     GNERF_CONV_STAMP(1);
     if (total > 1) stage_w(tap1, chunk1 * kCK, 1);
-    if constexpr (kWaves == 4) {
-#pragma unroll
-    for (int f = 0; f < 12; f++) load_frag(0, 0, 0, f, A[0], B[0]);
-    for (int s = 0; s < total; s++) {
-        phase(A[0], B[0], true, tap, s & 1, 1, A[1], B[1]);
-        // (bare waits and barrier: __syncthreads() would drain vmcnt where the compiler sees fit)
-        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
-        const bool more = s + 1 < total, new_chunk = more && tap == n_taps - 1;
-        if (s + 2 < total) stage_w(tap2, chunk2 * kCK, s & 1);
-        if (new_chunk) stage_x((chunk + 1) * kCK);
-        phase(A[1], B[1], more && !new_chunk, tap1, (s + 1) & 1, 0, A[0], B[0]);
-        if (new_chunk) {
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __builtin_amdgcn_s_barrier();
-            asm volatile("" ::: "memory");
-#pragma unroll
-            for (int f = 0; f < 12; f++) load_frag(tap1, (s + 1) & 1, 0, f, A[0], B[0]);
-        }
-        tap = tap1; chunk = chunk1; tap1 = tap2; chunk1 = chunk2;
-        next_step(tap2, chunk2);
-    }
-    } else {
-    // Eight waves: per k-step the wave reads its ten fragments, waits for them and issues its sixteen MFMAs; nothing is double-buffered in
+    // Per k-step the wave reads its eight fragments, waits for them and issues its sixteen MFMAs; nothing is double-buffered in
     // registers -- three other waves of the SIMD have MFMAs to issue while this one waits.  The step's barrier sits where BOTH k-steps'
     // fragments of this step's weight buffer are in registers (behind the second read): the buffer then takes the step after next.
     for (int s = 0; s < total; s++) {
 #pragma unroll
-        for (int f = 0; f < kCB + kPB; f++) load_frag(tap, s & 1, 0, f, A[0], B[0]);
-#if GNERF_CONV_COUNTED_WAITS
-        // (the reads return in order: a pair of channel blocks starts as soon as ITS two weight fragments are there)
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int g = 0; g < kCB / 2; g++) {
-            if (kCB - 2 - 2 * g == 6) asm volatile("s_waitcnt lgkmcnt(6)" ::: "memory");
-            else if (kCB - 2 - 2 * g == 4) asm volatile("s_waitcnt lgkmcnt(4)" ::: "memory");
-            else if (kCB - 2 - 2 * g == 2) asm volatile("s_waitcnt lgkmcnt(2)" ::: "memory");
-            else asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            __builtin_amdgcn_sched_barrier(0);
-            mfma_group(g, A[0], B[0]);
-            __builtin_amdgcn_sched_barrier(0);
-        }
-#else
+        for (int f = 0; f < kCB + kPB; f++) load_frag(tap, s & 1, 0, f, A, B);
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-        for (int g = 0; g < kCB / 2; g++) mfma_group(g, A[0], B[0]);
+        for (int g = 0; g < kCB / 2; g++) mfma_group(g, A, B);
         __builtin_amdgcn_sched_barrier(0);
-#endif
 #pragma unroll
-        for (int f = 0; f < kCB + kPB; f++) load_frag(tap, s & 1, 1, f, A[0], B[0]);
+        for (int f = 0; f < kCB + kPB; f++) load_frag(tap, s & 1, 1, f, A, B);
         asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();
         asm volatile("" ::: "memory");
@@ -398,7 +313,7 @@ __global__ __launch_bounds__(kConvThreads, kWaves == 8 ? 4 : 2) void conv3x3_epi
         if (new_chunk) stage_x((chunk + 1) * kCK);
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-        for (int g = 0; g < kCB / 2; g++) mfma_group(g, A[0], B[0]);
+        for (int g = 0; g < kCB / 2; g++) mfma_group(g, A, B);
         __builtin_amdgcn_sched_barrier(0);
         if (new_chunk) {
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -407,7 +322,6 @@ __global__ __launch_bounds__(kConvThreads, kWaves == 8 ? 4 : 2) void conv3x3_epi
         }
         tap = tap1; chunk = chunk1; tap1 = tap2; chunk1 = chunk2;
         next_step(tap2, chunk2);
-    }
     }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     GNERF_CONV_STAMP(2);
@@ -423,14 +337,12 @@ __global__ __launch_bounds__(kConvThreads, kWaves == 8 ? 4 : 2) void conv3x3_epi
     auto registers_to_lds = [&](auto has_clamp) {
     const float clampv = decltype(has_clamp)::value ? fabsf(a.clamp) : -1.f;
     if constexpr (decltype(has_clamp)::value) __builtin_assume(clampv >= 0.f);
-#if GNERF_CONV_EPILOGUE_F32
     // Round 6: the epilogue in fp32 on the accumulators, ONE rounding at the end.
     //     y = clamp(lrelu((acc * dcoef + noise + bias)) * gain) * next_scale
     //       = med3(max(u, alpha u), -c, c) * next_scale,   u = acc * (dcoef gain) + (bias gain) + (noise gain)       (gain > 0, 0 <= alpha <= 1)
     // Per value: one fused multiply-add, one add, the lrelu's multiply and max, the clamp's v_med3, the next layer's multiply -- the three
     // fp32 multiply / add steps as packed instructions on accumulator pairs -- and half a v_cvt_pk_f16_f32: 4.5 vector instructions where
-    // the form that reproduced the two-launch route's fp16 roundings (conv output, demodulated value, activated value: GNERF_CONV_EPILOGUE_F32=0)
-    // took 18, most of them conversions.  Against the reference's fp32 arithmetic (networks_stylegan2.py:41-98, bias_act.py:92-122) this is
+    // the form that reproduced the two-launch route's fp16 roundings (conv output, demodulated value, activated value) took 18, most of them conversions.  Against the reference's fp32 arithmetic (networks_stylegan2.py:41-98, bias_act.py:92-122) this is
     // CLOSER than the fp16 chain it replaces: the only rounding left is the output's.  Per-channel operands are scaled by the gain once per
     // channel block, the lane's four noise values once per tile.
     typedef float v2f __attribute__((ext_vector_type(2)));
@@ -517,39 +429,6 @@ __global__ __launch_bounds__(kConvThreads, kWaves == 8 ? 4 : 2) void conv3x3_epi
 #endif
         }
     }
-#else
-#pragma unroll
-    for (int cbw = 0; cbw < kCB; cbw++) {
-        const int cb = wco * kCB + cbw;
-        const int c4 = cb * 16 + hq * 4;                           // this lane's four consecutive output channels (of the workgroup's 128)
-        float sc[4] = {1.f, 1.f, 1.f, 1.f}, nx[4] = {1.f, 1.f, 1.f, 1.f}, bv[4] = {0.f, 0.f, 0.f, 0.f};
-        if constexpr (SCALE) { const float4 v = *reinterpret_cast<const float4*>(ep + c4 * 4); sc[0] = v.x; sc[1] = v.y; sc[2] = v.z; sc[3] = v.w; }
-        if constexpr (NEXT) {
-            const float4 v = *reinterpret_cast<const float4*>(ep + 512 + c4 * 4);
-            nx[0] = round_to<__half>(v.x); nx[1] = round_to<__half>(v.y); nx[2] = round_to<__half>(v.z); nx[3] = round_to<__half>(v.w);
-        }
-        if (a.bias) {
-            typedef _Float16 h4v __attribute__((ext_vector_type(4)));
-            const h4v hb = __builtin_bit_cast(h4v, *reinterpret_cast<const uint2*>(ep + 1024 + c4 * 2));
-#pragma unroll
-            for (int k = 0; k < 4; k++) bv[k] = float(hb[k]);
-        }
-#pragma unroll
-        for (int pb = 0; pb < kPB; pb++) {
-            const int prow = kRowsPW * wrow + (pb >> 1), pcol = (pb & 1) * 16 + r;
-            const int p = prow * kTW + pcol;
-            Pk<__half, 4> in;
-#pragma unroll
-            for (int k = 0; k < 4; k++) in.v[k] = __float2half(acc[cbw][pb][k]);          // what the convolution alone would have stored
-            float nz = 0.f;
-            if constexpr (NOISE) nz = a.noise[(y0 + prow) * W + x0 + pcol];
-            Pk<__half, 4> out;
-            if constexpr (MODE == 1) out = in;                         // the transposed convolution leaves as plain fp16 (blur + epilogue follow)
-            else out = modconv_epilogue_vec<__half, 4, kActLrelu01, SCALE, NOISE, NEXT>(in, sc, nz, a.round_noise != 0, bv, nx, a.alpha, a.gain, clampv);
-            *reinterpret_cast<uint2*>(os + p * 256 + (((c4 >> 3) ^ (p & 15)) << 4) + ((c4 >> 2) & 1) * 8) = __builtin_bit_cast(uint2, out);
-        }
-    }
-#endif
     };
     if (MODE == 0 && a.clamp >= 0.f) registers_to_lds(std::true_type{}); else registers_to_lds(std::false_type{});
 #ifdef GNERF_ABLATE_CONVNOSTORE
@@ -616,10 +495,10 @@ __global__ __launch_bounds__(kConvThreads, kWaves == 8 ? 4 : 2) void conv3x3_epi
             const int yy = y0 + it * kStorePix / kTW, xc = x0 + it * kStorePix % kTW;     // (uniform) row of the tile, first of this trip's columns
             if constexpr (MODE == 1) {                                 // position (yy, xx) of phase (py, px) -> output pixel (2 yy + py, 2 xx + px); the grid of tiles overhangs
                 _Float16* const row = a.y + ((size_t(n) * a.out_h + size_t(2 * yy + ph_y)) * a.out_w + size_t(2 * xc + ph_x)) * Cout + co0;
-                if (yy < Hp && xc + lp < Wp) { if (GNERF_CONV_NT & 2) __builtin_nontemporal_store(__builtin_bit_cast(u4nt, v), reinterpret_cast<u4nt*>(row + out_lane)); else *reinterpret_cast<uint4*>(row + out_lane) = v; }
+                if (yy < Hp && xc + lp < Wp) *reinterpret_cast<uint4*>(row + out_lane) = v;
             } else {
                 _Float16* const row = a.y + (size_t(n) * H * W + size_t(yy) * W + xc) * Cout + co0;
-                if (GNERF_CONV_NT & 6) __builtin_nontemporal_store(__builtin_bit_cast(u4nt, v), reinterpret_cast<u4nt*>(row + out_lane)); else *reinterpret_cast<uint4*>(row + out_lane) = v;
+                __builtin_nontemporal_store(__builtin_bit_cast(u4nt, v), reinterpret_cast<u4nt*>(row + out_lane));     // (non-temporal: see the note in front of kWaves)
             }
         }
     }
@@ -721,9 +600,6 @@ int launch_conv3x3(const char* what, const void* x, const void* w_packed, void* 
     a.rgb_w = static_cast<const _Float16*>(rgb_w); a.rgb_bias = rgb_bias; a.rgb_clamp = rgb_clamp; a.img = img;
     const dim3 grid((a.n_tiles + kNumXCD - 1) / kNumXCD * kNumXCD, cout / kCO), block(kConvThreads);
     hipStream_t s = as_stream(stream);
-#if !GNERF_CONV_EPILOGUE_F32
-    if (img) return fail(GNERF_E_UNSUPPORTED, "%s: this build (GNERF_CONV_EPILOGUE_F32=0) has no ToRGB tail", what);
-#else
     if constexpr (!OUT32) {
         if (img) {
             static PerDeviceOnce once_rgb[2];
@@ -737,7 +613,6 @@ int launch_conv3x3(const char* what, const void* x, const void* w_packed, void* 
             return check_launch(what);
         }
     }
-#endif
 #define GNERF_CONV(SC, NZ, NX) do { \
         static PerDeviceOnce once; \
         if (int rc = once.raise_lds(conv3x3_epilogue_kernel<0, SC, NZ, NX, OUT32>, what, kConvLds)) return rc; \

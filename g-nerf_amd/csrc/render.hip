@@ -10,8 +10,8 @@
 // This file holds the pieces every kernel shares (depth proposals, importance resampling, the ray march, DPP scans),
 // the GENERIC kernel described below (any sample count up to 256+256), the entry points and the kernel choice.  The
 // kernels that run G-NeRF's actual configurations are in the .inl files included further down:
-//   render_pipe.inl  3 shader waves + 1 scalar wave per workgroup, three rays in flight: up to 48+48 and up to 96+96 samples
-//   render_coop.inl  3 waves per ray with barrier-separated phases (and the 16-sample shade tile all of them use)
+//   render_pipe.inl   3 shader waves + 1 scalar wave per workgroup, three rays in flight: up to 144+144 samples
+//   render_shade.inl  the 16-sample shade tile, decoder staging and plane taps the pipelined and backward kernels share
 //   render_bwd.inl   the backward pass (plane + decoder gradients) of the renderer and of run_model
 //
 // Generic kernel: ONE WAVE (a 64-lane workgroup) owns a ray at a time and walks a small tile of rays
@@ -59,9 +59,9 @@ struct Params {
                             // a multiple of 16, in the ray SEQUENCE, so that no 16-ray tile straddles items -- linear_pad() below.  (Kept in a
                             // field the forward already has: one more kernel argument cost the headline kernel eight spilled SGPRs.)
     int total_rays;
-    int split_shift;        // small launches: a 16-ray tile is shared by 1 << split_shift workgroups (coop / generic / backward kernels)
+    int split_shift;        // small launches: a 16-ray tile is shared by 1 << split_shift workgroups (generic / backward kernels)
     int pipe_unit;          // pipelined kernel: rays dealt to a workgroup at a time (kPipeUnit; fewer for launches that do not fill the chip)
-    unsigned tex_pitch, row_pitch, plane_pitch;     // byte addressing of a texel, see plane_taps (render_coop.inl)
+    unsigned tex_pitch, row_pitch, plane_pitch;     // byte addressing of a texel, see plane_taps (render_shade.inl)
     int64_t item_bytes;     // bytes from one item's planes to the next: 3 * H * W * 128, or 0 when every item reads the same planes (planes_shared)
     const float* absmax;    // GNERF_MLP_AUTO: max |planes| (one device float) for choose_mlp
     TorchRandDraw draw_c, draw_f;   // rng_mode: the two draws torch's generator would have made (raygen.h)
@@ -115,12 +115,9 @@ __device__ __forceinline__ float dpp_mov(float old, float src) {
 // no source (and rows the row_mask leaves out) are simply not written, i.e. keep their own value, which is the scan's identity step.
 // Written through update_dpp + an arithmetic instruction the compiler can only fold the full-mask row shifts of the sum (old = 0 is
 // its bound_ctrl zero); every row_bcast step and every step of the product scan came out as v_mov (old) + v_mov_dpp + op: 10 / 18
-// vector instructions per scan instead of 6, on the wave whose per-ray pass is 476 of them (GNERF_DPP_INPLACE=0 is that form).
+// vector instructions per scan instead of 6, on the wave whose per-ray pass is 476 of them.
 // The s_nop 1 are the two wait states a DPP read needs after the VALU write of its source; the compiler's hazard recogniser does not
 // look inside (or behind) inline assembly, so the blocks begin and end with one as well.
-#ifndef GNERF_DPP_INPLACE
-#define GNERF_DPP_INPLACE 1
-#endif
 #define GNERF_SCAN6(OP, ZF)                                                                 \
     "s_nop 1\n\t"                                                                           \
     OP " %0, %0, %0 row_shr:1 row_mask:0xf bank_mask:0xf" ZF "\n\ts_nop 1\n\t"              \
@@ -130,34 +127,15 @@ __device__ __forceinline__ float dpp_mov(float old, float src) {
     OP " %0, %0, %0 row_bcast:15 row_mask:0xa bank_mask:0xf\n\ts_nop 1\n\t"                 \
     OP " %0, %0, %0 row_bcast:31 row_mask:0xc bank_mask:0xf\n\ts_nop 1"
 __device__ __forceinline__ float wave_scan_add(float v, int /*lane*/) {         // inclusive
-#if GNERF_DPP_INPLACE
     asm(GNERF_SCAN6("v_add_f32_dpp", " bound_ctrl:1") : "+v"(v));
-#else
-    v += dpp_mov<0x111, 0xf>(0.f, v);
-    v += dpp_mov<0x112, 0xf>(0.f, v);
-    v += dpp_mov<0x114, 0xf>(0.f, v);
-    v += dpp_mov<0x118, 0xf>(0.f, v);
-    v += dpp_mov<0x142, 0xa>(0.f, v);
-    v += dpp_mov<0x143, 0xc>(0.f, v);
-#endif
     return v;
 }
 __device__ __forceinline__ float wave_scan_mul(float v, int /*lane*/) {         // inclusive
-#if GNERF_DPP_INPLACE
     asm(GNERF_SCAN6("v_mul_f32_dpp", "") : "+v"(v));
-#else
-    v *= dpp_mov<0x111, 0xf>(1.f, v);
-    v *= dpp_mov<0x112, 0xf>(1.f, v);
-    v *= dpp_mov<0x114, 0xf>(1.f, v);
-    v *= dpp_mov<0x118, 0xf>(1.f, v);
-    v *= dpp_mov<0x142, 0xa>(1.f, v);
-    v *= dpp_mov<0x143, 0xc>(1.f, v);
-#endif
     return v;
 }
 // two independent sums at once: the steps of one fill a wait state of the other
 __device__ __forceinline__ void wave_scan_add2(float& a, float& b) {
-#if GNERF_DPP_INPLACE
 #define GNERF_STEP2(CTRL)                                                       \
     "v_add_f32_dpp %0, %0, %0 " CTRL "\n\tv_add_f32_dpp %1, %1, %1 " CTRL "\n\ts_nop 0\n\t"
     asm("s_nop 1\n\t"
@@ -170,9 +148,6 @@ __device__ __forceinline__ void wave_scan_add2(float& a, float& b) {
         "s_nop 0"
         : "+v"(a), "+v"(b));
 #undef GNERF_STEP2
-#else
-    a = wave_scan_add(a, 0); b = wave_scan_add(b, 0);
-#endif
 }
 #undef GNERF_SCAN6
 __device__ __forceinline__ float wave_last(float v) {                            // lane 63's value, in every lane
@@ -728,9 +703,9 @@ __global__ __launch_bounds__(64) void query_kernel(gnerf_render_params p, float 
     }
 }
 
-// ---- GNERF_MLP_AUTO: which decoder arithmetic may this call use?  Evaluated by every workgroup of the pipe / coop kernels before
+// ---- GNERF_MLP_AUTO: which decoder arithmetic may this call use?  Evaluated by every workgroup of the pipelined kernels before
 // it stages the decoder (one wave, a few hundred loads from L2, ~0.1 % of a workgroup's work): no separate launch.
-// The f16 hi/lo split (render_coop.inl) represents an operand v as hi + lo with |v - hi - lo| <= max(2^-22 |v|, 2^-25): fp32-grade
+// The f16 hi/lo split (render_shade.inl) represents an operand v as hi + lo with |v - hi - lo| <= max(2^-22 |v|, 2^-25): fp32-grade
 // for operands well inside f16's range, but an ABSOLUTE 2^-25 per operand once the low half goes subnormal, and inf/NaN once the high
 // half overflows.  With A = max |planes| (the features are convex combinations of texels, so |x| <= A), W1' = log2(e) W1 and the
 // row norms R1 = max_r ||W1'[r,:]||_2, R2 = max_r ||W2[r,:]||_2 the decision is
@@ -804,7 +779,7 @@ __device__ __forceinline__ int choose_mlp(const Params& P, float* smem, bool* so
     return choice;
 }
 
-#include "render_coop.inl"
+#include "render_shade.inl"
 #include "render_pipe.inl"
 #include "render_bwd.inl"
 
@@ -920,27 +895,24 @@ extern "C" int gnerf_render_forward(const gnerf_render_params* p, gnerf_stream_t
     while (P.split_shift < 2 && (int64_t(P.n_tiles) << (P.split_shift + 1)) <= int64_t(kNumCU) * 4) P.split_shift++;
     const int per_xcd = ((P.n_tiles << P.split_shift) + kNumXCD - 1) / kNumXCD;
     const dim3 grid(per_xcd * kNumXCD);
-    // Kernel choice (GNERF_RENDER_KERNEL=pipe|coop|generic forces one, for A/B runs):
-    //   pipe    3 shader waves + 1 scalar wave, three rays in flight: up to 144+144 samples with importance sampling (1, 2 or 3 tiles per wave)
-    //   coop    3 waves per ray, phases separated by barriers: up to 96+96 samples
-    //   generic one wave per ray: everything else (up to 256+256)
+    // Kernel choice (GNERF_RENDER_KERNEL=pipe|generic forces one, for A/B runs):
+    //   pipe    3 shader waves + 1 scalar wave, three rays in flight: up to 144+144 samples, importance sampling optional (1, 2 or 3 tiles per wave)
+    //   generic one wave per ray: everything else (up to 256+256, or planes too large for 32-bit tap offsets)
     // A/B and test overrides, read per call (the parity tests switch kernels inside one process): two getenv walks of the
     // environment, ~0.1 us against the ~10 us of a launch
     const char* force = getenv("GNERF_RENDER_KERNEL");
     const char* force_mlp = getenv("GNERF_RENDER_MLP");                      // f16x3 | f32: overrides params.mlp_mode
     const bool small_planes = int64_t(p->plane_h) * p->plane_w * 3 * 128 < (int64_t(1) << 32);
-    bool pipe = P.tiles_c <= 9 && P.tiles_f >= 1 && P.tiles_f <= 9 && small_planes;
+    bool pipe = P.tiles_c <= 9 && P.tiles_f <= 9 && small_planes;
     const int pipe_tp = (P.tiles_c <= 3 && P.tiles_f <= 3) ? 1 : ((P.tiles_c <= 6 && P.tiles_f <= 6) ? 2 : 3);   // 16-sample tiles per shader wave and pass
-    bool coop = P.tiles_c <= 2 * kCoopWaves && P.tiles_f <= 2 * kCoopWaves && small_planes;
-    if (force && !strcmp(force, "generic")) pipe = coop = false;
-    if (force && !strcmp(force, "coop")) { pipe = false; if (!coop) return fail(GNERF_E_UNSUPPORTED, "render: cooperative kernel does not cover %d+%d samples", S, F); }
+    if (force && !strcmp(force, "generic")) pipe = false;
     if (force && !strcmp(force, "pipe") && !pipe) return fail(GNERF_E_UNSUPPORTED, "render: pipelined kernel does not cover %d+%d samples", S, F);
-    // Decoder arithmetic of the pipe / coop kernels (the generic kernel is fp32 throughout).
+    // Decoder arithmetic of the pipelined kernel (the generic kernel is fp32 throughout).
     int mlp = p->mlp_mode;
     if (force_mlp && !strcmp(force_mlp, "f16x3")) mlp = GNERF_MLP_F16X3;
     if (force_mlp && !strcmp(force_mlp, "f32")) mlp = GNERF_MLP_F32;
     if (mlp != GNERF_MLP_AUTO && mlp != GNERF_MLP_F16X3 && mlp != GNERF_MLP_F32) return fail(GNERF_E_ARG, "render: mlp_mode %d is not one of GNERF_MLP_*", mlp);
-    if ((pipe || coop) && mlp == GNERF_MLP_AUTO) {
+    if (pipe && mlp == GNERF_MLP_AUTO) {
         // the choice is made on the device, by every workgroup for itself (no host round trip, graph-capturable): see choose_mlp
         P.absmax = p->planes_absmax;
         hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;
@@ -975,7 +947,7 @@ extern "C" int gnerf_render_forward(const gnerf_render_params* p, gnerf_stream_t
         if (g < kNumXCD) g = kNumXCD;
         if (g > capacity) g = capacity;
         const bool gen = !p->ray_origins || p->rng_mode != GNERF_RNG_TENSORS;       // the call makes its rays and / or its draws in the kernel
-        const size_t lds_bytes = pipe_lds_floats(pipe_tp, mlp, gen) * sizeof(float);
+        const size_t lds_bytes = pipe_lds_floats(pipe_tp, mlp) * sizeof(float);
         const dim3 gd((unsigned)g), bd(kPipeThreads);
         // the instantiation with compile-time sample counts (render_pipe_body<.., FULL>) where the call fills the slots exactly
         bool full = S == 48 * pipe_tp && F == 48 * pipe_tp && !p->disparity_space_sampling && !p->ray_start_per_ray && !p->debug && !p->sigma_noise_coarse;
@@ -1012,22 +984,6 @@ extern "C" int gnerf_render_forward(const gnerf_render_params* p, gnerf_stream_t
     } else
     if (!p->ray_origins || p->rng_mode != GNERF_RNG_TENSORS) {
         return fail(GNERF_E_UNSUPPORTED, "render: in-kernel rays / draws need the pipelined kernel (48+48 or 96+96 samples); got %d+%d", S, F);
-    } else
-    if (coop) {
-        const int tc1 = (P.tiles_c + kCoopWaves - 1) / kCoopWaves, tf1 = (P.tiles_f + kCoopWaves - 1) / kCoopWaves;
-        const dim3 block(kCoopThreads);
-        const size_t lds_bytes = coop_lds_floats(16 * (P.tiles_c + P.tiles_f), mlp) * sizeof(float);
-#define GNERF_COOP(TC, TF) do { if (mlp == kMlpAuto) hipLaunchKernelGGL((render_kernel_coop<TC, TF, kMlpAuto>), grid, block, lds_bytes, s, P); \
-                                else if (mlp == kMlpF16x3) hipLaunchKernelGGL((render_kernel_coop<TC, TF, kMlpF16x3>), grid, block, lds_bytes, s, P); \
-                                else hipLaunchKernelGGL((render_kernel_coop<TC, TF, kMlpF32>), grid, block, lds_bytes, s, P); } while (0)
-        if (tc1 == 1 && tf1 == 0) GNERF_COOP(1, 0);
-        else if (tc1 == 1 && tf1 == 1) GNERF_COOP(1, 1);
-        else if (tc1 == 1 && tf1 == 2) GNERF_COOP(1, 2);
-        else if (tc1 == 2 && tf1 == 0) GNERF_COOP(2, 0);
-        else if (tc1 == 2 && tf1 == 1) GNERF_COOP(2, 1);
-        else GNERF_COOP(2, 2);
-#undef GNERF_COOP
-        if (int e = check_launch("render_kernel_coop")) return e;
     } else {
         const size_t lds_bytes = scratch_floats(16 * (P.tiles_c + P.tiles_f), P.tiles_c + P.tiles_f) * sizeof(float);
         if (lds_bytes > 160 * 1024) return fail(GNERF_E_ARG, "render: %d+%d samples need %zu bytes of LDS (> 160 KiB)", S, F, lds_bytes);

@@ -134,7 +134,7 @@ __device__ __forceinline__ void bwd_gather_tile(const Params& P, const BwdLds& L
 }
 
 // The same lookup for kernels that hold no scatter state (render_bwd_tiles_kernel): the tile's 24 texel loads run as the forward's ROLLING
-// window (coop_shade_tile, render_coop.inl) -- the three planes of step 0 in flight together, and as soon as a plane of step 0 has been
+// window (shade_tile, render_shade.inl) -- the three planes of step 0 in flight together, and as soon as a plane of step 0 has been
 // blended the same plane of step 1 is issued -- instead of six dependent rounds of four loads: with two waves per SIMD a round trip to
 // L2 per round was a third of the tile's time.
 template <class PosFn>
@@ -175,7 +175,7 @@ __device__ __forceinline__ void bwd_gather_tile_rolling(const Params& P, const B
         tex[a][pl][2] = *reinterpret_cast<const v4f*>(planes + (off[a][pl].z + cq16));
         tex[a][pl][3] = *reinterpret_cast<const v4f*>(planes + (off[a][pl].w + cq16));
     };
-    auto blend = [&](int a, int pl, v4f& acc) {                 // the forward's chain (coop_shade_tile): same features, same bits
+    auto blend = [&](int a, int pl, v4f& acc) {                 // the forward's chain (shade_tile): same features, same bits
         auto bc = [](float w) { return (v4f){w, w, w, w}; };
         acc = pl == 0 ? tex[a][pl][0] * wgt[a][pl][0] : __builtin_elementwise_fma(tex[a][pl][0], bc(wgt[a][pl][0]), acc);
         acc = __builtin_elementwise_fma(tex[a][pl][1], bc(wgt[a][pl][1]), acc);
@@ -719,17 +719,9 @@ struct BwdTileF32 {
 // tile's scale -- when the scale changes from one tile to the next they are multiplied by the ratio, a power of two (exact; fp32 has
 // the range) -- so that the matrix instructions accumulate into them directly.
 // Valid under the same guard as the forward's f16 arithmetic (choose_mlp: features, weights, activations in f16's range).
-#ifndef GNERF_K2_SPLIT
-#define GNERF_K2_SPLIT split_f16x8
-#endif
-#ifdef GNERF_K2_NO_FENCE
-#define GNERF_K2_PHASE_FENCE()
-#else
-#define GNERF_K2_PHASE_FENCE() __builtin_amdgcn_sched_barrier(0)
-#endif
 struct BwdTileF16 {
     static constexpr int kMlp = kMlpF16x3;
-    CoopLds C;                       // the forward's fragments (w1 = fragment base, w2 = density row * ln2, b1 * log2e, b2 scaled)
+    ShadeLds C;                      // the forward's fragments (w1 = fragment base, w2 = density row * ln2, b1 * log2e, b2 scaled)
     const _Float16* g1; const _Float16* g3;
     const float* ws_true;            // W2[0][:]
     float* stage; float* tbuf; float* hbuf;
@@ -771,12 +763,12 @@ struct BwdTileF16 {
         const int j = lane & 15, g = lane >> 4;
         const _Float16* w1h = reinterpret_cast<const _Float16*>(C.w1);
         const _Float16* w2h = w1h + 2 * kW1FragHalves;
-        // ---- decoder forward (coop_shade_tile's f16 branch): p' = log2(e) pre-activation, hv = log2(1 + 2^p') = H / ln 2, o' = -log2(e) o
+        // ---- decoder forward (shade_tile's f16 branch): p' = log2(e) pre-activation, hv = log2(1 + 2^p') = H / ln 2, o' = -log2(e) o
         const v4f f_lo = *reinterpret_cast<const v4f*>(stage + j * kStagePitch + 8 * g);
         const v4f f_hi = *reinterpret_cast<const v4f*>(stage + j * kStagePitch + 8 * g + 4);
         const float f[8] = {f_lo[0], f_lo[1], f_lo[2], f_lo[3], f_hi[0], f_hi[1], f_hi[2], f_hi[3]};
         unsigned fh_u[4], fl_u[4];
-        GNERF_K2_SPLIT(f, fh_u, fl_u);
+        split_f16x8(f, fh_u, fl_u);
         const h8 fh = as_h8((u4v){fh_u[0], fh_u[1], fh_u[2], fh_u[3]}), fl = as_h8((u4v){fl_u[0], fl_u[1], fl_u[2], fl_u[3]});
         v4f hv[4];
         {
@@ -812,7 +804,7 @@ struct BwdTileF16 {
             }
             *reinterpret_cast<v4f*>(hbuf + j * kHPitch + 16 * m + 4 * g) = hv[m];               // H / ln2 as [sample][hidden], for dW2's B operand
         }
-        GNERF_K2_PHASE_FENCE();
+        __builtin_amdgcn_sched_barrier(0);
         v4f o[2];
         {
             const float bc0 = C.b2[1 + j], bc1 = C.b2[17 + j];
@@ -822,7 +814,7 @@ struct BwdTileF16 {
             for (int s = 0; s < 2; s++) {
                 unsigned xh[4], xl[4];
                 const float xs[8] = {hv[2 * s][0], hv[2 * s][1], hv[2 * s][2], hv[2 * s][3], hv[2 * s + 1][0], hv[2 * s + 1][1], hv[2 * s + 1][2], hv[2 * s + 1][3]};
-                GNERF_K2_SPLIT(xs, xh, xl);
+                split_f16x8(xs, xh, xl);
                 x_hi[s] = as_h8((u4v){xh[0], xh[1], xh[2], xh[3]});
                 x_lo[s] = as_h8((u4v){xl[0], xl[1], xl[2], xl[3]});
             }
@@ -838,7 +830,7 @@ struct BwdTileF16 {
                 }
             }
         }
-        GNERF_K2_PHASE_FENCE();
+        __builtin_amdgcn_sched_barrier(0);
         // ---- dO: colour c = 1.002 s - 0.001, s = sigmoid(o) = 1 / (1 + 2^o'); kept in registers too (A operand of dW2)
         const v4f vs = *reinterpret_cast<const v4f*>(vw + 4 * g);
         const float dsig_true = dsg[j];
@@ -885,7 +877,7 @@ struct BwdTileF16 {
             }
         }
         lds_wave_sync();
-        GNERF_K2_PHASE_FENCE();
+        __builtin_amdgcn_sched_barrier(0);
         // ---- dH^T[hidden][sample] = W2c^T dO^T (+ the density row on the vector ALU): B = this lane's sample row of dO, outputs 8g..8g+7
         v4f dh[4];
         {
@@ -893,7 +885,7 @@ struct BwdTileF16 {
             const v4f b_hi4 = *reinterpret_cast<const v4f*>(tbuf + j * kTPitch + 8 * g + 4);
             const float bv[8] = {b_lo4[0], b_lo4[1], b_lo4[2], b_lo4[3], b_hi4[0], b_hi4[1], b_hi4[2], b_hi4[3]};
             unsigned bh_u[4], bl_u[4];
-            GNERF_K2_SPLIT(bv, bh_u, bl_u);
+            split_f16x8(bv, bh_u, bl_u);
             const h8 bh = as_h8((u4v){bh_u[0], bh_u[1], bh_u[2], bh_u[3]}), bl = as_h8((u4v){bl_u[0], bl_u[1], bl_u[2], bl_u[3]});
 #pragma unroll
             for (int m = 0; m < 4; m++) {
@@ -907,11 +899,11 @@ struct BwdTileF16 {
                 dh[m] = GNERF_MFMA16(a_lo, bh, dh[m]);
             }
         }
-        GNERF_K2_PHASE_FENCE();
+        __builtin_amdgcn_sched_barrier(0);
         // ---- dW2c[out][hidden] += dO^T (H / ln2): A = the dO values this lane computed (samples 4g..4g+3 of outputs 16o + j), B from hbuf
         {
             unsigned ah_u[4], al_u[4];
-            GNERF_K2_SPLIT(dO, ah_u, al_u);
+            split_f16x8(dO, ah_u, al_u);
 #pragma unroll
             for (int np = 0; np < 2; np++) {                       // hidden blocks 2 np, 2 np + 1
                 float bvals[8];
@@ -920,7 +912,7 @@ struct BwdTileF16 {
 #pragma unroll
                     for (int e = 0; e < 4; e++) bvals[4 * q + e] = hbuf[(4 * g + e) * kHPitch + 16 * (2 * np + q) + j];
                 unsigned bh_u[4], bl_u[4];
-                GNERF_K2_SPLIT(bvals, bh_u, bl_u);
+                split_f16x8(bvals, bh_u, bl_u);
 #pragma unroll
                 for (int q = 0; q < 2; q++) {
                     const h4 b_hi = as_h4(bh_u[2 * q], bh_u[2 * q + 1]), b_lo = as_h4(bl_u[2 * q], bl_u[2 * q + 1]);
@@ -936,7 +928,7 @@ struct BwdTileF16 {
                 }
             }
         }
-        GNERF_K2_PHASE_FENCE();
+        __builtin_amdgcn_sched_barrier(0);
         // ---- through softplus: d/dpre softplus(pre) = 1 - exp(-H) = 1 - 2^-(H / ln2)
 #pragma unroll
         for (int m = 0; m < 4; m++) {
@@ -945,7 +937,7 @@ struct BwdTileF16 {
             A.b1[m] += dh[m] * inv;
         }
         lds_wave_sync();                                            // every lane has read H from hbuf and its dO row from tbuf
-        GNERF_K2_PHASE_FENCE();
+        __builtin_amdgcn_sched_barrier(0);
         // ---- dX^T[channel][sample] = W1^T dPRE^T: B straight from this lane's dPRE registers (k order of the g3 fragments)
         v4f dx[2];
         dx[0] = dx[1] = (v4f){0.f, 0.f, 0.f, 0.f};
@@ -953,7 +945,7 @@ struct BwdTileF16 {
         for (int s = 0; s < 2; s++) {
             const float pv[8] = {dh[2 * s][0], dh[2 * s][1], dh[2 * s][2], dh[2 * s][3], dh[2 * s + 1][0], dh[2 * s + 1][1], dh[2 * s + 1][2], dh[2 * s + 1][3]};
             unsigned ph_u[4], pl_u[4];
-            GNERF_K2_SPLIT(pv, ph_u, pl_u);
+            split_f16x8(pv, ph_u, pl_u);
             const h8 p_hi = as_h8((u4v){ph_u[0], ph_u[1], ph_u[2], ph_u[3]}), p_lo = as_h8((u4v){pl_u[0], pl_u[1], pl_u[2], pl_u[3]});
 #pragma unroll
             for (int c = 0; c < 2; c++) {
@@ -969,7 +961,7 @@ struct BwdTileF16 {
         *reinterpret_cast<v4f*>(tbuf + j * kTPitch + 4 * g) = dx[0] * inv;                                         // dX[sample][channel], true units
         *reinterpret_cast<v4f*>(tbuf + j * kTPitch + 16 + 4 * g) = dx[1] * inv;
         lds_wave_sync();
-        GNERF_K2_PHASE_FENCE();
+        __builtin_amdgcn_sched_barrier(0);
         // ---- dW1[hidden][channel] += dPRE^T X: A = dPRE^T from hbuf, B = X^T from the staged features
         {
             float xv[8];
@@ -978,7 +970,7 @@ struct BwdTileF16 {
 #pragma unroll
                 for (int e = 0; e < 4; e++) xv[4 * c + e] = stage[(4 * g + e) * kStagePitch + 16 * c + j];
             unsigned xh_u[4], xl_u[4];
-            GNERF_K2_SPLIT(xv, xh_u, xl_u);
+            split_f16x8(xv, xh_u, xl_u);
 #pragma unroll
             for (int mp = 0; mp < 2; mp++) {
                 float av[8];
@@ -987,7 +979,7 @@ struct BwdTileF16 {
 #pragma unroll
                     for (int e = 0; e < 4; e++) av[4 * q + e] = hbuf[(4 * g + e) * kHPitch + 16 * (2 * mp + q) + j];
                 unsigned ah_u[4], al_u[4];
-                GNERF_K2_SPLIT(av, ah_u, al_u);
+                split_f16x8(av, ah_u, al_u);
 #pragma unroll
                 for (int q = 0; q < 2; q++) {
                     const h4 a_hi = as_h4(ah_u[2 * q], ah_u[2 * q + 1]), a_lo = as_h4(al_u[2 * q], al_u[2 * q + 1]);

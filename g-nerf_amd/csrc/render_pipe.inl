@@ -1,24 +1,24 @@
 // Pipelined render kernel: 3 SHADER WAVES + 1 SCALAR WAVE per workgroup, three rays in flight.
-// Included by render.hip (inside its anonymous namespace) after render_coop.inl.
+// Included by render.hip (inside its anonymous namespace) after render_shade.inl.
 //
-// In the cooperative kernel every ray alternates between phases that use all three waves (tri-plane lookups +
-// MLP) and phases only one wave can do (ray march, cdf, inverse-cdf, merge), with a workgroup barrier between
-// them: ablation (tools/ablate.py) shows ~35 % of its time is the single-wave phases and their bubbles.
+// A ray alternates between work that uses all three shader waves (tri-plane lookups + MLP) and work only one wave
+// can do (ray march, cdf, inverse-cdf, merge).  With all waves on one ray and a workgroup barrier between such phases,
+// ablation (tools/ablate.py) showed ~35 % of the time in the single-wave phases and their bubbles.
 // Here the per-sample scalar work of a ray runs on a dedicated fourth wave WHILE the three shader waves
 // shade another ray, so shader waves never wait for it:
 //
 //   step 2k+2:  shaders  A(k+1) coarse lookups+MLP        | scalar  D(k-1) merge + final march,  out(k-2)
 //   step 2k+3:  shaders  acc(k-1) colours, C(k) fine pass  | scalar  B(k+1) coarse march + importance,  P(k+2) depth proposals
 //
-// with ONE workgroup barrier per step (the hand-offs inside a tile are wave-private, see coop_shade_tile<false>).
+// with ONE workgroup barrier per step (the hand-offs inside a tile are wave-private, see shade_tile).
 // Rays r-1, r, r+1, r+2 are live at once: their per-sample scalars sit in a ring of four LDS slots, their
 // colours in shader-wave registers (3 coarse sets + 1 fine set = 32 VGPRs).  The scalar wave issues its global
 // loads (noise, ray) at the start of a step and consumes them at the end, behind the march/cdf work.
 // Workgroups are persistent-style: each takes a contiguous run of the locality-ordered ray sequence, so the
 // 3-step pipeline fill/drain is paid once per ~85 rays, not once per 16.
-// Instantiated for one 16-sample tile per shader wave and pass (depth_resolution <= 48, 1 <= importance <= 48: the
-// reference's training/inference default) and for two (up to 96+96: gen_videos.py's doubled counts, the ShapeNet config's
-// 64+64); other shapes use the coop / generic kernels.
+// Instantiated for one, two or three 16-sample tiles per shader wave and pass: up to 48+48 (the reference's training / inference
+// default), 96+96 (gen_videos.py's doubled counts, the ShapeNet config's 64+64) and 144+144.  Importance sampling is optional
+// (F = 0: the fine pass finds no tiles).  Other shapes use the generic kernel.
 
 #ifdef GNERF_STAMPS
 #define GNERF_DBG_PTR(x) ((float*)nullptr)
@@ -46,7 +46,7 @@ struct PipeSlot {
     float* t_e; float* sig_e; float* v_e; int* rank_e; float* s_t; float* s_sig; float* w_s; float* cdf;
     float* nf;      // [kMaxS] fine noise of this ray
     float* part;    // [3][32] colour partial sums of the shader waves
-    float* misc;    // [0..11] the ray per plane: (ou, du, ov, dv) x 3 (CoopRay, render_coop.inl)  [12] item (int)  [13] ray (int)  [14] w_sum  [15] wt_sum
+    float* misc;    // [0..11] the ray per plane: (ou, du, ov, dv) x 3 (ShadeRay, render_shade.inl)  [12] item (int)  [13] ray (int)  [14] w_sum  [15] wt_sum
 };
 constexpr int kMiscItem = 12, kMiscRay = 13, kMiscWsum = 14, kMiscWtsum = 15;
 // lane l < 12 of the scalar wave carries component misc_comp(l) of (origin xyz, direction xyz): plane l / 4, then ou, du, ov, dv
@@ -67,12 +67,10 @@ __device__ __forceinline__ PipeSlot pipe_slot(float* base, int slot) {
     return s;
 }
 
-__host__ __device__ inline size_t pipe_lds_floats(int tp, int mlp, bool gen = false) {
+__host__ __device__ inline size_t pipe_lds_floats(int tp, int mlp) {
     const size_t slot_floats = tp == 1 ? PipeDims<1>::kSlotFloats : (tp == 2 ? PipeDims<2>::kSlotFloats : PipeDims<3>::kSlotFloats);
     return size_t(weight_floats(mlp)) + 64 + 36 + size_t(kPipeSlots) * slot_floats + 3 * 16 * kStagePitch       // (tap records live in the staging rows)
-           + kPipeUnit * 8                                                                                         // GEN: the dealing unit's rays
-           + 4;                                                                                                    // GNERF_PIPE_FLAGS: the four progress counters
-    (void)gen;
+           + kPipeUnit * 8;                                                                                        // GEN: the dealing unit's rays
 }
 
 // position `seq` of the locality-ordered ray sequence -> ray index (or -1 past the end)
@@ -104,18 +102,6 @@ __device__ __forceinline__ int pipe_seq_to_ray(const Params& P, int64_t seq) {
 #ifndef GNERF_PIPE_WAVES_PER_SIMD
 #define GNERF_PIPE_WAVES_PER_SIMD 4
 #endif
-#ifndef GNERF_PIPE_ROTATE
-#define GNERF_PIPE_ROTATE 1
-#endif
-// GNERF_PIPE_FLAGS (round 6 experiment): the step barriers as role-to-role hand-offs through four LDS counters instead of s_barrier.
-// A half-step of a shader wave depends on the SCALAR wave's previous half-step only (depth proposals, importance depths, colour weights),
-// and the scalar wave's on all three shader waves' previous one (densities, colour partials); the three shader waves never exchange
-// anything.  s_barrier makes each of them wait for the slowest of the three every half-step (stamps: 11 % of a shader wave's time);
-// with counters a shader wave that is done goes on as soon as the scalar wave has finished its part -- which it has, it is the one
-// that waits (38 % of its time) -- so the three SIMDs' different loads average out over two half-steps instead of none.
-#ifndef GNERF_PIPE_FLAGS
-#define GNERF_PIPE_FLAGS 0
-#endif
 // FULL: the call fills the kernel's sample slots exactly (depth_resolution = depth_resolution_importance = 48 TP: the reference's 48+48
 // default, gen_videos.py's doubled 96+96) with plain stratified sampling (no disparity spacing, no per-ray limits) and no stage dump.
 // Sample counts, tile counts and every `k < S` predicate are then compile-time constants; the cold options are not compiled in at
@@ -138,23 +124,8 @@ __device__ __forceinline__ void render_pipe_body(const Params& P, float* smem, c
     constexpr int kPipeMaxS = D::kMaxS, kPipeSPad = D::kSPad, kSlotFloats = D::kSlotFloats, RND = D::kRounds;
     const gnerf_render_params& p = P.p;
     const int tid = threadIdx.x, lane = tid & 63;
-#if defined(GNERF_ROLE_ROT)
-    // experiment: which SIMD hosts the scalar wave.  Physical wave w of a workgroup sits on SIMD w; role = (w + rot) & 3 puts the scalar
-    // role of CU-mates on different SIMDs when their `rot` differ.  1: rot from the launch position (blockIdx / 256), 2: blockIdx / 8,
-    // 3: from the wave slot the hardware gave wave 0 (HW_ID.WAVE_ID)
-    int rot;
-    if (GNERF_ROLE_ROT == 1) rot = (blockIdx.x >> 8) & 3;
-    else if (GNERF_ROLE_ROT == 2) rot = (blockIdx.x >> 3) & 3;
-    else {
-        if (tid == 0) { unsigned hw; asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw)); reinterpret_cast<unsigned*>(smem)[0] = hw & 15u; }
-        __syncthreads();
-        rot = reinterpret_cast<const unsigned*>(smem)[0] & 3;
-        __syncthreads();
-    }
-    const int wv = __builtin_amdgcn_readfirstlane(((tid >> 6) + rot) & 3);
-#else
+    // (roles by wave index, as the hardware places them: rotating them in software stacks scalar waves onto one SIMD, 8 % slower -- DESIGN 3.1)
     const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-#endif
     const int S = FULL ? kPipeMaxS : p.depth_resolution, F = FULL ? kPipeMaxS : p.depth_resolution_importance;
     const int tiles_c = FULL ? 3 * TP : P.tiles_c, tiles_f = FULL ? 3 * TP : P.tiles_f;
     float* const debug = (FULL || BWD) ? nullptr : GNERF_DBG_PTR(p.debug);       // (the backward's params carry no debug buffer)
@@ -162,15 +133,14 @@ __device__ __forceinline__ void render_pipe_body(const Params& P, float* smem, c
     // fully unrolled 4-wide key scans below need no bounds checks
     constexpr int fine_e0 = kPipeMaxS, s_pad = kPipeSPad;
     const int n_all = S + F;
-    CoopLds L;
+    ShadeLds L;
     float* slots = smem + weight_floats(MLP) + 64 + 36;
     // A wave's tap records (16 records of kFwdTapStride = 28 dwords, 24 of them used) and its staging rows (16 rows of kFwdStagePitch
-    // = 32 dwords, swizzled) share one area of 16 x kStagePitch dwords.  What makes that safe is an ORDER inside coop_shade_tile, not a
+    // = 32 dwords, swizzled) share one area of 16 x kStagePitch dwords.  What makes that safe is an ORDER inside shade_tile, not a
     // layout: every read of a record -- the offsets of both lookup steps and, last, step 1's weights (`w1`, fetched right before `row0`
     // is stored and kept in front of that store by pin()) -- is issued before the first row is written, and the rows have been read back
-    // (f_lo / f_hi) before the next tile's records are written; LDS operations of one wave execute in issue order.  Both layouts must fit
-    // the area whatever tools/build_variants.sh sets GNERF_TAP_STRIDE / GNERF_STAGE_SWZ to.  Those 4.6 KB are what lets FOUR workgroups
-    // share a CU's 160 KB.
+    // (f_lo / f_hi) before the next tile's records are written; LDS operations of one wave execute in issue order.  Those 4.6 KB
+    // are what lets FOUR workgroups share a CU's 160 KB.
     static_assert(16 * kFwdTapStride <= 16 * kStagePitch && 16 * kFwdStagePitch <= 16 * kStagePitch && kFwdTapStride >= kTapDwords,
                   "tap records and staging rows share 16 x kStagePitch dwords per wave");
     L.taps = slots + kPipeSlots * kSlotFloats;
@@ -649,7 +619,7 @@ __device__ __forceinline__ void render_pipe_body(const Params& P, float* smem, c
         const float id_item = ids[0], id_ray = ids[1], r_ou = uv[0], r_du = uv[1], r_ov = uv[2], r_dv = uv[3];
         const int ray_id = __builtin_amdgcn_readfirstlane(__float_as_int(id_ray));
         if (ray_id < 0) return false;
-        CoopRay R;
+        ShadeRay R;
         const int item = __builtin_amdgcn_readfirstlane(__float_as_int(id_item));
         R.planes_item = reinterpret_cast<const char*>(p.planes_nhwc) + int64_t(item) * P.item_bytes;
         R.ou = r_ou; R.du = r_du; R.ov = r_ov; R.dv = r_dv;
@@ -662,8 +632,8 @@ __device__ __forceinline__ void render_pipe_body(const Params& P, float* smem, c
         for (int i = 0; i < TP; i++) {
             const int tile = wv + 3 * i;
             if (TP > 1 && tile >= (fine ? tiles_f : tiles_c)) continue;       // wave-uniform: this wave has no such tile
-            coop_shade_tile<false, MLP>(P, L, R, t_list, count, tile, tile < (fine ? tiles_f : tiles_c), (fine ? sl.sig_e + fine_e0 : sl.sig_e), lane, wv, col[i], st, sp_direct,
-                                        i == 0, depth0);
+            shade_tile<MLP>(P, L, R, t_list, count, tile, tile < (fine ? tiles_f : tiles_c), (fine ? sl.sig_e + fine_e0 : sl.sig_e), lane, wv, col[i], st, sp_direct,
+                            i == 0, depth0);
         }
         return true;
     };
@@ -719,9 +689,6 @@ __device__ __forceinline__ void render_pipe_body(const Params& P, float* smem, c
     // waves, and every step ends when it does: give it issue priority (costs the shaders little, it is mostly waiting
     // on LDS round trips).
     if (wv == 3) __builtin_amdgcn_s_setprio(GNERF_SCALAR_PRIO);
-#if GNERF_PIPE_FLAGS && GNERF_PIPE_ROTATE
-    if (tid < 4) reinterpret_cast<int*>(unit_rays + kPipeUnit * 8)[tid] = 0;
-#endif
     __syncthreads();                                            // weights are in LDS
     if (wv == 3) { propose_issue(0); propose_finish(0); }
     __syncthreads();
@@ -737,7 +704,8 @@ __device__ __forceinline__ void render_pipe_body(const Params& P, float* smem, c
     // (Measured on top of this and dropped: issuing a tile's tap records and its first twelve texel loads BEFORE the barrier that
     // precedes it, with depth proposals one ray earlier and five ray slots, so that the L2 round trip runs under the barrier
     // wait -- 0.617 ms: the two other waves of the SIMD already cover that latency, and the loads' registers are then live across
-    // the barrier; its first version spilled two of the loaded vectors, i.e. waited for them on the spot: 0.71 ms.)
+    // the barrier; its first version spilled two of the loaded vectors, i.e. waited for them on the spot: 0.71 ms.  Role-to-role
+    // hand-offs through LDS progress counters in place of the two barriers per ray: bit-identical and 2.5 % slower)
     if constexpr (BWD) {
         if (wv < 3) {
             v4f cc[TP][2] = {}, cf[TP][2] = {};
@@ -761,57 +729,25 @@ __device__ __forceinline__ void render_pipe_body(const Params& P, float* smem, c
         }
         return;
     }
-#if GNERF_PIPE_ROTATE
     // Round 6: the three coarse colour sets change ROLES instead of registers.  Ray k+1's coarse colours are produced in step 2k+2 and
     // consumed in step 2k+7, so three sets are live; the loop used to shift them along every iteration (cc0 = cc1, cc1 = cc2: 16
     // v_mov_b32 at the bottom and 8 at the top, where the compiler parks the loop-carried set -- 72 vector instructions per ray over the
     // three waves).  Unrolled three times, iteration k + i writes set (i + 2) % 3 and reads set i % 3: no copies.  Both roles run
     // the same number of iterations, rounded up to a multiple of three (the extra ones find no ray and only meet at the barriers).
     const int k_last = -1 + 3 * ((nr + 3 + 2) / 3) - 1;
-#if GNERF_PIPE_FLAGS
-    // progress[0..2]: half-steps the shader waves have finished; progress[3]: the scalar wave's.  One lane writes, every lane of a waiting
-    // wave reads the same word(s).  LDS operations of a wave are performed in issue order and the LDS serves one request at a time, so a
-    // counter written after a wave's data is seen after that data, and data read before a counter is written has been read by then.
-    volatile int* const progress = reinterpret_cast<volatile int*>(unit_rays + kPipeUnit * 8);
-    int my_steps = 0;
-    auto step_done_shader = [&]() {
-        my_steps++;
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        if (lane == 0) progress[wv] = my_steps;
-        // go on once the scalar wave has finished the same half-step
-        while (__builtin_amdgcn_readfirstlane(progress[3]) < my_steps) __builtin_amdgcn_s_sleep(1);
-        asm volatile("" ::: "memory");
-    };
-    auto step_done_scalar = [&]() {
-        my_steps++;
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        if (lane == 0) progress[3] = my_steps;
-        while (true) {
-            const int a0 = progress[0], a1 = progress[1], a2 = progress[2];
-            if (__builtin_amdgcn_readfirstlane(min(a0, min(a1, a2))) >= my_steps) break;
-            __builtin_amdgcn_s_sleep(1);
-        }
-        asm volatile("" ::: "memory");
-    };
-#define GNERF_STEP_SYNC_SHADER() step_done_shader()
-#define GNERF_STEP_SYNC_SCALAR() step_done_scalar()
-#else
-#define GNERF_STEP_SYNC_SHADER() __syncthreads()
-#define GNERF_STEP_SYNC_SCALAR() __syncthreads()
-#endif
     if (wv < 3) {
         v4f ca[TP][2] = {}, cb[TP][2] = {}, cd[TP][2] = {}, cf[TP][2] = {};
         bool la = false, lb = false, ld = false;
         auto iter = [&](int k, v4f (&c0)[TP][2], v4f (&c2)[TP][2], bool l0, bool& l2) {
             l2 = shade(k + 1, false, c2);
             GNERF_STAMP(st, 5);
-            GNERF_STEP_SYNC_SHADER();
+            __syncthreads();
             GNERF_STAMP(st, 6);         // barrier wait, even step
             accumulate(k - 1, l0, c0, cf);
             GNERF_STAMP(st, 10);        // colour accumulate
             shade(k, true, cf);
             GNERF_STAMP(st, 5);
-            GNERF_STEP_SYNC_SHADER();
+            __syncthreads();
             GNERF_STAMP(st, 7);         // barrier wait, odd step
         };
         for (int k = -1; k <= k_last; k += 3) {         // sets (k-1, k, k+1) = (a, b, d), then (b, d, a), then (d, a, b)
@@ -826,55 +762,8 @@ __device__ __forceinline__ void render_pipe_body(const Params& P, float* smem, c
             output(k - 2);
             GNERF_STAMP(st, 9);         // outputs
             GNERF_STAMP(st, 5);         // rounding
-            GNERF_STEP_SYNC_SCALAR();
-            GNERF_STAMP(st, 6);         // barrier wait, even step
-            propose_issue(k + 2);
-            importance(k + 1);
-            GNERF_STAMP(st, 11);        // coarse march + importance
-            propose_finish(k + 2);
-            GNERF_STAMP(st, 12);        // depth proposals
-            GNERF_STAMP(st, 5);
-            GNERF_STEP_SYNC_SCALAR();
-            GNERF_STAMP(st, 7);         // barrier wait, odd step
-        }
-    }
-#undef GNERF_STEP_SYNC_SHADER
-#undef GNERF_STEP_SYNC_SCALAR
-#else
-    if (wv < 3) {
-        v4f cc0[TP][2] = {}, cc1[TP][2] = {}, cc2[TP][2] = {}, cf[TP][2] = {};      // coarse colours of rays k-1, k, k+1; fine colours of ray k-1
-        bool live0 = false, live1 = false, live2 = false;                            // do rays k-1, k, k+1 exist (from their coarse pass)
-        for (int k = -1; k <= nr + 1; k++) {
-            // ---- step 2k+2
-            live2 = shade(k + 1, false, cc2);
-            GNERF_STAMP(st, 5);
             __syncthreads();
             GNERF_STAMP(st, 6);         // barrier wait, even step
-            // ---- step 2k+3
-            accumulate(k - 1, live0, cc0, cf);
-            GNERF_STAMP(st, 10);        // colour accumulate
-            shade(k, true, cf);
-#pragma unroll
-            for (int i = 0; i < TP; i++) {
-#pragma unroll
-                for (int n = 0; n < 2; n++) { cc0[i][n] = cc1[i][n]; cc1[i][n] = cc2[i][n]; }
-            }
-            live0 = live1; live1 = live2;
-            GNERF_STAMP(st, 5);
-            __syncthreads();
-            GNERF_STAMP(st, 7);         // barrier wait, odd step
-        }
-    } else {
-        for (int k = -1; k <= nr + 1; k++) {
-            // ---- step 2k+2
-            finalize(k - 1);
-            GNERF_STAMP(st, 8);         // merge + final march
-            output(k - 2);
-            GNERF_STAMP(st, 9);         // outputs
-            GNERF_STAMP(st, 5);         // rounding
-            __syncthreads();
-            GNERF_STAMP(st, 6);         // barrier wait, even step
-            // ---- step 2k+3
             propose_issue(k + 2);
             importance(k + 1);
             GNERF_STAMP(st, 11);        // coarse march + importance
@@ -885,7 +774,6 @@ __device__ __forceinline__ void render_pipe_body(const Params& P, float* smem, c
             GNERF_STAMP(st, 7);         // barrier wait, odd step
         }
     }
-#endif
 #ifdef GNERF_STAMPS
     if (lane == 0 && p.debug) {
         unsigned long long* out = reinterpret_cast<unsigned long long*>(p.debug) + (size_t(blockIdx.x) * 4 + wv) * 16;
@@ -904,10 +792,12 @@ __device__ __forceinline__ void render_pipe_body(const Params& P, float* smem, c
     if (wv == 3 && lane == 0) range.flush(P);
 }
 
+// GNERF_MLP_AUTO: every workgroup evaluates the (cheap, deterministic) range bounds itself -- choose_mlp in render.hip -- and runs
+// the body of the arithmetic they allow: one launch, no select kernel, no second grid that returns at once.
 template <int TP, int MLP, bool FULL, bool GEN = false>
 __global__ __launch_bounds__(kPipeThreads, TP == 1 ? GNERF_PIPE_WAVES_PER_SIMD : (TP == 2 ? GNERF_PIPE2_WAVES_PER_SIMD : 2)) void render_kernel_pipe(Params P) {
     extern __shared__ __align__(16) float smem[];
-    if constexpr (MLP == kMlpAuto) {            // see render_kernel_coop
+    if constexpr (MLP == kMlpAuto) {
         bool sp_direct;
         if (choose_mlp(P, smem, &sp_direct) == kMlpF32) render_pipe_body<TP, kMlpF32, FULL, GEN>(P, smem);
         else                                           render_pipe_body<TP, kMlpF16x3, FULL, GEN>(P, smem, nullptr, nullptr, sp_direct);

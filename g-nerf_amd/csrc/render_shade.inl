@@ -1,48 +1,35 @@
-// Cooperative render kernel: THREE WAVES PER RAY.  Included by render.hip (inside its anonymous namespace).
+// The 16-sample shade tile of the pipelined forward kernel (render_pipe.inl), with the decoder staging and plane taps it shares with
+// the backward (render_bwd.inl).  Included by render.hip (inside its anonymous namespace).
 //
 // The one-wave-per-ray kernel (render_kernel_generic) is limited by what one wave must keep: ~100 VGPRs of
 // decoder weights plus 12 KiB of LDS for the colours of the 96 samples of its ray, which caps a CU at 8 waves,
 // and its instruction stream repeats the same tap-address arithmetic in all 8 lanes that share a sample.
-// Here a 192-lane workgroup owns one ray at a time and each wave shades every third 16-sample tile:
+// A shade tile is one wave's 16 samples of a ray:
 //   * colours stay in REGISTERS (8 per tile per lane) until the final weights are known -- no LDS spill;
 //   * decoder weights live once per workgroup in LDS (padded rows, ds_read_b128 fragments right before the
-//     MFMAs that use them), so a wave needs < 128 VGPRs and a CU holds 12-15 waves;
+//     MFMAs that use them);
 //   * bilinear tap addresses and weights are computed ONCE per (sample, plane) -- 48 lanes of a wave do the
 //     3 planes of 16 samples -- and handed to the 8 lanes that read a texel through a 96-byte LDS record;
 //   * plane texels are addressed as SGPR base + 32-bit VGPR offset (no 64-bit address arithmetic).
-// Per-sample scalars and the merge work exactly as in the generic kernel, spread over the 192 lanes.
-// Instantiated for <= 1 or 2 tiles per wave and pass (48+48 and 96+96 samples); anything else uses the
-// generic kernel.
 
-constexpr int kCoopWaves = 3;
-constexpr int kCoopThreads = 64 * kCoopWaves;
 constexpr int kW1Pitch = 36;        // floats per LDS row of W1 [64 x 32]
 constexpr int kW2Pitch = 68;        // floats per LDS row of W2 [33 x 64]
 constexpr int kTapDwords = 24;      // per sample: 3 planes x (4 byte offsets + 4 weights)
-// LDS layout knobs of the forward shade tile (tools/build_variants.sh D:GNERF_TAP_STRIDE=.. / D:GNERF_STAGE_SWZ=..):
+// LDS layout of the forward shade tile:
 //  * record stride in dwords.  ds_write_b128 is serviced in groups of 8 consecutive lanes on 32 banks: the 8 samples of a group
 //    write 16 bytes each at j * stride, conflict-free when stride / 4 is odd (28: yes, 24: 2-way).  The 8 lanes that read a record
 //    share an address; a ds_read_b128 group (16 lanes, 64 banks) sees 4 distinct records: b * stride / 4 mod 16 distinct for b = 0..3.
 //  * staging rows: pitch 32 with the 16-byte chunk index XORed by ((row >> 1) & 5) makes both the 8-lane row writes and the
 //    (sample j, k-group g) reads of the MFMA operand conflict-free; the round-1 layout (pitch 36, no swizzle) has 2-way conflicts in
 //    two of the sixteen slots of every read group.
-// Round 5 defaults: stride 28, swizzled rows, the lookup window pinned plane by plane (GNERF_LOOKUP_ROLL, see coop_shade_tile).
-// Counters at config 2 (profiles/r05_lds_attribution.json): SQ_LDS_BANK_CONFLICT 12.10 M -> 4.24 M per launch, of which 4.23 M are
-// the scalar wave's (a build without the shade tile shows them alone): conflicts / LDS-active 0.33 -> 0.12.  The round-4 layout is
-// -DGNERF_TAP_STRIDE=24 -DGNERF_STAGE_SWZ=0 -DGNERF_LOOKUP_ROLL=0.
-#ifndef GNERF_TAP_STRIDE
-#define GNERF_TAP_STRIDE 28
-#endif
-#ifndef GNERF_STAGE_SWZ
-#define GNERF_STAGE_SWZ 1
-#endif
-#ifndef GNERF_LOOKUP_ROLL
-#define GNERF_LOOKUP_ROLL 4
-#endif
-constexpr int kFwdTapStride = GNERF_TAP_STRIDE;
-constexpr int kFwdStagePitch = GNERF_STAGE_SWZ ? 32 : kStagePitch;
+// Round 5: stride 28, swizzled rows, the lookup window pinned plane by plane (see shade_tile) in place of the round-4 layout (stride
+// 24, pitch-36 rows, unpinned window).  Counters at config 2 (profiles/r05_lds_attribution.json): SQ_LDS_BANK_CONFLICT 12.10 M ->
+// 4.24 M per launch, of which 4.23 M are the scalar wave's (a build without the shade tile shows them alone): conflicts / LDS-active
+// 0.33 -> 0.12.
+constexpr int kFwdTapStride = 28;
+constexpr int kFwdStagePitch = 32;
 static_assert(kFwdTapStride >= 24 && kFwdTapStride <= kStagePitch && kFwdTapStride % 4 == 0, "tap records live in the staging rows");
-__device__ __forceinline__ int stage_swz(int row) { return GNERF_STAGE_SWZ ? ((row >> 1) & 5) : 0; }
+__device__ __forceinline__ int stage_swz(int row) { return (row >> 1) & 5; }
 
 // Decoder weights in LDS.  Two formats, BOTH shipped (template parameter MLP of the kernels; chosen per call, see
 // choose_mlp in render.hip):
@@ -103,21 +90,14 @@ __host__ __device__ constexpr int weight_floats(int mlp) {
     return mlp == kMlpF32 ? kWeightFloatsF32 : (mlp == kMlpF16x3 ? kWeightFloatsF16 : (kWeightFloatsF32 > kWeightFloatsF16 ? kWeightFloatsF32 : kWeightFloatsF16));
 }
 
-struct CoopLds {
+struct ShadeLds {
     float* w1; float* w2; float* b1; float* b2;
     float* b2c;      // f16x3 decoder: [32][4] the colour biases, each four times -- layer 2's accumulator initialisation is then two ds_read_b128
                      // per tile instead of a two-word read and eight v_mov_b32 (round 6)
-    float* t_e; float* sig_e; float* v_e; int* rank_e; float* s_t; float* s_sig; float* w_s; float* cdf;
     float* taps;     // [waves][16][24]           wave w's records at taps + w * wave_pitch_taps
     float* stage;    // [waves][16][kStagePitch]  wave w's rows at stage + w * wave_pitch_stage
     int wave_pitch_taps, wave_pitch_stage;     // (the pipelined kernel lays the two over each other: see render_pipe_body)
-    float* part;     // [waves][32] colour partial sums, then [4] ray scalars
 };
-
-__host__ __device__ inline size_t coop_lds_floats(int s_pad, int mlp) {
-    return size_t(weight_floats(mlp)) + 64 + 36 + size_t(8) * s_pad +
-           kCoopWaves * 16 * kFwdTapStride + kCoopWaves * 16 * kStagePitch + kCoopWaves * 32 + 4;
-}
 
 #ifdef GNERF_ABLATE_MFMA         // timing-only build: one FMA per lane instead of a matrix instruction
 #define GNERF_MFMA(a, b, c) ((c) + (a) * (b))
@@ -162,9 +142,6 @@ __device__ __forceinline__ float sigmoid_rgb_hw(float x) {      // sigmoid(x) * 
 // Byte addressing of a texel: y * row_pitch + x * tex_pitch + plane offset (Params::tex_pitch / row_pitch / plane_pitch):
 // [3N,H,W,32] planes have tex_pitch 128, plane offset pl * H * W * 128; the interleaved [N,H,W,96] form (channels_last of the
 // backbone's [N,96,H,W] output) has tex_pitch 384, plane offset pl * 128.  Pitches and coordinates are < 2^24: 24-bit multiplies.
-#ifndef GNERF_TAPS_LEAN
-#define GNERF_TAPS_LEAN 1
-#endif
 __device__ __forceinline__ void plane_taps(int H, int W, float u, float v, unsigned tex_pitch, unsigned row_pitch, unsigned plane_bytes_off, uint4& off, v4f& wgt) {
     float ix = ((u + 1.f) * float(W) - 1.f) * 0.5f;
     float iy = ((v + 1.f) * float(H) - 1.f) * 0.5f;
@@ -173,7 +150,6 @@ __device__ __forceinline__ void plane_taps(int H, int W, float u, float v, unsig
     const float x0f = floorf(ix), y0f = floorf(iy);
     const float fx = ix - x0f, fy = iy - y0f;
     const int x0 = int(x0f), y0 = int(y0f), x1 = x0 + 1, y1 = y0 + 1;
-#if GNERF_TAPS_LEAN
     // round 6, same values from fewer instructions: "0 <= x < W" is ONE unsigned compare (a negative index is a huge unsigned one; the
     // compiler cannot make that step itself, it does not know W > 0), and the clamp to the last texel one v_med3_i32 instead of
     // v_max_i32 + v_min_i32 (it only folds the pair when both bounds are constants): 8 compares + 4 mask ands + 8 min / max -> 4 + 0 + 4
@@ -185,13 +161,6 @@ __device__ __forceinline__ void plane_taps(int H, int W, float u, float v, unsig
     const unsigned cx0 = __umul24(unsigned(clamp0(x0, W - 1)), tex_pitch), cx1 = __umul24(unsigned(clamp0(x1, W - 1)), tex_pitch);
     const unsigned cy0 = __umul24(unsigned(clamp0(y0, H - 1)), row_pitch) + plane_bytes_off;
     const unsigned cy1 = __umul24(unsigned(clamp0(y1, H - 1)), row_pitch) + plane_bytes_off;
-#else
-    const float wx0 = (x0 >= 0 && x0 < W) ? 1.f - fx : 0.f, wx1 = (x1 >= 0 && x1 < W) ? fx : 0.f;
-    const float wy0 = (y0 >= 0 && y0 < H) ? (1.f - fy) * (1.f / 3.f) : 0.f, wy1 = (y1 >= 0 && y1 < H) ? fy * (1.f / 3.f) : 0.f;
-    const unsigned cx0 = __umul24(unsigned(min(max(x0, 0), W - 1)), tex_pitch), cx1 = __umul24(unsigned(min(max(x1, 0), W - 1)), tex_pitch);
-    const unsigned cy0 = __umul24(unsigned(min(max(y0, 0), H - 1)), row_pitch) + plane_bytes_off;
-    const unsigned cy1 = __umul24(unsigned(min(max(y1, 0), H - 1)), row_pitch) + plane_bytes_off;
-#endif
     off = make_uint4(cy0 + cx0, cy0 + cx1, cy1 + cx0, cy1 + cx1);
     wgt = (v4f){wx0 * wy0, wx1 * wy0, wx0 * wy1, wx1 * wy1};
 }
@@ -220,7 +189,7 @@ struct Stamps { __device__ __forceinline__ void reset() {} };
 
 // Copy the decoder into LDS (all threads of the workgroup; a barrier must follow).  base = start of the weight area.
 template <int MLP>
-__device__ __forceinline__ void stage_decoder(CoopLds& L, float* base, const gnerf_render_params& p, int tid, int nthreads) {
+__device__ __forceinline__ void stage_decoder(ShadeLds& L, float* base, const gnerf_render_params& p, int tid, int nthreads) {
     L.w1 = base;
     L.b1 = base + weight_floats(MLP);
     L.b2 = L.b1 + 64;
@@ -289,25 +258,20 @@ __device__ __forceinline__ float row_total(float v) {
 
 // Round 6: a lane of the tap set-up (sample j, plane pl = lane >> 4) needs two coordinates of the point, u = (ou + t du) s and
 // v = (ov + t dv) s with (u, v) = (x, y), (x, z), (z, x) for planes 0, 1, 2 (renderer.py:23-53).  It used to form all three of
-// x, y, z and pick two with three v_cndmask per tile; now the ray arrives as the lane's own (ou, du, ov, dv) -- the cooperative kernel
-// selects once per ray, the pipelined kernels' scalar wave parks the twelve values per plane in the slot and a lane reads its four in
-// one ds_read_b128 (render_pipe.inl: kMiscUV).  Same operations on the same operands: bit-identical.
-struct CoopRay {
+// x, y, z and pick two with three v_cndmask per tile; now the ray arrives as the lane's own (ou, du, ov, dv) -- the pipelined kernels'
+// scalar wave parks the twelve values per plane in the slot and a lane reads its four in one ds_read_b128 (render_pipe.inl: kMiscUV).
+// Same operations on the same operands: bit-identical.
+struct ShadeRay {
     const char* planes_item;    // uniform
     const float* sig_noise = nullptr;   // uniform: this ray's and this pass's density noise (gnerf_render_params.sigma_noise_*), or null
     float ou, du, ov, dv;       // per lane (by plane)
-    __device__ __forceinline__ void set(float ox, float oy, float oz, float dx, float dy, float dz, int lane) {
-        const int pl = lane >> 4;
-        ou = pl == 2 ? oz : ox; du = pl == 2 ? dz : dx;
-        ov = pl == 0 ? oy : (pl == 1 ? oz : ox); dv = pl == 0 ? dy : (pl == 1 ? dz : dx);
-    }
 };
 
 // Shade one 16-sample tile: depths t_list[16*tile ...] (clamped to count-1) -> density into sig_list (if
 // active) and this lane's 8 colour values (channel lane&15 of block n, samples 4*(lane>>4)..+3) into col.
 // The tap records and the staging rows are private to the calling wave, so the two hand-offs inside need
-// only wave-level ordering: BLOCK_SYNC=false uses lds_wave_sync() (s_waitcnt, no s_barrier) and the call may
-// then sit in wave-divergent control flow; BLOCK_SYNC=true keeps workgroup barriers (all waves must call).
+// only wave-level ordering: lds_wave_sync() (s_waitcnt, no s_barrier), and the call may sit in wave-divergent
+// control flow.
 __device__ __forceinline__ void lds_wave_sync() {
     // LDS instructions of one wave execute in order, so a hand-off between lanes of the SAME wave only needs the
     // writes to have been issued before the reads: wait for this wave's LDS queue and stop the compiler from moving
@@ -315,10 +279,10 @@ __device__ __forceinline__ void lds_wave_sync() {
     // load/store in flight (vmcnt(0)), serialising the scalar wave's prefetches and output stores.
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
 }
-template <bool BLOCK_SYNC, int MLP>
-__device__ __forceinline__ void coop_shade_tile(const Params& P, const CoopLds& L, const CoopRay& R, const float* t_list, int count,
-                                                int tile, bool active, float* sig_list, int lane, int wv, v4f (&col)[2], Stamps& st, bool sp_direct = false,
-                                                bool have_depth = false, float depth_in = 0.f) {
+template <int MLP>
+__device__ __forceinline__ void shade_tile(const Params& P, const ShadeLds& L, const ShadeRay& R, const float* t_list, int count,
+                                           int tile, bool active, float* sig_list, int lane, int wv, v4f (&col)[2], Stamps& st, bool sp_direct = false,
+                                           bool have_depth = false, float depth_in = 0.f) {
 #ifdef GNERF_ABLATE_SHADE       // timing-only build: no lookups, no MLP
     if (active && lane < 16 && 16 * tile + lane < count) sig_list[16 * tile + lane] = t_list[16 * tile + lane] - 2.7f;
     col[0] = (v4f){0.1f, 0.2f, 0.3f, 0.4f}; col[1] = col[0];
@@ -332,7 +296,7 @@ __device__ __forceinline__ void coop_shade_tile(const Params& P, const CoopLds& 
         const int j = lane & 15, pl = lane >> 4;
         const int idx = min(16 * tile + j, count - 1);
         const float depth = have_depth ? depth_in : t_list[idx];       // (the pipelined kernels fetch it with the ray's parameters, one round trip)
-        // plane 0 (x,y), 1 (x,z), 2 (z,x): see CoopRay.  The roundings are the ones this code has always had -- o + t d as one fused
+        // plane 0 (x,y), 1 (x,z), 2 (z,x): see ShadeRay.  The roundings are the ones this code has always had -- o + t d as one fused
         // operation, the box scale as a multiply of its own -- pinned: with the per-plane select gone, fp contraction would otherwise
         // merge the scale into plane_taps' `u + 1` (an empty asm is opaque to it and costs nothing)
         float u = __builtin_fmaf(depth, R.du, R.ou) * P.box_scale;
@@ -344,7 +308,7 @@ __device__ __forceinline__ void coop_shade_tile(const Params& P, const CoopLds& 
         *reinterpret_cast<uint4*>(rec) = off;
         *reinterpret_cast<v4f*>(rec + 4) = wgt;
     }
-    if (BLOCK_SYNC) __syncthreads(); else lds_wave_sync();
+    lds_wave_sync();
     GNERF_STAMP(st, 1);         // tap setup
     // ---- lookup: 8 lanes per texel, 8 samples per step
     const int b = lane >> 3, cq16 = (lane & 7) * 16;
@@ -353,27 +317,6 @@ __device__ __forceinline__ void coop_shade_tile(const Params& P, const CoopLds& 
     // round trip overlaps the first instead of following it.  Measured alternatives (tools/ablate.py, config 2): all 24
     // in flight (96 VGPRs) halves the lookup time but costs a wave per SIMD and is slower overall; one step after the
     // other (the previous default) exposes two full round trips.
-    uint4 off[2][3];
-    v4f wgt[2][3], tex[2][3][4];
-    auto read_records = [&](int a) {
-        const float* rec = taps + (8 * a + b) * kFwdTapStride;
-#pragma unroll
-        for (int pl = 0; pl < 3; pl++) {
-            off[a][pl] = *reinterpret_cast<const uint4*>(rec + pl * 8);
-            wgt[a][pl] = *reinterpret_cast<const v4f*>(rec + pl * 8 + 4);
-        }
-    };
-    auto issue = [&](int a, int pl) {
-#ifdef GNERF_ABLATE_GATHER      // timing-only build: no texel loads (outputs are wrong)
-        tex[a][pl][0] = (v4f){float(off[a][pl].x + cq16), 1.f, 2.f, 3.f}; tex[a][pl][1] = (v4f){float(off[a][pl].y), 1.f, 2.f, 3.f};
-        tex[a][pl][2] = (v4f){float(off[a][pl].z), 1.f, 2.f, 3.f};        tex[a][pl][3] = (v4f){float(off[a][pl].w), 1.f, 2.f, 3.f};
-#else
-        tex[a][pl][0] = *reinterpret_cast<const v4f*>(R.planes_item + (off[a][pl].x + cq16));
-        tex[a][pl][1] = *reinterpret_cast<const v4f*>(R.planes_item + (off[a][pl].y + cq16));
-        tex[a][pl][2] = *reinterpret_cast<const v4f*>(R.planes_item + (off[a][pl].z + cq16));
-        tex[a][pl][3] = *reinterpret_cast<const v4f*>(R.planes_item + (off[a][pl].w + cq16));
-#endif
-    };
     // One fused multiply-add per tap, chained through the sample's 12 taps (the first tap of the first plane starts the accumulator).
     // History: round 1 had this form and dropped it -- with hipcc 7.2's code for it (v_pk_fma_f32 chains whose weight operand is the
     // high register of a pair, selected on src1) lanes 48-63 of ~3 % of the rays differed from run to run; round 3's inline-asm op_sel
@@ -381,34 +324,9 @@ __device__ __forceinline__ void coop_shade_tile(const Params& P, const CoopLds& 
     // then while another wave of the SIMD runs v_mfma_f32_16x16x32_f16); with the build exchanging the sources of every such
     // instruction (2 550 of them in this form) the chain is bit-stable (tools/determinism.py: 0 of 10 x 65 536 rays) and 1 % faster
     // than four products summed per plane (24 instead of 28 packed instructions per sample pair).
-    auto blend = [&](int a, int pl, v4f& acc) {
-        auto bc = [](float w) { return (v4f){w, w, w, w}; };
-        acc = pl == 0 ? tex[a][pl][0] * wgt[a][pl][0] : __builtin_elementwise_fma(tex[a][pl][0], bc(wgt[a][pl][0]), acc);
-        acc = __builtin_elementwise_fma(tex[a][pl][1], bc(wgt[a][pl][1]), acc);
-        acc = __builtin_elementwise_fma(tex[a][pl][2], bc(wgt[a][pl][2]), acc);
-        acc = __builtin_elementwise_fma(tex[a][pl][3], bc(wgt[a][pl][3]), acc);
-    };
-    (void)read_records; (void)issue; (void)blend;       // (the pinned orders below fetch records where they are needed)
     v4f acc0, acc1;
     float* const row0 = stage + b * kFwdStagePitch + (((lane & 7) ^ stage_swz(b)) * 4);
     float* const row1 = stage + (8 + b) * kFwdStagePitch + (((lane & 7) ^ stage_swz(8 + b)) * 4);
-#if GNERF_LOOKUP_ROLL == 0
-    read_records(0);
-    issue(0, 0); issue(0, 1); issue(0, 2);
-    read_records(1);
-    __builtin_amdgcn_sched_barrier(0);
-    blend(0, 0, acc0); issue(1, 0);
-    __builtin_amdgcn_sched_barrier(0);
-    blend(0, 1, acc0); issue(1, 1);
-    __builtin_amdgcn_sched_barrier(0);
-    blend(0, 2, acc0); issue(1, 2);
-    __builtin_amdgcn_sched_barrier(0);
-    // (the staging rows stay [sample][kStagePitch]: 2-way conflicts on the writes and on the reads; fragment order for the reads makes
-    //  the writes 8-way -- 8 lanes of a sample land on one bank group -- and was 3 % slower overall)
-    *reinterpret_cast<v4f*>(row0) = acc0;
-    blend(1, 0, acc1); blend(1, 1, acc1); blend(1, 2, acc1);
-    *reinterpret_cast<v4f*>(row1) = acc1;
-#else
     // The rolling window, PINNED.  __builtin_amdgcn_sched_barrier only stops the machine scheduler: the blends are pure arithmetic
     // with no chain to it, and instruction selection linearised all of step 0's blends in front of the first barrier -- the emitted
     // stream was 12 loads, 12 waits + blends, 12 loads, 12 waits + blends: two exposed round trips per tile.  An empty asm that takes
@@ -437,9 +355,8 @@ __device__ __forceinline__ void coop_shade_tile(const Params& P, const CoopLds& 
         w0[pl] = *reinterpret_cast<const v4f*>(rec0 + pl * 8 + 4);
     }
 #pragma unroll
-    for (int pl = 0; pl < 3; pl++) {
+    for (int pl = 0; pl < 3; pl++) {            // a plane's four taps at a time
         const uint4 o1 = *reinterpret_cast<const uint4*>(rec1 + pl * 8);
-#if GNERF_LOOKUP_ROLL == 4          // a plane's four taps at a time
         acc0 = pl == 0 ? win[pl][0] * w0[pl][0] : __builtin_elementwise_fma(win[pl][0], bc(w0[pl][0]), acc0);
         acc0 = __builtin_elementwise_fma(win[pl][1], bc(w0[pl][1]), acc0);
         acc0 = __builtin_elementwise_fma(win[pl][2], bc(w0[pl][2]), acc0);
@@ -447,16 +364,6 @@ __device__ __forceinline__ void coop_shade_tile(const Params& P, const CoopLds& 
         pin(acc0);
         load4(win[pl], o1);
         pin(acc0);
-#else                               // tap by tap: a load of step 1 leaves as soon as the same tap of step 0 has been consumed
-#pragma unroll
-        for (int t = 0; t < 4; t++) {
-            acc0 = (pl == 0 && t == 0) ? win[pl][t] * w0[pl][t] : __builtin_elementwise_fma(win[pl][t], bc(w0[pl][t]), acc0);
-            pin(acc0);
-            const unsigned ot = t == 0 ? o1.x : (t == 1 ? o1.y : (t == 2 ? o1.z : o1.w));
-            win[pl][t] = *reinterpret_cast<const v4f*>(R.planes_item + (ot + cq16));
-            pin(acc0);
-        }
-#endif
     }
     // (the records share their LDS with the staging rows: step 1's weights leave it BEFORE the first row is written over them)
     v4f w1[3];
@@ -472,8 +379,7 @@ __device__ __forceinline__ void coop_shade_tile(const Params& P, const CoopLds& 
         acc1 = __builtin_elementwise_fma(win[pl][3], bc(w1[pl][3]), acc1);
     }
     *reinterpret_cast<v4f*>(row1) = acc1;
-#endif
-    if (BLOCK_SYNC) __syncthreads(); else lds_wave_sync();
+    lds_wave_sync();
     GNERF_STAMP(st, 2);         // lookups (tap records, texel loads, blend, staging)
     const int j = lane & 15, g = lane >> 4;
     const v4f f_lo = *reinterpret_cast<const v4f*>(stage + j * kFwdStagePitch + (((2 * g) ^ stage_swz(j)) * 4));
@@ -675,300 +581,4 @@ __device__ __forceinline__ void coop_shade_tile(const Params& P, const CoopLds& 
     asm volatile("" :: "v"(col[0][0]), "v"(col[1][3]));
 #endif
     GNERF_STAMP(st, 4);         // activations + layer 2
-}
-
-template <int TC1, int TF1, int MLP>
-__device__ __forceinline__ void render_coop_body(const Params& P, float* smem, bool sp_direct = false) {
-    const gnerf_render_params& p = P.p;
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int S = p.depth_resolution, F = p.depth_resolution_importance;
-    const int s_pad = 16 * (P.tiles_c + P.tiles_f);
-    CoopLds L;
-    L.t_e = smem + weight_floats(MLP) + 64 + 36;
-    L.sig_e = L.t_e + s_pad;
-    L.v_e = L.sig_e + s_pad;
-    L.rank_e = reinterpret_cast<int*>(L.v_e + s_pad);
-    L.s_t = L.v_e + 2 * s_pad;
-    L.s_sig = L.s_t + s_pad;
-    L.w_s = L.s_sig + s_pad;
-    L.cdf = L.w_s + s_pad;
-    L.taps = L.cdf + s_pad;
-    L.stage = L.taps + kCoopWaves * 16 * kFwdTapStride;
-    L.wave_pitch_taps = 16 * kFwdTapStride; L.wave_pitch_stage = 16 * kStagePitch;
-    L.part = L.stage + kCoopWaves * 16 * kStagePitch;
-
-    const int n_groups = P.n_tiles << P.split_shift;
-    const int per_xcd = (n_groups + kNumXCD - 1) / kNumXCD;
-    const int group = (blockIdx.x % kNumXCD) * per_xcd + blockIdx.x / kNumXCD;
-    const int tile_id = group >> P.split_shift;
-    const int rr_count = group < n_groups ? (kRaysPerWave >> P.split_shift) : 0;        // surplus workgroups of the rounded-up grid only report in
-    const int rr_first = (group & ((1 << P.split_shift) - 1)) * (kRaysPerWave >> P.split_shift);
-
-    // decoder -> LDS (padded rows), once per workgroup
-    stage_decoder<MLP>(L, smem, p, tid, kCoopThreads);
-
-    const int fine_e0 = 16 * P.tiles_c;
-    const int n_all = S + F;
-    DepthRange range;
-    Stamps st;
-    st.reset();
-
-    for (int rr = rr_first; rr < rr_first + rr_count; rr++) {
-        int64_t ray;
-        if (P.tiles_per_item > 0) {
-            const int item = tile_id / P.tiles_per_item, tt = tile_id % P.tiles_per_item;
-            const int tx = tt / P.tiles_y, ty = tt % P.tiles_y;
-            ray = int64_t(item) * p.rays_per_item + int64_t(ty * 4 + (rr >> 2)) * p.image_width + tx * 4 + (rr & 3);
-        } else {
-            ray = int64_t(tile_id) * kRaysPerWave + rr;
-            if (ray >= P.total_rays) break;
-        }
-        const int item = int(ray / p.rays_per_item);
-        CoopRay R;
-        R.planes_item = reinterpret_cast<const char*>(p.planes_nhwc) + int64_t(item) * P.item_bytes;
-        R.set(p.ray_origins[ray * 3 + 0], p.ray_origins[ray * 3 + 1], p.ray_origins[ray * 3 + 2],
-              p.ray_dirs[ray * 3 + 0], p.ray_dirs[ray * 3 + 1], p.ray_dirs[ray * 3 + 2], lane);
-        float* dbg = p.debug ? p.debug + ray * GNERF_DEBUG_SLOTS * n_all : nullptr;
-
-        // ---- stratified depth proposals (renderer.py:169-192)
-        for (int k = tid; k < S; k += kCoopThreads) {
-            const float u = p.noise_coarse[ray * S + k];
-            float d;
-            if (p.disparity_space_sampling) {
-                const float step = 1.0f / float(S - 1);
-                const float lin = (k < S / 2) ? __fmul_rn(step, float(k)) : __fsub_rn(1.0f, __fmul_rn(step, float(S - 1 - k)));
-                const float q = __fadd_rn(lin, __fmul_rn(u, P.disp_delta));
-                d = __fdiv_rn(1.0f, __fadd_rn(__fmul_rn(P.inv_start, __fsub_rn(1.0f, q)), __fmul_rn(P.inv_end, q)));
-            } else if (p.ray_start_per_ray) {
-                const float rs = p.ray_start_per_ray[ray], re = p.ray_end_per_ray[ray];
-                const float span = __fsub_rn(re, rs);
-                const float lin = __fadd_rn(rs, __fmul_rn(__fdiv_rn(float(k), float(S - 1)), span));
-                d = __fadd_rn(lin, __fmul_rn(u, __fdiv_rn(span, float(S - 1))));
-            } else {
-                const float step = __fdiv_rn(__fsub_rn(p.ray_end, p.ray_start), float(S - 1));
-                const float lin = (k < S / 2) ? __fadd_rn(p.ray_start, __fmul_rn(step, float(k)))
-                                              : __fsub_rn(p.ray_end, __fmul_rn(step, float(S - 1 - k)));
-                d = __fadd_rn(lin, __fmul_rn(u, P.delta));
-            }
-            L.t_e[k] = d;
-            if (dbg) dbg[GNERF_DBG_DEPTH_COARSE * n_all + k] = d;
-        }
-        for (int k = tid; k < s_pad; k += kCoopThreads) {
-            L.v_e[k] = 0.f;
-            if ((k >= S && k < fine_e0) || k >= fine_e0 + F) L.t_e[k] = INFINITY;      // tile padding sorts last
-        }
-        __syncthreads();
-
-        // ---- coarse pass: wave wv shades tiles wv, wv+3, ...
-        v4f col_c[TC1][2], col_f[TF1 > 0 ? TF1 : 1][2];
-#pragma unroll
-        for (int i = 0; i < TC1; i++) {
-            const int t = wv + kCoopWaves * i;
-            R.sig_noise = p.sigma_noise_coarse ? p.sigma_noise_coarse + ray * S : nullptr;
-            coop_shade_tile<true, MLP>(P, L, R, L.t_e, S, t, t < P.tiles_c, L.sig_e, lane, wv, col_c[i], st, sp_direct);
-        }
-        __syncthreads();
-        if (dbg) for (int k = tid; k < S; k += kCoopThreads) dbg[GNERF_DBG_SIGMA_COARSE * n_all + k] = L.sig_e[k];
-
-        float w_sum = 0.f, wt_sum = 0.f;
-        if (TF1 > 0 && F > 0) {
-            const int n_w = S - 3;
-            if (wv == 0) {
-                march(L.t_e, L.sig_e, L.w_s, S, lane, w_sum, wt_sum);
-                // wave-local hand-off of w_s (LDS ops of one wave execute in order; stop the compiler reordering)
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-                __builtin_amdgcn_wave_barrier();
-                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-                float part = 0.f;
-                for (int i = lane; i < n_w; i += 64) {
-                    const float w0 = L.w_s[i], w1 = L.w_s[i + 1], w2 = L.w_s[i + 2];
-                    const float pw = ((fmaxf(w0, w1) + fmaxf(w1, w2)) * 0.5f + 0.01f) + 1e-5f;
-                    L.s_sig[i] = pw;
-                    part += pw;
-                }
-                const float inv_total = __builtin_amdgcn_rcpf(wave_sum(part));
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-                __builtin_amdgcn_wave_barrier();
-                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-                float carry = 0.f;
-                for (int base = 0; base < n_w; base += 64) {
-                    const int i = base + lane;
-                    const float pdf = (i < n_w) ? L.s_sig[i] * inv_total : 0.f;
-                    const float incl = wave_scan_add(pdf, lane) + carry;
-                    if (i < n_w) L.cdf[i + 1] = incl;
-                    carry = wave_last(incl);
-                }
-                if (lane == 0) L.cdf[0] = 0.f;
-            }
-            __syncthreads();
-            if (dbg) for (int k = tid; k < S - 1; k += kCoopThreads) dbg[GNERF_DBG_WEIGHT_COARSE * n_all + k] = L.w_s[k];
-            for (int i = tid; i < F; i += kCoopThreads) {
-                const float u = p.noise_fine[ray * F + i];
-                int lo = 0, hi = n_w + 1;
-                while (lo < hi) { const int mid = (lo + hi) >> 1; if (L.cdf[mid] <= u) lo = mid + 1; else hi = mid; }
-                const int below = max(lo - 1, 0), above = min(lo, n_w);
-                const float cb = L.cdf[below], ca = L.cdf[above];
-                const float bb = (L.t_e[below] + L.t_e[below + 1]) * 0.5f;
-                const float ba = (L.t_e[above] + L.t_e[above + 1]) * 0.5f;
-                float denom = ca - cb;
-                if (denom < 1e-5f) denom = 1.f;
-                const float d = bb + (u - cb) * __builtin_amdgcn_rcpf(denom) * (ba - bb);
-                L.t_e[fine_e0 + i] = d;
-                if (dbg) dbg[GNERF_DBG_DEPTH_FINE * n_all + i] = d;
-            }
-            __syncthreads();
-
-            // ---- fine pass
-#pragma unroll
-            for (int i = 0; i < TF1; i++) {
-                const int t = wv + kCoopWaves * i;
-                R.sig_noise = p.sigma_noise_fine ? p.sigma_noise_fine + ray * F : nullptr;
-                coop_shade_tile<true, MLP>(P, L, R, L.t_e + fine_e0, F, t, t < P.tiles_f, L.sig_e + fine_e0, lane, wv, col_f[i], st, sp_direct);
-            }
-            __syncthreads();
-            if (dbg) for (int k = tid; k < F; k += kCoopThreads) dbg[GNERF_DBG_SIGMA_FINE * n_all + k] = L.sig_e[fine_e0 + k];
-
-            // ---- merge by depth (renderer.py:157-167) = stable rank of every element of cat([coarse, fine]).
-            // Coarse depths ascend by construction (lin_k + u*delta with u < 1) up to rounding, so a coarse sample's rank is
-            // k + #(fine before it) and a fine sample's is #(coarse <= it) [binary search] + #(fine before it).
-            // Wave 0 ranks the fine samples, wave 1 the coarse ones; both count over the fine keys, read four at
-            // a time as LDS broadcasts.  Ties: coarse before fine, lower index first (what a stable sort gives).
-#ifdef GNERF_ABLATE_RANK
-            for (int q = tid; q < n_all; q += kCoopThreads) { const int e = q < S ? q : fine_e0 + (q - S); L.rank_e[e] = q; L.s_t[q] = L.t_e[e]; L.s_sig[q] = L.sig_e[e]; }
-#else
-            if (wv == 0) {
-                for (int i = lane; i < F; i += 64) {
-                    const float key = L.t_e[fine_e0 + i];
-                    int cnt = 0;
-                    for (int o2 = 0; o2 < 16 * P.tiles_f; o2 += 4) {
-                        const v4f k4 = *reinterpret_cast<const v4f*>(L.t_e + fine_e0 + o2);
-#pragma unroll
-                        for (int c2 = 0; c2 < 4; c2++) cnt += (k4[c2] < key || (k4[c2] == key && o2 + c2 < i)) ? 1 : 0;
-                    }
-                    int lo = 0, hi = S;                                  // number of coarse depths <= key
-                    while (lo < hi) { const int mid = (lo + hi) >> 1; if (L.t_e[mid] <= key) lo = mid + 1; else hi = mid; }
-                    // neighbouring coarse depths can be swapped by one ulp (see below), which can put the search off by
-                    // one: recount exactly in a window of four around its answer
-                    const int w0 = max(lo - 2, 0), w1 = min(lo + 2, S);
-                    lo = w0;
-                    for (int q = w0; q < w1; q++) lo += (L.t_e[q] <= key) ? 1 : 0;
-                    const int rank = cnt + lo;
-                    L.rank_e[fine_e0 + i] = rank;
-                    L.s_t[rank] = key;
-                    L.s_sig[rank] = L.sig_e[fine_e0 + i];
-                }
-            } else if (wv == 1) {
-                for (int k = lane; k < S; k += 64) {
-                    const float key = L.t_e[k];
-                    int cnt = 0;
-                    for (int o2 = 0; o2 < 16 * P.tiles_f; o2 += 4) {
-                        const v4f k4 = *reinterpret_cast<const v4f*>(L.t_e + fine_e0 + o2);
-#pragma unroll
-                        for (int c2 = 0; c2 < 4; c2++) cnt += (k4[c2] < key) ? 1 : 0;
-                    }
-                    // t_k = lin_k + u delta can round one ulp past t_{k+1} when u is within ~1e-5 of 1; only neighbours can
-                    // swap (the grid step is ~1e5 ulps), so the coarse samples sorted before k number k, k+1 or k-1
-                    if (k + 1 < S && L.t_e[k + 1] < key) cnt += 1;
-                    if (k > 0 && L.t_e[k - 1] > key) cnt -= 1;
-                    const int rank = k + cnt;
-                    L.rank_e[k] = rank;
-                    L.s_t[rank] = key;
-                    L.s_sig[rank] = L.sig_e[k];
-                }
-            }
-#endif
-            __syncthreads();
-            if (wv == 0) {
-                march(L.s_t, L.s_sig, L.w_s, n_all, lane, w_sum, wt_sum);
-                if (lane == 0) { L.part[kCoopWaves * 32] = w_sum; range.add(P, item, L.s_t[0], L.s_t[n_all - 1]); }
-            }
-            __syncthreads();
-            for (int q = tid; q < n_all; q += kCoopThreads) {
-                const int e = q < S ? q : fine_e0 + (q - S);
-                const int r = L.rank_e[e];
-                const float wl = r > 0 ? L.w_s[r - 1] : 0.f, wr = r < n_all - 1 ? L.w_s[r] : 0.f;
-                L.v_e[e] = (wl + wr) * 0.5f;
-            }
-            if (dbg) {
-                for (int k = tid; k < n_all; k += kCoopThreads) { dbg[GNERF_DBG_DEPTH_SORTED * n_all + k] = L.s_t[k]; dbg[GNERF_DBG_SIGMA_SORTED * n_all + k] = L.s_sig[k]; }
-                for (int k = tid; k < n_all - 1; k += kCoopThreads) dbg[GNERF_DBG_WEIGHT_FINAL * n_all + k] = L.w_s[k];
-            }
-        } else {
-            if (wv == 0) {
-                march(L.t_e, L.sig_e, L.w_s, S, lane, w_sum, wt_sum);
-                float mn = INFINITY, mx = -INFINITY;
-                for (int k = lane; k < S; k += 64) { mn = fminf(mn, L.t_e[k]); mx = fmaxf(mx, L.t_e[k]); }
-#pragma unroll
-                for (int o2 = 32; o2 > 0; o2 >>= 1) { mn = fminf(mn, __shfl_xor(mn, o2)); mx = fmaxf(mx, __shfl_xor(mx, o2)); }
-                if (lane == 0) { range.add(P, item, mn, mx); L.part[kCoopWaves * 32] = w_sum; }
-            }
-            __syncthreads();
-            for (int k = tid; k < S; k += kCoopThreads) {
-                const float wl = k > 0 ? L.w_s[k - 1] : 0.f, wr = k < S - 1 ? L.w_s[k] : 0.f;
-                L.v_e[k] = (wl + wr) * 0.5f;
-            }
-            if (dbg) for (int k = tid; k < S - 1; k += kCoopThreads) dbg[GNERF_DBG_WEIGHT_FINAL * n_all + k] = L.w_s[k];
-        }
-        __syncthreads();
-
-        // ---- colours: each wave sums its own tiles, partials meet in LDS
-        const int j = lane & 15, g = lane >> 4;
-        float acc[2] = {0.f, 0.f};
-#pragma unroll
-        for (int i = 0; i < TC1; i++) {
-            const int t = wv + kCoopWaves * i;
-            if (t < P.tiles_c) {
-                const v4f v = *reinterpret_cast<const v4f*>(L.v_e + 16 * t + 4 * g);
-#pragma unroll
-                for (int n = 0; n < 2; n++) acc[n] += v[0] * col_c[i][n][0] + v[1] * col_c[i][n][1] + v[2] * col_c[i][n][2] + v[3] * col_c[i][n][3];
-            }
-        }
-        if (TF1 > 0 && F > 0) {
-#pragma unroll
-            for (int i = 0; i < TF1; i++) {
-                const int t = wv + kCoopWaves * i;
-                if (t < P.tiles_f) {
-                    const v4f v = *reinterpret_cast<const v4f*>(L.v_e + fine_e0 + 16 * t + 4 * g);
-#pragma unroll
-                    for (int n = 0; n < 2; n++) acc[n] += v[0] * col_f[i][n][0] + v[1] * col_f[i][n][1] + v[2] * col_f[i][n][2] + v[3] * col_f[i][n][3];
-                }
-            }
-        }
-#pragma unroll
-        for (int n = 0; n < 2; n++) {
-            acc[n] += __shfl_xor(acc[n], 16);
-            acc[n] += __shfl_xor(acc[n], 32);
-        }
-        if (g < 2) L.part[wv * 32 + 16 * g + j] = g == 0 ? acc[0] : acc[1];
-        __syncthreads();
-        if (tid < 32) {
-            float c = L.part[tid] + L.part[32 + tid] + L.part[64 + tid];
-            const float ws = L.part[kCoopWaves * 32];
-            if (p.white_back) c = c + 1.f - ws;
-            p.out_rgb[ray * 32 + tid] = c * 2.f - 1.f;
-        }
-        if (tid == 0) {
-            float depth = wt_sum / w_sum;
-            if (depth != depth) depth = INFINITY;
-            p.out_depth[ray] = depth;
-            p.out_wsum[ray] = w_sum;
-        }
-        __syncthreads();
-    }
-    if (tid == 0) range.flush(P);
-}
-
-// GNERF_MLP_AUTO: every workgroup evaluates the (cheap, deterministic) range bounds itself -- choose_mlp in render.hip -- and runs
-// the body of the arithmetic they allow: one launch, no select kernel, no second grid that returns at once.
-template <int TC1, int TF1, int MLP>
-__global__ __launch_bounds__(kCoopThreads, 3) void render_kernel_coop(Params P) {
-    extern __shared__ __align__(16) float smem[];
-    if constexpr (MLP == kMlpAuto) {
-        bool sp_direct;
-        if (choose_mlp(P, smem, &sp_direct) == kMlpF32) render_coop_body<TC1, TF1, kMlpF32>(P, smem);
-        else                                           render_coop_body<TC1, TF1, kMlpF16x3>(P, smem, sp_direct);
-    } else {
-        render_coop_body<TC1, TF1, MLP>(P, smem);
-    }
 }

@@ -95,7 +95,7 @@ __host__ inline BinArgs bin_carve(char* base, const float* stage, float* grad, i
     return A;
 }
 
-// The bilinear footprint of one (sample, plane): plane_taps' arithmetic (render_coop.inl), kept in the form the records store.
+// The bilinear footprint of one (sample, plane): plane_taps' arithmetic (render_shade.inl), kept in the form the records store.
 struct TapGeom { int x0, y0; float fx, fy; unsigned valid; };            // valid: bit 0 x0, 1 x1, 2 y0, 3 y1 inside the plane
 __device__ __forceinline__ TapGeom tap_geom(int H, int W, float u, float v) {
     float ix = ((u + 1.f) * float(W) - 1.f) * 0.5f;

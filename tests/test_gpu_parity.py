@@ -123,7 +123,7 @@ def test_render_golden_stage_by_stage(dev, golden, case):
     assert float(((rgb.cpu().numpy() - g['out_rgb']) ** 2).mean()) < 1e-8
 
 
-@pytest.mark.parametrize('kernel', ['pipe', 'coop', 'generic'])
+@pytest.mark.parametrize('kernel', ['pipe', 'generic'])
 def test_render_density_noise_in_every_kernel(dev, golden, monkeypatch, kernel):
     """renderer.py:146-147 (`sigma += randn_like(sigma) * density_noise` in run_model) inside the fused kernels (round 6: it used to send a
     GPU call to the PyTorch-op form): the recorded draws of the reference-made fixture through each forward kernel, against the fixture,
@@ -202,7 +202,7 @@ def _random_scene(seed, N, res, S, F, hw, scale=1.5):
     dict(N=1, res=5, S=17, F=30, hw=(9, 11)),               # ragged everything: odd res (linear ray walk), partial MLP tiles
     dict(N=3, res=4, S=64, F=3, hw=(16, 16)),
     dict(N=1, res=4, S=4, F=5, hw=(4, 4)),                  # smallest importance-sampled case (S-3 = 1 pdf bin)
-    dict(N=1, res=4, S=2, F=0, hw=(4, 4)),                  # smallest case at all
+    dict(N=1, res=4, S=2, F=0, hw=(4, 4)),                  # smallest case at all (pipelined kernel, no importance pass)
     dict(N=1, res=4, S=130, F=100, hw=(8, 8)),              # beyond 96+96: three-tiles-per-wave pipelined kernel, ragged tiles
     dict(N=1, res=8, S=128, F=128, hw=(16, 16)),            # gen_videos.py's doubling of the ShapeNet config's 64+64
     dict(N=1, res=4, S=144, F=144, hw=(8, 8)),              # ... its limit
@@ -232,6 +232,26 @@ def test_render_vs_oracle(dev, cfg):
     np.testing.assert_allclose(wsum.cpu().numpy(), ref_w.numpy(), atol=2e-4)
 
 
+@pytest.mark.parametrize('S', [2, 40, 96, 130])
+def test_render_without_importance_pass_on_pipelined_kernel(dev, S, monkeypatch):
+    """F = 0 (renderer.py:116-117: no importance pass) runs on the pipelined kernel, one, two or three tiles per shader wave: forced,
+    the call is accepted and matches the oracle."""
+    import gnerf_hip
+    from oracle import render_ref as R
+    monkeypatch.setenv('GNERF_RENDER_KERNEL', 'pipe')
+    planes, dec, o, d, nc, nf = _random_scene(13, N=2, res=8, S=S, F=0, hw=(24, 20))
+    opts = dict(depth_resolution=S, depth_resolution_importance=0, ray_start=2.25, ray_end=3.3, box_warp=1.0, clamp_mode='softplus')
+    ref_rgb, ref_depth, ref_w = R.render(planes, dec, o, d, opts, nc, nf)
+    nhwc = gnerf_hip.planes_to_nhwc(planes.to(dev))
+    rgb, depth, wsum = gnerf_hip.render_forward(nhwc, 2, [t.to(dev) for t in dec], o.to(dev), d.to(dev), nc.to(dev), None,
+                                                depth_resolution=S, depth_resolution_importance=0, ray_start=2.25, ray_end=3.3, box_warp=1.0,
+                                                image_width=8)
+    assert float(((rgb.cpu() - ref_rgb) ** 2).mean()) < 1e-8
+    np.testing.assert_allclose(rgb.cpu().numpy(), ref_rgb.numpy(), atol=2e-4)
+    np.testing.assert_allclose(depth.cpu().numpy(), ref_depth.numpy(), atol=2e-4)
+    np.testing.assert_allclose(wsum.cpu().numpy(), ref_w.numpy(), atol=2e-4)
+
+
 @pytest.mark.parametrize('S,F', [(48, 48), (24, 40), (96, 96), (128, 128)])
 def test_render_tied_fine_depths(dev, S, F):
     """Equal uniform draws give bit-identical fine depths: the merge must still produce a permutation (stable order,
@@ -254,7 +274,7 @@ def test_render_tied_fine_depths(dev, S, F):
     np.testing.assert_allclose(wsum.cpu().numpy(), ref_w.numpy(), atol=2e-4)
 
 
-@pytest.mark.parametrize('kernel,S', [('pipe', 48), ('pipe', 96), ('coop', 48), ('generic', 48)])
+@pytest.mark.parametrize('kernel,S', [('pipe', 48), ('pipe', 96), ('generic', 48)])
 def test_render_coarse_depths_swapped_by_rounding(dev, kernel, S, monkeypatch):
     """Jitter u = 1 - 2^-24 makes lin_k + u*delta round one ulp past the next proposal (7 of the 47 neighbour pairs at
     the default limits): the coarse depths are then NOT ascending, and the merge must still be the reference's stable
@@ -444,7 +464,7 @@ def _scaled_scene(plane_scale, weight_scale, S, F, res=8):
     return planes * plane_scale, [t * weight_scale for t in dec], o, d, nc, nf
 
 
-@pytest.mark.parametrize('S,F', [(48, 48), (96, 96), (40, 0)])                   # pipe<1>, pipe<2>, coop
+@pytest.mark.parametrize('S,F', [(48, 48), (96, 96), (40, 0)])                   # pipe<1>, pipe<2>, pipe<1> without importance pass
 @pytest.mark.parametrize('weight_scale', [1e-3, 1.0, 1e3])
 @pytest.mark.parametrize('plane_scale', [1e-5, 1e-3, 1.0, 1e3, 1e5])
 def test_render_decoder_arithmetic_is_range_safe(dev, plane_scale, weight_scale, S, F):
@@ -552,7 +572,7 @@ def test_render_interleaved_plane_layout(dev):
     interleaved per texel = channels_last memory of the backbone's [N,96,H,W] output) give bit-identical forward results to the
     [3N,H,W,32] layout on every forward kernel, the same point queries, and the same gradients (laid out like the planes)."""
     import gnerf_hip
-    for S, F in ((48, 48), (96, 96), (40, 0), (130, 100), (150, 20)):            # pipe<1>, pipe<2>, coop, pipe<3>, generic
+    for S, F in ((48, 48), (96, 96), (40, 0), (130, 100), (150, 20)):            # pipe<1>, pipe<2>, pipe<1> (F = 0), pipe<3>, generic
         planes, dec, o, d, nc, nf = _random_scene(17, N=2, res=8, S=S, F=F, hw=(24, 20))
         N = 2
         sep = gnerf_hip.planes_to_nhwc(planes.to(dev))                                           # [6,24,20,32]

@@ -1,6 +1,6 @@
 """Bit-level run-to-run comparison of the render kernel on config 2: renders once with the stage dump, re-renders ten times and
 reports every ray whose rgb differs, with the first stage (debug slot) and samples that differ.
-usage: [GNERF_HIP_LIB=<.so>] [GNERF_RENDER_KERNEL=pipe|coop|generic] python tools/determinism.py"""
+usage: [GNERF_HIP_LIB=<.so>] [GNERF_RENDER_KERNEL=pipe|generic] python tools/determinism.py"""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [os.path.join(ROOT, 'g-nerf_amd'), ROOT]

@@ -2,7 +2,7 @@
 // every bilinear tap straight from L1/L2?  Two kernels do the SAME work on config 2's geometry (4 items x 128x128 rays, 48 coarse
 // depths, 3 x 32-channel 256x256 fp32 planes in the interleaved [N,H,W,96] layout, the bench's camera): per 16-sample slab (one sample
 // of each ray of the tile at depth index k) tap records for 16 x 3 (sample, plane) pairs, then the 12-tap x 32-channel blend, 8 lanes
-// per texel, exactly as the shipped kernel's lookup stage (render_coop.inl) -- reduced to one checksum per workgroup.
+// per texel, exactly as the shipped kernel's lookup stage (render_shade.inl) -- reduced to one checksum per workgroup.
 //   direct   24 global_load_dwordx4 per slab per lane group, addresses from the records                       (what ships)
 //   staged   the slab's footprint per plane (bounding box of the 16 samples' 2x2 taps; <= 6x6 texels, else that slab falls back to
 //            direct) is copied global -> LDS by the wave (8 lanes per 128-byte texel), and the 24 tap reads come from LDS
