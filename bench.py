@@ -2,7 +2,8 @@
 """Headline benchmark: rays/sec of the tri-plane importance renderer on BASELINE.json's config 2
 (renderer-only: 128x128 rays x (48+48) samples, 32-channel 256x256 tri-planes, batch 4 per GPU).
 
-    python bench.py --gpus 1 --steps 50 --warmup 5
+    python bench.py --gpus 1 --steps 50 --warmup 5            (the headline alone)
+    python bench.py --gpus 1 --steps 50 --warmup 5 --full     (and every side measurement)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
 One step = one pass of the hot path over one batch, what ImportanceRenderer.forward does per call on the
@@ -13,14 +14,17 @@ renderer.py:190/:241), the device-side choice of the decoder arithmetic, and the
 depth-clamp epilogue).  Inputs (planes, decoder, cameras) are resident in HBM before the timed region.
 `value` is that step.  `producer_layout_step` (top level, and `config.producer_layout_value`) is the same
 step when the planes arrive in the layout this repo's plane producer writes (channels_last [N,H,W,96] +
-max |planes|, read in place: no layout change inside the step; `--producer-layout` makes it the headline).
+max |planes|, read in place: no layout change inside the step; `--producer-layout` makes it the headline; measured with --full).
 Rays shard embarrassingly: each rank renders its own batch (weak scaling, no data-path collective); the only
 collectives are the barriers bracketing the timed region and the max-reduce of the elapsed time.
 
 Prints ONE JSON line (rank 0) with `roofline` (dominant kernel = render_kernel, timed with HIP events
-on the launch stream inside the timed region) and `cpu_baseline` (the CPU oracle on a bounded sample
-of the same workload, on this host's cores).  `--dump-outputs DIR` also writes what the last timed headline step returned (rgb,
-depth, weights_sum as DIR/<name>.npy, float32); its inputs and draws are the same in every run with the same arguments.
+on the launch stream inside the timed region).  A plain run sets up, warms up, times the headline's K-step regions and
+prints; `--full` adds what takes runs of its own: the 100 ms cross-check region, `producer_layout_step`, the clock under load,
+`inkernel_rng_step`, the forced decoder arithmetics, `roofline_backward`, `realistic_planes_step`, `secondary` (the gen_videos
+orbit) and `cpu_baseline` (the CPU oracle on a bounded sample of the same workload, on this host's cores).
+`--dump-outputs DIR` also writes what the last timed headline step returned (rgb, depth, weights_sum as DIR/<name>.npy,
+float32); its inputs and draws are the same in every run with the same arguments, with or without --full.
 """
 
 import argparse
@@ -874,12 +878,15 @@ def main():
     ap.add_argument('--reps', type=int, default=5, help='minimum repetitions of the timed K-step region (the median is reported; more are run until 0.3 s are covered)')
     ap.add_argument('--producer-layout', action='store_true', help='headline = the step on channels_last planes + max |planes| from the plane producer (no layout change in the step)')
     ap.add_argument('--nchw-input', action='store_true', help='(default since round 3; kept for old command lines)')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-secondary', action='store_true', help='skip the gen_videos frames/sec measurement')
-    ap.add_argument('--no-backward', action='store_true', help='skip the renderer-backward timing behind roofline_backward')
+    ap.add_argument('--full', action='store_true', help='measure everything beyond the headline too: the 100 ms cross-check region, the other plane '
+                    'layout, the clock under load, in-kernel rays / draws, forced decoder arithmetics, the renderer backward, the step on '
+                    'backbone-output planes, the gen_videos orbit and the CPU oracle (a plain run times the headline steps and nothing else)')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip the CPU oracle baseline')
+    ap.add_argument('--no-secondary', action='store_true', help='with --full: skip the gen_videos frames/sec measurement and the backbone-plane step')
+    ap.add_argument('--no-backward', action='store_true', help='with --full: skip the renderer-backward timing behind roofline_backward')
     ap.add_argument('--dump-outputs', metavar='DIR', default=None, help='write what the last timed headline step returned (rgb, depth, '
                     'weights_sum) to DIR/<name>.npy as float32; rank 0 only')
-    ap.add_argument('--full-line', action='store_true', help='with several ranks: every rank runs the whole line (forced arithmetics, in-kernel draws, '
+    ap.add_argument('--full-line', action='store_true', help='with --full and several ranks: every rank runs the whole line (forced arithmetics, in-kernel draws, '
                     'backward, backbone-plane step, both orbit flows); by default those run on rank 0 alone and the others go straight to the orbit')
     ap.add_argument('--stub-step', action='store_true', help=argparse.SUPPRESS)       # CPU rehearsal of the multi-rank plumbing (stub_main)
     ap.add_argument('--cpu-baseline-worker', type=int, default=0, help=argparse.SUPPRESS)      # child of cpu_baseline(): the all-cores figure
@@ -1037,33 +1044,36 @@ def main():
         for name, t in zip(('rgb', 'depth', 'weights_sum'), last_out[0]):
             np.save(os.path.join(args.dump_outputs, name + '.npy'), t.detach().float().cpu().numpy())
     assert gnerf_hip.last_mlp_choice(dev) == 'f16x3', 'config 2 is inside the f16 hi/lo range: the device-side choice must pick it'
-    # one long region (>= 100 ms of steps, whatever --steps is) as a cross-check of the K-step median
-    n_long = max(args.steps, int(0.1 / (elapsed / args.steps)) + 1)
-    if world > 1:
-        n_long = int(gnerf_harness.max_over_ranks(float(n_long), dev))
-    long_elapsed = sorted(timed_region(nchw_input=headline_nchw, n_steps=n_long)[0] for _ in range(3))[1]
-    # the other plane layout, and the render call with each shipped decoder arithmetic forced
-    other = sorted(timed_region(nchw_input=not headline_nchw) for _ in range(5))[2]
-    # the shader clock while the bench step runs (a one-wave sampler on a side stream: gnerf_clock_sample): the roofline's peak is
-    # cycles per second, and the chip holds well under the data sheet's 2.4 GHz under this kernel's load
-    clock_mhz = None
-    if rank == 0:
-        try:
-            clock_mhz = gnerf_hip.clock_under_load(lambda: [step(None, 'auto', headline_nchw) for _ in range(8)], microseconds=3000.0, device=dev)
-        except Exception as e:
-            clock_mhz = None
-            progress(f'clock sample failed: {type(e).__name__}: {e}')
-    progress('headline regions done; in-kernel rays / draws, forced arithmetics')
+    # What follows the headline and takes runs of its own (the cross-check region, the other layout, the clock, forced arithmetics,
+    # backward, backbone planes, the orbit, the CPU oracle) is measured with --full only: a plain run goes on to its result line.
+    kernel_ms_by_mlp = {'auto': kernel_ms}
+    if args.full:
+        # one long region (>= 100 ms of steps, whatever --steps is) as a cross-check of the K-step median
+        n_long = max(args.steps, int(0.1 / (elapsed / args.steps)) + 1)
+        if world > 1:
+            n_long = int(gnerf_harness.max_over_ranks(float(n_long), dev))
+        long_elapsed = sorted(timed_region(nchw_input=headline_nchw, n_steps=n_long)[0] for _ in range(3))[1]
+        # the other plane layout, and the render call with each shipped decoder arithmetic forced
+        other = sorted(timed_region(nchw_input=not headline_nchw) for _ in range(5))[2]
+        # the shader clock while the bench step runs (a one-wave sampler on a side stream: gnerf_clock_sample): the roofline's peak is
+        # cycles per second, and the chip holds well under the data sheet's 2.4 GHz under this kernel's load
+        clock_mhz = None
+        if rank == 0:
+            try:
+                clock_mhz = gnerf_hip.clock_under_load(lambda: [step(None, 'auto', headline_nchw) for _ in range(8)], microseconds=3000.0, device=dev)
+            except Exception as e:
+                clock_mhz = None
+                progress(f'clock sample failed: {type(e).__name__}: {e}')
+        progress('headline regions done; in-kernel rays / draws, forced arithmetics')
     # With several ranks the side measurements below (nothing in them scales: they describe the kernel) run on rank 0 ALONE, without
     # collectives, while the others go on to the orbit and wait at its first barrier: eight copies of them -- and eight concurrent
     # MIOpen solver searches for a flow nobody reads at N > 1 -- are what could push the first multi-GPU run over its time limit.
     # --full-line restores "every rank runs everything" (then with barriers, as at N = 1).
-    full = world == 1 or args.full_line
-    extras_here, solo = full or rank == 0, not full
-    side_ranks = world if full else 1
+    every_rank = world == 1 or args.full_line
+    extras_here, solo = args.full and (every_rank or rank == 0), not every_rank
+    side_ranks = world if every_rank else 1
     # the same two steps with rays and draws made inside the render kernel (SURVEY 8d "in-kernel Philox (throughput run -- state which)")
     inkernel = {}
-    kernel_ms_by_mlp = {'auto': kernel_ms}
     if extras_here:
         try:
             for name, nchw in (('nchw_input', True), ('producer_layout', False)):
@@ -1085,9 +1095,9 @@ def main():
 
     ranks = rank_identity(rank, world, dev)
 
-    progress('renderer backward')
     backward = None
     if not args.no_backward and extras_here:
+        progress('renderer backward')
         try:
             backward = backward_times(dev, planes_cl, dec, c2w, intr)
             backward['ratio_to_forward_kernel'] = backward['call_ms']['staged_scatter'] / kernel_ms
@@ -1096,7 +1106,7 @@ def main():
 
     realistic = None
     secondary = None
-    if not args.no_secondary:
+    if args.full and not args.no_secondary:
         try:
             del planes, planes_cl
             torch.cuda.empty_cache()
@@ -1108,8 +1118,8 @@ def main():
                     realistic = realistic_planes_step(dev, c2w, intr, args.steps, rank)
                 except Exception as e:
                     realistic = {'error': f'{type(e).__name__}: {e}'[:300]}
-            progress('gen_videos orbit (config 4)' + (', two flows' if full else ', fast flow (the reference flow is an N = 1 / --full-line figure)'))
-            secondary = gen_videos_secondary(rank, world, dev, flows=('fast', 'reference') if full else ('fast',))
+            progress('gen_videos orbit (config 4)' + (', two flows' if every_rank else ', fast flow (the reference flow is an N = 1 / --full-line figure)'))
+            secondary = gen_videos_secondary(rank, world, dev, flows=('fast', 'reference') if every_rank else ('fast',))
         except Exception as e:                                           # never lose the headline line to the secondary metric
             secondary = {'metric': 'frames/sec gen_videos', 'value': None, 'error': f'{type(e).__name__}: {e}'[:300]}
 
@@ -1121,23 +1131,23 @@ def main():
             traffic = json.load(open(tpath)).get('render_kernel_hbm_bytes_per_launch')
         pmc, pmc_source = latest_pmc()
         roof = roofline(kernel_ms_by_mlp['auto'], rays_per_call, S_COARSE, S_FINE, PLANE, N_ITEMS, pmc, pmc_source, traffic)     # the kernel the headline runs
-        roof['clock'] = {'mhz_while_the_step_runs': clock_mhz, 'mhz_the_peak_is_priced_at': CLOCK_HZ / 1e6,
-                         'frac_at_the_measured_clock': roof['frac'] * (CLOCK_HZ / 1e6) / clock_mhz if clock_mhz else None,
-                         'note': 'gnerf_clock_sample: one wave on a side stream reads s_memtime against the 100 MHz s_memrealtime for 3 ms of steps.  `frac` stays '
-                                 'priced at 2.4 GHz; at the clock the chip actually holds under this load the same kernel covers that much more of the '
-                                 'cycles it is given (profiles/r05_stamps.txt: 1.94-2.00 GHz inside the render kernel itself)'}
+        if args.full:
+            roof['clock'] = {'mhz_while_the_step_runs': clock_mhz, 'mhz_the_peak_is_priced_at': CLOCK_HZ / 1e6,
+                             'frac_at_the_measured_clock': roof['frac'] * (CLOCK_HZ / 1e6) / clock_mhz if clock_mhz else None,
+                             'note': 'gnerf_clock_sample: one wave on a side stream reads s_memtime against the 100 MHz s_memrealtime for 3 ms of steps.  `frac` stays '
+                                     'priced at 2.4 GHz; at the clock the chip actually holds under this load the same kernel covers that much more of the '
+                                     'cycles it is given (profiles/r05_stamps.txt: 1.94-2.00 GHz inside the render kernel itself)'}
         roof['build_head'] = build_head()
         roof['render_call_ms'] = kernel_ms_by_mlp
         roof['render_call_ms_note'] = ('HIP events around the render call of every 5th step inside the timed regions: auto = what the headline runs (every '
                                        'workgroup evaluates the range bounds itself and runs the f16x3 body here; `frac` is computed on it), f16x3 / f32 = '
-                                       'that arithmetic forced; each includes the depth-clamp epilogue')
+                                       'that arithmetic forced (--full only); each includes the depth-clamp epilogue')
         nchw_name = 'NCHW planes as BASELINE.md section 2 defines the input; the NCHW -> [3N,H,W,32] layout change (100 MB read + written) and max |planes| inside every step'
         cl_name = 'planes as gnerf_upsample2x_add_nhwc writes them (channels_last [N,H,W,96] + max |planes|), read in place: no layout change inside the step'
-        other_step = {'ms_per_step': 1e3 * other[0] / args.steps, 'value': total_rays / other[0], 'planes': nchw_name if not headline_nchw else cl_name}
         line = {
             'metric': 'rays/sec at 128^2 neural render, 96 depth samples',
             'value': total_rays / elapsed, 'unit': 'rays/s', 'n_gpus': world, 'steps': args.steps, 'warmup': args.warmup,
-            'ms_per_step': 1e3 * elapsed / args.steps, 'higher_is_better': True, 'scaling': 'weak', 'vs_baseline': None,
+            'ms_per_step': 1e3 * elapsed / args.steps, 'higher_is_better': True, 'scaling': 'weak', 'vs_baseline': None, 'full': args.full,
             # proof of what ran: ranks the process group saw, its backend ('nccl' = RCCL; None for one process), every rank's device
             'ranks_seen': dist.get_world_size() if world > 1 else 1, 'backend': dist.get_backend() if world > 1 else None,
             'self_launched': os.environ.get('GNERF_BENCH_SELF_LAUNCHED') == '1', 'ranks': ranks,
@@ -1148,42 +1158,47 @@ def main():
                             'ms_per_step_in_run_order': [round(1e3 * e / args.steps, 4) for e, _, _ in chrono],
                             'value_min': total_rays / regions[-1][0], 'value_max': total_rays / regions[0][0],
                             'spread_frac': (regions[-1][0] - regions[0][0]) / elapsed,
-                            'interquartile_spread_frac': (regions[(3 * len(regions)) // 4][0] - regions[len(regions) // 4][0]) / elapsed,
-                            'one_region_of_100ms': {'steps': n_long, 'ms_per_step': 1e3 * long_elapsed / n_long,
-                                                    'value': rays_per_call * n_long * world / long_elapsed}},
+                            'interquartile_spread_frac': (regions[(3 * len(regions)) // 4][0] - regions[len(regions) // 4][0]) / elapsed},
             'config': {'workload': 'config 2: 128x128 rays x (48+48) samples, 3x32x256x256 fp32 tri-planes, batch 4 per GPU; '
                                    + ('NCHW planes, repacked in every step' if headline_nchw else 'channels_last planes read in place'),
                        'step': ('NCHW->NHWC repack with max|planes| + ' if headline_nchw else '') + ('make_rays and the 2 torch.rand draws in one launch (gnerf_make_rays_and_draws: torch.rand\'s values bit for bit, generator advanced alike)' if FUSED_PREP else 'make_rays + 2 torch.rand draws') + ' + fused render kernel (device-side decoder-arithmetic choice) + depth clamp',
                        'planes': nchw_name if headline_nchw else cl_name,
-                       'rays_per_step_per_gpu': rays_per_call, 'parallelism': f'rays sharded over {world} GPU(s), no data-path collective',
-                       'producer_layout_value' if headline_nchw else 'nchw_input_value': other_step['value'],
-                       'producer_layout_ms_per_step' if headline_nchw else 'nchw_input_ms_per_step': other_step['ms_per_step']},
-            'producer_layout_step' if headline_nchw else 'nchw_input_step': other_step,
-            'inkernel_rng_step': dict(inkernel, note='the step with ray generation and both uniform draws inside the render kernel (cameras + torch\'s Philox '
-                                      'stream at the generator\'s offset; outputs and generator state equal the explicit-noise step\'s bit for bit: '
-                                      'tests/test_gpu_parity.py::test_render_with_inkernel_rays_and_draws); `value` above is the explicit-noise step'),
+                       'rays_per_step_per_gpu': rays_per_call, 'parallelism': f'rays sharded over {world} GPU(s), no data-path collective'},
             'per_rank': per_rank,
             'roofline': roof,
         }
-        if realistic is not None:
-            line['realistic_planes_step'] = realistic
-        if backward is not None:
-            line['roofline_backward'] = backward
-        line['secondary'] = secondary
-        line['side_measurements'] = 'every rank' if full else 'rank 0 alone, without collectives (inkernel_rng_step, forced arithmetics, roofline_backward, realistic_planes_step; orbit: fast flow only)'
+        if args.full:
+            line['repetitions']['one_region_of_100ms'] = {'steps': n_long, 'ms_per_step': 1e3 * long_elapsed / n_long,
+                                                          'value': rays_per_call * n_long * world / long_elapsed}
+            other_step = {'ms_per_step': 1e3 * other[0] / args.steps, 'value': total_rays / other[0], 'planes': nchw_name if not headline_nchw else cl_name}
+            line['config']['producer_layout_value' if headline_nchw else 'nchw_input_value'] = other_step['value']
+            line['config']['producer_layout_ms_per_step' if headline_nchw else 'nchw_input_ms_per_step'] = other_step['ms_per_step']
+            line['producer_layout_step' if headline_nchw else 'nchw_input_step'] = other_step
+            line['inkernel_rng_step'] = dict(inkernel, note='the step with ray generation and both uniform draws inside the render kernel (cameras + torch\'s Philox '
+                                             'stream at the generator\'s offset; outputs and generator state equal the explicit-noise step\'s bit for bit: '
+                                             'tests/test_gpu_parity.py::test_render_with_inkernel_rays_and_draws); `value` above is the explicit-noise step')
+            if realistic is not None:
+                line['realistic_planes_step'] = realistic
+            if backward is not None:
+                line['roofline_backward'] = backward
+            line['secondary'] = secondary
+            line['side_measurements'] = 'every rank' if every_rank else 'rank 0 alone, without collectives (inkernel_rng_step, forced arithmetics, roofline_backward, realistic_planes_step; orbit: fast flow only)'
+        else:
+            line['side_measurements'] = 'none: a plain run measures the headline alone (--full adds the cross-checks, the other plane layout, the clock, forced arithmetics, backward, backbone planes, the orbit and the CPU oracle)'
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()
     if rank == 0:
-        # the CPU oracle on this host's cores, in the same run at every N (north_star): after the process group is gone, so the other
-        # ranks are not held in a collective while rank 0 computes on the CPU for half a minute
-        line['cpu_baseline'] = None
-        if not args.no_cpu_baseline:
-            progress('CPU oracle baseline')
-            try:
-                line['cpu_baseline'] = cpu_baseline()
-            except Exception as e:                                      # never lose the line to the baseline
-                line['cpu_baseline'] = {'value': None, 'error': f'{type(e).__name__}: {e}'[:300]}
+        if args.full:
+            # the CPU oracle on this host's cores, in the same run at every N (north_star): after the process group is gone, so the other
+            # ranks are not held in a collective while rank 0 computes on the CPU for half a minute
+            line['cpu_baseline'] = None
+            if not args.no_cpu_baseline:
+                progress('CPU oracle baseline')
+                try:
+                    line['cpu_baseline'] = cpu_baseline()
+                except Exception as e:                                      # never lose the line to the baseline
+                    line['cpu_baseline'] = {'value': None, 'error': f'{type(e).__name__}: {e}'[:300]}
         sys.stdout.flush()
         os.write(result_fd, (json.dumps(line) + '\n').encode())
 

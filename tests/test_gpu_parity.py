@@ -2678,6 +2678,35 @@ def test_render_fine_samples_on_bin_edges(dev, S, F):
     np.testing.assert_allclose(wsum.cpu().numpy(), ref_w.numpy(), atol=2e-4)
 
 
+def test_bench_plain_run_is_the_headline_alone(dev, tmp_path):
+    """`python bench.py` without --full: the headline's fields and outputs, none of the side measurements, and little time beyond its steps."""
+    import json
+    import os
+    import subprocess
+    import sys
+    import time
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ)
+    for k in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK', 'MASTER_PORT'):
+        env.pop(k, None)
+    t0 = time.perf_counter()
+    r = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', '1', '--steps', '10', '--warmup', '2', '--dump-outputs', str(tmp_path)],
+                       capture_output=True, text=True, env=env, cwd=root, timeout=300)
+    wall = time.perf_counter() - t0
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1, lines
+    line = json.loads(lines[0])
+    assert line['full'] is False and line['steps'] == 10 and line['warmup'] == 2 and line['value'] > 1e6 and line['unit'] == 'rays/s'
+    assert line['higher_is_better'] is True and line['dtype'].startswith('f32') and line['ms_per_step'] > 0
+    assert abs(line['value'] - 4 * 128 * 128 / (line['ms_per_step'] * 1e-3)) < 1e-6 * line['value']
+    assert line['roofline']['kernel_ms'] > 0 and list(line['roofline']['render_call_ms']) == ['auto']
+    for k in ('secondary', 'cpu_baseline', 'roofline_backward', 'realistic_planes_step', 'inkernel_rng_step', 'producer_layout_step'):
+        assert k not in line, k
+    assert sorted(os.listdir(tmp_path)) == ['depth.npy', 'rgb.npy', 'weights_sum.npy']
+    assert wall < 120, wall
+
+
 @pytest.mark.parametrize('launcher', ['torch.distributed.run', 'self'])
 def test_bench_two_ranks_on_one_gpu(dev, launcher):
     """The multi-rank path of bench.py end to end (rendezvous, per-rank scene, barriers, max-over-ranks timing, one JSON line from
@@ -2699,7 +2728,7 @@ def test_bench_two_ranks_on_one_gpu(dev, launcher):
         env.pop(k, None)
     head = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '2', '--master-addr', '127.0.0.1',
             '--master-port', str(port)] if launcher != 'self' else [sys.executable]
-    r = subprocess.run(head + [os.path.join(root, 'bench.py'), '--gpus', '2', '--steps', '5', '--warmup', '2',
+    r = subprocess.run(head + [os.path.join(root, 'bench.py'), '--gpus', '2', '--steps', '5', '--warmup', '2', '--full',
                                '--no-cpu-baseline', '--no-secondary', '--no-backward'], capture_output=True, text=True, env=env, cwd=root, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]

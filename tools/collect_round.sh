@@ -14,8 +14,9 @@ a)
   tag=${2:-${RND}_final}
   bash tools/prof_forward.sh $tag > gpurun_out/prof_forward.log 2>&1
   rm -rf gpurun_out/prof_$tag
-  python bench.py --steps 50 --warmup 5 --reps 5 > gpurun_out/profiles/${tag}_bench.json 2> gpurun_out/bench.err
-  tail -c 300 gpurun_out/profiles/${tag}_bench.json
+  # the whole bench line (--full), after the counters above so that its roofline quotes them; it is kept in profiles/
+  python bench.py --full --steps 50 --warmup 5 --reps 5 > profiles/${tag}_bench.json
+  tail -c 300 profiles/${tag}_bench.json
   bash tools/prof_bwd.sh > gpurun_out/prof_bwd.log 2>&1
   cp gpurun_out/${RND}_backward_profile.json gpurun_out/profiles/ 2>/dev/null
   ls -la gpurun_out/profiles ;;

@@ -10,7 +10,7 @@ for v in 1 0 1 0; do
   timeout -k 10 300 python3 tools/bench_generator.py 2>/dev/null | grep '"config": 4' | head -1 | python3 -c "
 import sys, json
 d = json.loads(sys.stdin.read()); print(json.dumps({'fused_torgb': $v, 'frame_by_frame_eager': d['frames_per_s'], 'frame_by_frame_graph': d['graph_frames_per_s']}))" | tee -a $O/fused_torgb_ab.jsonl || exit 1
-  timeout -k 10 500 python3 bench.py --steps 20 --warmup 3 --reps 3 --no-cpu-baseline --no-backward 2>/dev/null | python3 -c "
+  timeout -k 10 500 python3 bench.py --full --steps 20 --warmup 3 --reps 3 --no-cpu-baseline --no-backward 2>/dev/null | python3 -c "
 import sys, json
 d = json.loads(sys.stdin.read().strip().splitlines()[-1])['secondary']
 print(json.dumps({'fused_torgb': $v, 'views8_graph': round(d['hip_graph_views_value'], 1), 'views8_eager': round(d['eager_views_value'], 1), 'graph': round(d['hip_graph_value'], 1), 'eager': round(d['eager_value'], 1)}))" | tee -a $O/fused_torgb_ab.jsonl || exit 1
