@@ -33,6 +33,7 @@ from training.volumetric_rendering.renderer import ImportanceRenderer
 from training.volumetric_rendering.ray_sampler import RaySampler
 
 import gnerf_harness as H
+import gnerf_hip
 
 LRELU_GAIN = math.sqrt(2)
 # Inference on a GPU: the ATen elementwise chains around each convolution (weight modulation / demodulation, noise, bias,
@@ -40,13 +41,6 @@ LRELU_GAIN = math.sqrt(2)
 # batch of fp16 layers uses the shared-weight form of the convolution (one batched MIOpen convolution instead of a grouped one
 # with per-sample weights: 2.2x faster at batch 4, tools/bench_upconv.py).  GNERF_MODCONV_FAST=0 keeps the plain PyTorch forms.
 _MODCONV_FAST = os.environ.get('GNERF_MODCONV_FAST', '1') != '0'
-
-
-# The fp16 blocks run channels_last on the fast path (memory [N,H,W,C]): MIOpen's fp16 convolutions compute in that layout and
-# otherwise transpose in and out around every call (tools/bench_sr_conv_layout.py: 0.63 ms of the superresolution at batch 4), and
-# the surrounding kernels (blur, epilogue, ToRGB) have channels_last forms.  GNERF_FP16_CHANNELS_LAST=0 keeps NCHW.  Inference fast path
-# only: under autograd (un-fused forms) the same switch measured G forward 12.7 -> 13.4 ms, G backward 26.6 -> 25.8 ms: no gain.
-_FP16_CHANNELS_LAST = os.environ.get('GNERF_FP16_CHANNELS_LAST', '1') != '0'
 
 
 def _is_channels_last(x):
@@ -58,61 +52,51 @@ def _fast_path(x, *params):
             and not (torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in params))))
 
 
+def _param_memo(module, tag, p, fn):
+    """fn() memoised on `module` per (tag, storage and version of parameter p), in the one slot clear_latent_caches drops: the converted,
+    pre-normalised and packed parameters of the fast path.  An inference tensor has no version counter: its entry is kept for its storage."""
+    key = (p.data_ptr(), None if p.is_inference() else p._version)
+    cache = module.__dict__.setdefault('_gnerf_param_cache', {})
+    hit = cache.get(tag)
+    if hit is None or hit[0] != key:
+        with torch.no_grad():
+            hit = cache[tag] = (key, fn())
+    return hit[1]
+
+
 def _cast_param(module, name, dtype):
     """getattr(module, name) in `dtype`, the converted copy cached per parameter version: the fp16 layers' biases are fp32 parameters,
     and converting them inside every kernel wrapper was ten 4-us copy launches per orbit frame (4 % of its GPU time,
-    profiles/r03_orbit_fast_flow_kernel_stats.csv)."""
+    profiles/r03_orbit_fast_flow_kernel_stats.csv); inference tensors and parameters in a graph are converted per call."""
     p = getattr(module, name)
     if p is None or p.dtype == dtype:
         return p
     if p.is_inference() or (torch.is_grad_enabled() and p.requires_grad):
         return p.to(dtype)
-    key = (p.data_ptr(), p._version, dtype)
-    cache = module.__dict__.setdefault('_gnerf_cast', {})
-    hit = cache.get(name)
-    if hit is None or hit[0] != key:
-        hit = (key, p.detach().to(dtype).contiguous())
-        cache[name] = hit
-    return hit[1]
+    return _param_memo(module, ('cast', name, dtype), p, lambda: p.detach().to(dtype).contiguous())
 
 
 def _prenormalised_weight(module, dtype, channels_last=False, transposed=False):
     """weight / (sqrt(fan_in) max|weight[o]|) in `dtype` (networks_stylegan2.py:63), cached per weight version: a constant at inference.
     channels_last: in that memory format (for channels_last activations); transposed: as [I,O,k,k] for conv_transpose2d."""
-    w = module.weight
-    key = (w.data_ptr(), w._version if not w.is_inference() else None, dtype, channels_last, transposed)
-    cache = module.__dict__.setdefault('_gnerf_prenorm', {})
-    hit = cache.get(key[2:])
-    if hit is None or hit[0] != key:
-        with torch.no_grad():
-            v = (w * (1 / math.sqrt(w[0].numel()) / w.norm(float('inf'), dim=[1, 2, 3], keepdim=True))).to(dtype)
-            if transposed:
-                v = v.transpose(0, 1)
-            hit = (key, v.contiguous(memory_format=torch.channels_last if channels_last else torch.contiguous_format))
-        cache[key[2:]] = hit
-    return hit[1]
+    def make():
+        w = module.weight
+        v = (w * (1 / math.sqrt(w[0].numel()) / w.norm(float('inf'), dim=[1, 2, 3], keepdim=True))).to(dtype)
+        return (v.transpose(0, 1) if transposed else v).contiguous(memory_format=torch.channels_last if channels_last else torch.contiguous_format)
+    return _param_memo(module, ('prenorm', dtype, channels_last, transposed), module.weight, make)
 
 
 def _packed_prenormalised_weight(module, dtype, transposed=False):
     """The pre-normalised weight in the tap-major [9, O, I] form of gnerf_hip.conv3x3_epilogue (csrc/conv3x3.hip) -- transposed: in the
     by-output-phase form of gnerf_hip.conv_transpose3x3_s2 -- cached like the convolution forms above."""
-    w = module.weight
-    key = (w.data_ptr(), w._version if not w.is_inference() else None, dtype)
-    name = '_gnerf_prenorm_packed_t' if transposed else '_gnerf_prenorm_packed'
-    hit = module.__dict__.get(name)
-    if hit is None or hit[0] != key:
-        import gnerf_hip
-        pack = gnerf_hip.pack_conv_transpose3x3_weights if transposed else gnerf_hip.pack_conv3x3_weights
-        hit = (key, pack(_prenormalised_weight(module, dtype), dtype))
-        module.__dict__[name] = hit
-    return hit[1]
+    pack = gnerf_hip.pack_conv_transpose3x3_weights if transposed else gnerf_hip.pack_conv3x3_weights
+    return _param_memo(module, ('packed', dtype, transposed), module.weight, lambda: pack(_prenormalised_weight(module, dtype), dtype))
 
 
 def _packed_modulated_weight(module, nstyles, dtype, transposed=False):
     """pack(f16(pre-normalised weight x the ONE latent's normalised styles)): the input scaling of a layer folded into its packed weights, which is
     the order the reference's own inference path takes it in (the fused form modulates the WEIGHTS, networks_stylegan2.py:66-75) -- one rounding
     per weight instead of one per activation, and no scaling pass over the activations.  A constant of (latent, weight): cached by _per_latent."""
-    import gnerf_hip
     w = module.weight
     with torch.no_grad():
         v = w * (1 / math.sqrt(w[0].numel()) / w.norm(float('inf'), dim=[1, 2, 3], keepdim=True)) * nstyles.reshape(1, -1, 1, 1).to(w.dtype)
@@ -126,33 +110,25 @@ _LATENT_WEIGHTS = os.environ.get('GNERF_LATENT_WEIGHTS', '1') != '0'
 # GNERF_FUSED_TORGB=0: the last block of the superresolution keeps its three launches (layer, ToRGB added to the running image) instead of the
 # layer's convolution with the ToRGB in its epilogue and no layer output at all (gnerf_conv3x3_epilogue_torgb_nhwc, round 6)
 _FUSED_TORGB = os.environ.get('GNERF_FUSED_TORGB', '1') != '0'
-_TORGB_DONE = object()             # what StyledConv.forward(..., torgb_tail=...) returns when the tail ran in the convolution's launch
 # GNERF_FUSED_CONV=0: the 3x3 layers of the shared-weight form go to MIOpen + gnerf_modconv_epilogue_nhwc (round 4's flow) instead of
 # the one-launch kernel of csrc/conv3x3.hip
 _FUSED_CONV = os.environ.get('GNERF_FUSED_CONV', '1') != '0'
-# GNERF_SHARED_AT_ONE=0: a batch of one keeps round 5's route (per-sample modulated weights into the framework's convolution)
-_SHARED_AT_ONE = os.environ.get('GNERF_SHARED_AT_ONE', '1') != '0'
 # GNERF_F32X3=0: the backbone's float32 3x3 layers stay with the framework's fp32 convolution (MIOpen) instead of the fp32-grade form of
 # csrc/conv3x3.hip (round 6: every product as three f16 matrix products of hi / lo splits, 2.5-3.3x MIOpen on the backbone's hot shapes)
 _F32X3 = os.environ.get('GNERF_F32X3', '1') != '0'
 # smallest image the fp32-grade form takes: the convolution at H, W >= 64, the x2 layers from H, W >= 32 (at 32^2 the kernel's 8 x 32 pixel
 # tiles leave most of the chip idle and MIOpen is faster: profiles/r06_conv_f32grade_gate.jsonl)
 _F32X3_MIN_CONV, _F32X3_MIN_UP = 64, 32
+# route names (StyledConv.route, ToRGB.route): the plain PyTorch forms of the reference's layer code, and the fp16 shared-weight forms
+_REFERENCE_ROUTES = ('_reference_fused', '_reference_unfused')
+_SHARED_ROUTES = ('_own', '_own_torgb', '_own_up', '_framework')
 
 
 def _packed_weight_f32x3(module, transposed=False):
     """The RAW float32 weight (no pre-normalisation: float32 layers have none, networks_stylegan2.py:61-64) split as [hi | hi | lo] and packed for
     gnerf_hip.conv3x3_f32x3_epilogue (or, transposed, conv_transpose3x3_s2_f32x3); cached per weight version."""
-    w = module.weight
-    key = (w.data_ptr(), w._version if not w.is_inference() else None)
-    name = '_gnerf_f32x3_packed_t' if transposed else '_gnerf_f32x3_packed'
-    hit = module.__dict__.get(name)
-    if hit is None or hit[0] != key:
-        import gnerf_hip
-        pack = gnerf_hip.pack_conv_transpose3x3_weights_f32x3 if transposed else gnerf_hip.pack_conv3x3_weights_f32x3
-        hit = (key, pack(w))
-        module.__dict__[name] = hit
-    return hit[1]
+    pack = gnerf_hip.pack_conv_transpose3x3_weights_f32x3 if transposed else gnerf_hip.pack_conv3x3_weights_f32x3
+    return _param_memo(module, ('f32x3', transposed), module.weight, lambda: pack(module.weight))
 
 
 def _latent_token(w):
@@ -217,7 +193,7 @@ def clear_latent_caches(root):
     The caches assume ONE stream per generator: the tensors are made on whichever stream first asked for them and later read in
     place (a HIP-graph capture of the same generator warms them up on its side stream before it captures: FrameProgram.__init__)."""
     for m in root.modules():
-        for k in ('_gnerf_latent_cache', '_gnerf_prenorm', '_gnerf_cast'):
+        for k in ('_gnerf_latent_cache', '_gnerf_param_cache', '_gnerf_scaled'):
             m.__dict__.pop(k, None)
 
 
@@ -319,164 +295,175 @@ class StyledConv(nn.Module):
         self.noise_strength = nn.Parameter(torch.zeros([]))
         self.bias = nn.Parameter(torch.zeros(c_out))
 
-    def _resampled_conv(self, x, weight, groups, weight_t=None, epilogue=None):
-        """weight [groups*O, I, 3, 3] (correlation form).  up == 1: 3x3 convolution with padding 1.  up == 2: stride-2
-        transposed convolution (kernel as is: the reference un-flips it twice), 2H+1 outputs per axis, then the low-pass
-        filter with gain up^2 and one pixel of padding -> 2H.  weight_t: the [groups*I, O, 3, 3] form, when the caller has it.
-        epilogue: keyword arguments of gnerf_hip.modconv_epilogue (no noise); the call then returns (x, done) and, where the fused
-        blur + epilogue kernel applies (x2 layers on channels_last activations), x already carries the epilogue (done = True)."""
-        fmt = torch.channels_last if _is_channels_last(x) else torch.contiguous_format
-        if self.up == 1:
-            x = F.conv2d(x, weight if fmt == torch.contiguous_format else weight.contiguous(memory_format=fmt), padding=1, groups=groups)
-            return (x, False) if epilogue is not None else x
-        if weight_t is not None and not torch.is_tensor(weight_t):          # ('phases', packed): the x2 layer on csrc/conv3x3.hip's transposed form
-            import gnerf_hip
-            x = gnerf_hip.conv_transpose3x3_s2(x, weight_t[1])
-            weight_t = False
-        if weight_t is None:
-            o, i = weight.shape[0] // groups, weight.shape[1]
-            weight_t = weight.reshape(groups, o, i, 3, 3).transpose(1, 2).reshape(groups * i, o, 3, 3)
-            if fmt == torch.channels_last:
-                weight_t = weight_t.contiguous(memory_format=fmt)
-        if weight_t is not False:
-            x = F.conv_transpose2d(x, weight_t, stride=2, groups=groups)
-        if epilogue is not None and groups == 1 and _is_channels_last(x) and x.shape[1] % 8 == 0:
-            import gnerf_hip                                # blur + epilogue in one pass over the activations (csrc/upfirdn2d.hip)
-            return gnerf_hip.blur_epilogue_channels_last(x, self.resample_filter, [1, 1, 1, 1], blur_gain=4, **epilogue), True
-        x = upfirdn2d.upfirdn2d(x, self.resample_filter, padding=[1, 1, 1, 1], gain=4)
-        return (x, False) if epilogue is not None else x
-
-    def forward(self, x, w, noise_mode='random', gain=1.0, fused=True, prescaled=False, next_layer=None, next_w=None, torgb_tail=None):
-        """prescaled: x already carries this layer's input scaling (see next_layer).  next_layer / next_w: the StyledConv that
-        consumes the result and its w; where the shared-weight channels_last form applies, that layer's `x * styles` is folded
-        into this layer's epilogue, and the call returns (x, folded) instead of x.
-        torgb_tail = (ToRGB module, its w, img): the caller needs only `img += torgb(layer(x))` (a block whose x nothing else reads); where the
-        one-launch form applies (gnerf_hip.conv3x3_epilogue_torgb) it runs, img is updated in place and the call returns _TORGB_DONE --
-        otherwise x as always, and the caller goes on as without the argument."""
-        assert noise_mode in ('random', 'const', 'none')
+    def route(self, x, w, noise_mode, fused=True, torgb_tail=False):
+        """The name of the method forward(x, w, noise_mode, fused=fused) runs on.  torgb_tail: the
+        caller would hand over the block's ToRGB (Block.forward asks before it upsamples its image)."""
+        if not _fast_path(x, w, self.weight, self.bias, self.noise_strength, self.affine.weight, self.affine.bias):
+            return '_reference_fused' if fused else '_reference_unfused'       # (w: a latent that needs a gradient takes the autograd forms)
         n, c_in, h, wd = x.shape
-        aff = (self.affine.weight, self.affine.bias)
-        fast = _fast_path(x, w, self.weight, self.bias, self.noise_strength, *aff)      # w: a latent that needs a gradient takes the autograd forms
-        styles = _per_latent(self, w, 'styles', aff, lambda: self.affine(w)) if fast else self.affine(w)
+        c_out, up = self.weight.shape[0], self.up
+        # the kernels' epilogues take noise as one [H, W] plane at the output's size: 'const', or 'random' for a single image
+        plane_noise = noise_mode == 'none' or self.resolution ** 2 * (n if noise_mode == 'random' else 1) == h * wd * up * up
+        if x.dtype == torch.float32:
+            return '_f32x3' if (_F32X3 and c_out % 128 == 0 and c_in % 8 == 0 and plane_noise and (
+                (up == 1 and min(h, wd) >= _F32X3_MIN_CONV and gnerf_hip.conv3x3_f32x3_supported(x, c_out))
+                or (up == 2 and min(h, wd) >= _F32X3_MIN_UP and gnerf_hip.conv_transpose3x3_s2_f32x3_supported(x, c_out)))) else '_per_sample'
+        if _FUSED_CONV and _is_channels_last(x):
+            if up == 1 and gnerf_hip.conv3x3_epilogue_supported(x, c_out) and plane_noise:
+                return '_own_torgb' if torgb_tail and gnerf_hip.conv3x3_epilogue_torgb_supported(x, c_out) else '_own'
+            if up == 2 and gnerf_hip.conv_transpose3x3_s2_supported(x, c_out):
+                return '_own_up'
+        return '_framework'
+
+    def forward(self, x, w, noise_mode='random', gain=1.0, fused=True, prescaled=False, next_layer=None, next_w=None, torgb_tail=None, route=None):
+        """The layer on route(x, w, noise_mode, fused), or on `route` if the caller has asked.  prescaled: x already carries this layer's input
+        scaling.  next_layer / next_w: the StyledConv that consumes the result and its w; the shared-weight routes fold its `x * styles` into this
+        layer's epilogue where x is channels_last, and the call returns (x, folded) instead of x.  torgb_tail = (ToRGB, its w, img) with route
+        '_own_torgb' (route(..., torgb_tail=True)'s choice): `img += torgb(layer(x))` in the convolution's launch, and the output is None."""
+        assert noise_mode in ('random', 'const', 'none')
+        route = route or self.route(x, w, noise_mode, fused)
+        styles = self.affine(w) if route in _REFERENCE_ROUTES else _per_latent(self, w, 'styles', (self.affine.weight, self.affine.bias), lambda: self.affine(w))
         noise = None
         if noise_mode == 'random':
-            noise = torch.randn([n, 1, self.resolution, self.resolution], device=x.device) * self.noise_strength
+            noise = torch.randn([x.shape[0], 1, self.resolution, self.resolution], device=x.device) * self.noise_strength
         elif noise_mode == 'const':
             noise = self.noise_const * self.noise_strength
-        folded = False
-        assert not prescaled or (fast and x.dtype == torch.float16 and (n > 1 or _SHARED_AT_ONE))
-        if fast:
-            import gnerf_hip
-            half = x.dtype == torch.float16
-            cl = _is_channels_last(x)
-            c_out = self.weight.shape[0]
-            clamp = self.conv_clamp * gain if self.conv_clamp is not None else None
-            mine = aff + (self.weight,)
-            if (not half and _F32X3 and c_out % 128 == 0 and c_in % 8 == 0 and (noise is None or noise.numel() == (h * self.up) * (wd * self.up))
-                    and ((self.up == 1 and min(h, wd) >= _F32X3_MIN_CONV and gnerf_hip.conv3x3_f32x3_supported(x, c_out))
-                         or (self.up == 2 and min(h, wd) >= _F32X3_MIN_UP and gnerf_hip.conv_transpose3x3_s2_f32x3_supported(x, c_out)))):
-                # float32 layer in fp32-GRADE arithmetic on the f16 matrix cores (csrc/conv3x3.hip, OUT32): the reference's un-fused form --
-                # x * styles, convolution with the layer's weight, demodulation coefficients after it (networks_stylegan2.py:76-83) -- with the
-                # scaling folded into the hi / lo split of the activations and everything behind the convolution in its epilogue
-                dco = _per_latent(self, w, 'dco32', mine, lambda: gnerf_hip.modulate_weights(self.weight, styles, True, out_dtype=torch.float32, want_weights=False, want_dcoefs=True)[1])
-                x3 = gnerf_hip.split_f16x3(x if cl else x.contiguous(memory_format=torch.channels_last), styles)
-                if self.up == 1:
-                    x = gnerf_hip.conv3x3_f32x3_epilogue(x3, _packed_weight_f32x3(self), self.bias, scale=dco, noise=noise, gain=LRELU_GAIN * gain, clamp=clamp)
-                else:
-                    x = gnerf_hip.conv_transpose3x3_s2_f32x3(x3, _packed_weight_f32x3(self, transposed=True))
-                    if noise is None:
-                        x = gnerf_hip.blur_epilogue_channels_last(x, self.resample_filter, [1, 1, 1, 1], blur_gain=4, bias=self.bias, scale=dco, act='lrelu',
-                                                                  gain=LRELU_GAIN * gain, clamp=clamp)
-                    else:
-                        x = upfirdn2d.upfirdn2d(x, self.resample_filter, padding=[1, 1, 1, 1], gain=4)
-                        x = gnerf_hip.modconv_epilogue(x, self.bias, scale=dco, noise=noise, act='lrelu', gain=LRELU_GAIN * gain, clamp=clamp)
-                return (x, folded) if next_layer is not None else x
-            # shared-weight form: activations scaled by the styles, demodulation in the epilogue.  Round 6: also at n == 1 -- one latent is
-            # trivially "shared", and it is the call gen_videos.py makes (one camera per synthesis, gen_videos.py:154-171): the frame-by-frame
-            # orbit then runs its 3x3 layers on csrc/conv3x3.hip like the batched one instead of per-sample weights + MIOpen
-            if half and (n > 1 or _SHARED_AT_ONE):
-                dco = _per_latent(self, w, 'dco', mine, lambda: gnerf_hip.modulate_weights(self.weight, styles, True, out_dtype=x.dtype, want_weights=False, want_dcoefs=True)[1])
-                own_plain = _FUSED_CONV and self.up == 1 and cl and gnerf_hip.conv3x3_epilogue_supported(x, c_out) and (noise is None or noise.numel() == h * wd)
-                own_up = self.up == 2 and _FUSED_CONV and cl and gnerf_hip.conv_transpose3x3_s2_supported(x, c_out)
-                packed = None           # the layer's packed weights when they carry its input scaling (round 6: ONE latent for the whole batch)
-                if not prescaled:
-                    nst = _per_latent(self, w, 'nstyles', aff, lambda: gnerf_hip.normalise_styles(styles))
-                    if _LATENT_WEIGHTS and _rows_share_latent(w) and (own_plain or own_up) and _latent_cacheable(w, mine):     # (packing per call would cost more than the scaling pass)
-                        packed = _per_latent(self, w, ('packed_mod', x.dtype), mine, lambda: _packed_modulated_weight(self, nst[:1], x.dtype, transposed=self.up == 2))
-                    else:
-                        x = gnerf_hip.scale_channels(x, nst)
-                nxt = None
-                if next_layer is not None and cl and _fast_path(x, next_w, next_layer.weight, next_layer.bias, next_layer.noise_strength, next_layer.affine.weight, next_layer.affine.bias):
-                    nxt_aff = (next_layer.affine.weight, next_layer.affine.bias)
-                    nxt = _per_latent(next_layer, next_w, 'nstyles', nxt_aff, lambda: gnerf_hip.normalise_styles(next_layer.affine(next_w)))
-                    folded = True
-                if own_plain and torgb_tail is not None and nxt is None and gnerf_hip.conv3x3_epilogue_torgb_supported(x, c_out):
-                    # ... and the block's ToRGB, added to the running image, in the same launch; no layer output is written (round 6)
-                    tg, w_rgb, img = torgb_tail
-                    rgb_aff = (tg.affine.weight, tg.affine.bias)
-                    rgb_styles = _per_latent(tg, w_rgb, 'styles', rgb_aff, lambda: tg.affine(w_rgb) * tg.weight_gain)
-                    rgb_w = _per_latent(tg, w_rgb, 'rgbw16', rgb_aff + (tg.weight,), lambda: gnerf_hip.torgb_weights(tg.weight, rgb_styles))
-                    gnerf_hip.conv3x3_epilogue_torgb(x, packed if packed is not None else _packed_prenormalised_weight(self, x.dtype), img, rgb_w, _cast_param(tg, 'bias', x.dtype),
-                                                     tg.conv_clamp, bias=_cast_param(self, 'bias', x.dtype), scale=dco, noise=noise, round_noise=True,
-                                                     gain=LRELU_GAIN * gain, clamp=clamp)
-                    return _TORGB_DONE
-                if own_plain:
-                    # convolution + demodulation + noise + bias + lrelu + clamp (+ the next layer's input scaling) in one launch
-                    x = gnerf_hip.conv3x3_epilogue(x, packed if packed is not None else _packed_prenormalised_weight(self, x.dtype), _cast_param(self, 'bias', x.dtype), scale=dco, noise=noise,
-                                                   round_noise=True, gain=LRELU_GAIN * gain, clamp=clamp, next_scale=nxt)
-                    return (x, folded) if next_layer is not None else x
-                epi = dict(bias=_cast_param(self, 'bias', x.dtype), scale=dco, act='lrelu', gain=LRELU_GAIN * gain, clamp=clamp, next_scale=nxt) if noise is None else None
-                if own_up:
-                    w_t = ('phases', packed if packed is not None else _packed_prenormalised_weight(self, x.dtype, transposed=True))        # the x2 layer's transposed convolution on our own kernel
-                else:
-                    w_t = _prenormalised_weight(self, x.dtype, cl, transposed=True) if self.up == 2 else None
-                out = self._resampled_conv(x, _prenormalised_weight(self, x.dtype, cl), 1, weight_t=w_t, epilogue=epi)
-                x, done = out if epi is not None else (out, False)
-                if not done:
-                    if nxt is not None and not _is_channels_last(x):          # (the convolution gave back another layout: scale separately)
-                        x = gnerf_hip.modconv_epilogue(x, _cast_param(self, 'bias', x.dtype), scale=dco, noise=noise, round_noise=True, act='lrelu', gain=LRELU_GAIN * gain, clamp=clamp)
-                        x = gnerf_hip.scale_channels(x, nxt)
-                    else:
-                        x = gnerf_hip.modconv_epilogue(x, _cast_param(self, 'bias', x.dtype), scale=dco, noise=noise, round_noise=True, act='lrelu', gain=LRELU_GAIN * gain, clamp=clamp,
-                                                       next_scale=nxt)
-                return (x, folded) if next_layer is not None else x
-            # per-sample weights in one launch, already in the order and memory format the convolution takes them
-            # ([N,O,I,3,3] for conv2d, [N,I,O,3,3] for conv_transpose2d: re-ordering 38 MB of fp32 weights per up-layer was a
-            # strided copy per call); constants of an orbit, like the styles
-            wts = _per_latent(self, w, ('wts', x.dtype, cl), mine,
-                              lambda: gnerf_hip.modulate_weights(self.weight, styles, True, out_dtype=x.dtype, transposed=self.up == 2, channels_last=cl)[0])
-            wts = wts.reshape(-1, *wts.shape[2:]) if n > 1 else wts[0]
-            epi = dict(bias=_cast_param(self, 'bias', x.dtype), act='lrelu', gain=LRELU_GAIN * gain, clamp=clamp) if (noise is None and n == 1) else None
-            x = self._resampled_conv(x.reshape(1, n * c_in, h, wd) if n > 1 else x, None if self.up == 2 else wts, n, weight_t=wts if self.up == 2 else None,
-                                     epilogue=epi)
-            x, done = x if epi is not None else (x, False)
-            x = x.reshape(n, c_out, *x.shape[2:]) if n > 1 else x
-            if not done:
-                x = gnerf_hip.modconv_epilogue(x, _cast_param(self, 'bias', x.dtype), noise=noise, act='lrelu', gain=LRELU_GAIN * gain, clamp=clamp)
-            return (x, folded) if next_layer is not None else x
-        # The reference's own flow (modulated_conv2d, networks_stylegan2.py:41-98, called from SynthesisLayer.forward :315-334 with
-        # padding = kernel_size // 2 and flip_weight = (up == 1)): PyTorch ops for the modulation, the convolution through
-        # torch_utils.ops.conv2d_resample and the demodulation through torch_utils.ops.fma -- the overlay's modules on a GPU, i.e. what
-        # a G-NeRF checkout gets from this repo without any of the kernels above.
-        if fused:
-            wts = _modulated_weights(self.weight, styles, True, x.dtype == torch.float16).to(x.dtype)          # [N,O,I,3,3]
-            c_out = wts.shape[1]
-            x = conv2d_resample.conv2d_resample(x=x.reshape(1, n * c_in, h, wd), w=wts.reshape(n * c_out, c_in, 3, 3), f=self.resample_filter,
-                                                up=self.up, padding=1, groups=n, flip_weight=(self.up == 1))
-            x = x.reshape(n, c_out, *x.shape[2:])
-            if noise is not None:
-                x = x.add_(noise)
-        else:
-            weight = self.weight
-            if x.dtype == torch.float16:
-                weight, styles = _prenormalize(weight, styles)
-            dcoefs = _demod_coefficients(weight, styles).to(x.dtype)[:, :, None, None]
-            x = conv2d_resample.conv2d_resample(x=x * styles.to(x.dtype)[:, :, None, None], w=weight.to(x.dtype), f=self.resample_filter,
-                                                up=self.up, padding=1, flip_weight=(self.up == 1))
-            x = fma.fma(x, dcoefs, noise.to(x.dtype)) if noise is not None else x * dcoefs
         clamp = self.conv_clamp * gain if self.conv_clamp is not None else None
-        x = bias_act.bias_act(x, self.bias.to(x.dtype), act='lrelu', gain=LRELU_GAIN * gain, clamp=clamp)
-        return (x, folded) if next_layer is not None else x
+        if route in _SHARED_ROUTES:     # (nxt: the next layer's input scaling, where this layer's epilogue carries it)
+            x, dco, packed, nxt = self._shared_operands(x, w, styles, route, prescaled, next_layer, next_w)
+            x = getattr(self, route)(x, dco, packed, nxt, noise, LRELU_GAIN * gain, clamp, torgb_tail)
+        else:
+            assert not prescaled
+            x, nxt = getattr(self, route)(x, w, styles, noise, LRELU_GAIN * gain, clamp), None
+        return (x, nxt is not None) if next_layer is not None else x
+
+    def _conv(self, x, weight, groups=1):
+        """3x3 convolution, padding 1, on the framework's kernels: weight [groups*O, I, 3, 3] (correlation form), in x's memory format."""
+        return F.conv2d(x, weight.contiguous(memory_format=torch.channels_last) if _is_channels_last(x) else weight, padding=1, groups=groups)
+
+    def _conv_transposed(self, x, weight_t, groups=1):
+        """Stride-2 transposed convolution on the framework's kernels, weight_t [groups*I, O, 3, 3] as is (the reference un-flips it twice): 2H+1."""
+        return F.conv_transpose2d(x, weight_t, stride=2, groups=groups)
+
+    def _blur(self, x, epilogue=None):
+        """The low-pass filter after the transposed convolution (gain 4, one pixel of padding: 2H+1 -> 2H) -> (x, whether `epilogue` ran):
+        keyword arguments of gnerf_hip.modconv_epilogue without noise, applied in the same pass where the fused kernel takes x (channels_last)."""
+        if epilogue is not None and _is_channels_last(x) and x.shape[1] % 8 == 0:
+            return gnerf_hip.blur_epilogue_channels_last(x, self.resample_filter, [1, 1, 1, 1], blur_gain=4, **epilogue), True
+        return upfirdn2d.upfirdn2d(x, self.resample_filter, padding=[1, 1, 1, 1], gain=4), False
+
+    def _f32x3(self, x, w, styles, noise, gain, clamp):
+        """fp32-GRADE arithmetic on the f16 matrix cores (csrc/conv3x3.hip, OUT32): the reference's un-fused form -- x * styles, convolution with
+        the layer's weight, demodulation coefficients after it (networks_stylegan2.py:76-83) -- with the scaling folded into the hi / lo split of
+        the activations and everything behind the convolution in its epilogue."""
+        dco = _per_latent(self, w, 'dco32', (self.affine.weight, self.affine.bias, self.weight),
+                          lambda: gnerf_hip.modulate_weights(self.weight, styles, True, out_dtype=torch.float32, want_weights=False, want_dcoefs=True)[1])
+        x3 = gnerf_hip.split_f16x3(x.contiguous(memory_format=torch.channels_last), styles)
+        if self.up == 1:
+            return gnerf_hip.conv3x3_f32x3_epilogue(x3, _packed_weight_f32x3(self), self.bias, scale=dco, noise=noise, gain=gain, clamp=clamp)
+        x, done = self._blur(gnerf_hip.conv_transpose3x3_s2_f32x3(x3, _packed_weight_f32x3(self, transposed=True)),
+                             dict(bias=self.bias, scale=dco, act='lrelu', gain=gain, clamp=clamp) if noise is None else None)
+        return x if done else gnerf_hip.modconv_epilogue(x, self.bias, scale=dco, noise=noise, act='lrelu', gain=gain, clamp=clamp)
+
+    def _per_sample(self, x, w, styles, noise, gain, clamp):
+        """Per-sample weights in one launch, in the order and memory format the grouped convolution takes ([N,O,I,3,3], or [N,I,O,3,3] for
+        conv_transpose2d: re-ordering 38 MB of fp32 weights per up-layer was a strided copy per call); constants of an orbit, like the styles."""
+        n, c_in, h, wd = x.shape
+        cl = _is_channels_last(x)
+        wts = _per_latent(self, w, ('wts', x.dtype, cl), (self.affine.weight, self.affine.bias, self.weight),
+                          lambda: gnerf_hip.modulate_weights(self.weight, styles, True, out_dtype=x.dtype, transposed=self.up == 2, channels_last=cl)[0])
+        wts = wts.reshape(-1, *wts.shape[2:]) if n > 1 else wts[0]
+        x = x.reshape(1, n * c_in, h, wd) if n > 1 else x
+        if self.up == 1:
+            x, done = self._conv(x, wts, n), False
+        else:
+            x, done = self._blur(self._conv_transposed(x, wts, n), dict(bias=self.bias, act='lrelu', gain=gain, clamp=clamp) if noise is None and n == 1 else None)
+        x = x.reshape(n, self.weight.shape[0], *x.shape[2:]) if n > 1 else x
+        return x if done else gnerf_hip.modconv_epilogue(x, self.bias, noise=noise, act='lrelu', gain=gain, clamp=clamp)
+
+    # -- fp16 layers: the shared-weight form (activations scaled by the styles, ONE convolution for the batch, demodulation in the epilogue), also
+    # at n == 1 (round 6): the call gen_videos.py makes (gen_videos.py:154-171), so the frame-by-frame orbit runs on csrc/conv3x3.hip too.
+
+    def _shared_operands(self, x, w, styles, route, prescaled, next_layer, next_w):
+        """(x, dco, packed, nxt): x with its input scaling -- from the previous layer (prescaled), in `packed` (our kernels' packed weights when the
+        batch shares ONE latent, round 6; else None) or a scaling pass --, the demodulation coefficients, the next layer's scaling or None."""
+        aff = (self.affine.weight, self.affine.bias)
+        mine = aff + (self.weight,)
+        cl = _is_channels_last(x)
+        dco = _per_latent(self, w, 'dco', mine, lambda: gnerf_hip.modulate_weights(self.weight, styles, True, out_dtype=x.dtype, want_weights=False, want_dcoefs=True)[1])
+        packed = None
+        if not prescaled:
+            nst = _per_latent(self, w, 'nstyles', aff, lambda: gnerf_hip.normalise_styles(styles))
+            if _LATENT_WEIGHTS and route != '_framework' and _rows_share_latent(w) and _latent_cacheable(w, mine):     # (packing per call would cost more than the scaling pass)
+                packed = _per_latent(self, w, ('packed_mod', x.dtype), mine, lambda: _packed_modulated_weight(self, nst[:1], x.dtype, transposed=self.up == 2))
+            else:
+                x = gnerf_hip.scale_channels(x, nst)
+        nxt = None
+        if next_layer is not None and cl and _fast_path(x, next_w, next_layer.weight, next_layer.bias, next_layer.noise_strength, next_layer.affine.weight, next_layer.affine.bias):
+            nxt = _per_latent(next_layer, next_w, 'nstyles', (next_layer.affine.weight, next_layer.affine.bias), lambda: gnerf_hip.normalise_styles(next_layer.affine(next_w)))
+        return x, dco, packed, nxt
+
+    def _own(self, x, dco, packed, nxt, noise, gain, clamp, torgb_tail):
+        """Convolution + demodulation + noise + bias + lrelu + clamp (+ the next layer's input scaling) in one launch (csrc/conv3x3.hip)."""
+        return gnerf_hip.conv3x3_epilogue(x, packed if packed is not None else _packed_prenormalised_weight(self, x.dtype), _cast_param(self, 'bias', x.dtype),
+                                          scale=dco, noise=noise, round_noise=True, gain=gain, clamp=clamp, next_scale=nxt)
+
+    def _own_torgb(self, x, dco, packed, nxt, noise, gain, clamp, torgb_tail):
+        """_own with the block's ToRGB in the same launch, added to the running image; no layer output is written (round 6)."""
+        tg, w_rgb, img = torgb_tail
+        rgb_aff = (tg.affine.weight, tg.affine.bias)
+        rgb_styles = _per_latent(tg, w_rgb, 'styles', rgb_aff, lambda: tg.affine(w_rgb) * tg.weight_gain)
+        rgb_w = _per_latent(tg, w_rgb, 'rgbw16', rgb_aff + (tg.weight,), lambda: gnerf_hip.torgb_weights(tg.weight, rgb_styles))
+        gnerf_hip.conv3x3_epilogue_torgb(x, packed if packed is not None else _packed_prenormalised_weight(self, x.dtype), img, rgb_w, _cast_param(tg, 'bias', x.dtype),
+                                         tg.conv_clamp, bias=_cast_param(self, 'bias', x.dtype), scale=dco, noise=noise, round_noise=True, gain=gain, clamp=clamp)
+
+    def _own_up(self, x, dco, packed, nxt, noise, gain, clamp, torgb_tail):
+        """The x2 layer's transposed convolution on our own kernel (csrc/conv3x3.hip's by-output-phase form), then the blur and epilogue."""
+        x = gnerf_hip.conv_transpose3x3_s2(x, packed if packed is not None else _packed_prenormalised_weight(self, x.dtype, transposed=True))
+        return self._shared_epilogue(x, dco, nxt, noise, gain, clamp)
+
+    def _framework(self, x, dco, packed, nxt, noise, gain, clamp, torgb_tail):
+        """The convolution on the framework's kernels (MIOpen), then the (blur and) epilogue."""
+        if self.up == 1:
+            x = self._conv(x, _prenormalised_weight(self, x.dtype, _is_channels_last(x)))
+        else:
+            x = self._conv_transposed(x, _prenormalised_weight(self, x.dtype, _is_channels_last(x), transposed=True))
+        return self._shared_epilogue(x, dco, nxt, noise, gain, clamp)
+
+    def _shared_epilogue(self, x, dco, nxt, noise, gain, clamp):
+        """After a shared-weight convolution: the blur (x2 layers), demodulation, noise, bias, lrelu, clamp and the next layer's input scaling."""
+        bias = _cast_param(self, 'bias', x.dtype)
+        if self.up == 2:
+            x, done = self._blur(x, dict(bias=bias, scale=dco, act='lrelu', gain=gain, clamp=clamp, next_scale=nxt) if noise is None else None)
+            if done:
+                return x
+        split = nxt is not None and not _is_channels_last(x)           # (the convolution gave back another layout: scale separately)
+        x = gnerf_hip.modconv_epilogue(x, bias, scale=dco, noise=noise, round_noise=True, act='lrelu', gain=gain, clamp=clamp, next_scale=None if split else nxt)
+        return gnerf_hip.scale_channels(x, nxt) if split else x
+
+    # -- the reference's own flow (modulated_conv2d, networks_stylegan2.py:41-98, from SynthesisLayer.forward :315-334, padding = 1, flip_weight =
+    # (up == 1)): PyTorch ops for the modulation, the convolution through torch_utils.ops.conv2d_resample and the demodulation through
+    # torch_utils.ops.fma -- the overlay's modules on a GPU, i.e. what a G-NeRF checkout gets from this repo without any of the kernels above.
+
+    def _reference_fused(self, x, w, styles, noise, gain, clamp):
+        n, c_in, h, wd = x.shape
+        wts = _modulated_weights(self.weight, styles, True, x.dtype == torch.float16).to(x.dtype)          # [N,O,I,3,3]
+        x = conv2d_resample.conv2d_resample(x=x.reshape(1, n * c_in, h, wd), w=wts.reshape(-1, c_in, 3, 3), f=self.resample_filter,
+                                            up=self.up, padding=1, groups=n, flip_weight=(self.up == 1))
+        x = x.reshape(n, -1, *x.shape[2:])
+        if noise is not None:
+            x = x.add_(noise)
+        return bias_act.bias_act(x, self.bias.to(x.dtype), act='lrelu', gain=gain, clamp=clamp)
+
+    def _reference_unfused(self, x, w, styles, noise, gain, clamp):
+        weight = self.weight
+        if x.dtype == torch.float16:
+            weight, styles = _prenormalize(weight, styles)
+        dcoefs = _demod_coefficients(weight, styles).to(x.dtype)[:, :, None, None]
+        x = conv2d_resample.conv2d_resample(x=x * styles.to(x.dtype)[:, :, None, None], w=weight.to(x.dtype), f=self.resample_filter,
+                                            up=self.up, padding=1, flip_weight=(self.up == 1))
+        x = fma.fma(x, dcoefs, noise.to(x.dtype)) if noise is not None else x * dcoefs
+        return bias_act.bias_act(x, self.bias.to(x.dtype), act='lrelu', gain=gain, clamp=clamp)
 
 
 class ToRGB(nn.Module):
@@ -490,46 +477,62 @@ class ToRGB(nn.Module):
         self.bias = nn.Parameter(torch.zeros(c_out))
         self.weight_gain = 1 / math.sqrt(c_in)
 
+    def route(self, x, w, fused=True):
+        """The route forward(x, w, fused) takes, as the name of its method."""
+        if not _fast_path(x, w, self.weight, self.bias, self.affine.weight, self.affine.bias):
+            return '_reference_fused' if fused else '_reference_unfused'
+        if x.dtype == torch.float16 and _is_channels_last(x) and self.weight.shape[0] == 3 and x.shape[1] in gnerf_hip.TORGB_CHANNELS:
+            return '_stream'
+        if x.dtype == torch.float32 and _is_channels_last(x):
+            return '_gemm'
+        return '_scaled' if x.dtype == torch.float16 and x.shape[0] > 1 else '_per_sample'
+
     def streams_into_image(self, x, w):
         """True when forward(x, w, ..., accumulate_into=img) adds the layer's output to the block's running image in its own launch."""
-        import gnerf_hip
-        return (_fast_path(x, w, self.weight, self.bias, self.affine.weight, self.affine.bias) and x.dtype == torch.float16 and _is_channels_last(x)
-                and self.weight.shape[0] == 3 and x.shape[1] in gnerf_hip.TORGB_CHANNELS)
+        return self.route(x, w) == '_stream'
 
     def forward(self, x, w, fused=True, accumulate_into=None):
-        n, c_in, h, wd = x.shape
+        route = self.route(x, w, fused)
+        assert accumulate_into is None or route == '_stream'
         aff = (self.affine.weight, self.affine.bias)
-        fast = _fast_path(x, w, self.weight, self.bias, *aff)
-        styles = _per_latent(self, w, 'styles', aff, lambda: self.affine(w) * self.weight_gain) if fast else self.affine(w) * self.weight_gain
-        assert accumulate_into is None or self.streams_into_image(x, w)
-        if fast:
-            import gnerf_hip
-            if x.dtype == torch.float16 and _is_channels_last(x) and self.weight.shape[0] == 3 and c_in in gnerf_hip.TORGB_CHANNELS:
-                return gnerf_hip.torgb_channels_last(x, self.weight, styles, _cast_param(self, 'bias', x.dtype), clamp=self.conv_clamp,
-                                                     accumulate_into=accumulate_into)      # one streaming read of x
-            if x.dtype == torch.float32 and _is_channels_last(x):
-                # float32 channels_last (what the fp32-grade convolution hands over): the 1x1 modulated convolution is a GEMM on the tensor's own
-                # memory, [H W, C] x [C, O] per sample with the styles folded into the small operand -- no scaling pass over x, no layout change,
-                # and bit-reproducible (MIOpen's fp32 channels_last 1x1 kernels for 512 -> 96 and 256 -> 96 are not: they differ by an ulp from
-                # call to call, tools/dbg_f32x3_det.py; the grouped per-sample form below would copy a batch back to NCHW for its reshape)
-                # [O, C] x [C, H W] per sample, the activations as the TRANSPOSED operand (their channels_last memory is [H W, C]): the result is
-                # a dense NCHW image, which is what it is added to (the block's running image, upsample2d_add_channels_last's `y`)
-                wmod = _per_latent(self, w, 'wmod', aff + (self.weight,), lambda: (self.weight.reshape(1, -1, c_in) * styles[:, None, :]).contiguous())
-                xt = x.permute(0, 2, 3, 1).reshape(n, h * wd, c_in).transpose(1, 2)
-                if self.conv_clamp is None:
-                    return torch.baddbmm(self.bias.reshape(1, -1, 1), wmod, xt).reshape(n, -1, h, wd)
-                x = torch.bmm(wmod, xt).reshape(n, -1, h, wd)
-            elif x.dtype == torch.float16 and n > 1:
-                x = F.conv2d(gnerf_hip.scale_channels(x, styles), self.weight.to(x.dtype))
-            else:
-                wts = _per_latent(self, w, ('wts', x.dtype), aff + (self.weight,), lambda: gnerf_hip.modulate_weights(self.weight, styles, False, out_dtype=x.dtype)[0])
-                x = F.conv2d(x.reshape(1, n * c_in, h, wd), wts.reshape(-1, c_in, 1, 1), groups=n).reshape(n, -1, h, wd)
-            return gnerf_hip.modconv_epilogue(x, _cast_param(self, 'bias', x.dtype), act='linear', gain=1.0, clamp=self.conv_clamp)
-        if fused:                       # (the reference's flow, as in StyledConv.forward)
-            wts = _modulated_weights(self.weight, styles, False, False).to(x.dtype)
-            x = conv2d_resample.conv2d_resample(x=x.reshape(1, n * c_in, h, wd), w=wts.reshape(-1, c_in, 1, 1), groups=n).reshape(n, -1, h, wd)
-        else:
-            x = conv2d_resample.conv2d_resample(x=x * styles.to(x.dtype)[:, :, None, None], w=self.weight.to(x.dtype))
+        styles = self.affine(w) * self.weight_gain if route in _REFERENCE_ROUTES else _per_latent(self, w, 'styles', aff, lambda: self.affine(w) * self.weight_gain)
+        return getattr(self, route)(x, w, styles, accumulate_into)
+
+    def _stream(self, x, w, styles, img):          # one streaming read of x, the result added to img when there is one
+        return gnerf_hip.torgb_channels_last(x, self.weight, styles, _cast_param(self, 'bias', x.dtype), clamp=self.conv_clamp, accumulate_into=img)
+
+    def _gemm(self, x, w, styles, img):
+        """float32 channels_last (what the fp32-grade convolution hands over): [O, C] x [C, H W] per sample on the tensor's own memory, the
+        styles folded into the small operand, the activations (memory [H W, C]) as the TRANSPOSED one -- no scaling pass, no layout change, and
+        bit-reproducible (MIOpen's fp32 channels_last 1x1 kernels for 512 -> 96 and 256 -> 96 differ by an ulp from call to call,
+        tools/dbg_f32x3_det.py).  The result is a dense NCHW image, what it is added to (the running image, upsample2d_add_channels_last's y)."""
+        n, c_in, h, wd = x.shape
+        wmod = _per_latent(self, w, 'wmod', (self.affine.weight, self.affine.bias, self.weight), lambda: (self.weight.reshape(1, -1, c_in) * styles[:, None, :]).contiguous())
+        xt = x.permute(0, 2, 3, 1).reshape(n, h * wd, c_in).transpose(1, 2)
+        if self.conv_clamp is None:
+            return torch.baddbmm(self.bias.reshape(1, -1, 1), wmod, xt).reshape(n, -1, h, wd)
+        return self._epilogue(torch.bmm(wmod, xt).reshape(n, -1, h, wd))
+
+    def _scaled(self, x, w, styles, img):          # an fp16 batch: the styles scale the activations, one convolution for the batch
+        return self._epilogue(F.conv2d(gnerf_hip.scale_channels(x, styles), self.weight.to(x.dtype)))
+
+    def _per_sample(self, x, w, styles, img):
+        n, c_in, h, wd = x.shape
+        wts = _per_latent(self, w, ('wts', x.dtype), (self.affine.weight, self.affine.bias, self.weight),
+                          lambda: gnerf_hip.modulate_weights(self.weight, styles, False, out_dtype=x.dtype)[0])
+        return self._epilogue(F.conv2d(x.reshape(1, n * c_in, h, wd), wts.reshape(-1, c_in, 1, 1), groups=n).reshape(n, -1, h, wd))
+
+    def _epilogue(self, x):
+        return gnerf_hip.modconv_epilogue(x, _cast_param(self, 'bias', x.dtype), act='linear', gain=1.0, clamp=self.conv_clamp)
+
+    def _reference_fused(self, x, w, styles, img):          # (the reference's flow, as in StyledConv)
+        n, c_in, h, wd = x.shape
+        wts = _modulated_weights(self.weight, styles, False, False).to(x.dtype)
+        x = conv2d_resample.conv2d_resample(x=x.reshape(1, n * c_in, h, wd), w=wts.reshape(-1, c_in, 1, 1), groups=n).reshape(n, -1, h, wd)
+        return bias_act.bias_act(x, self.bias.to(x.dtype), clamp=self.conv_clamp)
+
+    def _reference_unfused(self, x, w, styles, img):
+        x = conv2d_resample.conv2d_resample(x=x * styles.to(x.dtype)[:, :, None, None], w=self.weight.to(x.dtype))
         return bias_act.bias_act(x, self.bias.to(x.dtype), clamp=self.conv_clamp)
 
 
@@ -555,52 +558,48 @@ class Block(nn.Module):
     def forward(self, x, img, ws, noise_mode='random', force_fp32=False, fused_modconv=None, discard_x=False):
         """discard_x: the caller reads only the image (the superresolution's last block): x may come back as None."""
         dtype = torch.float16 if self.use_fp16 and ws.is_cuda and not force_fp32 else torch.float32
-        upsampled = False
         fused = (not self.training) if fused_modconv in (None, 'inference_only') else bool(fused_modconv)      # networks_stylegan2.py:433-434
         ws = ws.unbind(dim=1)
+        w1 = ws[self.num_conv - 1]
         if self.c_in == 0:
-            x = self.const.to(dtype).unsqueeze(0).repeat(ws[0].shape[0], 1, 1, 1)
-            x = self.conv1(x, ws[0], noise_mode, fused=fused)
+            x, folded = self.const.to(dtype).unsqueeze(0).repeat(ws[0].shape[0], 1, 1, 1), False
         else:
             fast = _fast_path(x, ws[0], self.conv0.weight, self.conv1.weight, self.torgb.weight)
-            # the reference's block entry fixes the layout as well as the type (networks_stylegan2.py:438, fp16_channels_last = False)
+            # the reference's block entry fixes the layout as well as the type (networks_stylegan2.py:438); the fast path runs fp16 channels_last:
+            # MIOpen's fp16 convolutions compute in it (else 0.63 ms of transposes in the superresolution, tools/bench_sr_conv_layout.py)
             x = x.to(dtype) if fast else x.to(dtype=dtype, memory_format=torch.contiguous_format)
-            if dtype == torch.float16 and _FP16_CHANNELS_LAST and x.is_cuda and x.shape[1] % 8 == 0 and fast:
+            if dtype == torch.float16 and x.is_cuda and x.shape[1] % 8 == 0 and fast:
                 x = x.contiguous(memory_format=torch.channels_last)
             x, folded = self.conv0(x, ws[0], noise_mode, fused=fused, next_layer=self.conv1, next_w=ws[1])
-            tail = None
-            if (discard_x and _FUSED_TORGB and img is not None and img.is_cuda and img.dtype == torch.float32 and not self.emit_channels_last
-                    and self.torgb.streams_into_image(x, ws[-1]) and not torch.is_grad_enabled()):
-                # the layer's convolution takes the ToRGB into its epilogue and adds the result to the (upsampled) running image: no x is written
-                if self.up == 2:
-                    img, upsampled = upfirdn2d.upsample2d(img, self.resample_filter), True
-                if img.is_contiguous() and tuple(img.shape) == (x.shape[0], 3, x.shape[2], x.shape[3]):
-                    tail = (self.torgb, ws[-1], img)
-            x = self.conv1(x, ws[1], noise_mode, fused=fused, prescaled=folded, torgb_tail=tail)
-            if x is _TORGB_DONE:
-                return None, img
-        if (img is not None and img.is_cuda and img.dtype == torch.float32 and not self.emit_channels_last and self.torgb.streams_into_image(x, ws[-1])
-                and not (torch.is_grad_enabled() and img.requires_grad)):
-            # upsample the running image, then let ToRGB add its output to it in its own launch (no fp16 y, no conversion, no add kernel)
-            if self.up == 2 and not upsampled:
-                img = upfirdn2d.upsample2d(img, self.resample_filter)
+        # img += ToRGB(x) in a launch that runs anyway where it can: ToRGB's streaming kernel adds to the (upsampled) running image -- no fp16
+        # y, no conversion, no add kernel --, and where nothing else reads x, conv1 takes the ToRGB into its epilogue and writes no x at all
+        into_img = img is not None and img.is_cuda and img.dtype == torch.float32 and not self.emit_channels_last and not (torch.is_grad_enabled() and img.requires_grad)
+        route = None
+        if (into_img and discard_x and _FUSED_TORGB and not torch.is_grad_enabled() and self.torgb.streams_into_image(x, ws[-1]) and img.is_contiguous()
+                and (img.shape[0], img.shape[1], img.shape[2] * self.up, img.shape[3] * self.up) == (x.shape[0], 3, x.shape[2], x.shape[3])):
+            route = self.conv1.route(x, w1, noise_mode, fused, torgb_tail=True)
+        y = None                        # (ToRGB's output, where it is not added to the image in a launch of its own)
+        if route != '_own_torgb':
+            x = self.conv1(x, w1, noise_mode, fused=fused, prescaled=folded, route=route)
+            if not (into_img and self.torgb.streams_into_image(x, ws[-1])):
+                y = self.torgb(x, ws[-1], fused=fused).float()
+        if img is not None and self.up == 2 and not (self.emit_channels_last and img.is_cuda):
+            img = upfirdn2d.upsample2d(img, self.resample_filter)
+        if route == '_own_torgb':
+            self.conv1(x, w1, noise_mode, fused=fused, prescaled=folded, torgb_tail=(self.torgb, ws[-1], img), route=route)
+            return None, img
+        if y is None:
             if img.is_contiguous() and tuple(img.shape) == (x.shape[0], 3, x.shape[2], x.shape[3]):
                 return x, self.torgb(x, ws[-1], fused=fused, accumulate_into=img)
             y = self.torgb(x, ws[-1], fused=fused).float()
-            return x, img.add_(y)
-        y = self.torgb(x, ws[-1], fused=fused).float()
-        if img is not None and self.up == 2 and self.emit_channels_last and img.is_cuda:
-            return x, upfirdn2d.upsample2d_add_channels_last(img, y.contiguous(), self.resample_filter)
-        if img is not None and self.up == 2:
-            img = upfirdn2d.upsample2d(img, self.resample_filter)
         if img is None:
             return x, y
-        if torch.is_grad_enabled() and (img.requires_grad or y.requires_grad):
-            # Out of place under autograd: the super-resolution's first block receives `img` as a VIEW of the feature image it
-            # also convolves (triplane.py:86), and in fp32 the in-place form overwrites what that convolution saved for its
-            # backward pass (the reference's own block64 raises here when trained without fp16; with fp16 its cast makes a copy).
-            return x, img + y
-        return x, img.add_(y)
+        if self.up == 2 and self.emit_channels_last and img.is_cuda:
+            return x, upfirdn2d.upsample2d_add_channels_last(img, y.contiguous(), self.resample_filter)
+        # Out of place under autograd: the super-resolution's first block receives `img` as a VIEW of the feature image it also convolves
+        # (triplane.py:86), and in fp32 the in-place form overwrites what that convolution saved for its backward pass (the reference's own
+        # block64 raises here when trained without fp16; with fp16 its cast makes a copy).
+        return x, (img + y if torch.is_grad_enabled() and (img.requires_grad or y.requires_grad) else img.add_(y))
 
 
 class Synthesis(nn.Module):

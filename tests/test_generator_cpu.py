@@ -140,15 +140,24 @@ def record_reference(ref):
     np.savez_compressed(FIXTURE, **{'gen_' + k: v for k, v in gen.items()}, **{'shapes_' + k: v for k, v in shapes.items()})
 
 
-def test_clear_latent_caches():
+def test_clear_latent_caches_drops_every_cache():
     """gnerf_generator.clear_latent_caches drops the per-latent / per-parameter caches the fast path hangs on the modules (ADVICE r3:
-    several hundred MB over the backbone with no release hook)."""
+    several hundred MB over the backbone with no release hook): the converted biases, the pre-normalised weights and the packed weights of
+    our own kernels (fp16 and fp32-grade, plain and transposed) included."""
     import torch
     import gnerf_generator as GG
     m = torch.nn.Linear(2, 2)
     m.__dict__['_gnerf_latent_cache'] = {'x': (None, None, torch.zeros(3))}
-    m.__dict__['_gnerf_prenorm'] = {'k': (None, torch.zeros(3))}
-    root = torch.nn.Sequential(m)
+    conv = GG.StyledConv(8, 128, 16, 8).requires_grad_(False)
+    with torch.no_grad():
+        cached = [GG._cast_param(conv, 'bias', torch.float16), GG._prenormalised_weight(conv, torch.float16, channels_last=True),
+                  GG._packed_prenormalised_weight(conv, torch.float16), GG._packed_prenormalised_weight(conv, torch.float16, transposed=True),
+                  GG._packed_weight_f32x3(conv), GG._packed_weight_f32x3(conv, transposed=True)]
+        again = [GG._cast_param(conv, 'bias', torch.float16), GG._prenormalised_weight(conv, torch.float16, channels_last=True),
+                 GG._packed_prenormalised_weight(conv, torch.float16), GG._packed_prenormalised_weight(conv, torch.float16, transposed=True),
+                 GG._packed_weight_f32x3(conv), GG._packed_weight_f32x3(conv, transposed=True)]
+    assert all(a is b for a, b in zip(cached, again))                  # each is made once per parameter version
+    root = torch.nn.Sequential(m, conv)
     assert len(GG.latent_cache_tensors(root)) == 1
     GG.clear_latent_caches(root)
-    assert '_gnerf_latent_cache' not in m.__dict__ and '_gnerf_prenorm' not in m.__dict__ and GG.latent_cache_tensors(root) == []
+    assert GG.latent_cache_tensors(root) == [] and not any(k.startswith('_gnerf') for mod in root.modules() for k in mod.__dict__)

@@ -21,7 +21,7 @@ def wrap(name, mod):
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record(); y = orig(x, *a, **k); e1.record()
         y0 = y[0] if isinstance(y, tuple) else y
-        records.setdefault(name, {'in': list(x.shape), 'dtype': str(x.dtype).replace('torch.', ''), 'out': list(y0.shape), 'fmt': 'channels_last' if (x.ndim == 4 and x.stride(1) == 1 and x.shape[1] > 1) else 'nchw', 'ev': []})['ev'].append((e0, e1))
+        records.setdefault(name, {'in': list(x.shape), 'dtype': str(x.dtype).replace('torch.', ''), 'out': None if y0 is None else list(y0.shape), 'fmt': 'channels_last' if (x.ndim == 4 and x.stride(1) == 1 and x.shape[1] > 1) else 'nchw', 'ev': []})['ev'].append((e0, e1))
         return y
     mod.forward = fwd
 for name, mod in G.named_modules():
