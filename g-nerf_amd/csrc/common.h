@@ -61,6 +61,12 @@ template <> __device__ __forceinline__ void store_as<__half>(__half* p, int64_t 
 constexpr int kNumCU = 256;   // MI355X
 constexpr int kNumXCD = 8;
 
+// The render workspace (gnerf_render_workspace_bytes; zeroed once by the caller, left zeroed by every call) is shared by the
+// render calls (words below kStatsWord0: depth range, diagnostics, per-item ranges) and gnerf_planes_to_nhwc_stats' max |planes|
+// reduction: kStatsShards lines of {max bits, ticket}, then one line for the total, 128 bytes apart.
+constexpr int kStatsWord0 = 8224, kStatsShards = 32, kStatsLineWords = 32;
+constexpr int kWorkspaceWords = kStatsWord0 + (kStatsShards + 1) * kStatsLineWords;
+
 // ---- the modulated convolution's epilogue on one vector of adjacent channels (shared by csrc/modconv.hip and the fused
 // blur + epilogue of csrc/upfirdn2d.hip):
 //   t = round_T(x * T(sc) + noise)        (SCALE / NOISE; the fp16 form is one packed half FMA / multiply per pair, see modconv.hip)

@@ -2,8 +2,7 @@
 //
 // gnerf_planes_to_nhwc: the reference keeps tri-planes NCHW (training/triplane.py:74), where the 32 channels
 // of one texel are 256 KB apart.  The renderer wants one texel = one 128-byte line, so planes are
-// transposed once per batch to [plane, y, x, channel] through a 32x64 LDS tile: reads are coalesced
-// along x, writes are whole texels.
+// transposed once per batch to [plane, y, x, channel]: reads are coalesced along x, writes are whole texels.
 //
 // gnerf_make_rays: RaySampler.forward (training/volumetric_rendering/ray_sampler.py:24-63).
 
@@ -43,13 +42,42 @@ __device__ __forceinline__ void publish_absmax(unsigned m, unsigned* out) {
     }
 }
 
-// (Measured and dropped, round 3: the same tile with 16-byte global accesses on both sides -- a lane reads four pixels of a channel and
-// writes four channels of a pixel.  Alone it is faster, 34.5 -> 29.8 us for 2 x 100 MB on a warm Infinity Cache; inside bench.py's step,
-// where the source comes from HBM and the render kernel reads the result next, the step got SLOWER: 0.578 -> 0.591 ms, two runs each
-// way on one box, render call unchanged.  The dword form stays.)
+// The same maximum without a zeroed output word (no fill launch in front): the workgroups of a launch reduce into the render
+// workspace's statistics lines (common.h), which are zero when idle.  Workgroup b goes to shard b % shards; each shard is a
+// {max bits, ticket} line, so a shard sees gridDim / 32 same-address atomics, not gridDim.  Every access to those words is an
+// agent-scope atomic, and a workgroup's ticket add is issued only after its maximum has returned (s_waitcnt vmcnt(0)): the
+// workgroup whose add returns the shard's last ticket therefore reads every maximum of its shard, and it takes the shard's
+// value on to the total line the same way.  The last shard's last workgroup writes the float and leaves every word zero.
+// Two streams never share a workspace, so concurrent calls do not meet.
+__device__ __forceinline__ void publish_absmax_ticket(unsigned m, unsigned* ws, float* out) {
+    __shared__ unsigned wave_max[4];
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) m = max(m, (unsigned)__shfl_xor((int)m, o));
+    if ((threadIdx.x & 63) == 0) wave_max[threadIdx.x >> 6] = m;
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    const unsigned b = max(max(wave_max[0], wave_max[1]), max(wave_max[2], wave_max[3]));
+    const unsigned shards = min(gridDim.x, unsigned(kStatsShards));
+    const unsigned s = blockIdx.x % shards, members = (gridDim.x - s + shards - 1) / shards;
+    unsigned* sh = ws + kStatsWord0 + kStatsLineWords * s;
+    unsigned* total = ws + kStatsWord0 + kStatsLineWords * kStatsShards;
+    if (b > __hip_atomic_load(sh, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(sh, b);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                  // the maximum is performed before the ticket is taken
+    if (atomicAdd(sh + 1, 1u) != members - 1) return;
+    const unsigned v = atomicExch(sh, 0u);                            // the shard's maximum; the shard back to idle
+    atomicExch(sh + 1, 0u);
+    if (v > __hip_atomic_load(total, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(total, v);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    if (atomicAdd(total + 1, 1u) != shards - 1) return;
+    const unsigned a = atomicExch(total, 0u);
+    atomicExch(total + 1, 0u);
+    *out = __uint_as_float(a);
+}
+
+// The general form (any channel count and size): a 32 x 64 LDS tile, dword accesses.
 template <bool STATS>
 __global__ __launch_bounds__(256) void nchw_to_nhwc_kernel(const float* __restrict__ src, float* __restrict__ dst,
-                                                           int c, int64_t hw, int tiles_p, int tiles_c, unsigned* absmax) {
+                                                           int c, int64_t hw, int tiles_p, int tiles_c, unsigned* ws, float* absmax) {
     __shared__ float tile[CT][PT + 1];
     int64_t t = blockIdx.x;
     const int tp = int(t % tiles_p); t /= tiles_p;
@@ -76,7 +104,56 @@ __global__ __launch_bounds__(256) void nchw_to_nhwc_kernel(const float* __restri
         const int px = e / CT, ch = e % CT;
         if (c0 + ch < c && p0 + px < hw) d[(p0 + px) * c + c0 + ch] = tile[ch][px];
     }
-    if (STATS) publish_absmax(amax, absmax);
+    if (STATS) publish_absmax_ticket(amax, ws, absmax);
+}
+
+// The form for 32k channels, h w % 4 == 0 and 16-byte aligned tensors (the renderer's planes): no LDS, 16-byte accesses on both
+// sides.  Lane cg + 8 xg of a wave holds the 4 x 4 block channels 4 cg .. 4 cg + 3 x pixels 4 xg .. 4 xg + 3: it loads four rows
+// along x and stores four channel quads, one per pixel.  A wave's load instruction reads eight whole 128-byte lines (32 pixels of
+// eight channels); a store instruction writes eight whole texels.  Workgroup: 32 channels x kV4Px pixels, two 16-byte loads of each
+// channel row in flight per lane.
+// In the step (profiles/r07_step_*_kernel_stats.csv, same box): 38.3 us where the dword form took 53.0 plus 4.3 for its fill launch;
+// the step 0.520 against 0.536 ms alternating (profiles/r07_repack_ab.jsonl), render kernel unchanged.  (Round 3's 16-byte form, which
+// went through an LDS tile, was faster alone but slowed the step; that code is gone and was not re-measured.)
+constexpr int kV4Trips = 2, kV4Px = 4 * 32 * kV4Trips;
+template <bool STATS>
+__global__ __launch_bounds__(256) void nchw_to_nhwc_v4_kernel(const float* __restrict__ src, float* __restrict__ dst,
+                                                              int c, int64_t hw, int tiles_p, int tiles_c, unsigned* ws, float* absmax) {
+    int64_t t = blockIdx.x;
+    const int tp = int(t % tiles_p); t /= tiles_p;
+    const int tc = int(t % tiles_c); t /= tiles_c;
+    const int64_t plane = t;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int cg = lane & 7, xg = lane >> 3;
+    const int ch0 = tc * CT + 4 * cg;
+    const float* s = src + (plane * c + ch0) * hw;
+    float* d = dst + plane * hw * c + ch0;
+    float4 v[kV4Trips][4];
+    int64_t px[kV4Trips];
+#pragma unroll
+    for (int j = 0; j < kV4Trips; j++) {
+        px[j] = int64_t(tp) * kV4Px + (j * 4 + wave) * 32 + 4 * xg;        // hw % 4 == 0: the four pixels are all in or all out
+        const int64_t pl = px[j] < hw ? px[j] : hw - 4;                     // past the end: a duplicate load, not a branch per load
+#pragma unroll
+        for (int k = 0; k < 4; k++) v[j][k] = *reinterpret_cast<const float4*>(s + k * hw + pl);
+    }
+    unsigned amax = 0u;
+#pragma unroll
+    for (int j = 0; j < kV4Trips; j++) {
+        if (px[j] < hw) {
+            float* o = d + px[j] * c;
+            *reinterpret_cast<float4*>(o)         = make_float4(v[j][0].x, v[j][1].x, v[j][2].x, v[j][3].x);
+            *reinterpret_cast<float4*>(o + c)     = make_float4(v[j][0].y, v[j][1].y, v[j][2].y, v[j][3].y);
+            *reinterpret_cast<float4*>(o + 2 * c) = make_float4(v[j][0].z, v[j][1].z, v[j][2].z, v[j][3].z);
+            *reinterpret_cast<float4*>(o + 3 * c) = make_float4(v[j][0].w, v[j][1].w, v[j][2].w, v[j][3].w);
+        }
+        if (STATS) {                                                        // (a duplicate cannot raise the maximum)
+#pragma unroll
+            for (int k = 0; k < 4; k++)
+                amax = max(max(amax, abs_bits(v[j][k].x)), max(max(abs_bits(v[j][k].y), abs_bits(v[j][k].z)), abs_bits(v[j][k].w)));
+        }
+    }
+    if (STATS) publish_absmax_ticket(amax, ws, absmax);
 }
 
 // Eight 16-byte loads in flight per lane on every trip, the ragged end included: an index past the end is clamped onto the last
@@ -304,34 +381,34 @@ extern "C" int gnerf_to_uint8_nhwc(const float* img, unsigned char* out, int n, 
     return check_launch("to_uint8_nhwc");
 }
 
-static int planes_to_nhwc_impl(const float* planes_nchw, float* planes_nhwc, int np, int c, int h, int w, float* absmax, bool stats,
-                               gnerf_stream_t stream) {
+static int planes_to_nhwc_impl(const float* planes_nchw, float* planes_nhwc, int np, int c, int h, int w, float* absmax, void* workspace,
+                               bool stats, gnerf_stream_t stream) {
     using namespace gnerf;
-    if (!planes_nchw || !planes_nhwc || (stats && !absmax)) return fail(GNERF_E_ARG, "planes_to_nhwc: null pointer");
+    if (!planes_nchw || !planes_nhwc || (stats && (!absmax || !workspace))) return fail(GNERF_E_ARG, "planes_to_nhwc: null pointer");
     if (np < 1 || c < 1 || h < 1 || w < 1) return fail(GNERF_E_ARG, "planes_to_nhwc: empty tensor");
     const int64_t hw = int64_t(h) * w;
-    const int tiles_p = int((hw + PT - 1) / PT), tiles_c = (c + CT - 1) / CT;
+    const bool v4 = c % CT == 0 && hw % 4 == 0 && !(reinterpret_cast<uintptr_t>(planes_nchw) & 15) && !(reinterpret_cast<uintptr_t>(planes_nhwc) & 15);
+    const int px_tile = v4 ? kV4Px : PT;
+    const int tiles_p = int((hw + px_tile - 1) / px_tile), tiles_c = (c + CT - 1) / CT;
     const int64_t blocks = int64_t(tiles_p) * tiles_c * np;
     if (blocks > INT32_MAX) return fail(GNERF_E_ARG, "planes_to_nhwc: tensor too large");
-    if (stats) {
-        if (hipMemsetAsync(absmax, 0, sizeof(float), as_stream(stream)) != hipSuccess) return fail(GNERF_E_LAUNCH, "planes_to_nhwc: memset failed");
-        hipLaunchKernelGGL(nchw_to_nhwc_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, as_stream(stream),
-                           planes_nchw, planes_nhwc, c, hw, tiles_p, tiles_c, reinterpret_cast<unsigned*>(absmax));
-    } else {
-        hipLaunchKernelGGL(nchw_to_nhwc_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, as_stream(stream),
-                           planes_nchw, planes_nhwc, c, hw, tiles_p, tiles_c, static_cast<unsigned*>(nullptr));
-    }
+    unsigned* ws = static_cast<unsigned*>(workspace);
+    const dim3 grid((unsigned)blocks), block(256);
+    if (v4 && stats) hipLaunchKernelGGL(nchw_to_nhwc_v4_kernel<true>, grid, block, 0, as_stream(stream), planes_nchw, planes_nhwc, c, hw, tiles_p, tiles_c, ws, absmax);
+    else if (v4) hipLaunchKernelGGL(nchw_to_nhwc_v4_kernel<false>, grid, block, 0, as_stream(stream), planes_nchw, planes_nhwc, c, hw, tiles_p, tiles_c, ws, absmax);
+    else if (stats) hipLaunchKernelGGL(nchw_to_nhwc_kernel<true>, grid, block, 0, as_stream(stream), planes_nchw, planes_nhwc, c, hw, tiles_p, tiles_c, ws, absmax);
+    else hipLaunchKernelGGL(nchw_to_nhwc_kernel<false>, grid, block, 0, as_stream(stream), planes_nchw, planes_nhwc, c, hw, tiles_p, tiles_c, ws, absmax);
     return check_launch("planes_to_nhwc");
 }
 
 extern "C" int gnerf_planes_to_nhwc(const float* planes_nchw, float* planes_nhwc, int np, int c, int h, int w,
                                     gnerf_stream_t stream) {
-    return planes_to_nhwc_impl(planes_nchw, planes_nhwc, np, c, h, w, nullptr, false, stream);
+    return planes_to_nhwc_impl(planes_nchw, planes_nhwc, np, c, h, w, nullptr, nullptr, false, stream);
 }
 
 extern "C" int gnerf_planes_to_nhwc_stats(const float* planes_nchw, float* planes_nhwc, int np, int c, int h, int w,
-                                          float* absmax, gnerf_stream_t stream) {
-    return planes_to_nhwc_impl(planes_nchw, planes_nhwc, np, c, h, w, absmax, true, stream);
+                                          float* absmax, void* workspace, gnerf_stream_t stream) {
+    return planes_to_nhwc_impl(planes_nchw, planes_nhwc, np, c, h, w, absmax, workspace, true, stream);
 }
 
 extern "C" int gnerf_upsample2x_add_nhwc(const float* img, const float* y, const float* f_host, int flip, float gain, float* out,

@@ -807,7 +807,8 @@ void fill_pitches(Params& P) {
 
 }  // namespace
 
-extern "C" size_t gnerf_render_workspace_bytes(void) { return size_t(kClampItemWord0 + 2 * kClampMaxItems) * 4; }
+static_assert(kClampItemWord0 + 2 * kClampMaxItems <= kStatsWord0, "render words overlap the plane statistics");
+extern "C" size_t gnerf_render_workspace_bytes(void) { return size_t(kWorkspaceWords) * 4; }
 
 // Validation and derived launch parameters shared by the forward and backward entry points.
 static int fill_params(const gnerf_render_params* p, Params& P) {

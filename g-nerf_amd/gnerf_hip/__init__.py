@@ -23,7 +23,7 @@ _DTYPE_CODE = {torch.float32: F32, torch.float16: F16, torch.float64: F64}
 
 MAX_SAMPLES = 256
 DEBUG_SLOTS = 8
-ABI_VERSION = 11
+ABI_VERSION = 12
 # decoder arithmetic of the fused renderer (GNERF_MLP_* in include/gnerf_hip.h)
 MLP_MODES = {'auto': 0, 'f16x3': 1, 'f32': 2}
 
@@ -82,7 +82,7 @@ SIGNATURES = {
     'gnerf_grid_sample_2d': (_c_i, [_c_p, _c_p, _c_p, _c_i, _c_i, _c_i, _c_i, _c_i, ctypes.POINTER(_c_i64), _c_i, _c_i, _c_p]),
     'gnerf_grid_sample_2d_backward': (_c_i, [_c_p, _c_p, _c_p, _c_p, _c_p, _c_i, _c_i, _c_i, _c_i, _c_i, ctypes.POINTER(_c_i64), _c_i, _c_i, _c_p]),
     'gnerf_planes_to_nhwc': (_c_i, [_c_p, _c_p, _c_i, _c_i, _c_i, _c_i, _c_p]),
-    'gnerf_planes_to_nhwc_stats': (_c_i, [_c_p, _c_p, _c_i, _c_i, _c_i, _c_i, _c_p, _c_p]),
+    'gnerf_planes_to_nhwc_stats': (_c_i, [_c_p, _c_p, _c_i, _c_i, _c_i, _c_i, _c_p, _c_p, _c_p]),
     'gnerf_planes_absmax': (_c_i, [_c_p, _c_i64, _c_p, _c_p]),
     'gnerf_planes_from_nhwc': (_c_i, [_c_p, _c_p, _c_i, _c_i, _c_i, _c_i, _c_p]),
     'gnerf_make_rays': (_c_i, [_c_p, _c_p, _c_i, _c_i, _c_p, _c_p, _c_p]),
@@ -467,7 +467,7 @@ def planes_to_nhwc(planes, with_absmax=False):
     if with_absmax:
         amax = torch.empty([1], dtype=torch.float32, device=p.device)
         with _on_device(p.device):
-            code = load().gnerf_planes_to_nhwc_stats(_ptr(p), _ptr(out), np_, c, h, w, _ptr(amax), _stream(p))
+            code = load().gnerf_planes_to_nhwc_stats(_ptr(p), _ptr(out), np_, c, h, w, _ptr(amax), _workspace(p.device).data_ptr(), _stream(p))
         _check(code, 'gnerf_planes_to_nhwc_stats')
         return out, amax
     with _on_device(p.device):

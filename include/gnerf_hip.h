@@ -36,7 +36,7 @@
 extern "C" {
 #endif
 
-#define GNERF_ABI_VERSION 11
+#define GNERF_ABI_VERSION 12
 
 /* error codes */
 #define GNERF_OK            0
@@ -257,9 +257,11 @@ int gnerf_grid_sample_2d_backward(const void* grad_out, const void* image, const
 int gnerf_planes_to_nhwc(const float* planes_nchw, float* planes_nhwc, int np, int c, int h, int w,
                          gnerf_stream_t stream);
 /* The same layout change, also measuring max |planes| on the way (the planes are read anyway): *absmax (one device
- * float, overwritten) feeds gnerf_render_params.planes_absmax.  A NaN anywhere in the planes makes *absmax NaN. */
+ * float, overwritten) feeds gnerf_render_params.planes_absmax.  A NaN anywhere in the planes makes *absmax NaN.
+ * workspace: this stream's render workspace (gnerf_render_workspace_bytes(), zeroed once; every call leaves it zeroed, as
+ * gnerf_render_forward does); calls on different streams need different workspaces. */
 int gnerf_planes_to_nhwc_stats(const float* planes_nchw, float* planes_nhwc, int np, int c, int h, int w,
-                               float* absmax, gnerf_stream_t stream);
+                               float* absmax, void* workspace, gnerf_stream_t stream);
 /* max |x| over `numel` floats (any layout) -> *absmax (one device float, overwritten). */
 int gnerf_planes_absmax(const float* planes, int64_t numel, float* absmax, gnerf_stream_t stream);
 /* The tri-plane producer's last step, writing the renderer's layout directly (no layout change afterwards):
