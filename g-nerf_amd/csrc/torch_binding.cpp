@@ -9,7 +9,8 @@
 // tensors, outputs are allocated here with torch::empty, the launch goes to the current stream of x's device under a device
 // guard) -- and nothing else: no kernels live here, every function validates, allocates and calls the C ABI.  It exists for host
 // cost: a call through ctypes spends 10-12 us marshalling arguments in Python, this path ~3.
-// Also exported: render_forward (the fused renderer has no reference plugin; same C ABI call as gnerf_hip.render_forward).
+// Also exported: render_forward (the fused renderer has no reference plugin; same C ABI call as gnerf_hip.render_forward) and
+// marching_cubes (gnerf_hip.marching_cubes' count -> read counts -> emit sequence).
 //
 // Built ahead of time by csrc/build.sh (g++, no hipcc: there is no device code) into g-nerf_amd/gnerf_hip/gnerf_torch_ext.so.
 
@@ -262,6 +263,37 @@ std::tuple<Tensor, Tensor, Tensor> render_forward(Tensor planes_nhwc, int64_t n_
     return std::make_tuple(rgb, depth, wsum);
 }
 
+// ------------------------------------------------------------------------------------------------ marching cubes (shape_utils.py:58-61)
+
+// volume: contiguous float32 [d0, d1, d2] on a GPU.  Returns (verts [V,3] float32, faces [T,3] int32, counts int64 [3] on the host:
+// V, T, non-finite values).  When the volume holds a non-finite value or V >= 2^31 the emit pass is skipped and verts / faces are
+// empty: the Python layer reads the counts and raises.
+std::tuple<Tensor, Tensor, Tensor> marching_cubes(Tensor volume, double level) {
+    TORCH_CHECK(volume.is_cuda() && volume.scalar_type() == torch::kFloat32 && volume.is_contiguous() && volume.dim() == 3,
+                "marching_cubes: volume must be a contiguous float32 [d0, d1, d2] GPU tensor");
+    TORCH_CHECK(volume.size(0) >= 2 && volume.size(1) >= 2 && volume.size(2) >= 2 && volume.numel() < (int64_t(1) << 31),
+                "marching_cubes: every dimension must be >= 2 and the volume must have fewer than 2^31 points");
+    const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(at::device_of(volume));
+    const int d0 = int(volume.size(0)), d1 = int(volume.size(1)), d2 = int(volume.size(2));
+    size_t bytes = 0;
+    check_rc(gnerf_marching_cubes_workspace_bytes(d0, d1, d2, &bytes), "gnerf_marching_cubes_workspace_bytes");
+    Tensor ws = torch::empty({int64_t(bytes)}, volume.options().dtype(torch::kUInt8));
+    Tensor counts = torch::empty({3}, volume.options().dtype(torch::kInt64));
+    const float* vol = volume.data_ptr<float>();
+    check_rc(gnerf_marching_cubes_count(vol, d0, d1, d2, float(level), ws.data_ptr(), counts.data_ptr<int64_t>(), current_stream()),
+             "gnerf_marching_cubes_count");
+    Tensor host = counts.cpu();                                    // the op's one synchronisation
+    const int64_t* c = host.data_ptr<int64_t>();
+    const bool emit = c[2] == 0 && c[0] < (int64_t(1) << 31) && c[0] > 0;
+    Tensor verts = torch::empty({emit ? c[0] : 0, 3}, volume.options());
+    Tensor faces = torch::empty({emit ? c[1] : 0, 3}, volume.options().dtype(torch::kInt32));
+    if (emit)
+        check_rc(gnerf_marching_cubes_emit(vol, d0, d1, d2, float(level), ws.data_ptr(), verts.data_ptr<float>(),
+                                           c[1] > 0 ? faces.data_ptr<int32_t>() : nullptr, current_stream()),
+                 "gnerf_marching_cubes_emit");
+    return std::make_tuple(verts, faces, host);
+}
+
 }  // namespace
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -270,6 +302,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("filtered_lrelu", &filtered_lrelu);
     m.def("filtered_lrelu_act_", &filtered_lrelu_act_);
     m.def("render_forward", &render_forward);
+    m.def("marching_cubes", &marching_cubes);
     // the header version THIS extension was compiled against (a compile-time constant: gnerf_abi_version() would resolve in
     // libgnerf_hip.so at run time and compare the library with itself); gnerf_hip.ext() checks both against its own
     m.def("abi_version", []() { return int(GNERF_ABI_VERSION); });

@@ -17,7 +17,9 @@ Run with this repo's g-nerf_amd/ in front of the reference's g_nerf/ on PYTHONPA
 `--random-init` builds the FFHQ-config TriPlaneGenerator with seeded random weights and a random z instead of loading
 pickles (there are no checkpoints or network access in the build environment); where the reference tree is absent it is
 this repo's inference-only equivalent (gnerf_generator.Generator).  `--graph` replays the per-frame launch sequence from a
-HIP graph captured once (FrameProgram); `--shapes out.npy` also extracts the 512^3 density volume of gen_videos.py --shapes.
+HIP graph captured once (FrameProgram); `--shapes out.npy` also extracts the 512^3 density volume of gen_videos.py --shapes,
+`--shapes-mrc out.mrc` writes it as the reference's .mrc, and `--mesh out.ply` meshes it (shape_utils.py's step, shape_mi355x) while it
+is still on the device.
 """
 
 import argparse
@@ -233,6 +235,20 @@ def extract_density_grid(G, ws, resolution=512, max_batch=10000000, crop=True):
     return vol
 
 
+def mesh_density_grid(vol, ply_path, level=10.0):
+    """--mesh: the mesh shape_utils.convert_mrc makes of the .mrc of this volume (shape_utils.py:103-105: transpose(2, 1, 0), voxel
+    size 1, origin 0), made where the volume lives -- on a GPU the marching-cubes kernel reads it in HBM, only the mesh comes to the host.
+    Writes `ply_path`; returns (vertex count, triangle count, seconds spent in marching cubes)."""
+    import shape_mi355x
+    t0 = time.perf_counter()
+    verts, faces = shape_mi355x.marching_cubes(vol.permute(2, 1, 0).contiguous(), level)     # (reads its counts: synchronised)
+    dt = time.perf_counter() - t0
+    if isinstance(verts, torch.Tensor):
+        verts, faces = verts.cpu().numpy(), faces.cpu().numpy()
+    shape_mi355x.write_ply(ply_path, verts, faces)
+    return len(verts), len(faces), dt
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument('--network', help='generator pickle (G_ema)')
@@ -248,6 +264,9 @@ def main():
     ap.add_argument('--frames-per-call', type=int, default=1, help='cameras per synthesis call (views of the one latent in one renderer launch)')
     ap.add_argument('--out', default=None, help='write frames to this .npy (rank 0)')
     ap.add_argument('--shapes', default=None, help='also extract the 512^3 density volume (gen_videos.py --shapes) and save it to this .npy (rank 0)')
+    ap.add_argument('--shapes-mrc', default=None, help='also write the density volume as the reference\'s .mrc (gen_videos.py:221-222; rank 0)')
+    ap.add_argument('--mesh', default=None, help='also mesh the density volume on the device and write this .ply (shape_utils.py; rank 0)')
+    ap.add_argument('--mesh-level', type=float, default=10, help='isosurface level of --mesh (shape_utils.py:111)')
     ap.add_argument('--voxel-res', type=int, default=512)
     ap.add_argument('--no-solver-search', action='store_true', help='leave torch.backends.cudnn.benchmark off (MIOpen takes its first heuristic pick per shape)')
     args = ap.parse_args()
@@ -285,7 +304,7 @@ def main():
               f'(neural rendering {args.res}x{args.res}, {G.rendering_kwargs["depth_resolution"]}+{G.rendering_kwargs["depth_resolution_importance"]} samples)')
         if args.out:
             np.save(args.out, full.cpu().numpy())
-        if args.shapes:
+        if args.shapes or args.shapes_mrc or args.mesh:
             if device.type == 'cuda':
                 torch.cuda.synchronize()
             t0 = time.perf_counter()
@@ -294,7 +313,14 @@ def main():
                 torch.cuda.synchronize()
             dt = time.perf_counter() - t0
             print(f'density volume {args.voxel_res}^3: {dt:.3f} s = {args.voxel_res ** 3 / dt / 1e9:.2f} G points/s')
-            np.save(args.shapes, vol.cpu().numpy())
+            if args.shapes:
+                np.save(args.shapes, vol.cpu().numpy())
+            if args.shapes_mrc:
+                import shape_mi355x
+                shape_mi355x.write_mrc(args.shapes_mrc, vol.cpu().numpy())
+            if args.mesh:
+                nv, nf, dt = mesh_density_grid(vol, args.mesh, args.mesh_level)
+                print(f'mesh at level {args.mesh_level:g}: {dt * 1e3:.2f} ms, {nv} vertices, {nf} triangles -> {args.mesh}')
 
 
 if __name__ == '__main__':

@@ -23,7 +23,7 @@ _DTYPE_CODE = {torch.float32: F32, torch.float16: F16, torch.float64: F64}
 
 MAX_SAMPLES = 256
 DEBUG_SLOTS = 8
-ABI_VERSION = 12
+ABI_VERSION = 13
 # decoder arithmetic of the fused renderer (GNERF_MLP_* in include/gnerf_hip.h)
 MLP_MODES = {'auto': 0, 'f16x3': 1, 'f32': 2}
 
@@ -115,6 +115,9 @@ SIGNATURES = {
     'gnerf_torgb_nhwc': (_c_i, [_c_p, _c_p, _c_p, _c_p, _c_p, _c_i, _c_i, _c_i, _c_f, _c_p]),
     'gnerf_torgb_nhwc_accumulate': (_c_i, [_c_p, _c_p, _c_p, _c_p, _c_p, _c_i, _c_i, _c_i, _c_f, _c_p]),
     'gnerf_blur4_epilogue_nhwc': (_c_i, [_c_p, _c_p, _c_p, _c_i, _c_i, _c_i, _c_i, _c_i, _c_i, _c_i, _c_i, _c_i, _c_i, _c_f, _c_p, _c_p, _c_i, _c_f, _c_f, _c_f, _c_p, _c_p]),
+    'gnerf_marching_cubes_workspace_bytes': (_c_i, [_c_i, _c_i, _c_i, ctypes.POINTER(ctypes.c_size_t)]),
+    'gnerf_marching_cubes_count': (_c_i, [_c_p, _c_i, _c_i, _c_i, _c_f, _c_p, _c_p, _c_p]),
+    'gnerf_marching_cubes_emit': (_c_i, [_c_p, _c_i, _c_i, _c_i, _c_f, _c_p, _c_p, _c_p, _c_p]),
 }
 
 
@@ -1474,3 +1477,58 @@ def query_points_backward(planes_nhwc, n_items, decoder, points, box_warp, grad_
                                                   _ptr(g_planes), _ptr(gd[0]), _ptr(gd[1]), _ptr(gd[2]), _ptr(gd[3]), interleaved, _stream(pts))
     _check(code, 'gnerf_query_points_backward')
     return g_planes, g_dec
+
+
+def _marching_cubes_volume(volume):
+    _require_cuda(volume)
+    vol = volume.detach()
+    if vol.ndim != 3 or min(vol.shape) < 2:
+        raise ValueError(f'marching_cubes: volume must be [D0, D1, D2] with every D >= 2, got {tuple(vol.shape)}')
+    if vol.numel() >= 2 ** 31:
+        raise ValueError('marching_cubes: the volume must have fewer than 2^31 points')
+    return vol if (vol.dtype == torch.float32 and vol.is_contiguous()) else vol.to(torch.float32).contiguous()
+
+
+def _marching_cubes_result(verts, faces, counts):
+    n_verts, n_faces, n_bad = (int(c) for c in counts)
+    if n_bad:
+        raise ValueError(f'marching_cubes: the volume holds {n_bad} non-finite value(s)')
+    if n_verts >= 2 ** 31:
+        raise ValueError(f'marching_cubes: {n_verts} vertices do not fit int32 face indices')
+    return verts, faces
+
+
+def _marching_cubes_ctypes(vol, level):
+    """The ctypes route of marching_cubes (vol: what _marching_cubes_volume returns)."""
+    lib = load()
+    d0, d1, d2 = vol.shape
+    dev = vol.device
+    nbytes = ctypes.c_size_t()
+    _check(lib.gnerf_marching_cubes_workspace_bytes(d0, d1, d2, ctypes.byref(nbytes)), 'gnerf_marching_cubes_workspace_bytes')
+    ws = torch.empty(nbytes.value, dtype=torch.uint8, device=dev)
+    counts = torch.empty(3, dtype=torch.int64, device=dev)
+    with _on_device(dev):
+        _check(lib.gnerf_marching_cubes_count(_ptr(vol), d0, d1, d2, float(level), _ptr(ws), _ptr(counts), _stream(vol)), 'gnerf_marching_cubes_count')
+        host = counts.cpu()                                                      # the op's one synchronisation
+        n_verts, n_faces, n_bad = (int(c) for c in host)
+        emit = n_bad == 0 and 0 < n_verts < 2 ** 31
+        verts = torch.empty([n_verts if emit else 0, 3], dtype=torch.float32, device=dev)
+        faces = torch.empty([n_faces if emit else 0, 3], dtype=torch.int32, device=dev)
+        if emit:
+            _check(lib.gnerf_marching_cubes_emit(_ptr(vol), d0, d1, d2, float(level), _ptr(ws), _ptr(verts), _ptr(faces) if n_faces else None,
+                                                 _stream(vol)), 'gnerf_marching_cubes_emit')
+    return verts, faces, host
+
+
+@profiled('gnerf_hip::marching_cubes')
+def marching_cubes(volume, level):
+    """Triangle mesh of {v > level} of a CUDA volume [D0, D1, D2] (float32; other dtypes are converted) on the gfx950 kernel ->
+    (verts float32 [V, 3] in index space, faces int32 [T, 3]) on the volume's device, shapes (0, 3) when nothing crosses.  Rules, order and
+    winding: include/gnerf_hip.h, gnerf_marching_cubes_*; shape_mi355x.marching_cubes_numpy gives the same bits on the CPU.  Reads three
+    counts to the host between its two passes (so it is not graph-capturable).  Raises ValueError on a non-finite value."""
+    vol = _marching_cubes_volume(volume)
+    e = ext()
+    if e is not None:
+        with _on_device(vol.device):
+            return _marching_cubes_result(*e.marching_cubes(vol, float(level)))
+    return _marching_cubes_result(*_marching_cubes_ctypes(vol, level))

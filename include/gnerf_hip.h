@@ -6,7 +6,8 @@
  * All entry points enqueue work on `stream` (a hipStream_t passed as void*) and return
  * immediately; they return 0 on success and a negative GNERF_E_* code on failure
  * (gnerf_last_error() then holds a message for the calling thread).  No entry point
- * allocates, frees or synchronises, so all of them are hipGraph-capturable.
+ * allocates, frees or synchronises, so all of them are hipGraph-capturable (marching cubes as a whole is
+ * not: its caller reads counts to the host between its two passes, see gnerf_marching_cubes_count).
  *
  * Reference interfaces replaced (paths relative to the reference's g_nerf/):
  *   gnerf_bias_act          <- bias_act_plugin.bias_act            torch_utils/ops/bias_act.cpp:36
@@ -25,6 +26,8 @@
  *   gnerf_upsample2x_add_nhwc <- the backbone's last `upsample2d(img) + torgb(x)` (networks_stylegan2.py:456-463), channels_last
  *   gnerf_planes_from_nhwc  <- (the same for the plane gradient on the way back)
  *   gnerf_render_backward   <- autograd through renderer.py:88-140 (grid_sample_gradfix.py:62-77 for the planes)
+ *   gnerf_marching_cubes_*  <- skimage.measure.marching_cubes as shape_utils.py:58-61 calls it (new rules, table and order:
+ *                              shape_mi355x.py; the one family of entry points that needs a host synchronisation in between)
  */
 #ifndef GNERF_HIP_H
 #define GNERF_HIP_H
@@ -36,7 +39,7 @@
 extern "C" {
 #endif
 
-#define GNERF_ABI_VERSION 12
+#define GNERF_ABI_VERSION 13
 
 /* error codes */
 #define GNERF_OK            0
@@ -494,6 +497,28 @@ int gnerf_query_points_backward(const float* planes_nhwc, int n_items, int plane
                                 const float* grad_sigma, const float* grad_rgb,
                                 float* grad_planes_nhwc, float* grad_w1, float* grad_b1, float* grad_w2, float* grad_b2,
                                 int planes_interleaved, gnerf_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
+ * (ABI 13) Marching cubes: the triangle mesh of a level set of a dense float32 volume [d0, d1, d2] (axis 2 fastest, contiguous,
+ * every d >= 2, d0 * d1 * d2 < 2^31) -- what shape_utils.py:58-61 asks skimage.measure.marching_cubes for, with this project's own rules
+ * (g-nerf_amd/shape_mi355x.py states them and holds a numpy port that gives the same bits):
+ *   a lattice point is INSIDE iff v > level; one vertex per lattice edge p -> p + e_a (a = 0, 1, 2) whose endpoints disagree, at
+ *   coord_a = i_a + t, t = (level - v_p) / (v_{p+e_a} - v_p) (float32, correctly rounded, no contraction), the other two coordinates p's
+ *   indices (index space: spacing and origin are the caller's); vertices in lexicographic order of (linear index of p, a); faces as
+ *   int32 vertex triples in order of the cell's lower corner, then csrc/mesh_tables.h's order, right-hand normal from inside to outside.
+ * Three calls:
+ *   gnerf_marching_cubes_workspace_bytes: *bytes = the workspace both passes share (4 bytes per lattice point + small per-block arrays).
+ *   gnerf_marching_cubes_count: counts (device int64 [3]) = {vertices V, triangles T, non-finite values}; the workspace then holds
+ *     what the emit pass needs (no initialisation needed before).
+ *   gnerf_marching_cubes_emit: the same volume, level and workspace -> verts float32 [V, 3], faces int32 [T, 3] (NULL when the count
+ *     is 0).  The caller reads the counts to the host in between (the op's only synchronisation), sizes the outputs from them, and
+ *     does not call emit when the volume holds a non-finite value or V >= 2^31 (faces hold int32 ids).
+ * Because of that read the op cannot be captured in a graph (count and emit alone are capturable, the sizing in between is not). */
+int gnerf_marching_cubes_workspace_bytes(int d0, int d1, int d2, size_t* bytes);
+int gnerf_marching_cubes_count(const float* volume, int d0, int d1, int d2, float level, void* workspace, int64_t* counts,
+                               gnerf_stream_t stream);
+int gnerf_marching_cubes_emit(const float* volume, int d0, int d1, int d2, float level, const void* workspace, float* verts,
+                              int32_t* faces, gnerf_stream_t stream);
 
 #ifdef __cplusplus
 }
