@@ -65,7 +65,9 @@ constexpr int kNumXCD = 8;
 // render calls (words below kStatsWord0: depth range, diagnostics, per-item ranges) and gnerf_planes_to_nhwc_stats' max |planes|
 // reduction: kStatsShards lines of {max bits, ticket}, then one line for the total, 128 bytes apart.
 constexpr int kStatsWord0 = 8224, kStatsShards = 32, kStatsLineWords = 32;
-constexpr int kWorkspaceWords = kStatsWord0 + (kStatsShards + 1) * kStatsLineWords;
+// (ABI 14) behind them, the pipelined render kernel's dealing counters: one per XCD, each on a 128-byte line of its own (render_pipe.inl).
+constexpr int kDealWord0 = kStatsWord0 + (kStatsShards + 1) * kStatsLineWords, kDealLineWords = 32;
+constexpr int kWorkspaceWords = kDealWord0 + kNumXCD * kDealLineWords;
 
 // ---- the modulated convolution's epilogue on one vector of adjacent channels (shared by csrc/modconv.hip and the fused
 // blur + epilogue of csrc/upfirdn2d.hip):

@@ -34,6 +34,7 @@
 
 #include "common.h"
 #include "raygen.h"
+#include "pipe_dealing.h"
 #include <cstdlib>
 #include <cstring>
 
@@ -61,6 +62,7 @@ struct Params {
     int total_rays;
     int split_shift;        // small launches: a 16-ray tile is shared by 1 << split_shift workgroups (generic / backward kernels)
     int pipe_unit;          // pipelined kernel: rays dealt to a workgroup at a time (kPipeUnit; fewer for launches that do not fill the chip)
+    unsigned* deal_counters;        // pipelined forward: the workspace's per-XCD counters when units are dealt on demand, else null (static dealing)
     unsigned tex_pitch, row_pitch, plane_pitch;     // byte addressing of a texel, see plane_taps (render_shade.inl)
     int64_t item_bytes;     // bytes from one item's planes to the next: 3 * H * W * 128, or 0 when every item reads the same planes (planes_shared)
     const float* absmax;    // GNERF_MLP_AUTO: max |planes| (one device float) for choose_mlp
@@ -434,7 +436,8 @@ __device__ __forceinline__ void march(const float* t, const float* sig, float* w
 }
 
 // ---- the call-wide depth range (ray_marcher.py:49-50).
-// Workspace words: [0] ~ord_encode(min depth)  [1] ord_encode(max depth)  [3] clamp blocks finished.
+// Workspace words: [0] ~ord_encode(min depth)  [1] ord_encode(max depth)  [3] clamp blocks finished;
+// [kDealWord0 + 32 x]: units of XCD x's range dealt on demand by the pipelined kernel (render_pipe.inl).
 // ALL ZERO means idle ("min = +inf, max = -inf"): the caller provides a zeroed workspace once and every call leaves it
 // zeroed (clamp_depth_kernel's last block), so no launch is spent on initialising it.
 // (Also tried: letting the last render workgroup to finish apply the clamp itself for small launches, to save the second
@@ -621,6 +624,7 @@ __global__ __launch_bounds__(256) void clamp_depth_kernel(float* depth, unsigned
     __syncthreads();
     if (last) {                                                  // the last block puts the workspace back to idle
         if (threadIdx.x == 0) { ws[0] = 0u; ws[1] = 0u; ws[3] = 0u; }
+        if (threadIdx.x < kNumXCD) ws[kDealWord0 + threadIdx.x * kDealLineWords] = 0u;      // the render kernel's dealing counters
         for (int i = threadIdx.x; i < 2 * n_items_per_item_clamp; i += 256) ws[kClampItemWord0 + i] = 0u;
     }
 }
@@ -854,6 +858,7 @@ static int fill_params(const gnerf_render_params* p, Params& P) {
     P.total_rays = int(total);
     P.split_shift = 0;
     P.pipe_unit = 8;
+    P.deal_counters = nullptr;
     P.absmax = nullptr;
     P.draw_c = P.draw_f = TorchRandDraw{};
     P.draw_item_ctr = 0;
@@ -947,13 +952,22 @@ extern "C" int gnerf_render_forward(const gnerf_render_params* p, gnerf_stream_t
         int64_t g = ((total_seq + P.pipe_unit - 1) / P.pipe_unit + kNumXCD - 1) / kNumXCD * kNumXCD;
         if (g < kNumXCD) g = kNumXCD;
         if (g > capacity) g = capacity;
+        // Units are dealt on demand where workgroups get more than one (nothing to balance otherwise); clamp_depth_kernel, which
+        // follows every forward launch on this stream, returns the counters to zero.  -DGNERF_PIPE_STATIC_DEALING (a variant build) and
+        // GNERF_PIPE_DEALING=static (read per call, like the overrides above: the tests compare the two in one process) keep the static form.
+#ifndef GNERF_PIPE_STATIC_DEALING
+        if (total_seq >= capacity * kPipeUnit) {
+            const char* dealing = getenv("GNERF_PIPE_DEALING");
+            if (!dealing || strcmp(dealing, "static") != 0) P.deal_counters = static_cast<unsigned*>(p->workspace) + kDealWord0;
+        }
+#endif
         const bool gen = !p->ray_origins || p->rng_mode != GNERF_RNG_TENSORS;       // the call makes its rays and / or its draws in the kernel
         const size_t lds_bytes = pipe_lds_floats(pipe_tp, mlp) * sizeof(float);
         const dim3 gd((unsigned)g), bd(kPipeThreads);
         // the instantiation with compile-time sample counts (render_pipe_body<.., FULL>) where the call fills the slots exactly
         bool full = S == 48 * pipe_tp && F == 48 * pipe_tp && !p->disparity_space_sampling && !p->ray_start_per_ray && !p->debug && !p->sigma_noise_coarse;
-#ifdef GNERF_STAMPS
-        full = full || (S == 48 * pipe_tp && F == 48 * pipe_tp && !p->disparity_space_sampling && !p->ray_start_per_ray);     // the timing build's `debug` is its stamp buffer
+#if defined(GNERF_STAMPS) || defined(GNERF_WG_STAMPS)
+        full = full || (S == 48 * pipe_tp && F == 48 * pipe_tp && !p->disparity_space_sampling && !p->ray_start_per_ray && !p->sigma_noise_coarse);     // the timing build's `debug` is its stamp buffer
 #endif
         if (const char* f = getenv("GNERF_PIPE_FULL")) full = full && strcmp(f, "0") != 0;       // A/B runs and the tests' cross-check
         if (gen) {

@@ -20,7 +20,7 @@
 // default), 96+96 (gen_videos.py's doubled counts, the ShapeNet config's 64+64) and 144+144.  Importance sampling is optional
 // (F = 0: the fine pass finds no tiles).  Other shapes use the generic kernel.
 
-#ifdef GNERF_STAMPS
+#if defined(GNERF_STAMPS) || defined(GNERF_WG_STAMPS)      // (these builds' `debug` is their stamp buffer)
 #define GNERF_DBG_PTR(x) ((float*)nullptr)
 #else
 #define GNERF_DBG_PTR(x) (x)
@@ -70,8 +70,13 @@ __device__ __forceinline__ PipeSlot pipe_slot(float* base, int slot) {
 __host__ __device__ inline size_t pipe_lds_floats(int tp, int mlp) {
     const size_t slot_floats = tp == 1 ? PipeDims<1>::kSlotFloats : (tp == 2 ? PipeDims<2>::kSlotFloats : PipeDims<3>::kSlotFloats);
     return size_t(weight_floats(mlp)) + 64 + 36 + size_t(kPipeSlots) * slot_floats + 3 * 16 * kStagePitch       // (tap records live in the staging rows)
-           + kPipeUnit * 8;                                                                                        // GEN: the dealing unit's rays
+           + kPipeUnit * 8                                                                                         // GEN: the dealing unit's rays
+           + 4;                                                                                                    // on-demand dealing: the run's length
 }
+// Four TP = 1 workgroups share a CU's 160 KiB of LDS (GNERF_PIPE_WAVES_PER_SIMD): growth past that would silently drop to three.
+static_assert(4 * sizeof(float) * (size_t(weight_floats(kMlpF32) > weight_floats(kMlpF16x3) ? weight_floats(kMlpF32) : weight_floats(kMlpF16x3)) + 64 + 36
+                                   + size_t(kPipeSlots) * PipeDims<1>::kSlotFloats + 3 * 16 * kStagePitch + kPipeUnit * 8 + 4) <= 160 * 1024,
+              "a TP = 1 workgroup of the pipelined render kernel must fit a CU's LDS four times");
 
 // position `seq` of the locality-ordered ray sequence -> ray index (or -1 past the end)
 // PADDED: instantiations of the backward only (linear_pad(P) is never set on a forward call: the forward kernels do not carry the branch)
@@ -147,24 +152,32 @@ __device__ __forceinline__ void render_pipe_body(const Params& P, float* smem, c
     L.stage = L.taps;
     L.wave_pitch_taps = L.wave_pitch_stage = 16 * kStagePitch;
 
-    // This workgroup's share of the locality-ordered ray sequence.  Workgroups b, b+8, ... share an XCD (round-robin
+    // This workgroup's share of the locality-ordered ray sequence (pipe_dealing.h).  Workgroups b, b+8, ... share an XCD (round-robin
     // dispatch), and each XCD owns a contiguous eighth of the sequence.  Inside an XCD the sequence is dealt to its W
-    // workgroups in UNITS of kPipeUnit consecutive rays, round-robin: at any moment the W workgroups are within a few
+    // workgroups in UNITS of kPipeUnit consecutive rays, in order: at any moment the W workgroups are within a few
     // units of each other, i.e. on neighbouring rays, so the XCD's 4 MB L2 holds the texels they share.  (Giving each
     // workgroup one long contiguous run instead spreads the XCD over 96 distant image regions: measured 1.3 GB of L2
     // misses per launch; dealing units of 8 rays is 10 % faster, 4-16 are within 3 % of each other.)  Speed only -- any assignment is correct.
+    // The forward deals ON DEMAND where the launcher hands it counters (P.deal_counters: launches with more than one unit per
+    // workgroup): a workgroup's first unit is its own index, every further one comes from its XCD's counter -- one relaxed
+    // fetch-add by one lane of the scalar wave, issued while the LAST ray of a unit is proposed and consumed one ray later, behind a
+    // whole pipeline step.  The run's length `nr` is then unknown until the counter runs out: it stays kPipeRunOpen until the scalar
+    // wave meets a unit past the XCD's range, closes the run at that ray and publishes the length through `nr_word`; the shader waves
+    // pick it up every third iteration, where both roles decide on the same value whether to go on (it is written between the
+    // two barriers of an iteration and read behind the second).  Until they have it they find the run's end in the ray slots:
+    // propose_finish marks every ray past the end.  No workgroup waits for another.  The backward stays on static dealing.
     const int64_t total_seq = (P.tiles_per_item > 0 || (BWD && linear_pad(P) > 0)) ? int64_t(P.n_tiles) * 16 : int64_t(P.total_rays);
-    const int W = gridDim.x / kNumXCD, xcd = blockIdx.x % kNumXCD, wg = blockIdx.x / kNumXCD;
-    const int64_t x0 = total_seq * xcd / kNumXCD, x1 = total_seq * (xcd + 1) / kNumXCD;
     const int unit = P.pipe_unit;
-    const int n_units = int((x1 - x0 + unit - 1) / unit);
-    const int my_units = n_units > wg ? (n_units - wg + W - 1) / W : 0;
-    const int nr = my_units * unit;
-    auto local_to_ray = [&](int r) -> int {
-        const int64_t seq = x0 + (int64_t(wg) + int64_t(r / unit) * W) * unit + r % unit;
-        return seq < x1 ? pipe_seq_to_ray<BWD>(P, seq) : -1;
-    };
+    PipeDeal deal;
+    deal.init(total_seq, kNumXCD, blockIdx.x % kNumXCD, gridDim.x / kNumXCD, blockIdx.x / kNumXCD, unit);
+    const bool dyn = !BWD && P.deal_counters != nullptr;        // (uniform over the launch)
+    constexpr int kPipeRunOpen = 1 << 30;
+    int nr = dyn ? (deal.has_unit() ? kPipeRunOpen : 0) : deal.static_units() * unit;      // local rays 0 .. nr - 1; per wave: see above
+    unsigned next_unit = 0;                                     // scalar wave, lane 0: what the fetch-add returned
 
+#ifdef GNERF_WG_STAMPS
+    const unsigned long long wg_t0 = __builtin_amdgcn_s_memrealtime();       // this workgroup's start, 100 MHz ticks (tools/wg_lifetimes.py)
+#endif
     stage_decoder<MLP>(L, smem, p, tid, kPipeThreads);
 
     Stamps st;
@@ -175,12 +188,29 @@ __device__ __forceinline__ void render_pipe_body(const Params& P, float* smem, c
     int pre_ray_id = -1;
 
     float* const unit_rays = L.taps + 3 * 16 * kStagePitch;        // GEN: [kPipeUnit][8] origin, direction of the current dealing unit's rays
-    auto propose_issue = [&](int r) {           // P(r), first half: start the global loads (or make the values: GEN)
-        pre_ray_id = (r >= 0 && r < nr) ? local_to_ray(r) : -1;
-        if (GEN && p.cam2world && r >= 0 && r < nr && r % unit == 0 && lane < unit) {
+    int* const nr_word = reinterpret_cast<int*>(unit_rays + kPipeUnit * 8);
+    auto propose_issue = [&](int r) {           // P(r), first half: start the global loads (or make the values: GEN).  Called for r = 0, 1, 2, ... in turn
+        pre_ray_id = -1;
+        if (r < 0 || r >= nr) return;
+        const int pos = r % unit;
+        if (pos == 0 && r > 0) {                // a new unit
+            if constexpr (BWD) deal.advance_static();
+            else if (!dyn) deal.advance_static();
+            else if (!deal.advance_to(deal.fetched_unit(unsigned(__builtin_amdgcn_readfirstlane(int(next_unit)))))) {
+                nr = r;                         // the XCD's range is dealt out: this workgroup's run ends in front of ray r
+                if (lane == 0) *nr_word = r;
+                return;
+            }
+        }
+        if constexpr (!BWD) {
+            if (dyn && pos == unit - 1 && lane == 0)
+                next_unit = __hip_atomic_fetch_add(P.deal_counters + (blockIdx.x % kNumXCD) * kDealLineWords, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+        { const int64_t seq = deal.seq(pos); pre_ray_id = seq >= 0 ? pipe_seq_to_ray<BWD>(P, seq) : -1; }
+        if (GEN && p.cam2world && pos == 0 && lane < unit) {
             // rays of this dealing unit, one lane each (r .. r + unit - 1 are consecutive positions of the sequence)
-            const int64_t seq = x0 + (int64_t(wg) + int64_t(r / unit) * W) * unit + lane;
-            const int id = seq < x1 ? pipe_seq_to_ray<BWD>(P, seq) : -1;
+            const int64_t seq = deal.seq(lane);
+            const int id = seq >= 0 ? pipe_seq_to_ray<BWD>(P, seq) : -1;
             if (id >= 0) {
                 const int item = id / p.rays_per_item, m = id - item * p.rays_per_item;
                 const float* M = p.cam2world + item * 16;
@@ -214,7 +244,7 @@ __device__ __forceinline__ void render_pipe_body(const Params& P, float* smem, c
             }
         }
         if (GEN && p.cam2world) {
-            if (lane < 12) pre_ray = unit_rays[(r % unit) * 8 + misc_comp(lane)];       // (LDS operations of one wave execute in order)
+            if (lane < 12) pre_ray = unit_rays[pos * 8 + misc_comp(lane)];       // (LDS operations of one wave execute in order)
         } else {
             if (lane < 12) { const int c = misc_comp(lane); pre_ray = c < 3 ? p.ray_origins[ray * 3 + c] : p.ray_dirs[ray * 3 + c - 3]; }
         }
@@ -227,8 +257,12 @@ __device__ __forceinline__ void render_pipe_body(const Params& P, float* smem, c
         }
     };
     auto propose_finish = [&](int r) {          // P(r), second half: depth proposals (renderer.py:169-192) into the slot
-        if (r < 0 || r >= nr) return;
+        if (r < 0) return;
         PipeSlot sl = pipe_slot<TP>(slots, r & (kPipeSlots - 1));
+        if (r >= nr) {                          // on demand: the shader waves may not know the run's length yet -- the slot tells them
+            if (dyn && lane == kMiscRay) sl.misc[kMiscRay] = __int_as_float(-1);
+            return;
+        }
         if (lane == kMiscRay) sl.misc[kMiscRay] = __int_as_float(pre_ray_id);
         if (pre_ray_id < 0) return;
 #pragma unroll
@@ -690,8 +724,13 @@ __device__ __forceinline__ void render_pipe_body(const Params& P, float* smem, c
     // on LDS round trips).
     if (wv == 3) __builtin_amdgcn_s_setprio(GNERF_SCALAR_PRIO);
     __syncthreads();                                            // weights are in LDS
-    if (wv == 3) { propose_issue(0); propose_finish(0); }
+    if (wv == 3) {
+        if (dyn && lane == 0) *nr_word = nr;
+        propose_issue(0); propose_finish(0);
+    }
     __syncthreads();
+    auto refresh_nr = [&]() { if (dyn) nr = __builtin_amdgcn_readfirstlane(*nr_word); };
+    refresh_nr();
     st.reset();
 #ifdef GNERF_STAMPS
     // clock of the timed part: shader cycles (s_memtime) per 100 MHz tick (s_memrealtime), and where the wave sits (HW_ID)
@@ -734,7 +773,8 @@ __device__ __forceinline__ void render_pipe_body(const Params& P, float* smem, c
     // v_mov_b32 at the bottom and 8 at the top, where the compiler parks the loop-carried set -- 72 vector instructions per ray over the
     // three waves).  Unrolled three times, iteration k + i writes set (i + 2) % 3 and reads set i % 3: no copies.  Both roles run
     // the same number of iterations, rounded up to a multiple of three (the extra ones find no ray and only meet at the barriers).
-    const int k_last = -1 + 3 * ((nr + 3 + 2) / 3) - 1;
+    // (On demand the count follows `nr`: re-evaluated after every third iteration by both roles, from the same published value.)
+    auto last_iteration = [](int n) { return -1 + 3 * ((n + 3 + 2) / 3) - 1; };
     if (wv < 3) {
         v4f ca[TP][2] = {}, cb[TP][2] = {}, cd[TP][2] = {}, cf[TP][2] = {};
         bool la = false, lb = false, ld = false;
@@ -750,12 +790,14 @@ __device__ __forceinline__ void render_pipe_body(const Params& P, float* smem, c
             __syncthreads();
             GNERF_STAMP(st, 7);         // barrier wait, odd step
         };
-        for (int k = -1; k <= k_last; k += 3) {         // sets (k-1, k, k+1) = (a, b, d), then (b, d, a), then (d, a, b)
+        for (int k = -1; k <= last_iteration(nr); k += 3) {         // sets (k-1, k, k+1) = (a, b, d), then (b, d, a), then (d, a, b)
             iter(k, ca, cd, la, ld);
             iter(k + 1, cb, ca, lb, la);
             iter(k + 2, cd, cb, ld, lb);
+            refresh_nr();
         }
     } else {
+        int k_last = last_iteration(nr), k_check = 1;
         for (int k = -1; k <= k_last; k++) {
             finalize(k - 1);
             GNERF_STAMP(st, 8);         // merge + final march
@@ -772,6 +814,7 @@ __device__ __forceinline__ void render_pipe_body(const Params& P, float* smem, c
             GNERF_STAMP(st, 5);
             __syncthreads();
             GNERF_STAMP(st, 7);         // barrier wait, odd step
+            if (k == k_check) { k_last = last_iteration(nr); k_check += 3; }       // (the scalar wave's own `nr` is the published one)
         }
     }
 #ifdef GNERF_STAMPS
@@ -787,6 +830,19 @@ __device__ __forceinline__ void render_pipe_body(const Params& P, float* smem, c
         ext[1] = __builtin_amdgcn_s_memtime() - clk_c0;
         ext[2] = __builtin_amdgcn_s_memrealtime() - clk_r0;
         ext[3] = clk_r0;
+    }
+#endif
+#ifdef GNERF_WG_STAMPS
+    // Two stamps per workgroup, nothing inside the loops: where it ran, when it started, when its scalar wave left the last barrier.
+    if (wv == 3 && lane == 0 && p.debug) {
+        unsigned long long* out = reinterpret_cast<unsigned long long*>(p.debug) + size_t(blockIdx.x) * 4;
+        unsigned hw, xcc;
+        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw));
+        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
+        out[0] = hw | ((unsigned long long)(xcc & 15u) << 32);
+        out[1] = wg_t0;
+        out[2] = __builtin_amdgcn_s_memrealtime();
+        out[3] = (unsigned long long)nr;
     }
 #endif
     if (wv == 3 && lane == 0) range.flush(P);

@@ -39,7 +39,7 @@
 extern "C" {
 #endif
 
-#define GNERF_ABI_VERSION 13
+#define GNERF_ABI_VERSION 14
 
 /* error codes */
 #define GNERF_OK            0
@@ -330,7 +330,7 @@ typedef struct gnerf_render_params {
     float* out_wsum;     /* [n_items, rays_per_item, 1]   sum of the final weights */
     /* workspace of gnerf_render_workspace_bytes() bytes (holds the call-wide depth range used by the
        global clamp of ray_marcher.py:49-50, or one range per item: depth_clamp_per_item).  ZERO it once after allocation;
-       every call leaves it zeroed.
+       every call leaves it zeroed.  (ABI 14) It also holds the pipelined kernel's eight ray-dealing counters, and is larger for it.
        One workspace per stream that renders concurrently. */
     void*  workspace;
     /* optional stage dump for debugging/parity: float32 [n*m, GNERF_DEBUG_SLOTS, S+F]; NULL in production */
