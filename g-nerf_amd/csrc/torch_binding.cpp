@@ -10,7 +10,7 @@
 // guard) -- and nothing else: no kernels live here, every function validates, allocates and calls the C ABI.  It exists for host
 // cost: a call through ctypes spends 10-12 us marshalling arguments in Python, this path ~3.
 // Also exported: render_forward (the fused renderer has no reference plugin; same C ABI call as gnerf_hip.render_forward) and
-// marching_cubes (gnerf_hip.marching_cubes' count -> read counts -> emit sequence).
+// marching_cubes (gnerf_hip.marching_cubes' count -> read counts -> emit sequence), ssim_forward / ssim_backward (gnerf_hip.ssim_*).
 //
 // Built ahead of time by csrc/build.sh (g++, no hipcc: there is no device code) into g-nerf_amd/gnerf_hip/gnerf_torch_ext.so.
 
@@ -294,6 +294,66 @@ std::tuple<Tensor, Tensor, Tensor> marching_cubes(Tensor volume, double level) {
     return std::make_tuple(verts, faces, host);
 }
 
+// ------------------------------------------------------------------------------------------------ SSIM (pytorch_msssim's _ssim)
+
+void check_ssim_images(const Tensor& x, const Tensor& y, const std::vector<double>& window, const char* what) {
+    TORCH_CHECK(x.is_cuda() && y.is_cuda() && x.device() == y.device(), what, ": X and Y must reside on one CUDA device");
+    TORCH_CHECK(x.dim() == 4 && x.sizes() == y.sizes() && x.scalar_type() == y.scalar_type(), what, ": X and Y must be [N, C, H, W] of one shape and dtype");
+    TORCH_CHECK(x.scalar_type() == torch::kFloat32 || x.scalar_type() == torch::kFloat16, what, ": the kernel takes float32 and float16 images");
+    TORCH_CHECK(window.size() % 2 == 1 && window.size() <= GNERF_SSIM_MAX_WIN, what, ": the window must have an odd length of at most ", GNERF_SSIM_MAX_WIN);
+    TORCH_CHECK(x.numel() > 0 && x.size(0) <= INT_MAX && x.size(1) <= INT_MAX && x.size(2) <= INT_MAX && x.size(3) <= INT_MAX, what, ": empty or oversized image");
+}
+
+// -> (ssim [N, C], cs [N, C]) float32
+std::tuple<Tensor, Tensor> ssim_forward(Tensor x, Tensor y, std::vector<double> window, double C1, double C2) {
+    check_ssim_images(x, y, window, "ssim_forward");
+    const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(at::device_of(x));
+    const int n = int(x.size(0)), c = int(x.size(1)), h = int(x.size(2)), w = int(x.size(3)), win = int(window.size());
+    size_t bytes = 0;
+    check_rc(gnerf_ssim_workspace_bytes(n, c, h, w, win, &bytes), "gnerf_ssim_workspace_bytes");
+    Tensor ws = torch::empty({int64_t(bytes)}, x.options().dtype(torch::kUInt8));
+    Tensor out = torch::empty({2, n, c}, x.options().dtype(torch::kFloat32));
+    float wf[GNERF_SSIM_MAX_WIN] = {0};
+    for (int i = 0; i < win; i++) wf[i] = float(window[i]);
+    int64_t xs[4], ys[4];
+    strides4(x, xs);
+    strides4(y, ys);
+    check_rc(gnerf_ssim_forward(x.data_ptr(), y.data_ptr(), dtype_code(x, "ssim_forward"), n, c, h, w, xs, ys, wf, win, float(C1), float(C2),
+                                ws.data_ptr(), out.data_ptr<float>(), out.data_ptr<float>() + int64_t(n) * c, current_stream()),
+             "gnerf_ssim_forward");
+    return std::make_tuple(out[0], out[1]);
+}
+
+// g_ssim / g_cs: contiguous float32 [N, C] or None.  -> (dX, dY) like X / Y, an undefined tensor (None) where not needed
+std::tuple<c10::optional<Tensor>, c10::optional<Tensor>> ssim_backward(Tensor x, Tensor y, std::vector<double> window, double C1, double C2,
+                                                                       c10::optional<Tensor> g_ssim, c10::optional<Tensor> g_cs, bool need_dx, bool need_dy) {
+    check_ssim_images(x, y, window, "ssim_backward");
+    TORCH_CHECK(need_dx || need_dy, "ssim_backward: neither gradient is asked for");
+    TORCH_CHECK(g_ssim.has_value() || g_cs.has_value(), "ssim_backward: g_ssim and g_cs are both None");
+    const int n = int(x.size(0)), c = int(x.size(1)), h = int(x.size(2)), w = int(x.size(3)), win = int(window.size());
+    auto upstream = [&](const c10::optional<Tensor>& g) -> const float* {
+        if (!g.has_value()) return nullptr;
+        TORCH_CHECK(g->is_cuda() && g->device() == x.device() && g->scalar_type() == torch::kFloat32 && g->is_contiguous() && g->dim() == 2 &&
+                    g->size(0) == n && g->size(1) == c, "ssim_backward: upstream gradients must be contiguous float32 [N, C] on X's device");
+        return g->data_ptr<float>();
+    };
+    const float* gs = upstream(g_ssim);
+    const float* gc = upstream(g_cs);
+    const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(at::device_of(x));
+    c10::optional<Tensor> dx, dy;
+    int64_t xs[4], ys[4], dxs[4] = {0, 0, 0, 0}, dys[4] = {0, 0, 0, 0};
+    strides4(x, xs);
+    strides4(y, ys);
+    if (need_dx) { dx = torch::empty_like(x); strides4(*dx, dxs); }
+    if (need_dy) { dy = torch::empty_like(y); strides4(*dy, dys); }
+    float wf[GNERF_SSIM_MAX_WIN] = {0};
+    for (int i = 0; i < win; i++) wf[i] = float(window[i]);
+    check_rc(gnerf_ssim_backward(x.data_ptr(), y.data_ptr(), dtype_code(x, "ssim_backward"), n, c, h, w, xs, ys, wf, win, float(C1), float(C2), gs, gc,
+                                 need_dx ? dx->data_ptr() : nullptr, dxs, need_dy ? dy->data_ptr() : nullptr, dys, current_stream()),
+             "gnerf_ssim_backward");
+    return std::make_tuple(dx, dy);
+}
+
 }  // namespace
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -303,6 +363,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("filtered_lrelu_act_", &filtered_lrelu_act_);
     m.def("render_forward", &render_forward);
     m.def("marching_cubes", &marching_cubes);
+    m.def("ssim_forward", &ssim_forward);
+    m.def("ssim_backward", &ssim_backward);
     // the header version THIS extension was compiled against (a compile-time constant: gnerf_abi_version() would resolve in
     // libgnerf_hip.so at run time and compare the library with itself); gnerf_hip.ext() checks both against its own
     m.def("abi_version", []() { return int(GNERF_ABI_VERSION); });

@@ -52,8 +52,8 @@ R1_GAMMA = 1.0
 # the G + D step
 
 
-def generator_loss(G, D, batch, res=64, **synthesis_kwargs):
-    """training_loop.py:328-375 without the SSIM / VGG terms.  Returns (loss, parts, generated images)."""
+def generator_loss(G, D, batch, res=64, ssim=False, **synthesis_kwargs):
+    """training_loop.py:328-375 without the VGG terms, and without the SSIM terms unless `ssim`.  Returns (loss, parts, generated images)."""
     ws = G.mapping(batch['z'], batch['c'])
     gen = G.synthesis(ws, batch['c'], neural_rendering_resolution=res, **synthesis_kwargs)
     real = batch['loss_image']
@@ -61,9 +61,18 @@ def generator_loss(G, D, batch, res=64, **synthesis_kwargs):
     l1 = (real - gen['image'].float()).abs().mean((1, 2, 3))
     l1_raw = (real_raw - gen['image_raw'].float()).abs().mean((1, 2, 3))
     factor = batch['factor']
-    recon = ((l1 + l1_raw) * factor).sum() / (factor.sum() + 1e-6)
+    parts = dict(l1=l1.detach().mean(), l1_raw=l1_raw.detach().mean())
+    if ssim:
+        from torch_utils.ops import ssim as ssim_ops                     # (through the module, so that a test can swap the route)
+        l_ssim = 1 - ssim_ops.ssim(real * 0.5 + 0.5, gen['image'].float() * 0.5 + 0.5, data_range=1.0, size_average=False)           # :343-344
+        l_ssim_raw = 1 - ssim_ops.ssim(real_raw * 0.5 + 0.5, gen['image_raw'].float() * 0.5 + 0.5, data_range=1.0, size_average=False)  # :352-353
+        recon = ((l1 + l_ssim + l1_raw + l_ssim_raw) * factor).sum() / (factor.sum() + 1e-6)
+        parts.update(ssim=l_ssim.detach().mean(), ssim_raw=l_ssim_raw.detach().mean())
+    else:
+        recon = ((l1 + l1_raw) * factor).sum() / (factor.sum() + 1e-6)
     loss_gan = F.softplus(-D(gen['image_depth'], batch['c'])).mean()
-    return recon + 1.2 * loss_gan, dict(l1=l1.detach().mean(), l1_raw=l1_raw.detach().mean(), gan=loss_gan.detach()), gen
+    parts['gan'] = loss_gan.detach()
+    return recon + 1.2 * loss_gan, parts, gen
 
 
 def discriminator_backward(D, fake_depth, batch, r1_gamma=R1_GAMMA, **d_kwargs):
@@ -79,14 +88,14 @@ def discriminator_backward(D, fake_depth, batch, r1_gamma=R1_GAMMA, **d_kwargs):
     return dict(d_gen=loss_gen.detach().mean(), d_real=loss_real.detach().mean(), d_r1=loss_r1.detach().mean())
 
 
-def gd_train_step(G, D, opt_G, opt_D, batch, res=64, bucket_bytes=None, timers=None, synthesis_kwargs=None, d_kwargs=None):
+def gd_train_step(G, D, opt_G, opt_D, batch, res=64, bucket_bytes=None, timers=None, synthesis_kwargs=None, d_kwargs=None, ssim=False):
     """One optimiser step of G and one of D; returns the dict of loss terms."""
     mark = _marker(timers, batch['c'])
     synthesis_kwargs, d_kwargs = synthesis_kwargs or {}, d_kwargs or {}
     opt_G.zero_grad(set_to_none=True)
     G.requires_grad_(True)
     t = mark('G forward')
-    loss, parts, gen = generator_loss(G, lambda img, c: D(img, c, **d_kwargs), batch, res, **synthesis_kwargs)
+    loss, parts, gen = generator_loss(G, lambda img, c: D(img, c, **d_kwargs), batch, res, ssim=ssim, **synthesis_kwargs)
     t()
     t = mark('G backward')
     loss.backward()
@@ -207,6 +216,7 @@ def main():
     ap.add_argument('--grad-mb', type=float, default=123.0, help='renderer mode: size of the flat gradient vector (reference G: 123 MB)')
     ap.add_argument('--bucket-mb', type=float, default=0.0, help='exchange the flat vector in pieces of this size (0 = one collective)')
     ap.add_argument('--force-fp32', action='store_true', help='full mode: no fp16 in the super-resolution and discriminator blocks')
+    ap.add_argument('--ssim', action='store_true', help='full mode: add the (1 - SSIM) terms of training_loop.py:343-344,352-353 on image and image_raw')
     ap.add_argument('--device', default=None)
     ap.add_argument('--marked', action='store_true', help='bracket the timed steps with the marker kernel of tools/orbit_marked.py (MARKED_SCRIPT=... tools/prof_orbit.sh: '
                                                           'per-kernel statistics of the steps alone, warm-up excluded)')
@@ -251,11 +261,11 @@ def main():
         kw = dict(synthesis_kwargs=dict(force_fp32=True), d_kwargs=dict(force_fp32=True)) if args.force_fp32 else {}
 
         def one(timers=None):
-            return gd_train_step(G, D, opt_G, opt_D, batch, args.res, bucket, timers, **kw)
+            return gd_train_step(G, D, opt_G, opt_D, batch, args.res, bucket, timers, ssim=args.ssim, **kw)
         modules = (G, D)
         n_grad = (sum(p.numel() for p in G.parameters()), sum(p.numel() for p in D.parameters()))
         what = (f'config 5: G + D step, {args.batch} items/GPU, 64^2 rays x (48+48) samples, SR to 512^2 '
-                f'({"fp32" if args.force_fp32 or not use_gpu else "fp16 SR / D blocks"}), loss L1 + L1 + 1.2 softplus(-D(depth)), R1 on D, two flat all-reduces of '
+                f'({"fp32" if args.force_fp32 or not use_gpu else "fp16 SR / D blocks"}), loss L1 + L1{" + (1 - SSIM) x 2" if args.ssim else ""} + 1.2 softplus(-D(depth)), R1 on D, two flat all-reduces of '
                 f'{4 * n_grad[0] / 1e6:.1f} MB (G) and {4 * n_grad[1] / 1e6:.1f} MB (D), Adam x2; random-init FFHQ-config generator, synthetic batch')
     else:
         own = 4 * (args.batch * 3 * 32 * args.plane_res ** 2 + 4257)
@@ -301,7 +311,7 @@ def main():
             'images_per_s': world * args.batch * args.steps / elapsed,
             'rays_per_s': world * args.batch * args.res ** 2 * args.steps / elapsed,
             'phase_ms_rank0': {k: round(v, 3) for k, v in phases.items()},
-            'losses': {k: float(v) for k, v in parts.items()},
+            'losses': {k: float(v) for k, v in parts.items()}, 'ssim_terms': bool(args.ssim and args.mode == 'full'),
             'exchange': 'one all-reduce per optimiser' if bucket is None else f'{args.bucket_mb} MB buckets, async', 'device': str(dev)}))
     if world > 1:
         import torch.distributed as dist

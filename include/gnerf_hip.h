@@ -28,6 +28,8 @@
  *   gnerf_render_backward   <- autograd through renderer.py:88-140 (grid_sample_gradfix.py:62-77 for the planes)
  *   gnerf_marching_cubes_*  <- skimage.measure.marching_cubes as shape_utils.py:58-61 calls it (new rules, table and order:
  *                              shape_mi355x.py; the one family of entry points that needs a host synchronisation in between)
+ *   gnerf_ssim_*            <- pytorch_msssim's ssim / ms_ssim as training_loop.py:341-376 calls them (a Python package of grouped
+ *                              convolutions there; no native counterpart)
  */
 #ifndef GNERF_HIP_H
 #define GNERF_HIP_H
@@ -39,7 +41,7 @@
 extern "C" {
 #endif
 
-#define GNERF_ABI_VERSION 14
+#define GNERF_ABI_VERSION 15
 
 /* error codes */
 #define GNERF_OK            0
@@ -519,6 +521,30 @@ int gnerf_marching_cubes_count(const float* volume, int d0, int d1, int d2, floa
                                gnerf_stream_t stream);
 int gnerf_marching_cubes_emit(const float* volume, int d0, int d1, int d2, float level, const void* workspace, float* verts,
                               int32_t* faces, gnerf_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
+ * (ABI 15) SSIM of two images X, Y [n, c, h, w] (float32 or float16, any strides, given in elements) and its gradient -- the
+ * per-channel pair that pytorch_msssim's `_ssim` returns, from which its ssim and ms_ssim are built (torch_utils/ops/ssim.py):
+ *   window: `win` HOST floats g[0..win-1] (odd win <= GNERF_SSIM_MAX_WIN, h >= win and w >= win), applied separably per channel as a
+ *   VALID correlation, so the map is (h - win + 1) x (w - win + 1);
+ *   mu1 = g*X, mu2 = g*Y, s1 = g*X^2 - mu1^2, s2 = g*Y^2 - mu2^2, s12 = g*XY - mu1 mu2;
+ *   cs_map = (2 s12 + C2) / (s1 + s2 + C2), ssim_map = (2 mu1 mu2 + C1) / (mu1^2 + mu2^2 + C1) * cs_map;
+ *   ssim_nc[n * c] / cs_nc[n * c] (float32) = the means of ssim_map / cs_map over the map.  Arithmetic in float32.
+ * Sums are taken in a fixed order without atomics: the same bits on every run, and an item's results do not depend on the batch around it.
+ *   gnerf_ssim_workspace_bytes: *bytes = what gnerf_ssim_forward needs as workspace (per-tile partial sums; no initialisation needed).
+ *   gnerf_ssim_forward: two launches.
+ *   gnerf_ssim_backward: one launch that recomputes the moments (the forward saves nothing).  g_ssim / g_cs [n * c] float32 are the
+ *     gradients of the loss w.r.t. ssim_nc / cs_nc; either may be NULL (= zeros), not both.  dx / dy (X's dtype, [n, c, h, w] with
+ *     their own strides) receive the gradients w.r.t. X / Y; either may be NULL (not computed), not both.  Every element is written. */
+#define GNERF_SSIM_MAX_WIN 11
+int gnerf_ssim_workspace_bytes(int n, int c, int h, int w, int win, size_t* bytes);
+int gnerf_ssim_forward(const void* x, const void* y, int dtype, int n, int c, int h, int w, const int64_t* x_strides,
+                       const int64_t* y_strides, const float* window, int win, float C1, float C2, void* workspace, float* ssim_nc,
+                       float* cs_nc, gnerf_stream_t stream);
+int gnerf_ssim_backward(const void* x, const void* y, int dtype, int n, int c, int h, int w, const int64_t* x_strides,
+                        const int64_t* y_strides, const float* window, int win, float C1, float C2, const float* g_ssim,
+                        const float* g_cs, void* dx, const int64_t* dx_strides, void* dy, const int64_t* dy_strides,
+                        gnerf_stream_t stream);
 
 #ifdef __cplusplus
 }
