@@ -358,7 +358,343 @@ __global__ __launch_bounds__(kThreads) void torgb_nhwc_kernel(const __half* __re
     }
 }
 
+// ---------------------------------------------------------------------------------------------
+// Backward of the two elementwise passes (training: the convolution between them stays with the framework's autograd).  With
+//   g = dy * act'(.) * gain * [y strictly inside the clamp]                 (the mask read from the SAVED y, exactly as bias_act.hip's
+//                                                                            gradient form does: lrelu by the sign of y / gain)
+// one pass writes dx = round_T(g * T(scale)) and leaves the three reductions as per-wave / per-workgroup partial sums in a workspace:
+//   dscale[n,c] = sum_pixels g x,   dbias[c] = sum_{n,pixels} g,   dnoise[(n,)p] = sum_(n,)c g
+// which two small finishing launches add up.  No atomics anywhere, every sum in float32 in an order that depends on the shape alone
+// (and, for an item's dx / dscale, not on the batch it sits in): two runs give the same bits.  MASK = false is the backward of
+// scale_channels (g = the incoming gradient).  Traffic: dy + y (+ x when dscale is wanted) in, dx out; the partials are < 7 % of that.
+
+template <int CTRL> __device__ __forceinline__ float dpp_add(float v) {
+    return v + __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xF, 0xF, true));
+}
+
+// Sum over aligned groups of `width` (a power of two <= 64) adjacent lanes, the total in every lane of the group.  All 64 lanes must be
+// active.  Within a row of 16 lanes on DPP (quad permutes, then the two mirrors: each step adds the other half, whose lanes already
+// agree), across rows through the LDS crossbar.
+__device__ __forceinline__ float group_sum(float v, unsigned width) {
+    if (width >= 2) v = dpp_add<0xB1>(v);              // quad_perm [1,0,3,2]
+    if (width >= 4) v = dpp_add<0x4E>(v);              // quad_perm [2,3,0,1]
+    if (width >= 8) v = dpp_add<0x141>(v);             // row_half_mirror
+    if (width >= 16) v = dpp_add<0x140>(v);            // row_mirror
+    if (width >= 32) v += __shfl_xor(v, 16);
+    if (width >= 64) v += __shfl_xor(v, 32);
+    return v;
+}
+
+struct EpiBwdArgs {
+    const void* dy; const void* y; const void* x; void* dx;
+    const float* scale;      // [n, channels] or NULL
+    float* row_g;            // partial sums of g (for dbias) or NULL;   NCHW [n*channels][parts], NHWC [n][parts][channels]
+    float* row_gx;           // partial sums of g x (for dscale) or NULL, same shape
+    float* pix_g;            // [n][slots][pixels] sums of g over a slot's channels (for dnoise) or NULL
+    unsigned channels, pixels, parts, slots;
+    unsigned chunk_len;      // NCHW: channels per workgroup
+    unsigned ppb, cv, cvp;   // NHWC: pixels per workgroup, channel vectors, the same rounded up to a power of two
+    float slope, gain, clamp;
+};
+
+// one element's g from dy and the saved y
+template <bool MASK>
+__device__ __forceinline__ float epilogue_grad(float d, float yv, float sgn, const EpiBwdArgs& a) {
+    if constexpr (!MASK) return d * a.gain;            // (linear, no clamp; gain 1 for scale_channels: exact)
+    float gg = (yv * sgn > 0.f ? d : d * a.slope) * a.gain;
+    if (a.clamp >= 0.f) gg = (yv > -a.clamp && yv < a.clamp) ? gg : 0.f;
+    return gg;
+}
+
+// NCHW.  grid (pixel tiles of 256 * VEC, channel chunks, n).  A lane keeps VEC adjacent pixels and walks over the chunk's channels: the
+// pixel sums stay in its registers, the row sums are reduced per wave and stored per (row, tile, wave).
+template <class T, int VEC, bool MASK, bool NEEDX>
+__global__ __launch_bounds__(kThreads) void epilogue_backward_kernel(EpiBwdArgs a) {
+    typedef Pk<T, VEC> P;
+    const unsigned n = blockIdx.z, chunk = blockIdx.y, tile = blockIdx.x;
+    const unsigned p = (tile * kThreads + threadIdx.x) * VEC;
+    const bool ok = p < a.pixels;                      // (pixels % VEC == 0)
+    const unsigned c0 = chunk * a.chunk_len, c1 = min(a.channels, c0 + a.chunk_len);
+    const unsigned wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const float sgn = a.gain > 0.f ? 1.f : (a.gain < 0.f ? -1.f : 0.f);
+    const T* dy = static_cast<const T*>(a.dy);
+    const T* y = static_cast<const T*>(a.y);
+    const T* x = static_cast<const T*>(a.x);
+    T* dx = static_cast<T*>(a.dx);
+    float dn[VEC];
+#pragma unroll
+    for (int k = 0; k < VEC; k++) dn[k] = 0.f;
+    for (unsigned c = c0; c < c1; c++) {
+        const unsigned row = n * a.channels + c;
+        const int64_t off = int64_t(row) * a.pixels + p;
+        float sg = 0.f, sgx = 0.f;
+        if (ok) {
+            const P vdy = *reinterpret_cast<const P*>(dy + off);
+            P vy, vx, out;
+            if constexpr (MASK) vy = *reinterpret_cast<const P*>(y + off);
+            if constexpr (NEEDX) vx = *reinterpret_cast<const P*>(x + off);
+            const float sc = a.scale ? round_to<T>(a.scale[row]) : 1.f;
+#pragma unroll
+            for (int k = 0; k < VEC; k++) {
+                const float gg = epilogue_grad<MASK>(float(load_as<T>(vdy.v, k)), MASK ? float(load_as<T>(vy.v, k)) : 0.f, sgn, a);
+                sg += gg;
+                if constexpr (NEEDX) sgx = fmaf(gg, float(load_as<T>(vx.v, k)), sgx);
+                dn[k] += gg;
+                store_as<T>(out.v, k, gg * sc);
+            }
+            if (dx) *reinterpret_cast<P*>(dx + off) = out;
+        }
+        const unsigned slot = row * a.parts + tile * 4 + wave;
+        if (a.row_g) {
+            sg = group_sum(sg, 64);
+            if (lane == 0) a.row_g[slot] = sg;
+        }
+        if constexpr (NEEDX) {
+            sgx = group_sum(sgx, 64);
+            if (lane == 0) a.row_gx[slot] = sgx;
+        }
+    }
+    if (a.pix_g && ok) {
+        float* dst = a.pix_g + (int64_t(n) * a.slots + chunk) * a.pixels + p;
+#pragma unroll
+        for (int k = 0; k < VEC; k++) dst[k] = dn[k];
+    }
+}
+
+// Channels_last.  grid (pixel blocks of ppb, n).  The workgroup is 256 / cvp pixel rows of cvp lanes, a lane keeps ONE vector of VEC
+// adjacent channels (lanes cv .. cvp-1 idle) and walks over pixels: the channel sums stay in its registers and meet the other pixel
+// rows' in LDS at the end, the pixel sums are reduced over the pixel's lanes at every step (per wave: `slots` waves share a pixel when
+// cvp > 64).
+template <class T, int VEC, bool MASK, bool NEEDX>
+__global__ __launch_bounds__(kThreads) void epilogue_backward_nhwc_kernel(EpiBwdArgs a) {
+    typedef Pk<T, VEC> P;
+    __shared__ float red[2][kThreads * VEC];
+    const unsigned n = blockIdx.y, blk = blockIdx.x;
+    const unsigned j = threadIdx.x & (a.cvp - 1), r = threadIdx.x / a.cvp, rows = kThreads / a.cvp;
+    const bool active = j < a.cv;
+    const unsigned c0 = j * VEC;
+    const unsigned width = min(a.cvp, 64u);
+    const float sgn = a.gain > 0.f ? 1.f : (a.gain < 0.f ? -1.f : 0.f);
+    const T* dy = static_cast<const T*>(a.dy);
+    const T* y = static_cast<const T*>(a.y);
+    const T* x = static_cast<const T*>(a.x);
+    T* dx = static_cast<T*>(a.dx);
+    float sc[VEC], sg[VEC], sgx[VEC];
+#pragma unroll
+    for (int k = 0; k < VEC; k++) {
+        sc[k] = (a.scale && active) ? round_to<T>(a.scale[int64_t(n) * a.channels + c0 + k]) : 1.f;
+        sg[k] = 0.f; sgx[k] = 0.f;
+    }
+    const unsigned p0 = blk * a.ppb, p1 = min(a.pixels, p0 + a.ppb);
+    for (unsigned q = p0; q < p1; q += rows) {         // (uniform trip count: the reduction below needs every lane)
+        const unsigned p = q + r;
+        float pg = 0.f;
+        if (active && p < p1) {
+            const int64_t off = (int64_t(n) * a.pixels + p) * a.channels + c0;
+            const P vdy = *reinterpret_cast<const P*>(dy + off);
+            P vy, vx, out;
+            if constexpr (MASK) vy = *reinterpret_cast<const P*>(y + off);
+            if constexpr (NEEDX) vx = *reinterpret_cast<const P*>(x + off);
+#pragma unroll
+            for (int k = 0; k < VEC; k++) {
+                const float gg = epilogue_grad<MASK>(float(load_as<T>(vdy.v, k)), MASK ? float(load_as<T>(vy.v, k)) : 0.f, sgn, a);
+                sg[k] += gg;
+                if constexpr (NEEDX) sgx[k] = fmaf(gg, float(load_as<T>(vx.v, k)), sgx[k]);
+                pg += gg;
+                store_as<T>(out.v, k, gg * sc[k]);
+            }
+            if (dx) *reinterpret_cast<P*>(dx + off) = out;
+        }
+        if (a.pix_g) {
+            pg = group_sum(pg, width);
+            if ((threadIdx.x & (width - 1)) == 0 && p < p1) a.pix_g[(int64_t(n) * a.slots + (j >> 6)) * a.pixels + p] = pg;
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < VEC; k++) { red[0][threadIdx.x * VEC + k] = sg[k]; red[1][threadIdx.x * VEC + k] = sgx[k]; }
+    __syncthreads();
+    if (threadIdx.x < a.cv) {                          // (pixel row 0: j == threadIdx.x)
+        const int64_t dst = (int64_t(n) * a.parts + blk) * a.channels + c0;
+#pragma unroll
+        for (int k = 0; k < VEC; k++) {
+            float s = 0.f, sx = 0.f;
+            for (unsigned rr = 0; rr < rows; rr++) { s += red[0][(rr * a.cvp + j) * VEC + k]; sx += red[1][(rr * a.cvp + j) * VEC + k]; }
+            if (a.row_g) a.row_g[dst + k] = s;
+            if (NEEDX) a.row_gx[dst + k] = sx;
+        }
+    }
+}
+
+// One wave per result: dscale[n,c] = the row's `parts` partial sums of g x, dbias[c] = the n * parts partial sums of g of channel c.
+// Element (n, c, k) of either workspace at n * sn + c * sc + k * sk.
+__global__ __launch_bounds__(kThreads) void epilogue_backward_rows_kernel(const float* __restrict__ row_g, const float* __restrict__ row_gx,
+                                                                          float* __restrict__ dscale, float* __restrict__ dbias,
+                                                                          unsigned n, unsigned channels, unsigned parts, int64_t sn, int64_t sc, int64_t sk) {
+    const unsigned w = blockIdx.x * (kThreads / 64) + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    const unsigned rows = n * channels;
+    float s = 0.f;
+    if (w < rows) {
+        if (!dscale) return;
+        const float* src = row_gx + (w / channels) * sn + (w % channels) * sc;
+        for (unsigned k = lane; k < parts; k += 64) s += src[k * sk];
+        s = group_sum(s, 64);
+        if (lane == 0) dscale[w] = s;
+    } else if (w < rows + channels) {
+        if (!dbias) return;
+        const float* src = row_g + (w - rows) * sc;
+        for (unsigned i = lane; i < n * parts; i += 64) s += src[(i / parts) * sn + (i % parts) * sk];
+        s = group_sum(s, 64);
+        if (lane == 0) dbias[w - rows] = s;
+    }
+}
+
+// dnoise[i, p] = sum over slot of pix_g[i][slot][p] (per item), or dnoise[p] = the same summed over the items as well
+__global__ __launch_bounds__(kThreads) void epilogue_backward_noise_kernel(const float* __restrict__ pix_g, float* __restrict__ dnoise,
+                                                                           unsigned n, unsigned slots, unsigned pixels, int per_item) {
+    const int64_t i = int64_t(blockIdx.x) * kThreads + threadIdx.x;
+    if (i >= int64_t(per_item ? n : 1) * pixels) return;
+    const unsigned p = unsigned(i % pixels);
+    const unsigned first = per_item ? unsigned(i / pixels) * slots : 0, count = per_item ? slots : n * slots;
+    float s = 0.f;
+    for (unsigned k = 0; k < count; k++) s += pix_g[int64_t(first + k) * pixels + p];
+    dnoise[i] = s;
+}
+
+// How a shape is cut into workgroups and what the workspace holds: a function of (layout, dtype, channels, pixels, vector width) alone.
+struct BwdPlan {
+    int vec;
+    unsigned parts, slots, chunk_len, blocks, ppb, cv, cvp;
+    size_t row_floats, pix_floats;                     // one of row_g / row_gx; pix_g
+};
+
+bool make_bwd_plan(bool nhwc, int dtype, int n, int channels, int pixels, bool vec, BwdPlan& pl) {
+    const int full = dtype == GNERF_F16 ? 8 : 4;
+    pl = BwdPlan{};
+    if (!nhwc) {
+        pl.vec = vec && pixels % full == 0 ? full : 1;
+        const unsigned tiles = (unsigned(pixels) / pl.vec + kThreads - 1) / kThreads;
+        pl.blocks = tiles;
+        pl.parts = tiles * (kThreads / 64);
+        const unsigned want = tiles >= 256 ? 1u : 256u / tiles;            // ~256 workgroups per item, at least 16 channels each
+        pl.chunk_len = min(unsigned(channels), max(16u, (unsigned(channels) + want - 1) / want));
+        pl.slots = (unsigned(channels) + pl.chunk_len - 1) / pl.chunk_len;
+    } else {
+        pl.vec = vec && channels % full == 0 ? full : 1;
+        pl.cv = unsigned(channels) / pl.vec;
+        if (pl.cv > kThreads) return false;
+        pl.cvp = 1;
+        while (pl.cvp < pl.cv) pl.cvp <<= 1;
+        pl.slots = pl.cvp > 64 ? pl.cvp / 64 : 1;
+        const unsigned rows = kThreads / pl.cvp;
+        pl.ppb = max(rows * 4, (unsigned(pixels) + 255) / 256);
+        pl.ppb = (pl.ppb + rows - 1) / rows * rows;
+        pl.blocks = (unsigned(pixels) + pl.ppb - 1) / pl.ppb;
+        pl.parts = pl.blocks;
+    }
+    pl.row_floats = size_t(n) * channels * pl.parts;
+    pl.pix_floats = size_t(n) * pl.slots * pixels;
+    return true;
+}
+
+int epilogue_backward_impl(const char* what, bool nhwc, bool mask, const void* dy, const void* y, const void* x, const float* scale, int dtype,
+                           int n, int channels, int pixels, int noise_per_item, int act, float alpha, float gain, float clamp,
+                           void* dx, float* dscale, float* dbias, float* dnoise, void* workspace, gnerf_stream_t stream) {
+    if (!dy) return fail(GNERF_E_ARG, "%s: null pointer", what);
+    if (n < 1 || n > 65535 || channels < 1 || pixels < 1 || int64_t(pixels) * channels > INT32_MAX) return fail(GNERF_E_ARG, "%s: bad shape", what);
+    if (dtype != GNERF_F16 && dtype != GNERF_F32) return fail(GNERF_E_ARG, "%s: dtype must be float32 or float16", what);
+    if (mask && act != 1 && act != 3) return fail(GNERF_E_UNSUPPORTED, "%s: only linear and lrelu", what);
+    if (mask && !y && (act == 3 || clamp >= 0.f)) return fail(GNERF_E_ARG, "%s: the saved output is needed for lrelu and for a clamp", what);
+    if (dscale && !x) return fail(GNERF_E_ARG, "%s: dscale needs x", what);
+    if (!dx && !dscale && !dbias && !dnoise) return GNERF_OK;
+    if ((dscale || dbias || dnoise) && !workspace) return fail(GNERF_E_ARG, "%s: the reductions need the workspace", what);
+    const bool al = ((reinterpret_cast<uintptr_t>(dy) | reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(dx)) & 15) == 0;
+    BwdPlan pl;
+    if (!make_bwd_plan(nhwc, dtype, n, channels, pixels, al, pl))
+        return fail(GNERF_E_UNSUPPORTED, "%s: %d channels_last channels that fill no whole 16-byte vectors (at most %d then)", what, channels, kThreads);
+    mask = mask && (act == 3 || clamp >= 0.f);         // (linear without a clamp: g = dy * gain, y is not read)
+    float* ws = static_cast<float*>(workspace);
+    const bool direct = dnoise && (noise_per_item || n == 1) && pl.slots == 1;          // the pixel sums ARE the result
+    EpiBwdArgs a{dy, mask ? y : nullptr, dscale ? x : nullptr, dx, scale,
+                 dbias ? ws : nullptr, dscale ? ws + pl.row_floats : nullptr, dnoise ? (direct ? dnoise : ws + 2 * pl.row_floats) : nullptr,
+                 unsigned(channels), unsigned(pixels), pl.parts, pl.slots, pl.chunk_len, pl.ppb, pl.cv, pl.cvp,
+                 act == 3 ? alpha : 1.f, gain, clamp};
+    hipStream_t s = as_stream(stream);
+    const dim3 g = nhwc ? dim3(pl.blocks, n) : dim3(pl.blocks, pl.slots, n);
+#define GNERF_BWD2(K_, T_, V_, M_) do { \
+        if (dscale) hipLaunchKernelGGL((K_<T_, V_, M_, true>), g, dim3(kThreads), 0, s, a); \
+        else        hipLaunchKernelGGL((K_<T_, V_, M_, false>), g, dim3(kThreads), 0, s, a); } while (0)
+#define GNERF_BWD1(K_, T_, V_) do { if (mask) GNERF_BWD2(K_, T_, V_, true); else GNERF_BWD2(K_, T_, V_, false); } while (0)
+#define GNERF_BWD(K_) do { \
+        if (dtype == GNERF_F16) { if (pl.vec == 8) GNERF_BWD1(K_, __half, 8); else GNERF_BWD1(K_, __half, 1); } \
+        else                    { if (pl.vec == 4) GNERF_BWD1(K_, float, 4); else GNERF_BWD1(K_, float, 1); } } while (0)
+    if (nhwc) GNERF_BWD(epilogue_backward_nhwc_kernel); else GNERF_BWD(epilogue_backward_kernel);
+#undef GNERF_BWD
+#undef GNERF_BWD1
+#undef GNERF_BWD2
+    int rc = check_launch(what);
+    if (rc != GNERF_OK) return rc;
+    if (dscale || dbias) {
+        const unsigned waves = unsigned(n) * channels + channels;
+        const int64_t sn = nhwc ? int64_t(pl.parts) * channels : int64_t(channels) * pl.parts, sc = nhwc ? 1 : pl.parts, sk = nhwc ? channels : 1;
+        hipLaunchKernelGGL(epilogue_backward_rows_kernel, dim3((waves + 3) / 4), dim3(kThreads), 0, s, a.row_g, a.row_gx, dscale, dbias,
+                           unsigned(n), unsigned(channels), pl.parts, sn, sc, sk);
+        if ((rc = check_launch(what)) != GNERF_OK) return rc;
+    }
+    if (dnoise && !direct) {
+        const int64_t outs = int64_t(noise_per_item ? n : 1) * pixels;
+        hipLaunchKernelGGL(epilogue_backward_noise_kernel, dim3(unsigned((outs + kThreads - 1) / kThreads)), dim3(kThreads), 0, s, a.pix_g, dnoise,
+                           unsigned(n), pl.slots, unsigned(pixels), noise_per_item);
+        rc = check_launch(what);
+    }
+    return rc;
+}
+
 }  // namespace
+
+extern "C" int gnerf_modconv_backward_workspace_bytes(int channels_last, int dtype, int n, int channels, int pixels, size_t* bytes) {
+    using namespace gnerf;
+    if (!bytes) return fail(GNERF_E_ARG, "modconv_backward_workspace_bytes: null pointer");
+    if (n < 1 || channels < 1 || pixels < 1 || (dtype != GNERF_F16 && dtype != GNERF_F32)) return fail(GNERF_E_ARG, "modconv_backward_workspace_bytes: bad argument");
+    size_t most = 0;
+    for (int vec = 0; vec < 2; vec++) {                // (which form runs depends on the pointers' alignment: room for either)
+        BwdPlan pl;
+        if (make_bwd_plan(channels_last != 0, dtype, n, channels, pixels, vec != 0, pl)) {
+            const size_t b = (2 * pl.row_floats + pl.pix_floats) * sizeof(float);
+            if (b > most) most = b;
+        }
+    }
+    *bytes = most;
+    return GNERF_OK;
+}
+
+extern "C" int gnerf_scale_channels_backward(const void* dxs, const void* x, const float* scale, int dtype, int n, int channels, int pixels,
+                                             void* dx, float* dscale, void* workspace, gnerf_stream_t stream) {
+    if (dx && !scale) return gnerf::fail(GNERF_E_ARG, "scale_channels_backward: dx needs the scale");
+    return epilogue_backward_impl("scale_channels_backward", false, false, dxs, nullptr, x, scale, dtype, n, channels, pixels, 0, 1, 0.f, 1.f, -1.f,
+                                  dx, dscale, nullptr, nullptr, workspace, stream);
+}
+
+extern "C" int gnerf_scale_channels_backward_nhwc(const void* dxs, const void* x, const float* scale, int dtype, int n, int pixels, int channels,
+                                                  void* dx, float* dscale, void* workspace, gnerf_stream_t stream) {
+    if (dx && !scale) return gnerf::fail(GNERF_E_ARG, "scale_channels_backward_nhwc: dx needs the scale");
+    return epilogue_backward_impl("scale_channels_backward_nhwc", true, false, dxs, nullptr, x, scale, dtype, n, channels, pixels, 0, 1, 0.f, 1.f, -1.f,
+                                  dx, dscale, nullptr, nullptr, workspace, stream);
+}
+
+extern "C" int gnerf_modconv_epilogue_backward(const void* dy, const void* y, const void* x, const float* scale, int dtype, int n, int channels, int pixels,
+                                               int noise_per_item, int act, float alpha, float gain, float clamp,
+                                               void* dx, float* dscale, float* dbias, float* dnoise, void* workspace, gnerf_stream_t stream) {
+    return epilogue_backward_impl("modconv_epilogue_backward", false, true, dy, y, x, scale, dtype, n, channels, pixels, noise_per_item, act, alpha, gain, clamp,
+                                  dx, dscale, dbias, dnoise, workspace, stream);
+}
+
+extern "C" int gnerf_modconv_epilogue_backward_nhwc(const void* dy, const void* y, const void* x, const float* scale, int dtype, int n, int pixels, int channels,
+                                                    int noise_per_item, int act, float alpha, float gain, float clamp,
+                                                    void* dx, float* dscale, float* dbias, float* dnoise, void* workspace, gnerf_stream_t stream) {
+    return epilogue_backward_impl("modconv_epilogue_backward_nhwc", true, true, dy, y, x, scale, dtype, n, channels, pixels, noise_per_item, act, alpha, gain, clamp,
+                                  dx, dscale, dbias, dnoise, workspace, stream);
+}
+
 
 extern "C" int gnerf_modulate_weights(const float* weight, const float* styles, void* out, int out_dtype, float* dcoefs,
                                       int n, int n_out, int n_in, int kk, int demodulate, int prenorm, int out_layout, gnerf_stream_t stream) {

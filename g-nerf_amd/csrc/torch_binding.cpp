@@ -10,7 +10,8 @@
 // guard) -- and nothing else: no kernels live here, every function validates, allocates and calls the C ABI.  It exists for host
 // cost: a call through ctypes spends 10-12 us marshalling arguments in Python, this path ~3.
 // Also exported: render_forward (the fused renderer has no reference plugin; same C ABI call as gnerf_hip.render_forward) and
-// marching_cubes (gnerf_hip.marching_cubes' count -> read counts -> emit sequence), ssim_forward / ssim_backward (gnerf_hip.ssim_*).
+// marching_cubes (gnerf_hip.marching_cubes' count -> read counts -> emit sequence), ssim_forward / ssim_backward (gnerf_hip.ssim_*),
+// modconv_backward (gnerf_hip.scale_channels_backward / modconv_epilogue_backward).
 //
 // Built ahead of time by csrc/build.sh (g++, no hipcc: there is no device code) into g-nerf_amd/gnerf_hip/gnerf_torch_ext.so.
 
@@ -354,6 +355,55 @@ std::tuple<c10::optional<Tensor>, c10::optional<Tensor>> ssim_backward(Tensor x,
     return std::make_tuple(dx, dy);
 }
 
+// ------------------------------------------------------------------------------------------------ modconv backward (csrc/modconv.hip)
+// One entry for gnerf_scale_channels_backward(_nhwc) (epilogue = false: dy is the gradient of x * scale, x its input) and
+// gnerf_modconv_epilogue_backward(_nhwc).  gnerf_hip.scale_channels_backward / modconv_epilogue_backward have validated the tensors (dy, y, x one
+// dtype and memory format, NCHW contiguous or channels_last; scale contiguous float32 [N, C]).  need_dnoise: 0 no, 1 one [H, W] plane, 2 [N, 1, H, W].
+// -> (dx, dscale [N, C], dbias [C], dnoise), float32 sums, None where not asked for.
+std::tuple<c10::optional<Tensor>, c10::optional<Tensor>, c10::optional<Tensor>, c10::optional<Tensor>> modconv_backward(
+        bool epilogue, Tensor dy, c10::optional<Tensor> y, c10::optional<Tensor> x, c10::optional<Tensor> scale, int act, double alpha, double gain, double clamp,
+        bool need_dx, bool need_dscale, bool need_dbias, int need_dnoise) {
+    TORCH_CHECK(dy.is_cuda() && dy.dim() == 4, "modconv_backward: dy must be a 4-D GPU tensor");
+    const bool nhwc = !dy.is_contiguous();
+    TORCH_CHECK(!nhwc || dy.is_contiguous(at::MemoryFormat::ChannelsLast), "modconv_backward: dy must be contiguous (NCHW) or channels_last");
+    auto same = [&](const c10::optional<Tensor>& t) { return !t.has_value() || (t->scalar_type() == dy.scalar_type() && same_layout(*t, dy) && t->device() == dy.device()); };
+    TORCH_CHECK(same(y) && same(x), "modconv_backward: y and x must match dy in shape, dtype and memory format");
+    const int n = int(dy.size(0)), c = int(dy.size(1)), pixels = int(dy.size(2) * dy.size(3));
+    TORCH_CHECK(!scale.has_value() || (scale->device() == dy.device() && scale->scalar_type() == torch::kFloat32 && scale->is_contiguous() && scale->numel() == int64_t(n) * c),
+                "modconv_backward: scale must be contiguous float32 [N, C] on dy's device");
+    TORCH_CHECK(!need_dscale || x.has_value(), "modconv_backward: dscale needs x");
+    const int dtype = dtype_code(dy, "modconv_backward");
+    const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(at::device_of(dy));
+    const auto f32 = dy.options().dtype(torch::kFloat32);
+    c10::optional<Tensor> dx, dscale, dbias, dnoise;
+    Tensor ws;
+    if (need_dx) dx = torch::empty_like(dy);
+    if (need_dscale) dscale = torch::empty({n, c}, f32);
+    if (need_dbias) dbias = torch::empty({c}, f32);
+    if (need_dnoise == 1) dnoise = torch::empty({dy.size(2), dy.size(3)}, f32);
+    if (need_dnoise == 2) dnoise = torch::empty({n, 1, dy.size(2), dy.size(3)}, f32);
+    if (need_dscale || need_dbias || need_dnoise) {
+        size_t bytes = 0;
+        check_rc(gnerf_modconv_backward_workspace_bytes(nhwc ? 1 : 0, dtype, n, c, pixels, &bytes), "gnerf_modconv_backward_workspace_bytes");
+        ws = torch::empty({int64_t(bytes < 16 ? 16 : bytes)}, dy.options().dtype(torch::kUInt8));
+    }
+    auto p = [](const c10::optional<Tensor>& t) -> void* { return t.has_value() ? t->data_ptr() : nullptr; };
+    const float* sp = static_cast<const float*>(p(scale));
+    void* wp = ws.defined() ? ws.data_ptr() : nullptr;
+    int rc;
+    if (!epilogue) {
+        rc = nhwc ? gnerf_scale_channels_backward_nhwc(dy.data_ptr(), p(x), sp, dtype, n, pixels, c, p(dx), static_cast<float*>(p(dscale)), wp, current_stream())
+                  : gnerf_scale_channels_backward(dy.data_ptr(), p(x), sp, dtype, n, c, pixels, p(dx), static_cast<float*>(p(dscale)), wp, current_stream());
+    } else {
+        rc = nhwc ? gnerf_modconv_epilogue_backward_nhwc(dy.data_ptr(), p(y), need_dscale ? p(x) : nullptr, sp, dtype, n, pixels, c, need_dnoise == 2, act, float(alpha), float(gain), float(clamp),
+                                                         p(dx), static_cast<float*>(p(dscale)), static_cast<float*>(p(dbias)), static_cast<float*>(p(dnoise)), wp, current_stream())
+                  : gnerf_modconv_epilogue_backward(dy.data_ptr(), p(y), need_dscale ? p(x) : nullptr, sp, dtype, n, c, pixels, need_dnoise == 2, act, float(alpha), float(gain), float(clamp),
+                                                    p(dx), static_cast<float*>(p(dscale)), static_cast<float*>(p(dbias)), static_cast<float*>(p(dnoise)), wp, current_stream());
+    }
+    check_rc(rc, epilogue ? "gnerf_modconv_epilogue_backward" : "gnerf_scale_channels_backward");
+    return std::make_tuple(dx, dscale, dbias, dnoise);
+}
+
 }  // namespace
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -365,6 +415,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("marching_cubes", &marching_cubes);
     m.def("ssim_forward", &ssim_forward);
     m.def("ssim_backward", &ssim_backward);
+    m.def("modconv_backward", &modconv_backward);
     // the header version THIS extension was compiled against (a compile-time constant: gnerf_abi_version() would resolve in
     // libgnerf_hip.so at run time and compare the library with itself); gnerf_hip.ext() checks both against its own
     m.def("abi_version", []() { return int(GNERF_ABI_VERSION); });

@@ -28,7 +28,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from torch_utils.ops import bias_act, conv2d_resample, fma, upfirdn2d
+from torch_utils.ops import bias_act, conv2d_resample, fma, modconv, upfirdn2d
 from training.volumetric_rendering.renderer import ImportanceRenderer
 from training.volumetric_rendering.ray_sampler import RaySampler
 
@@ -41,6 +41,10 @@ LRELU_GAIN = math.sqrt(2)
 # batch of fp16 layers uses the shared-weight form of the convolution (one batched MIOpen convolution instead of a grouped one
 # with per-sample weights: 2.2x faster at batch 4, tools/bench_upconv.py).  GNERF_MODCONV_FAST=0 keeps the plain PyTorch forms.
 _MODCONV_FAST = os.environ.get('GNERF_MODCONV_FAST', '1') != '0'
+# Training on a GPU (the un-fused form under autograd): the two elementwise passes around the convolution -- `x * styles` in front, demodulation +
+# noise + bias + activation + clamp behind -- run as the same kernels, with backward kernels of their own (torch_utils/ops/modconv.py); the
+# convolution keeps the framework's backward.  GNERF_MODCONV_TRAIN=0 keeps the PyTorch-op chain (fma.fma, bias_act) of `_reference_unfused`.
+_MODCONV_TRAIN = os.environ.get('GNERF_MODCONV_TRAIN', '1') != '0'
 
 
 def _is_channels_last(x):
@@ -50,6 +54,12 @@ def _is_channels_last(x):
 def _fast_path(x, *params):
     return (_MODCONV_FAST and x.is_cuda and (x.is_contiguous() or _is_channels_last(x)) and x.dtype in (torch.float16, torch.float32)
             and not (torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in params))))
+
+
+def _train_path(x):
+    """True where a layer that `_fast_path` has turned down runs its un-fused form on the `_train` route: a GPU tensor the kernels take."""
+    return (_MODCONV_TRAIN and _MODCONV_FAST and x.is_cuda and (x.is_contiguous() or _is_channels_last(x)) and x.dtype in (torch.float16, torch.float32)
+            and gnerf_hip.modconv_backward_available())
 
 
 def _param_memo(module, tag, p, fn):
@@ -299,7 +309,9 @@ class StyledConv(nn.Module):
         """The name of the method forward(x, w, noise_mode, fused=fused) runs on.  torgb_tail: the
         caller would hand over the block's ToRGB (Block.forward asks before it upsamples its image)."""
         if not _fast_path(x, w, self.weight, self.bias, self.noise_strength, self.affine.weight, self.affine.bias):
-            return '_reference_fused' if fused else '_reference_unfused'       # (w: a latent that needs a gradient takes the autograd forms)
+            if fused:
+                return '_reference_fused'                                      # (w: a latent that needs a gradient takes the autograd forms)
+            return '_train' if _train_path(x) else '_reference_unfused'
         n, c_in, h, wd = x.shape
         c_out, up = self.weight.shape[0], self.up
         # the kernels' epilogues take noise as one [H, W] plane at the output's size: 'const', or 'random' for a single image
@@ -441,6 +453,21 @@ class StyledConv(nn.Module):
         x = gnerf_hip.modconv_epilogue(x, bias, scale=dco, noise=noise, round_noise=True, act='lrelu', gain=gain, clamp=clamp, next_scale=None if split else nxt)
         return gnerf_hip.scale_channels(x, nxt) if split else x
 
+    def _train(self, x, w, styles, noise, gain, clamp):
+        """The un-fused form under autograd with the elementwise passes on the kernels (forward and backward: torch_utils/ops/modconv.py) and the
+        convolution (+ the x2 layers' blur) on the framework's, which keeps its own backward.  The fp16 pre-normalisation and the demodulation
+        coefficients are `_reference_unfused`'s, in PyTorch ops: their chains back to weight and affine are small tensors."""
+        weight = self.weight
+        if x.dtype == torch.float16:
+            weight, styles = _prenormalize(weight, styles)
+        dcoefs = _demod_coefficients(weight, styles)
+        x = modconv.scale_channels(x, styles)
+        if self.up == 1:
+            x = self._conv(x, weight.to(x.dtype))
+        else:
+            x, _ = self._blur(self._conv_transposed(x, weight.to(x.dtype).transpose(0, 1)))
+        return modconv.epilogue(x, dcoefs, noise, self.bias, act='lrelu', gain=gain, clamp=clamp)
+
     # -- the reference's own flow (modulated_conv2d, networks_stylegan2.py:41-98, from SynthesisLayer.forward :315-334, padding = 1, flip_weight =
     # (up == 1)): PyTorch ops for the modulation, the convolution through torch_utils.ops.conv2d_resample and the demodulation through
     # torch_utils.ops.fma -- the overlay's modules on a GPU, i.e. what a G-NeRF checkout gets from this repo without any of the kernels above.
@@ -480,7 +507,9 @@ class ToRGB(nn.Module):
     def route(self, x, w, fused=True):
         """The route forward(x, w, fused) takes, as the name of its method."""
         if not _fast_path(x, w, self.weight, self.bias, self.affine.weight, self.affine.bias):
-            return '_reference_fused' if fused else '_reference_unfused'
+            if fused:
+                return '_reference_fused'
+            return '_train' if _train_path(x) else '_reference_unfused'
         if x.dtype == torch.float16 and _is_channels_last(x) and self.weight.shape[0] == 3 and x.shape[1] in gnerf_hip.TORGB_CHANNELS:
             return '_stream'
         if x.dtype == torch.float32 and _is_channels_last(x):
@@ -524,6 +553,10 @@ class ToRGB(nn.Module):
 
     def _epilogue(self, x):
         return gnerf_hip.modconv_epilogue(x, _cast_param(self, 'bias', x.dtype), act='linear', gain=1.0, clamp=self.conv_clamp)
+
+    def _train(self, x, w, styles, img):          # the un-fused form under autograd, its elementwise passes on the kernels (StyledConv._train)
+        x = F.conv2d(modconv.scale_channels(x, styles), self.weight.to(x.dtype))
+        return modconv.epilogue(x, bias=self.bias, act='linear', clamp=self.conv_clamp)
 
     def _reference_fused(self, x, w, styles, img):          # (the reference's flow, as in StyledConv)
         n, c_in, h, wd = x.shape

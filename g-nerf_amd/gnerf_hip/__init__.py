@@ -123,7 +123,15 @@ SIGNATURES = {
                                   _c_f, _c_f, _c_p, _c_p, _c_p, _c_p]),
     'gnerf_ssim_backward': (_c_i, [_c_p, _c_p, _c_i, _c_i, _c_i, _c_i, _c_i, ctypes.POINTER(_c_i64), ctypes.POINTER(_c_i64), ctypes.POINTER(_c_f), _c_i,
                                    _c_f, _c_f, _c_p, _c_p, _c_p, ctypes.POINTER(_c_i64), _c_p, ctypes.POINTER(_c_i64), _c_p]),
+    'gnerf_modconv_backward_workspace_bytes': (_c_i, [_c_i, _c_i, _c_i, _c_i, _c_i, ctypes.POINTER(ctypes.c_size_t)]),
+    'gnerf_scale_channels_backward': (_c_i, [_c_p, _c_p, _c_p, _c_i, _c_i, _c_i, _c_i, _c_p, _c_p, _c_p, _c_p]),
+    'gnerf_scale_channels_backward_nhwc': (_c_i, [_c_p, _c_p, _c_p, _c_i, _c_i, _c_i, _c_i, _c_p, _c_p, _c_p, _c_p]),
+    'gnerf_modconv_epilogue_backward': (_c_i, [_c_p, _c_p, _c_p, _c_p, _c_i, _c_i, _c_i, _c_i, _c_i, _c_i, _c_f, _c_f, _c_f, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p]),
+    'gnerf_modconv_epilogue_backward_nhwc': (_c_i, [_c_p, _c_p, _c_p, _c_p, _c_i, _c_i, _c_i, _c_i, _c_i, _c_i, _c_f, _c_f, _c_f, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p]),
 }
+# exports added WITHOUT a new ABI version: a library of the same version built before them (a variant build behind GNERF_HIP_LIB) loads, and
+# what needs them asks modconv_backward_available()
+OPTIONAL_SYMBOLS = frozenset(n for n in SIGNATURES if n.startswith(('gnerf_modconv_backward_', 'gnerf_scale_channels_backward', 'gnerf_modconv_epilogue_backward')))
 
 
 def profiled(name):
@@ -154,7 +162,9 @@ def load():
                            f'(or python -c "import __graft_entry__ as g; g.build()"). There is no fallback path.')
     lib = ctypes.CDLL(LIB_PATH)
     for name, (res, args) in SIGNATURES.items():
-        fn = getattr(lib, name)
+        fn = getattr(lib, name, None) if name in OPTIONAL_SYMBOLS else getattr(lib, name)
+        if fn is None:
+            continue
         fn.restype = res
         fn.argtypes = args
     if lib.gnerf_abi_version() != ABI_VERSION:
@@ -709,6 +719,103 @@ def modconv_epilogue(x, bias=None, scale=None, noise=None, round_noise=False, ac
                                                  float(-1 if clamp is None else clamp), _stream(x))
     _check(code, 'gnerf_modconv_epilogue')
     return y
+
+
+def modconv_backward_available():
+    """True when the loaded library exports the backward kernels of scale_channels / modconv_epilogue (found by symbol, not by version)."""
+    if not is_available():
+        return False
+    lib = load()
+    return all(hasattr(lib, name) for name in OPTIONAL_SYMBOLS)
+
+
+def _modconv_backward_workspace(x, layout):
+    n, c, h, w = x.shape
+    nbytes = ctypes.c_size_t(0)
+    _check(load().gnerf_modconv_backward_workspace_bytes(1 if layout == 'nhwc' else 0, _DTYPE_CODE[x.dtype], n, c, h * w, ctypes.byref(nbytes)),
+           'gnerf_modconv_backward_workspace_bytes')
+    return torch.empty(max(nbytes.value, 16), dtype=torch.uint8, device=x.device)
+
+
+def _same_strides(a, b):
+    """Equal strides wherever the size is at least 2 (a dimension of size 1 has no meaningful stride)."""
+    return all(sa == sb for sz, sa, sb in zip(a.shape, a.stride(), b.stride()) if sz >= 2)
+
+
+def _like_activation(g, x, what):
+    """The incoming gradient `g` in x's dtype and memory format (autograd hands over whatever the consumer's backward produced)."""
+    if g.shape != x.shape or g.dtype != x.dtype or g.device != x.device:
+        raise RuntimeError(f'{what}: the gradient must match the activations in shape, dtype and device')
+    return g if _same_strides(g, x) else g.contiguous(memory_format=torch.channels_last if is_channels_last(x) else torch.contiguous_format)
+
+
+@profiled('gnerf_hip::scale_channels_backward')
+def scale_channels_backward(dxs, x, scale, need_dx=True, need_dscale=True):
+    """Backward of scale_channels(x, scale) for the incoming gradient dxs -> (dx like x, dscale float32 [N, C]); None where not asked for.
+    dx = round(dxs * scale) in x's dtype, dscale = sum over the pixels of dxs * x in float32 (fixed order, no atomics)."""
+    _require_cuda(dxs, x, scale)
+    layout = _activation_layout(x, 'scale_channels_backward')
+    dxs = _like_activation(dxs, x, 'scale_channels_backward')
+    n, c, h, w = x.shape
+    s32 = scale.detach().to(torch.float32).contiguous()
+    if s32.numel() != n * c:
+        raise RuntimeError('scale_channels_backward: scale must have N*C elements')
+    e = ext()
+    if e is not None and hasattr(e, 'modconv_backward'):
+        return e.modconv_backward(False, dxs, None, x, s32, 1, 0.0, 1.0, -1.0, bool(need_dx), bool(need_dscale), False, 0)[:2]
+    dx = torch.empty_like(x) if need_dx else None
+    dscale = torch.empty([n, c], dtype=torch.float32, device=x.device) if need_dscale else None
+    ws = _modconv_backward_workspace(x, layout) if need_dscale else None
+    with _on_device(x.device):
+        if layout == 'nhwc':
+            code = load().gnerf_scale_channels_backward_nhwc(_ptr(dxs), _ptr(x), _ptr(s32), _DTYPE_CODE[x.dtype], n, h * w, c, _ptr(dx), _ptr(dscale), _ptr(ws), _stream(x))
+        else:
+            code = load().gnerf_scale_channels_backward(_ptr(dxs), _ptr(x), _ptr(s32), _DTYPE_CODE[x.dtype], n, c, h * w, _ptr(dx), _ptr(dscale), _ptr(ws), _stream(x))
+    _check(code, 'gnerf_scale_channels_backward')
+    return dx, dscale
+
+
+@profiled('gnerf_hip::modconv_epilogue_backward')
+def modconv_epilogue_backward(dy, y, x, scale=None, act='lrelu', alpha=0.2, gain=1.0, clamp=None, need_dx=True, need_dscale=False, need_dbias=False,
+                              need_dnoise=None):
+    """Backward of modconv_epilogue for the incoming gradient dy -> (dx like dy, dscale [N,C], dbias [C], dnoise), float32 sums, None where not
+    asked for.  y: the forward's result (what the activation and clamp masks are read from; may be None for act='linear' without a clamp);
+    x: the forward's input (needed for dscale only, else None); need_dnoise: None, 'plane' ([H,W]) or 'item' ([N,1,H,W]).
+    Definition and guarantees: include/gnerf_hip.h, gnerf_modconv_epilogue_backward."""
+    _require_cuda(dy, y, x, scale)
+    layout = _activation_layout(dy, 'modconv_epilogue_backward')
+    if act not in ('linear', 'lrelu'):
+        raise RuntimeError('modconv_epilogue_backward: act must be linear or lrelu')
+    if need_dnoise not in (None, 'plane', 'item'):
+        raise RuntimeError("modconv_epilogue_backward: need_dnoise must be None, 'plane' or 'item'")
+    if y is None and (act == 'lrelu' or clamp is not None):
+        raise RuntimeError('modconv_epilogue_backward: the forward output y is needed for lrelu and for a clamp')
+    if need_dscale and (x is None or scale is None):
+        raise RuntimeError('modconv_epilogue_backward: dscale needs x and scale')
+    for t in (y, x):
+        if t is not None and (t.shape != dy.shape or t.dtype != dy.dtype or not _same_strides(t, dy)):
+            raise RuntimeError('modconv_epilogue_backward: y and x must match dy in shape, dtype and memory format')
+    n, c, h, w = dy.shape
+    s32 = None if scale is None else scale.detach().to(torch.float32).contiguous()
+    if s32 is not None and s32.numel() != n * c:
+        raise RuntimeError('modconv_epilogue_backward: scale must have N*C elements')
+    dev = dy.device
+    e = ext()
+    if e is not None and hasattr(e, 'modconv_backward'):
+        return e.modconv_backward(True, dy, y, x if need_dscale else None, s32, 3 if act == 'lrelu' else 1, float(alpha), float(gain), float(-1 if clamp is None else clamp),
+                                  bool(need_dx), bool(need_dscale), bool(need_dbias), {None: 0, 'plane': 1, 'item': 2}[need_dnoise])
+    dx = torch.empty_like(dy) if need_dx else None
+    dscale = torch.empty([n, c], dtype=torch.float32, device=dev) if need_dscale else None
+    dbias = torch.empty([c], dtype=torch.float32, device=dev) if need_dbias else None
+    dnoise = None if need_dnoise is None else torch.empty([n, 1, h, w] if need_dnoise == 'item' else [h, w], dtype=torch.float32, device=dev)
+    ws = _modconv_backward_workspace(dy, layout) if (need_dscale or need_dbias or need_dnoise) else None
+    args = (_ptr(dy), _ptr(y), _ptr(x) if need_dscale else None, _ptr(s32), _DTYPE_CODE[dy.dtype], n) + ((h * w, c) if layout == 'nhwc' else (c, h * w)) + (
+        1 if need_dnoise == 'item' else 0, 3 if act == 'lrelu' else 1, float(alpha), float(gain), float(-1 if clamp is None else clamp),
+        _ptr(dx), _ptr(dscale), _ptr(dbias), _ptr(dnoise), _ptr(ws), _stream(dy))
+    with _on_device(dev):
+        code = (load().gnerf_modconv_epilogue_backward_nhwc if layout == 'nhwc' else load().gnerf_modconv_epilogue_backward)(*args)
+    _check(code, 'gnerf_modconv_epilogue_backward')
+    return dx, dscale, dbias, dnoise
 
 
 def clock_under_load(run, microseconds=3000.0, device=None):

@@ -121,6 +121,31 @@ int gnerf_scale_channels_nhwc(const void* x, const float* scale, void* y, int dt
 int gnerf_modconv_epilogue_nhwc(const void* x, void* y, int dtype, int n, int pixels, int channels,
                                 const float* scale, const float* noise, int noise_per_item, int round_noise, const void* bias,
                                 int act, float alpha, float gain, float clamp, const float* next_scale, gnerf_stream_t stream);
+/* The backward of the two passes above (training: the convolution between them keeps the framework's own backward).  New exports of
+ * ABI 15: detect them by symbol (gnerf_hip.modconv_backward_available()), not by version.  Activations float32 / float16 as [n, channels,
+ * pixels] (NCHW) or, in the _nhwc forms, [n, pixels, channels]; every reduction is accumulated in float32 without atomics in an order
+ * the shape alone fixes (two runs give the same bits; an item's dx and dscale do not depend on the rest of the batch).  Every output
+ * may be NULL.  workspace: gnerf_modconv_backward_workspace_bytes(...) bytes of device memory, no initialisation needed (NULL is
+ * accepted when only dx is asked for).
+ *   gnerf_scale_channels_backward(_nhwc): dx = round_T(dxs * T(scale[n,c])), dscale[n,c] = sum_pixels dxs * x (float32).
+ *   gnerf_modconv_epilogue_backward(_nhwc): the adjoint of t = x * scale + noise, y = clamp(act(t + bias) * gain), act 1 linear or
+ *     3 lrelu, with bias_act's gradient convention (the mask is read from the SAVED output: lrelu's slope by the sign of y / gain, the
+ *     clamp passes where -clamp < y < clamp): g = dy * act' * gain * [inside],
+ *       dx = round_T(g * T(scale[n,c])) (g without a scale), dscale[n,c] = sum_pixels g * x, dbias[c] = sum_{n,pixels} g,
+ *       dnoise[pixels] (or [n, pixels] when noise_per_item) = sum_c g          (all sums float32).
+ *     y may be NULL for act 1 without a clamp, x when dscale is NULL.
+ * Launches: one pass over the activations (reads dy, y and -- for dscale -- x, writes dx) and up to two small finishing ones. */
+int gnerf_modconv_backward_workspace_bytes(int channels_last, int dtype, int n, int channels, int pixels, size_t* bytes);
+int gnerf_scale_channels_backward(const void* dxs, const void* x, const float* scale, int dtype, int n, int channels, int pixels,
+                                  void* dx, float* dscale, void* workspace, gnerf_stream_t stream);
+int gnerf_scale_channels_backward_nhwc(const void* dxs, const void* x, const float* scale, int dtype, int n, int pixels, int channels,
+                                       void* dx, float* dscale, void* workspace, gnerf_stream_t stream);
+int gnerf_modconv_epilogue_backward(const void* dy, const void* y, const void* x, const float* scale, int dtype, int n, int channels, int pixels,
+                                    int noise_per_item, int act, float alpha, float gain, float clamp,
+                                    void* dx, float* dscale, float* dbias, float* dnoise, void* workspace, gnerf_stream_t stream);
+int gnerf_modconv_epilogue_backward_nhwc(const void* dy, const void* y, const void* x, const float* scale, int dtype, int n, int pixels, int channels,
+                                         int noise_per_item, int act, float alpha, float gain, float clamp,
+                                         void* dx, float* dscale, float* dbias, float* dnoise, void* workspace, gnerf_stream_t stream);
 /* The 4x4 blur that follows a x2-upsampling transposed convolution (conv2d_resample.py:114-131) and the epilogue above in ONE pass over
  * channels_last activations: y = epilogue(round_T(blur(x) * blur_gain)), bit-identical to gnerf_upfirdn2d followed by
  * gnerf_modconv_epilogue_nhwc (no noise term: the layers that add noise run in NCHW float32 here).  x: [n, in_h, in_w, c] dense,
