@@ -6,7 +6,7 @@ The reference JIT-compiles CUDA sources with nvcc at first use.  Here the three 
 ONE ahead-of-time-built library, libgnerf_hip.so (hand-written gfx950 kernels, C ABI in
 include/gnerf_hip.h), reached through the thin PyTorch C++ extension gnerf_torch_ext.so
 (csrc/torch_binding.cpp: pybind entry points with the reference plugins' exact signatures), or through
-the ctypes binding in gnerf_hip/__init__.py when the extension is not built / GNERF_HIP_BINDING=ctypes.
+the ctypes binding in the gnerf_hip package when the extension is not built / GNERF_HIP_BINDING=ctypes.
 `sources`, `headers`, `source_dir` and the build keywords are accepted and ignored.  A missing library
 is an error: there is no silent fallback for GPU tensors."""
 

@@ -391,11 +391,13 @@ class ImportanceRenderer(torch.nn.Module):
             nhwc, amax = self._planes_nhwc(planes)
             if gnerf_hip.render_generated_supported(S, F, ray_start, ray_end, cfg['disparity_space_sampling'], plan=plan, numel_planes=nhwc.numel() // (1 if views else N)):
                 try:
+                    # rng= is not taken by render_forward's extension branch: this call always goes through ctypes, whose failures
+                    # carry the C ABI's return code (gnerf_hip.NativeError.code)
                     out = gnerf_hip.render_forward(nhwc, N, self._decoder_cache(fcs), ray_origins.detach(), ray_directions.detach(), None, None,
                                                    ray_start=ray_start, ray_end=ray_end, planes_absmax=amax, planes_shared=views, depth_clamp_per_item=views,
                                                    rng=plan, **cfg)
                 except RuntimeError as e:
-                    if 'failed (-3)' not in str(e):              # GNERF_E_UNSUPPORTED: the tensor form below; anything else is an error
+                    if getattr(e, 'code', None) != gnerf_hip.E_UNSUPPORTED:      # GNERF_E_UNSUPPORTED: the tensor form below; anything else is an error
                         raise
                 else:
                     gnerf_hip.commit_philox_plan(plan)

@@ -904,10 +904,10 @@ def test_views_of_one_item_equal_separate_calls(dev):
                 nc, nf = torch.rand(N * res * res, S, device=dev), (torch.rand(N * res * res, F, device=dev) if F else None)
                 kw = dict(depth_resolution=S, depth_resolution_importance=F, ray_start=2.25, ray_end=3.3, box_warp=1.0, image_width=res)
                 for binding in ('ext', 'ctypes'):
-                    old = gnerf_hip._ext
+                    old = gnerf_hip._native._ext
                     try:
                         if binding == 'ctypes':
-                            gnerf_hip._ext = False
+                            gnerf_hip._native._ext = False
                         got = gnerf_hip.render_forward(planes, N, w, o, d, nc, nf, planes_shared=True, depth_clamp_per_item=True, **kw)
                         # the same launch with the planes copied N times and a per-item clamp: the shared read changes nothing
                         rep = gnerf_hip.render_forward(planes.repeat(N, 1, 1, 1), N, w, o, d, nc, nf, depth_clamp_per_item=True, **kw)
@@ -922,7 +922,7 @@ def test_views_of_one_item_equal_separate_calls(dev):
                         assert torch.equal(whole[0], got[0]) and torch.equal(whole[2], got[2])
                         assert float(whole[1].min()) <= float(got[1].min()) and float(whole[1].max()) >= float(got[1].max())
                     finally:
-                        gnerf_hip._ext = old
+                        gnerf_hip._native._ext = old
         # the workspace is back to idle (all zero): the next call-wide clamp starts from nothing
         torch.cuda.synchronize()
         for ws in gnerf_hip._workspaces.values():

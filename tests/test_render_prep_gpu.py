@@ -109,3 +109,55 @@ def test_step_prep_has_no_fill_launch(dev):
     assert any('nchw_to_nhwc' in n for n in kernels) and any('rays_and_draws' in n for n in kernels), names
     assert not any('fill' in n.lower() or 'memset' in n.lower() for n in names), names
     assert len(kernels) == 2, kernels
+
+
+def test_render_params_four_forms(dev):
+    """The one builder of gnerf_render_params: tensor rays or cameras, crossed with tensor noise or an rng plan.  Float32 contiguous
+    arguments are passed by pointer (no conversion copy), every scalar field is its argument, and the fields of the alternative not
+    taken stay null / zero.  Launches nothing."""
+    import gnerf_hip
+    N, res, S, F = 2, 4, 48, 48
+    M = res * res
+    planes = torch.randn(3 * N, 4, 4, 32, device=dev)
+    dec = (torch.randn(64, 32, device=dev), torch.randn(64, device=dev), torch.randn(33, 64, device=dev), torch.randn(33, device=dev))
+    o, d = torch.randn(N, M, 3, device=dev), torch.randn(N, M, 3, device=dev)
+    c2w, intr = torch.randn(N, 4, 4, device=dev), torch.randn(N, 3, 3, device=dev)
+    nc, nf = torch.rand(N * M, S, device=dev), torch.rand(N * M, F, device=dev)
+    amax = torch.ones(1, device=dev)
+    plan = gnerf_hip.torch_philox_plan(dev, N, M, S, F, advance=False)
+    plan_fields = dict(rng_mode=1, rng_per_item=0, rng_seed=plan.seed, rng_offset_coarse=plan.offset_coarse, rng_offset_fine=plan.offset_fine,
+                       rng_offset_item_stride=plan.item_stride, rng_threads_coarse=plan.threads_coarse, rng_threads_fine=plan.threads_fine)
+
+    def build(rays, noise, rs=2.25, re=3.25, image_width=7, cameras=None, rng=None, F=F):
+        return gnerf_hip._render_params(planes, N, dec, rays[0], rays[1], noise[0], noise[1], S, F, rs, re, 1.5, True, False, image_width, 'render_forward',
+                                        amax, 'f32', False, True, cameras, rng)
+
+    for with_cameras in (False, True):
+        for with_rng in (False, True):
+            p, keep, m = build((None, None) if with_cameras else (o, d), (None, None) if with_rng else (nc, nf),
+                               cameras=(c2w, intr, res) if with_cameras else None, rng=plan if with_rng else None)
+            tag = (with_cameras, with_rng)
+            assert m == M and p.rays_per_item == M, tag
+            want_ptr = dict(planes_nhwc=planes, w1=dec[0], b1=dec[1], w2=dec[2], b2=dec[3], planes_absmax=amax,
+                            ray_origins=None if with_cameras else o, ray_dirs=None if with_cameras else d,
+                            cam2world=c2w if with_cameras else None, intrinsics=intr if with_cameras else None,
+                            noise_coarse=None if with_rng else nc, noise_fine=None if with_rng else nf,
+                            ray_start_per_ray=None, ray_end_per_ray=None, sigma_noise_coarse=None, sigma_noise_fine=None,
+                            out_rgb=None, out_depth=None, out_wsum=None, workspace=None, debug=None)
+            for name, t in want_ptr.items():
+                assert getattr(p, name) == (None if t is None else t.data_ptr()), (tag, name)
+            want = dict(n_items=N, plane_h=4, plane_w=4, image_width=res if with_cameras else 7, depth_resolution=S, depth_resolution_importance=F,
+                        ray_start=2.25, ray_end=3.25, box_warp=1.5, white_back=1, disparity_space_sampling=0,
+                        mlp_mode=gnerf_hip.MLP_MODES['f32'], planes_interleaved=0, planes_shared=0, depth_clamp_per_item=1)
+            want.update(plan_fields if with_rng else dict.fromkeys(plan_fields, 0))
+            for name, v in want.items():
+                assert getattr(p, name) == v, (tag, name)
+    cams = (c2w, intr, res)
+    with pytest.raises(RuntimeError, match='give rays or cameras, not both'):
+        build((o, d), (nc, nf), cameras=cams)
+    with pytest.raises(RuntimeError, match='give noise tensors or an rng plan, not both'):
+        build((o, d), (nc, nf), rng=plan)
+    with pytest.raises(RuntimeError, match='in-kernel rays / draws take scalar ray limits'):
+        build((None, None), (nc, nf), rs=torch.full([N, M, 1], 2.25, device=dev), re=torch.full([N, M, 1], 3.3, device=dev), cameras=cams)
+    with pytest.raises(RuntimeError, match='render_forward: noise_fine required when depth_resolution_importance > 0'):
+        build((None, None), (nc, None), cameras=cams)

@@ -80,7 +80,7 @@ def check(what, got, ref, err32, half_output=False):
 def test_kernel_matches_float64(dev, monkeypatch, name, layout, half, binding):
     import gnerf_hip
     if binding == 'ctypes':
-        monkeypatch.setattr(gnerf_hip, 'ext', lambda: None)
+        monkeypatch.setattr(gnerf_hip._native, 'ext', lambda: None)
     else:
         assert gnerf_hip.ext() is not None, 'gnerf_torch_ext.so is not built'
     X, Y, L, k, gs, gc, ref, errs = references(name, half)
