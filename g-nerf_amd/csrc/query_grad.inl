@@ -1,0 +1,199 @@
+// Position gradient of run_model (renderer.py:142-148): dL/dpoints from dL/dsigma and / or dL/drgb.  Included by render.hip after
+// render_bwd.inl, whose decoder staging, MLP forward and MFMA conventions it shares (D layout col = lane & 15, rows = 4 * (lane >> 4) + r).
+//
+// Upstream this is autograd through grid_sample's coordinate gradient (zero padding, align_corners=False) and the decoder.  Here a wave
+// takes 16-point tiles through
+//   1. the tap records of the tile (lanes 0..47: point = lane & 15, plane = lane >> 4): byte offsets, the blend weights, and the
+//      weights of the blend's two derivatives d/du and d/dv (the pixel scale W/2, H/2 and the plane mean's 1/3 folded in);
+//   2. the lookup (8 lanes x 16 B per texel) and the decoder forward of query_bwd_kernel;
+//   3. the decoder backward to dX[16][32] = dL/d(mean feature) -- no weight gradients, and without the colour half when there is no
+//      dL/drgb (normals) -- on exact fp32 matrix products;
+//   4. a second lookup of the same texels against the derivative weights: per plane gu = sum_c dX[c] df_c/du, gv likewise, the 32-channel
+//      dots reduced inside the 8-lane group, and
+//        dL/dpoint = (2 / box_warp) * (gu_0 + gu_1 + gv_2,  gv_0,  gv_1 + gu_2)            planes read (x,y), (x,z), (z,x).
+// Every point owns its three outputs: plain stores, no atomics, the same bits on every run.
+
+constexpr int kGradRecDwords = 16;      // per (point, plane): 4 byte offsets, 4 blend weights, 4 d/du weights, 4 d/dv weights
+__host__ __device__ inline size_t query_grad_wave_floats() { return 16 * kStagePitch + 16 * kTPitch + 16 * 3 * kGradRecDwords; }
+
+struct QueryGradArgs {
+    const float* points; const float* grad_sigma; const float* grad_rgb;      // either gradient may be NULL
+    float* grad_points;
+    int n_points, tiles_per_item, n_tiles;
+};
+
+// plane_taps (render_shade.inl) with the derivative of the blend: a tap outside the image is a zero texel, so with the taps
+// (t00 t10 / t01 t11) and fractions (fx, fy)   df/dix = (t10 - t00)(1 - fy) + (t11 - t01) fy,   df/diy = (t01 - t00)(1 - fx) + (t11 - t10) fx
+// and dix/du = W / 2, diy/dv = H / 2 (u, v in [-1, 1], align_corners=False).  floor's derivative is the one-sided one, as grid_sample's.
+__device__ __forceinline__ void plane_taps_grad(int H, int W, float u, float v, unsigned tex_pitch, unsigned row_pitch, unsigned plane_bytes_off,
+                                                uint4& off, v4f& wgt, v4f& du, v4f& dv) {
+    float ix = ((u + 1.f) * float(W) - 1.f) * 0.5f;
+    float iy = ((v + 1.f) * float(H) - 1.f) * 0.5f;
+    ix = clamp_nn(ix, -1.5f, float(W) + 0.5f);           // beyond the clamp every tap is outside: weights and derivatives are all zero
+    iy = clamp_nn(iy, -1.5f, float(H) + 0.5f);
+    const float x0f = floorf(ix), y0f = floorf(iy);
+    const float fx = ix - x0f, fy = iy - y0f;
+    const int x0 = int(x0f), y0 = int(y0f), x1 = x0 + 1, y1 = y0 + 1;
+    auto inside = [](int i, int n) { return unsigned(i) < unsigned(n); };
+    auto clamp0 = [](int i, int last) { return min(max(i, 0), last); };
+    const bool in_x0 = inside(x0, W), in_x1 = inside(x1, W), in_y0 = inside(y0, H), in_y1 = inside(y1, H);
+    const float wx0 = in_x0 ? 1.f - fx : 0.f, wx1 = in_x1 ? fx : 0.f;
+    const float wy0 = in_y0 ? (1.f - fy) * (1.f / 3.f) : 0.f, wy1 = in_y1 ? fy * (1.f / 3.f) : 0.f;
+    const float sx = 0.5f * float(W), sy = 0.5f * float(H) * (1.f / 3.f);
+    const float dx0 = in_x0 ? -sx : 0.f, dx1 = in_x1 ? sx : 0.f;
+    const float dy0 = in_y0 ? -sy : 0.f, dy1 = in_y1 ? sy : 0.f;
+    const unsigned cx0 = __umul24(unsigned(clamp0(x0, W - 1)), tex_pitch), cx1 = __umul24(unsigned(clamp0(x1, W - 1)), tex_pitch);
+    const unsigned cy0 = __umul24(unsigned(clamp0(y0, H - 1)), row_pitch) + plane_bytes_off;
+    const unsigned cy1 = __umul24(unsigned(clamp0(y1, H - 1)), row_pitch) + plane_bytes_off;
+    off = make_uint4(cy0 + cx0, cy0 + cx1, cy1 + cx0, cy1 + cx1);
+    wgt = (v4f){wx0 * wy0, wx1 * wy0, wx0 * wy1, wx1 * wy1};
+    du = (v4f){dx0 * wy0, dx1 * wy0, dx0 * wy1, dx1 * wy1};
+    dv = (v4f){wx0 * dy0, wx1 * dy0, wx0 * dy1, wx1 * dy1};
+}
+
+// sum over the 8 lanes that share a point (lanes 8b .. 8b+7); every lane gets the total
+__device__ __forceinline__ float group8_total(float v) {
+    v += __shfl_xor(v, 1);
+    v += __shfl_xor(v, 2);
+    v += __shfl_xor(v, 4);
+    return v;
+}
+
+// RGB: a colour gradient is given.  Without it the colour half of layer 2 is evaluated in neither direction.
+template <bool RGB>
+__global__ __launch_bounds__(kBwdThreads, 3) void query_grad_kernel(Params P, QueryGradArgs Q) {
+    extern __shared__ __align__(16) float smem[];
+    const gnerf_render_params& p = P.p;
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    float* w1 = smem;
+    float* w2 = w1 + 64 * kW1Pitch;
+    float* b1 = w2 + 33 * kW2Pitch;
+    float* b2 = b1 + 64;
+    for (int i = tid; i < 64 * 32; i += kBwdThreads) w1[(i >> 5) * kW1Pitch + (i & 31)] = p.w1[i];
+    for (int i = tid; i < 33 * 64; i += kBwdThreads) w2[(i >> 6) * kW2Pitch + (i & 63)] = p.w2[i];
+    if (tid < 64) b1[tid] = p.b1[tid];
+    if (tid < 36) b2[tid] = tid < 33 ? p.b2[tid] : 0.f;
+    __syncthreads();
+    BwdLds L = {};
+    L.w1 = w1; L.w2 = w2; L.b1 = b1; L.b2 = b2;
+    L.stage = smem + kBwdWeightFloats + size_t(wv) * query_grad_wave_floats();
+    L.tbuf = L.stage + 16 * kStagePitch;
+    float* recs = L.tbuf + 16 * kTPitch;
+    const int j = lane & 15, g = lane >> 4, b = lane >> 3, cq = lane & 7, cq16 = cq * 16;
+    const int H = p.plane_h, W = p.plane_w;
+    const int64_t plane_floats = int64_t(3) * H * W * 32;
+    for (int tile = blockIdx.x * kBwdWaves + wv; tile < Q.n_tiles; tile += gridDim.x * kBwdWaves) {
+        const int item = tile / Q.tiles_per_item, t = tile % Q.tiles_per_item;
+        const char* planes = reinterpret_cast<const char*>(p.planes_nhwc + int64_t(item) * plane_floats);
+        const float* pts = Q.points + int64_t(item) * Q.n_points * 3;
+        const int64_t pt0 = int64_t(item) * Q.n_points + 16 * t;
+        // ---- 1. tap records (points past the end of a partial last tile repeat the last point; they are never written)
+        if (lane < 48) {
+            const int pl = lane >> 4;
+            const int64_t idx = min(16 * t + j, Q.n_points - 1);
+            const float px = pts[idx * 3 + 0] * P.box_scale, py = pts[idx * 3 + 1] * P.box_scale, pz = pts[idx * 3 + 2] * P.box_scale;
+            const float u = pl == 2 ? pz : px;
+            const float v = pl == 0 ? py : (pl == 1 ? pz : px);
+            uint4 off; v4f wgt, du, dv;
+            plane_taps_grad(H, W, u, v, P.tex_pitch, P.row_pitch, unsigned(pl) * P.plane_pitch, off, wgt, du, dv);
+            float* rec = recs + (j * 3 + pl) * kGradRecDwords;
+            *reinterpret_cast<uint4*>(rec) = off;
+            *reinterpret_cast<v4f*>(rec + 4) = wgt;
+            *reinterpret_cast<v4f*>(rec + 8) = du;
+            *reinterpret_cast<v4f*>(rec + 12) = dv;
+        }
+        lds_wave_sync();
+        // ---- 2. lookup: 8 points per step, 8 lanes x 16 bytes per texel; mean features staged as X[point][channel]
+#pragma unroll
+        for (int a = 0; a < 2; a++) {
+            const int js = 8 * a + b;
+            v4f acc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int pl = 0; pl < 3; pl++) {
+                const float* rec = recs + (js * 3 + pl) * kGradRecDwords;
+                const uint4 off = *reinterpret_cast<const uint4*>(rec);
+                const v4f wgt = *reinterpret_cast<const v4f*>(rec + 4);
+                const v4f t00 = *reinterpret_cast<const v4f*>(planes + off.x + cq16);
+                const v4f t10 = *reinterpret_cast<const v4f*>(planes + off.y + cq16);
+                const v4f t01 = *reinterpret_cast<const v4f*>(planes + off.z + cq16);
+                const v4f t11 = *reinterpret_cast<const v4f*>(planes + off.w + cq16);
+                acc += t00 * wgt[0] + t10 * wgt[1] + t01 * wgt[2] + t11 * wgt[3];
+            }
+            *reinterpret_cast<v4f*>(L.stage + js * kStagePitch + 4 * cq) = acc;
+        }
+        lds_wave_sync();
+        v4f h[4], o[2];
+        float sig;
+        bwd_mlp_forward(L, lane, h, o, sig);
+        // ---- 3. decoder backward: dO -> dH^T -> through softplus -> dX^T (bwd_tile_core without the weight gradients)
+        const float dsig = (Q.grad_sigma && 16 * t + j < Q.n_points) ? Q.grad_sigma[pt0 + j] : 0.f;
+        v4f dh[4];
+#pragma unroll
+        for (int m = 0; m < 4; m++) dh[m] = *reinterpret_cast<const v4f*>(L.w2 + 16 * m + 4 * g) * dsig;
+        if constexpr (RGB) {
+#pragma unroll
+            for (int n = 0; n < 2; n++) {
+#pragma unroll
+                for (int r = 0; r < 4; r++) {
+                    const int q = 4 * g + r;
+                    const float gc = 16 * t + q < Q.n_points ? Q.grad_rgb[(pt0 + q) * 32 + 16 * n + j] : 0.f;
+                    const float e = __builtin_amdgcn_exp2f(o[n][r] * -1.44269504088896341f);
+                    const float s = __builtin_amdgcn_rcpf(1.0f + e);
+                    L.tbuf[q * kTPitch + 16 * n + j] = gc * (1.002f * s * (1.f - s));        // rgb = 1.002 sigmoid(o) - 0.001 (triplane.py:134)
+                }
+            }
+            lds_wave_sync();
+#pragma unroll
+            for (int s = 0; s < 8; s++) {
+                const float bT = L.tbuf[j * kTPitch + 4 * s + g];
+#pragma unroll
+                for (int m = 0; m < 4; m++)
+                    dh[m] = __builtin_amdgcn_mfma_f32_16x16x4f32(L.w2[(1 + 4 * s + g) * kW2Pitch + 16 * m + j], bT, dh[m], 0, 0, 0);
+            }
+        }
+        v4f dx[2];
+        dx[0] = dx[1] = (v4f){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int m = 0; m < 4; m++) {
+#pragma unroll
+            for (int r = 0; r < 4; r++) {
+                const float dpre = dh[m][r] * (1.f - exp_hw(-h[m][r]));          // d/dpre softplus(pre) = 1 - exp(-softplus(pre))
+                const float* row = L.w1 + (16 * m + 4 * g + r) * kW1Pitch + j;
+                dx[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(row[0], dpre, dx[0], 0, 0, 0);
+                dx[1] = __builtin_amdgcn_mfma_f32_16x16x4f32(row[16], dpre, dx[1], 0, 0, 0);
+            }
+        }
+        lds_wave_sync();                                                         // every lane has read dO
+        *reinterpret_cast<v4f*>(L.tbuf + j * kTPitch + 4 * g) = dx[0];           // dX[point][channel]
+        *reinterpret_cast<v4f*>(L.tbuf + j * kTPitch + 16 + 4 * g) = dx[1];
+        lds_wave_sync();
+        // ---- 4. the same texels against the derivative weights
+#pragma unroll
+        for (int a = 0; a < 2; a++) {
+            const int js = 8 * a + b;
+            const v4f dxv = *reinterpret_cast<const v4f*>(L.tbuf + js * kTPitch + 4 * cq);
+            float gx = 0.f, gy = 0.f, gz = 0.f;
+#pragma unroll
+            for (int pl = 0; pl < 3; pl++) {
+                const float* rec = recs + (js * 3 + pl) * kGradRecDwords;
+                const uint4 off = *reinterpret_cast<const uint4*>(rec);
+                const v4f du = *reinterpret_cast<const v4f*>(rec + 8);
+                const v4f dv = *reinterpret_cast<const v4f*>(rec + 12);
+                const v4f t00 = *reinterpret_cast<const v4f*>(planes + off.x + cq16);
+                const v4f t10 = *reinterpret_cast<const v4f*>(planes + off.y + cq16);
+                const v4f t01 = *reinterpret_cast<const v4f*>(planes + off.z + cq16);
+                const v4f t11 = *reinterpret_cast<const v4f*>(planes + off.w + cq16);
+                const v4f fu = (t00 * du[0] + t10 * du[1] + t01 * du[2] + t11 * du[3]) * dxv;
+                const v4f fv = (t00 * dv[0] + t10 * dv[1] + t01 * dv[2] + t11 * dv[3]) * dxv;
+                const float su = (fu[0] + fu[1]) + (fu[2] + fu[3]), sv = (fv[0] + fv[1]) + (fv[2] + fv[3]);
+                if (pl == 0) { gx += su; gy += sv; }
+                else if (pl == 1) { gx += su; gz += sv; }
+                else { gz += su; gx += sv; }
+            }
+            gx = group8_total(gx); gy = group8_total(gy); gz = group8_total(gz);
+            if (cq < 3 && 16 * t + js < Q.n_points)
+                Q.grad_points[(pt0 + js) * 3 + cq] = (cq == 0 ? gx : (cq == 1 ? gy : gz)) * P.box_scale;
+        }
+        lds_wave_sync();                                                         // the records and dX are the next tile's to overwrite
+    }
+}

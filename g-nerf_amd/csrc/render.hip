@@ -786,6 +786,7 @@ __device__ __forceinline__ int choose_mlp(const Params& P, float* smem, bool* so
 #include "render_shade.inl"
 #include "render_pipe.inl"
 #include "render_bwd.inl"
+#include "query_grad.inl"
 
 // (PerDeviceOnce: csrc/common.h)
 
@@ -1217,4 +1218,36 @@ extern "C" int gnerf_query_points_backward(const float* planes_nhwc, int n_items
     if (blocks > int64_t(kNumCU) * 2) blocks = int64_t(kNumCU) * 2;
     hipLaunchKernelGGL(query_bwd_kernel, dim3((unsigned)blocks), dim3(kBwdThreads), lds_bytes, as_stream(stream), P, Q);
     return check_launch("query_bwd_kernel");
+}
+
+extern "C" int gnerf_query_points_grad(const float* planes_nhwc, int n_items, int plane_h, int plane_w,
+                                       const float* points, int n_points, float box_warp,
+                                       const float* w1, const float* b1, const float* w2, const float* b2,
+                                       const float* grad_sigma, const float* grad_rgb, float* grad_points,
+                                       int planes_interleaved, gnerf_stream_t stream) {
+    using namespace gnerf;
+    Params P = {};
+    gnerf_render_params& p = P.p;
+    p.planes_interleaved = planes_interleaved;
+    p.planes_nhwc = planes_nhwc; p.n_items = n_items; p.plane_h = plane_h; p.plane_w = plane_w;
+    p.w1 = w1; p.b1 = b1; p.w2 = w2; p.b2 = b2; p.box_warp = box_warp;
+    if (int e = check_common(&p)) return e;
+    if (!points || !grad_points) return fail(GNERF_E_ARG, "query_points_grad: null pointer");
+    if (n_points < 1) return fail(GNERF_E_ARG, "query_points_grad: n_points must be positive");
+    if (!grad_sigma && !grad_rgb) return fail(GNERF_E_ARG, "query_points_grad: grad_sigma and grad_rgb are both null");
+    if (!(int64_t(plane_h) * plane_w * 3 * 128 < (int64_t(1) << 32))) return fail(GNERF_E_UNSUPPORTED, "query_points_grad: planes too large for 32-bit tap offsets");
+    P.box_scale = float(2.0 / double(box_warp));
+    fill_pitches(P);
+    QueryGradArgs Q;
+    Q.points = points; Q.grad_sigma = grad_sigma; Q.grad_rgb = grad_rgb; Q.grad_points = grad_points; Q.n_points = n_points;
+    Q.tiles_per_item = (n_points + 15) / 16;
+    const int64_t tiles = int64_t(n_items) * Q.tiles_per_item;
+    if (tiles > INT32_MAX) return fail(GNERF_E_ARG, "query_points_grad: too many points");
+    Q.n_tiles = int(tiles);
+    const size_t lds_bytes = (kBwdWeightFloats + kBwdWaves * query_grad_wave_floats()) * sizeof(float);         // 49.3 KB: three workgroups per CU (the kernel is compiled for three waves per SIMD)
+    int64_t blocks = (tiles + kBwdWaves - 1) / kBwdWaves;
+    if (blocks > int64_t(kNumCU) * 3) blocks = int64_t(kNumCU) * 3;
+    if (grad_rgb) hipLaunchKernelGGL(query_grad_kernel<true>, dim3((unsigned)blocks), dim3(kBwdThreads), lds_bytes, as_stream(stream), P, Q);
+    else          hipLaunchKernelGGL(query_grad_kernel<false>, dim3((unsigned)blocks), dim3(kBwdThreads), lds_bytes, as_stream(stream), P, Q);
+    return check_launch("query_grad_kernel");
 }

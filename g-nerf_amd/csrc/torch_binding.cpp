@@ -11,7 +11,7 @@
 // cost: a call through ctypes spends 10-12 us marshalling arguments in Python, this path ~3.
 // Also exported: render_forward (the fused renderer has no reference plugin; same C ABI call as gnerf_hip.render_forward) and
 // marching_cubes (gnerf_hip.marching_cubes' count -> read counts -> emit sequence), ssim_forward / ssim_backward (gnerf_hip.ssim_*),
-// modconv_backward (gnerf_hip.scale_channels_backward / modconv_epilogue_backward).
+// modconv_backward (gnerf_hip.scale_channels_backward / modconv_epilogue_backward), query_points_grad (gnerf_hip.query_points_grad).
 //
 // Built ahead of time by csrc/build.sh (g++, no hipcc: there is no device code) into g-nerf_amd/gnerf_hip/gnerf_torch_ext.so.
 
@@ -264,6 +264,35 @@ std::tuple<Tensor, Tensor, Tensor> render_forward(Tensor planes_nhwc, int64_t n_
     return std::make_tuple(rgb, depth, wsum);
 }
 
+// ------------------------------------------------------------------------------------------------ position gradient of the point query
+
+// gnerf_hip.query_points_grad has converted the tensors (contiguous float32 on one GPU; planes [3N,H,W,32] or [N,H,W,96], points [N,P,3]) and
+// checked the gradients' sizes; grad_sigma / grad_rgb: None where absent.  -> grad_points [N,P,3].
+Tensor query_points_grad(Tensor planes_nhwc, int64_t n_items, Tensor w1, Tensor b1, Tensor w2, Tensor b2, Tensor points, double box_warp,
+                         c10::optional<Tensor> grad_sigma, c10::optional<Tensor> grad_rgb) {
+    auto f32c = [](const Tensor& t, const char* name) {
+        TORCH_CHECK(t.is_cuda() && t.scalar_type() == torch::kFloat32 && t.is_contiguous(), "query_points_grad: ", name, " must be a contiguous float32 GPU tensor");
+    };
+    f32c(planes_nhwc, "planes_nhwc"); f32c(w1, "w1"); f32c(b1, "b1"); f32c(w2, "w2"); f32c(b2, "b2"); f32c(points, "points");
+    const bool separate = planes_nhwc.dim() == 4 && planes_nhwc.size(3) == 32 && planes_nhwc.size(0) == 3 * n_items;
+    const bool interleaved = planes_nhwc.dim() == 4 && planes_nhwc.size(3) == 96 && planes_nhwc.size(0) == n_items;
+    TORCH_CHECK(separate || interleaved, "query_points_grad: planes_nhwc must be [3N,H,W,32] or [N,H,W,96]");
+    TORCH_CHECK(w1.numel() == 64 * 32 && b1.numel() == 64 && w2.numel() == 33 * 64 && b2.numel() == 33, "query_points_grad: decoder must be the 32->64->33 MLP");
+    TORCH_CHECK(points.dim() == 3 && points.size(0) == n_items && points.size(2) == 3 && points.size(1) <= INT_MAX, "query_points_grad: points must be [N,P,3]");
+    const int64_t n_pts = points.size(1);
+    const float* gs = nullptr;
+    const float* gc = nullptr;
+    if (grad_sigma.has_value()) { f32c(*grad_sigma, "grad_sigma"); TORCH_CHECK(grad_sigma->numel() == n_items * n_pts, "query_points_grad: grad_sigma must have N*P elements"); gs = grad_sigma->data_ptr<float>(); }
+    if (grad_rgb.has_value()) { f32c(*grad_rgb, "grad_rgb"); TORCH_CHECK(grad_rgb->numel() == n_items * n_pts * 32, "query_points_grad: grad_rgb must have N*P*32 elements"); gc = grad_rgb->data_ptr<float>(); }
+    const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(at::device_of(points));
+    Tensor out = torch::empty({n_items, n_pts, 3}, points.options());
+    check_rc(gnerf_query_points_grad(planes_nhwc.data_ptr<float>(), int(n_items), int(planes_nhwc.size(1)), int(planes_nhwc.size(2)),
+                                     points.data_ptr<float>(), int(n_pts), float(box_warp), w1.data_ptr<float>(), b1.data_ptr<float>(),
+                                     w2.data_ptr<float>(), b2.data_ptr<float>(), gs, gc, out.data_ptr<float>(), interleaved ? 1 : 0, current_stream()),
+             "gnerf_query_points_grad");
+    return out;
+}
+
 // ------------------------------------------------------------------------------------------------ marching cubes (shape_utils.py:58-61)
 
 // volume: contiguous float32 [d0, d1, d2] on a GPU.  Returns (verts [V,3] float32, faces [T,3] int32, counts int64 [3] on the host:
@@ -412,6 +441,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("filtered_lrelu", &filtered_lrelu);
     m.def("filtered_lrelu_act_", &filtered_lrelu_act_);
     m.def("render_forward", &render_forward);
+    m.def("query_points_grad", &query_points_grad);
     m.def("marching_cubes", &marching_cubes);
     m.def("ssim_forward", &ssim_forward);
     m.def("ssim_backward", &ssim_backward);

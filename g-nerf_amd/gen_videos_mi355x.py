@@ -19,7 +19,7 @@ pickles (there are no checkpoints or network access in the build environment); w
 this repo's inference-only equivalent (gnerf_generator.Generator).  `--graph` replays the per-frame launch sequence from a
 HIP graph captured once (FrameProgram); `--shapes out.npy` also extracts the 512^3 density volume of gen_videos.py --shapes,
 `--shapes-mrc out.mrc` writes it as the reference's .mrc, and `--mesh out.ply` meshes it (shape_utils.py's step, shape_mi355x) while it
-is still on the device.
+is still on the device; `--mesh-attrs normals|colors|all` adds the density field's normals and the decoder's colours per vertex.
 """
 
 import argparse
@@ -202,15 +202,58 @@ def voxel_samples(lo, hi, n, cube_length, device):
     return torch.stack([s0 * size + origin, s1 * size + origin, s2 * size + origin], dim=-1).unsqueeze(0)
 
 
+def _stack3(a, b, c):
+    return torch.stack([a, b, c], dim=-1) if isinstance(a, torch.Tensor) else np.stack([a, b, c], axis=-1)
+
+
+def lattice_to_world(index_coords, resolution, cube_length):
+    """The continuous extension of voxel_samples: lattice coordinates (s0, s1, s2) [..., 3] (a torch tensor or a numpy array; integers
+    are the lattice points, point s0 n^2 + s1 n + s2 of create_samples) -> world positions.  The reference's lattice is sheared --
+    its first two indices are float divisions of the linear index without a floor --, so the point is
+    ((s0 + s1/n + s2/n^2), (s1 + s2/n), s2) * size + origin with size = cube_length / (n - 1), origin = -cube_length / 2."""
+    n = resolution
+    origin, size = -cube_length / 2, cube_length / (n - 1)
+    s0, s1, s2 = index_coords[..., 0], index_coords[..., 1], index_coords[..., 2]
+    return _stack3((s0 + s1 / n + s2 / (n * n)) * size + origin, (s1 + s2 / n) * size + origin, s2 * size + origin)
+
+
+def mesh_to_lattice(verts, resolution):
+    """Mesh vertices (index space of vol.permute(2, 1, 0), vol = sigmas.reshape(r, r, r).flip(0): what mesh_density_grid meshes)
+    -> lattice coordinates (s0, s1, s2) of lattice_to_world: the permute swaps the outer axes, the flip mirrors the first."""
+    return _stack3((resolution - 1) - verts[..., 2], verts[..., 1], verts[..., 0])
+
+
+def mesh_to_world_jacobian(resolution, cube_length):
+    """J = d world / d mesh-index of lattice_to_world(mesh_to_lattice(v)): a constant 3x3 (float64 numpy), rows = world axes."""
+    n, size = resolution, cube_length / (resolution - 1)
+    return size * np.array([[1 / (n * n), 1 / n, -1.0], [1 / n, 1.0, 0.0], [1.0, 0.0, 0.0]])
+
+
+def normals_to_mesh_frame(normals_world, resolution, cube_length):
+    """World-space normals [..., 3] -> the mesh's index frame, in which the .ply's vertices stay: a normal is a covector (the gradient
+    of a scalar field), so it transforms with the transpose, normalise(J^T n); zero vectors stay zero."""
+    J = mesh_to_world_jacobian(resolution, cube_length)
+    if isinstance(normals_world, torch.Tensor):
+        m = normals_world @ torch.as_tensor(J, dtype=normals_world.dtype, device=normals_world.device)        # rows: (J^T n)^T = n^T J
+        length = m.norm(dim=-1, keepdim=True)
+        return torch.where(length > 0, m / length, torch.zeros_like(m))
+    m = np.asarray(normals_world) @ J.astype(np.asarray(normals_world).dtype)
+    length = np.linalg.norm(m, axis=-1, keepdims=True)
+    return np.where(length > 0, m / np.where(length > 0, length, 1), 0).astype(m.dtype)
+
+
 @torch.no_grad()
-def extract_density_grid(G, ws, resolution=512, max_batch=10000000, crop=True):
+def extract_density_grid(G, ws, resolution=512, max_batch=10000000, crop=True, planes=None, return_planes=False):
     """The density volume gen_videos.py --shapes writes to .mrc (gen_videos.py:189-224): sigma at resolution^3 lattice points of
     the box, flipped along the first axis, borders zeroed.  The reference calls G.sample_mixed per chunk of 10^7 points, which
     re-runs the StyleGAN2 backbone for every chunk (14 passes at 512^3); here the planes are made once and every chunk goes
-    through ImportanceRenderer.run_model (the fused point-query kernel on a GPU).  Returns a float32 tensor [r, r, r] on ws' device."""
+    through ImportanceRenderer.run_model (the fused point-query kernel on a GPU).  Returns a float32 tensor [r, r, r] on ws' device.
+    planes / return_planes: take the tri-planes [N,3,32,H,W] instead of running the backbone, and hand them back as (vol, planes) --
+    mesh_density_grid evaluates vertex attributes on the same planes."""
     device = ws.device
-    planes = G.backbone.synthesis(ws, noise_mode='const')
-    planes = planes.view(len(planes), 3, 32, planes.shape[-2], planes.shape[-1])
+    if planes is None:
+        planes = G.backbone.synthesis(ws, noise_mode='const')
+        planes = planes.view(len(planes), 3, 32, planes.shape[-2], planes.shape[-1])
     total = resolution ** 3
     sigmas = torch.empty(total, dtype=torch.float32, device=device)
     for head in range(0, total, max_batch):
@@ -232,20 +275,57 @@ def extract_density_grid(G, ws, resolution=512, max_batch=10000000, crop=True):
         vol[:, -pad_top:] = 0
         vol[:, :, :pad] = 0
         vol[:, :, -pad:] = 0
-    return vol
+    return (vol, planes) if return_planes else vol
 
 
-def mesh_density_grid(vol, ply_path, level=10.0):
+MESH_ATTRS = ('none', 'normals', 'colors', 'all')
+
+
+@torch.no_grad()
+def mesh_vertex_attributes(G, planes, verts, resolution, want_normals=True, want_colors=True, max_batch=4000000):
+    """Per-vertex attributes of a mesh of extract_density_grid's volume, evaluated at the vertices' world positions on verts' device:
+    (normals float32 [V, 3] in the mesh's index frame or None, colors uint8 [V, 3] or None).  Normals are those of the density field,
+    -grad sigma normalised (ImportanceRenderer.query_normals: the position-gradient kernel on a GPU); colours the decoder's first
+    three channels (image_raw is feature_image[:, :3]) as clip((c * 0.5 + 0.5) * 255), rounded."""
+    kw = G.rendering_kwargs
+    planes = planes[:1]
+    normals, colors = [], []
+    for head in range(0, len(verts), max_batch):
+        world = lattice_to_world(mesh_to_lattice(verts[head:head + max_batch].float(), resolution), resolution, kw['box_warp']).unsqueeze(0)
+        if want_normals:
+            normals.append(normals_to_mesh_frame(G.renderer.query_normals(planes, G.decoder, world, kw)[1][0], resolution, kw['box_warp']))
+        if want_colors:
+            dirs = torch.zeros_like(world)
+            dirs[..., -1] = -1
+            rgb = G.renderer.run_model(planes, G.decoder, world, dirs, dict(kw, density_noise=0))['rgb'][0, :, :3]
+            colors.append(((rgb * 0.5 + 0.5) * 255).clamp(0, 255).round().to(torch.uint8))
+    empty = verts.new_zeros([0, 3])
+    return (torch.cat(normals or [empty]) if want_normals else None), (torch.cat(colors or [empty.to(torch.uint8)]) if want_colors else None)
+
+
+def mesh_density_grid(vol, ply_path, level=10.0, attrs=None, G=None, planes=None):
     """--mesh: the mesh shape_utils.convert_mrc makes of the .mrc of this volume (shape_utils.py:103-105: transpose(2, 1, 0), voxel
     size 1, origin 0), made where the volume lives -- on a GPU the marching-cubes kernel reads it in HBM, only the mesh comes to the host.
+    attrs: None / 'none', 'normals', 'colors' or 'all' -- per-vertex attributes (mesh_vertex_attributes) of generator G on `planes`
+    (extract_density_grid(..., return_planes=True)), evaluated on the device too; the vertices stay in index space, as the reference's.
     Writes `ply_path`; returns (vertex count, triangle count, seconds spent in marching cubes)."""
     import shape_mi355x
+    attrs = 'none' if attrs is None else attrs
+    if attrs not in MESH_ATTRS:
+        raise ValueError(f'mesh_density_grid: attrs must be one of {MESH_ATTRS}')
+    if attrs != 'none' and (G is None or planes is None):
+        raise ValueError('mesh_density_grid: vertex attributes need the generator G and the planes the volume was made from')
     t0 = time.perf_counter()
     verts, faces = shape_mi355x.marching_cubes(vol.permute(2, 1, 0).contiguous(), level)     # (reads its counts: synchronised)
     dt = time.perf_counter() - t0
+    normals = colors = None
+    if attrs != 'none':
+        v = verts if isinstance(verts, torch.Tensor) else torch.from_numpy(verts).to(vol.device)
+        normals, colors = mesh_vertex_attributes(G, planes, v, vol.shape[0], attrs in ('normals', 'all'), attrs in ('colors', 'all'))
+        normals, colors = (None if t is None else t.cpu().numpy() for t in (normals, colors))
     if isinstance(verts, torch.Tensor):
         verts, faces = verts.cpu().numpy(), faces.cpu().numpy()
-    shape_mi355x.write_ply(ply_path, verts, faces)
+    shape_mi355x.write_ply(ply_path, verts, faces, normals=normals, colors=colors)
     return len(verts), len(faces), dt
 
 
@@ -267,6 +347,7 @@ def main():
     ap.add_argument('--shapes-mrc', default=None, help='also write the density volume as the reference\'s .mrc (gen_videos.py:221-222; rank 0)')
     ap.add_argument('--mesh', default=None, help='also mesh the density volume on the device and write this .ply (shape_utils.py; rank 0)')
     ap.add_argument('--mesh-level', type=float, default=10, help='isosurface level of --mesh (shape_utils.py:111)')
+    ap.add_argument('--mesh-attrs', choices=MESH_ATTRS, default='none', help='per-vertex attributes of --mesh: normals of the density field and / or the decoder\'s colours')
     ap.add_argument('--voxel-res', type=int, default=512)
     ap.add_argument('--no-solver-search', action='store_true', help='leave torch.backends.cudnn.benchmark off (MIOpen takes its first heuristic pick per shape)')
     args = ap.parse_args()
@@ -308,7 +389,7 @@ def main():
             if device.type == 'cuda':
                 torch.cuda.synchronize()
             t0 = time.perf_counter()
-            vol = extract_density_grid(G, orbit_latents(G, z, device), args.voxel_res)
+            vol, planes = extract_density_grid(G, orbit_latents(G, z, device), args.voxel_res, return_planes=True)
             if device.type == 'cuda':
                 torch.cuda.synchronize()
             dt = time.perf_counter() - t0
@@ -319,8 +400,10 @@ def main():
                 import shape_mi355x
                 shape_mi355x.write_mrc(args.shapes_mrc, vol.cpu().numpy())
             if args.mesh:
-                nv, nf, dt = mesh_density_grid(vol, args.mesh, args.mesh_level)
-                print(f'mesh at level {args.mesh_level:g}: {dt * 1e3:.2f} ms, {nv} vertices, {nf} triangles -> {args.mesh}')
+                t0 = time.perf_counter()
+                nv, nf, dt = mesh_density_grid(vol, args.mesh, args.mesh_level, attrs=args.mesh_attrs, G=G, planes=planes)
+                print(f'mesh at level {args.mesh_level:g}: {dt * 1e3:.2f} ms, {nv} vertices, {nf} triangles -> {args.mesh}'
+                      + (f' (with {args.mesh_attrs}: {(time.perf_counter() - t0) * 1e3:.2f} ms in all, file included)' if args.mesh_attrs != 'none' else ''))
 
 
 if __name__ == '__main__':

@@ -307,3 +307,30 @@ def query_points_backward(planes_nhwc, n_items, decoder, points, box_warp, grad_
             float(box_warp), _ptr(w1), _ptr(b1), _ptr(w2), _ptr(b2), _ptr(gs), _ptr(gc), _ptr(g_planes), _ptr(gd[0]), _ptr(gd[1]), _ptr(gd[2]),
             _ptr(gd[3]), interleaved)
     return g_planes, g_dec
+
+
+@profiled('gnerf_hip::query_points_grad')
+def query_points_grad(planes_nhwc, n_items, decoder, points, box_warp, grad_sigma, grad_rgb):
+    """Gradient of query_points with respect to the POINTS: grad_sigma [N,P,1] / grad_rgb [N,P,32] (either may be None, not both)
+    -> grad_points [N,P,3] float32 (include/gnerf_hip.h states the maths).  grad_rgb None skips the decoder's colour half: with
+    grad_sigma = ones the result is the density field's gradient, whose negative is the surface normal.  No atomics: the same bits
+    on every run and through either binding."""
+    w1, b1, w2, b2 = [_f32c(t) for t in decoder]
+    _require_cuda(planes_nhwc, points, w1, grad_sigma, grad_rgb)
+    interleaved = planes_layout(planes_nhwc, n_items, 'query_points_grad')
+    pts = _points(points, n_items, 'query_points_grad')
+    n_pts = pts.shape[1]
+    if grad_sigma is None and grad_rgb is None:
+        raise RuntimeError('query_points_grad: grad_sigma and grad_rgb are both None')
+    gs = None if grad_sigma is None else _f32c(grad_sigma)
+    gc = None if grad_rgb is None else _f32c(grad_rgb)
+    if (gs is not None and gs.numel() != n_items * n_pts) or (gc is not None and gc.numel() != n_items * n_pts * 32):
+        raise RuntimeError('query_points_grad: output gradients must match the forward outputs')
+    e = _native.ext()
+    if e is not None:
+        with _on_device(pts.device):
+            return e.query_points_grad(planes_nhwc, n_items, w1, b1, w2, b2, pts, float(box_warp), gs, gc)
+    g_pts = torch.empty([n_items, n_pts, 3], dtype=torch.float32, device=pts.device)
+    _launch('gnerf_query_points_grad', pts, _ptr(planes_nhwc), n_items, planes_nhwc.shape[1], planes_nhwc.shape[2], _ptr(pts), n_pts, float(box_warp),
+            _ptr(w1), _ptr(b1), _ptr(w2), _ptr(b2), _ptr(gs), _ptr(gc), _ptr(g_pts), interleaved)
+    return g_pts

@@ -247,38 +247,101 @@ def marching_cubes(volume, level, spacing=1.0, origin=(0.0, 0.0, 0.0)):
 
 
 # ---------------------------------------------------------------------------------------------------------------- PLY
-def write_ply(path, verts, faces):
+def write_ply(path, verts, faces, normals=None, colors=None):
     """Binary little-endian PLY with the layout plyfile writes for shape_utils.py's two elements (vertex x/y/z float, face
-    `list uchar int vertex_indices`)."""
+    `list uchar int vertex_indices`).  normals float [V, 3] and / or colors uint8 [V, 3] add `property float nx/ny/nz` and
+    `property uchar red/green/blue` to the vertex element, behind x y z, in that order: one packed record per vertex.  Without them the
+    file is the geometry-only one, byte for byte."""
     verts = np.ascontiguousarray(verts, dtype='<f4').reshape(-1, 3)
     faces = np.ascontiguousarray(faces, dtype='<i4').reshape(-1, 3)
+    fields, props = [('xyz', '<f4', (3,))], 'property float x\nproperty float y\nproperty float z\n'
+    if normals is not None:
+        fields.append(('n', '<f4', (3,)))
+        props += 'property float nx\nproperty float ny\nproperty float nz\n'
+    if colors is not None:
+        fields.append(('rgb', 'u1', (3,)))
+        props += 'property uchar red\nproperty uchar green\nproperty uchar blue\n'
+    vertex = np.zeros(len(verts), dtype=fields)                           # (a packed dtype: no padding between the fields)
+    vertex['xyz'] = verts
+    for name, arr, dtype in (('n', normals, '<f4'), ('rgb', colors, 'u1')):
+        if arr is not None:
+            arr = np.asarray(arr)
+            if arr.shape != (len(verts), 3) or (name == 'rgb' and arr.dtype != np.uint8):
+                raise ValueError('write_ply: normals must be float [V, 3] and colors uint8 [V, 3]')
+            vertex[name] = arr.astype(dtype, copy=False)
     header = ('ply\nformat binary_little_endian 1.0\n'
-              f'element vertex {len(verts)}\nproperty float x\nproperty float y\nproperty float z\n'
+              f'element vertex {len(verts)}\n{props}'
               f'element face {len(faces)}\nproperty list uchar int vertex_indices\nend_header\n')
     body = np.zeros(len(faces), dtype=[('n', 'u1'), ('i', '<i4', (3,))])
     body['n'] = 3
     body['i'] = faces
     with open(path, 'wb') as f:
         f.write(header.encode('ascii'))
-        f.write(verts.tobytes())
+        f.write(vertex.tobytes())
         f.write(body.tobytes())
 
 
-def read_ply(path):
-    """The inverse of write_ply (that layout only): (verts float32 [V, 3], faces int32 [T, 3])."""
+_PLY_TYPES = {'char': 'i1', 'int8': 'i1', 'uchar': 'u1', 'uint8': 'u1', 'short': '<i2', 'int16': '<i2', 'ushort': '<u2', 'uint16': '<u2',
+              'int': '<i4', 'int32': '<i4', 'uint': '<u4', 'uint32': '<u4', 'float': '<f4', 'float32': '<f4', 'double': '<f8', 'float64': '<f8'}
+
+
+def _read_ply_elements(path):
+    """(vertex records as a structured array with one field per property, faces int32 [T, 3]) of a binary little-endian PLY whose
+    elements are `vertex` (scalar properties only) then `face` (`list uchar int vertex_indices`, triangles): the property list of the
+    header is parsed, so any set of per-vertex attributes reads."""
     with open(path, 'rb') as f:
         data = f.read()
     end = data.index(b'end_header\n') + len(b'end_header\n')
-    header = data[:end].decode('ascii').split('\n')
-    if header[1] != 'format binary_little_endian 1.0':
+    lines = data[:end].decode('ascii').split('\n')
+    if lines[0] != 'ply' or lines[1] != 'format binary_little_endian 1.0':
         raise ValueError(f'{path}: not a binary little-endian PLY')
-    nv = int(header[2].split()[2])
-    nf = int(header[6].split()[2])
-    verts = np.frombuffer(data, dtype='<f4', count=nv * 3, offset=end).reshape(nv, 3)
-    body = np.frombuffer(data, dtype=[('n', 'u1'), ('i', '<i4', (3,))], count=nf, offset=end + nv * 12)
+    elements = []                                                        # [name, count, [property token lists]]
+    for line in lines[2:]:
+        tok = line.split()
+        if tok[:1] == ['element']:
+            elements.append([tok[1], int(tok[2]), []])
+        elif tok[:1] == ['property']:
+            if not elements:
+                raise ValueError(f'{path}: a property before any element')
+            elements[-1][2].append(tok[1:])
+    if [e[0] for e in elements] != ['vertex', 'face']:
+        raise ValueError(f'{path}: expected the elements vertex and face')
+    (_, nv, vprops), (_, nf, fprops) = elements
+    if any(len(t) != 2 or t[0] not in _PLY_TYPES for t in vprops) or len({t[1] for t in vprops}) != len(vprops):
+        raise ValueError(f'{path}: vertex properties must be distinct scalars')
+    if fprops != [['list', 'uchar', 'int', 'vertex_indices']]:
+        raise ValueError(f'{path}: the face element must be `property list uchar int vertex_indices`')
+    vdtype = np.dtype([(name, _PLY_TYPES[t]) for t, name in vprops])
+    vertex = np.frombuffer(data, dtype=vdtype, count=nv, offset=end)
+    body = np.frombuffer(data, dtype=[('n', 'u1'), ('i', '<i4', (3,))], count=nf, offset=end + nv * vdtype.itemsize)
     if nf and not np.all(body['n'] == 3):
         raise ValueError(f'{path}: a face is not a triangle')
-    return verts.copy(), body['i'].astype(np.int32)
+    return vertex, body['i'].astype(np.int32)
+
+
+def _ply_columns(vertex, names, dtype, path):
+    if any(n not in vertex.dtype.names for n in names):
+        if any(n in vertex.dtype.names for n in names):
+            raise ValueError(f'{path}: incomplete vertex attribute {"/".join(names)}')
+        return None
+    return np.stack([vertex[n] for n in names], axis=1).astype(dtype)
+
+
+def read_ply(path):
+    """The inverse of write_ply for the geometry, with or without per-vertex attributes: (verts float32 [V, 3], faces int32 [T, 3])."""
+    vertex, faces = _read_ply_elements(path)
+    verts = _ply_columns(vertex, ('x', 'y', 'z'), np.float32, path)
+    if verts is None:
+        raise ValueError(f'{path}: the vertex element has no x y z')
+    return verts, faces
+
+
+def read_ply_attrs(path):
+    """The optional per-vertex arrays of a .ply write_ply made: {'normals': float32 [V, 3], 'colors': uint8 [V, 3]}, each key present
+    only when the file holds it."""
+    vertex, _ = _read_ply_elements(path)
+    found = {'normals': _ply_columns(vertex, ('nx', 'ny', 'nz'), np.float32, path), 'colors': _ply_columns(vertex, ('red', 'green', 'blue'), np.uint8, path)}
+    return {k: v for k, v in found.items() if v is not None}
 
 
 def convert_sdf_samples_to_ply(volume, voxel_grid_origin, voxel_size, ply_filename_out, offset=None, scale=None, level=0.0):

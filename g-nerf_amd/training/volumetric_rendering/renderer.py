@@ -14,14 +14,17 @@ recomputes the ray's forward pass and keeps nothing between the passes, where up
 every intermediate of the op chain (~3 GB at the training shape).
 
 `run_model` (arbitrary points: sample / sample_mixed, incl. the density regulariser of training) has the
-same pair of kernels (query_points / query_points_backward).
+same pair of kernels (query_points / query_points_backward), and a third for the gradient of the points
+themselves (query_points_grad: normals of the density field, `query_normals`).
 
 The PyTorch-op form below is what runs for CPU tensors (the reference's own behaviour: all of its
-renderer is PyTorch ops), when the rays or points themselves need a gradient, or when `decoder` is
-not the OSGDecoder 32->64->33 MLP.  A GPU call never silently degrades because the native library is absent:
+renderer is PyTorch ops), when the rays themselves need a gradient, when the points need a SECOND-order
+gradient (`ImportanceRenderer.fused_point_grad = False`), or when `decoder` is not the OSGDecoder
+32->64->33 MLP.  A GPU call never silently degrades because the native library is absent:
 gnerf_hip raises.
 """
 
+import functools
 import math
 import warnings
 import weakref
@@ -66,8 +69,12 @@ def sample_from_planes(plane_axes, plane_features, coordinates, mode='bilinear',
     assert padding_mode == 'zeros'
     N, P, C, H, W = plane_features.shape
     M = coordinates.shape[1]
-    grid = project_onto_planes(plane_axes, (2 / box_warp) * coordinates).unsqueeze(1)
-    out = torch.nn.functional.grid_sample(plane_features.view(N * P, C, H, W), grid.float(), mode=mode,
+    # float64 planes and points -- an error in the reference, whose frames and grid are float32 -- keep their precision (query_normals
+    # is checked against the float64 oracle that way); every other call is the reference's, grid.float() included
+    f64 = plane_features.dtype == torch.float64 and coordinates.dtype == torch.float64
+    grid = project_onto_planes(plane_axes.double() if f64 else plane_axes, (2 / box_warp) * coordinates).unsqueeze(1)
+    grid = grid if f64 else grid.float()
+    out = torch.nn.functional.grid_sample(plane_features.view(N * P, C, H, W), grid, mode=mode,
                                           padding_mode=padding_mode, align_corners=False)
     return out.permute(0, 3, 2, 1).reshape(N, P, M, C)
 
@@ -194,12 +201,33 @@ def _producer_absmax(planes):
     return None
 
 
+def _once_differentiable_points(fn):
+    """torch.autograd.function.once_differentiable for _FusedQuery.backward, with two differences: the error of a double backward says
+    what to do, and it is raised whenever the first backward ran with a graph (create_graph=True) -- torch's decorator looks at the
+    incoming gradients only, and the gradient of `sigma.sum()` requires none: an eikonal term on the fused route would otherwise fail
+    with "does not require grad" or, worse, treat the first-order gradient as a constant."""
+    @functools.wraps(fn)
+    def wrapper(ctx, *args):
+        with torch.no_grad():
+            outputs = fn(ctx, *args)
+        if not torch.is_grad_enabled():
+            return outputs
+        err_fn = torch._C._functions.DelayedError(
+            b'the fused point query (gnerf_hip.query_points_backward / query_points_grad) is differentiable once: for a second-order '
+            b'gradient (e.g. an eikonal term) set ImportanceRenderer.fused_point_grad = False, which runs run_model as PyTorch ops',
+            len(outputs))
+        return err_fn(*[None if v is None else v.detach().requires_grad_(True) for v in outputs])
+    return wrapper
+
+
 class _FusedQuery(torch.autograd.Function):
-    """query_points / query_points_backward as one differentiable op (run_model for arbitrary points): gradients for the
-    planes and the decoder's effective weights, none for the points."""
+    """query_points / query_points_backward / query_points_grad as one differentiable op (run_model for arbitrary points):
+    gradients for the planes, the decoder's effective weights and the points, each from its own kernel and only when asked for.
+    First order only: a double backward raises (see `_once_differentiable_points`)."""
 
     @staticmethod
     def forward(ctx, planes, w1, b1, w2, b2, points, box_warp):
+        ctx.set_materialize_grads(False)        # an output the loss does not use arrives as None: the kernels skip its half of the decoder
         nhwc = _interleaved_view(planes.detach())
         if nhwc is None:
             nhwc = gnerf_hip.planes_to_nhwc(planes.detach().float())
@@ -209,8 +237,11 @@ class _FusedQuery(torch.autograd.Function):
         return sigma, rgb
 
     @staticmethod
-    @torch.autograd.function.once_differentiable
+    @_once_differentiable_points
     def backward(ctx, g_sigma, g_rgb):
+        grads = [None] * 7
+        if g_sigma is None and g_rgb is None:
+            return tuple(grads)
         planes, w1, b1, w2, b2, points = ctx.saved_tensors
         need_planes = ctx.needs_input_grad[0]
         need_decoder = any(ctx.needs_input_grad[1:5])
@@ -219,9 +250,11 @@ class _FusedQuery(torch.autograd.Function):
         interleaved = nhwc is not None
         if not interleaved:
             nhwc = gnerf_hip.planes_to_nhwc(planes.detach().float())
-        g_planes, g_dec = gnerf_hip.query_points_backward(nhwc, N, (w1, b1, w2, b2), points, ctx.box_warp, g_sigma, g_rgb,
-                                                          need_planes=need_planes, need_decoder=need_decoder)
-        grads = [None] * 7
+        if need_planes or need_decoder:
+            g_planes, g_dec = gnerf_hip.query_points_backward(nhwc, N, (w1, b1, w2, b2), points, ctx.box_warp, g_sigma, g_rgb,
+                                                              need_planes=need_planes, need_decoder=need_decoder)
+        if ctx.needs_input_grad[5]:
+            grads[5] = gnerf_hip.query_points_grad(nhwc, N, (w1, b1, w2, b2), points, ctx.box_warp, g_sigma, g_rgb).to(points.dtype)
         if need_planes:
             grads[0] = _planes_from_interleaved(g_planes, planes) if interleaved else gnerf_hip.planes_from_nhwc(g_planes, N).to(planes.dtype)
         if need_decoder:
@@ -243,6 +276,10 @@ def _warn_gpu_fallback(reason, what='ImportanceRenderer.forward'):
 
 
 class ImportanceRenderer(torch.nn.Module):
+    # run_model with points that require a gradient: True = the fused kernels (first-order gradients only: gnerf_hip.query_points_grad),
+    # False = the PyTorch-op form with its warning, which autograd can differentiate twice (an eikonal term needs that)
+    fused_point_grad = True
+
     def __init__(self):
         super().__init__()
         self.ray_marcher = MipRayMarcher2()
@@ -446,7 +483,9 @@ class ImportanceRenderer(torch.nn.Module):
             count = depths.shape[2]
             pts = (ray_origins.unsqueeze(-2) + depths * ray_directions.unsqueeze(-2)).reshape(N, -1, 3)
             dirs = ray_directions.unsqueeze(-2).expand(-1, -1, count, -1).reshape(N, -1, 3)
-            out = self._run_model(planes, decoder, pts, dirs, rendering_options, warn=False)        # (forward() has said why already)
+            # (forward() has said why already; the rays' gradient reaches these points, and this route stays PyTorch ops throughout,
+            #  as it always was: they do not go to the fused query)
+            out = self._run_model(planes, decoder, pts, dirs, rendering_options, warn=False, fused_points=False)
             return out['rgb'].reshape(N, M, count, out['rgb'].shape[-1]), out['sigma'].reshape(N, M, count, 1)
 
         colors_coarse, densities_coarse = shade(depths_coarse)
@@ -467,19 +506,20 @@ class ImportanceRenderer(torch.nn.Module):
         (entry point of TriPlaneGenerator.sample / sample_mixed, triplane.py:91-102)."""
         return self._run_model(planes, decoder, sample_coordinates, sample_directions, options)
 
-    def _run_model(self, planes, decoder, sample_coordinates, sample_directions, options, warn=True):
+    def _run_model(self, planes, decoder, sample_coordinates, sample_directions, options, warn=True, fused_points=None):
+        fused_points = self.fused_point_grad if fused_points is None else fused_points
         self.plane_axes = self.plane_axes.to(sample_coordinates.device)
         density_noise = options.get('density_noise', 0)
         if planes.device.type == 'cuda' and planes.ndim == 5 and planes.shape[1] == 3 and planes.shape[2] == 32:
             fcs = _osg_decoder_weights(decoder)
             points_need_grad = torch.is_grad_enabled() and sample_coordinates.requires_grad
-            if fcs is not None and not points_need_grad:
-                needs_graph = torch.is_grad_enabled() and (planes.requires_grad or any(p.requires_grad for p in decoder.parameters()))
+            if fcs is not None and (not points_need_grad or fused_points):
+                needs_graph = points_need_grad or (torch.is_grad_enabled() and (planes.requires_grad or any(p.requires_grad for p in decoder.parameters())))
                 if needs_graph:
                     fc1, fc2 = fcs
                     eff = (fc1.weight.float() * fc1.weight_gain, fc1.bias.float() * fc1.bias_gain,      # networks_stylegan2.py:121-127
                            fc2.weight.float() * fc2.weight_gain, fc2.bias.float() * fc2.bias_gain)
-                    sigma, rgb = _FusedQuery.apply(planes, *eff, sample_coordinates.detach(), options['box_warp'])
+                    sigma, rgb = _FusedQuery.apply(planes, *eff, sample_coordinates if points_need_grad else sample_coordinates.detach(), options['box_warp'])
                 else:
                     sigma, rgb = gnerf_hip.query_points(self._planes_nhwc(planes)[0], planes.shape[0], self._decoder_cache(fcs),
                                                         sample_coordinates.detach(), options['box_warp'])
@@ -488,7 +528,8 @@ class ImportanceRenderer(torch.nn.Module):
                     out['sigma'] = out['sigma'] + torch.randn_like(out['sigma']) * density_noise
                 return out
         if warn and planes.device.type == 'cuda':
-            _warn_gpu_fallback('the points need a gradient, the decoder is not the OSGDecoder MLP or the planes are not [N,3,32,H,W]', 'ImportanceRenderer.run_model')
+            _warn_gpu_fallback('the points need a gradient and fused_point_grad is False, the decoder is not the OSGDecoder MLP or the planes are not [N,3,32,H,W]',
+                               'ImportanceRenderer.run_model')
         feats = sample_from_planes(self.plane_axes, planes, sample_coordinates, padding_mode='zeros', box_warp=options['box_warp'])
         out = decoder(feats, sample_directions)
         if density_noise > 0:
@@ -506,6 +547,25 @@ class ImportanceRenderer(torch.nn.Module):
         dirs = torch.zeros_like(sample_coordinates)
         dirs[..., -1] = -1
         return self.run_model(planes, decoder, sample_coordinates, dirs, options)['sigma']
+
+    def query_normals(self, planes, decoder, sample_coordinates, options):
+        """(sigma [N,P,1], normals [N,P,3]) at arbitrary points: normals = -grad sigma / |grad sigma|, outward for a surface whose inside
+        is sigma > level (the mesh's convention); a point where the gradient is zero gets the exact zero vector.  density_noise is not
+        applied.  On a GPU one densities-only query and one gnerf_hip.query_points_grad (grad_sigma = ones, no colour half); on CPU
+        tensors (or a decoder the kernels do not take) autograd through the PyTorch-op form.  Not part of the reference's interface."""
+        fcs = _osg_decoder_weights(decoder) if planes.device.type == 'cuda' else None
+        if fcs is not None and planes.ndim == 5 and planes.shape[1] == 3 and planes.shape[2] == 32:
+            nhwc, dec, pts = self._planes_nhwc(planes)[0], self._decoder_cache(fcs), sample_coordinates.detach()
+            sigma = gnerf_hip.query_points(nhwc, planes.shape[0], dec, pts, options['box_warp'], want_rgb=False)[0]
+            grad = gnerf_hip.query_points_grad(nhwc, planes.shape[0], dec, pts, options['box_warp'], torch.ones_like(sigma), None)
+        else:
+            with torch.enable_grad():
+                pts = sample_coordinates.detach().requires_grad_(True)
+                sigma = self._run_model(planes.detach(), decoder, pts, torch.zeros_like(pts), dict(options, density_noise=0))['sigma']
+                grad, = torch.autograd.grad(sigma.sum(), pts)
+            sigma = sigma.detach()
+        length = grad.norm(dim=-1, keepdim=True)
+        return sigma, torch.where(length > 0, -grad / length, torch.zeros_like(grad))
 
     def sort_samples(self, all_depths, all_colors, all_densities):
         _, order = torch.sort(all_depths, dim=-2)

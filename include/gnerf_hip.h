@@ -525,6 +525,26 @@ int gnerf_query_points_backward(const float* planes_nhwc, int n_items, int plane
                                 float* grad_planes_nhwc, float* grad_w1, float* grad_b1, float* grad_w2, float* grad_b2,
                                 int planes_interleaved, gnerf_stream_t stream);
 
+/* Gradient of gnerf_query_points with respect to the POINTS (added without a new ABI version: no existing signature or struct
+ * changes): grad_sigma [n_items, n_points, 1] and grad_rgb [n_items, n_points, 32] (either may be NULL, not both) ->
+ * grad_points [n_items, n_points, 3] float32, every element WRITTEN (nothing accumulated, no zeroing needed).  Per point:
+ *   1. forward: the three lookups (planes read (x,y), (x,z), (z,x) of 2 p / box_warp), their mean, the decoder;
+ *   2. decoder backward to dX[32] = dL/d(mean feature): rgb = 1.002 sigmoid(o) - 0.001, the sigma row, layer 2^T, softplus' = sigmoid,
+ *      layer 1^T (the colour half is skipped when grad_rgb is NULL: normals of the density field);
+ *   3. per plane k with pixel coordinates (ix, iy), fractions (fx, fy) and taps t00 t10 t01 t11 (first index x; a tap outside
+ *      the image is zero; floor has its one-sided derivative, as in grid_sample with zero padding and align_corners=False):
+ *        df/dix = (t10 - t00)(1 - fy) + (t11 - t01) fy        df/diy = (t01 - t00)(1 - fx) + (t11 - t10) fx
+ *        gu_k = (W/2)(1/3) sum_c dX[c] df_c/dix               gv_k = (H/2)(1/3) sum_c dX[c] df_c/diy
+ *   4. grad_points = (2 / box_warp) (gu_0 + gu_1 + gv_2,  gv_0,  gv_1 + gu_2).
+ * Exact fp32 products (any finite planes), no atomics: bit-reproducible.  GNERF_E_UNSUPPORTED when one item's planes exceed 32-bit
+ * tap offsets (as gnerf_query_points_backward); GNERF_E_ARG for null pointers, n_points < 1 or both gradients NULL.
+ * Upstream: autograd through renderer.py:142-148 with sample_coordinates.requires_grad. */
+int gnerf_query_points_grad(const float* planes_nhwc, int n_items, int plane_h, int plane_w,
+                            const float* points, int n_points, float box_warp,
+                            const float* w1, const float* b1, const float* w2, const float* b2,
+                            const float* grad_sigma, const float* grad_rgb, float* grad_points,
+                            int planes_interleaved, gnerf_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------
  * (ABI 13) Marching cubes: the triangle mesh of a level set of a dense float32 volume [d0, d1, d2] (axis 2 fastest, contiguous,
  * every d >= 2, d0 * d1 * d2 < 2^31) -- what shape_utils.py:58-61 asks skimage.measure.marching_cubes for, with this project's own rules
