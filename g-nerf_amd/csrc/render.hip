@@ -62,6 +62,7 @@ struct Params {
     int total_rays;
     int split_shift;        // small launches: a 16-ray tile is shared by 1 << split_shift workgroups (generic / backward kernels)
     int pipe_unit;          // pipelined kernel: rays dealt to a workgroup at a time (kPipeUnit; fewer for launches that do not fill the chip)
+    int pipe_guided;        // pipelined forward, on demand with 8-ray units: c + 256 * (smallest unit) of the guided schedule (pipe_dealing.h), 0 = uniform units
     unsigned* deal_counters;        // pipelined forward: the workspace's per-XCD counters when units are dealt on demand, else null (static dealing)
     unsigned tex_pitch, row_pitch, plane_pitch;     // byte addressing of a texel, see plane_taps (render_shade.inl)
     int64_t item_bytes;     // bytes from one item's planes to the next: 3 * H * W * 128, or 0 when every item reads the same planes (planes_shared)
@@ -860,6 +861,7 @@ static int fill_params(const gnerf_render_params* p, Params& P) {
     P.split_shift = 0;
     P.pipe_unit = 8;
     P.deal_counters = nullptr;
+    P.pipe_guided = 0;
     P.absmax = nullptr;
     P.draw_c = P.draw_f = TorchRandDraw{};
     P.draw_item_ctr = 0;
@@ -956,10 +958,22 @@ extern "C" int gnerf_render_forward(const gnerf_render_params* p, gnerf_stream_t
         // Units are dealt on demand where workgroups get more than one (nothing to balance otherwise); clamp_depth_kernel, which
         // follows every forward launch on this stream, returns the counters to zero.  -DGNERF_PIPE_STATIC_DEALING (a variant build) and
         // GNERF_PIPE_DEALING=static (read per call, like the overrides above: the tests compare the two in one process) keep the static form.
+        // On demand the units shrink towards the end of every XCD's range (the GUIDED schedule of pipe_dealing.h; the kernel derives the
+        // level boundaries of its XCD from these two numbers and nothing else); GNERF_PIPE_DEALING=uniform keeps 8-ray units throughout,
+        // GNERF_PIPE_DEALING=guided:<c>:<smallest unit, 1 or 2> is the A/B form of the constants.
 #ifndef GNERF_PIPE_STATIC_DEALING
         if (total_seq >= capacity * kPipeUnit) {
             const char* dealing = getenv("GNERF_PIPE_DEALING");
-            if (!dealing || strcmp(dealing, "static") != 0) P.deal_counters = static_cast<unsigned*>(p->workspace) + kDealWord0;
+            if (!dealing || strcmp(dealing, "static") != 0) {
+                P.deal_counters = static_cast<unsigned*>(p->workspace) + kDealWord0;
+                int c = kPipeGuidedC, smallest = kPipeGuidedMin;
+                if (dealing && !strcmp(dealing, "uniform")) c = 0;
+                else if (dealing && !strncmp(dealing, "guided:", 7)) {
+                    if (sscanf(dealing + 7, "%d:%d", &c, &smallest) != 2 || c < 1 || c > 255 || (smallest != 1 && smallest != 2))
+                        return fail(GNERF_E_ARG, "render: GNERF_PIPE_DEALING=%s is not guided:<c in 1..255>:<1 or 2>", dealing);
+                }
+                if (P.pipe_unit == 8) P.pipe_guided = c > 0 ? c + 256 * smallest : 0;
+            }
         }
 #endif
         const bool gen = !p->ray_origins || p->rng_mode != GNERF_RNG_TENSORS;       // the call makes its rays and / or its draws in the kernel

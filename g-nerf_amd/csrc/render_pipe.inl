@@ -30,6 +30,14 @@
 #define GNERF_PIPE_UNIT 8
 #endif
 constexpr int kPipeUnit = GNERF_PIPE_UNIT;      // rays dealt to a workgroup at a time (see render_kernel_pipe)
+// guided dealing (pipe_dealing.h): each shrinking level covers kPipeGuidedC x (workgroups of the XCD) units; the smallest unit, 1 or 2 rays
+#ifndef GNERF_PIPE_GUIDED_C
+#define GNERF_PIPE_GUIDED_C 1
+#endif
+#ifndef GNERF_PIPE_GUIDED_MIN
+#define GNERF_PIPE_GUIDED_MIN 1
+#endif
+constexpr int kPipeGuidedC = GNERF_PIPE_GUIDED_C, kPipeGuidedMin = GNERF_PIPE_GUIDED_MIN;
 constexpr int kPipeThreads = 256;
 constexpr int kPipeSlots = 4;
 // TP = 16-sample tiles per shader wave and pass: 1 covers up to 48+48 samples (the reference's default), 2 up to 96+96, 3 up to 144+144
@@ -117,7 +125,7 @@ __device__ __forceinline__ int pipe_seq_to_ray(const Params& P, int64_t seq) {
 // chosen per launch: rays from the item's camera with gnerf_make_rays' arithmetic, draws as torch's device generator would have
 // made them (raygen.h).  Both run on the scalar wave, whose SIMD is the half-idle one: a ray's 96 draws are two
 // wave-wide Philox evaluations (~100 integer instructions each) in place of two loads, its direction is computed for a whole dealing
-// unit at a time (one lane per ray of the unit, parked in 256 bytes of LDS).
+// unit at a time (one lane per ray of the unit -- fewer lanes for the shortened units of guided dealing -- parked in 256 bytes of LDS).
 // BWD: the first pass of the renderer's backward (gnerf_render_backward, staged form) -- the same forward pipeline, but instead of
 // compositing colours it hands the backward's second kernel (render_bwd_tiles_kernel, render_bwd.inl) what it needs per sample, in
 // the ray's merged depth order: the depth, the colour weight v_r and dL/dsigma_r.  Shader waves reduce each sample's colours to
@@ -161,19 +169,24 @@ __device__ __forceinline__ void render_pipe_body(const Params& P, float* smem, c
     // The forward deals ON DEMAND where the launcher hands it counters (P.deal_counters: launches with more than one unit per
     // workgroup): a workgroup's first unit is its own index, every further one comes from its XCD's counter -- one relaxed
     // fetch-add by one lane of the scalar wave, issued while the LAST ray of a unit is proposed and consumed one ray later, behind a
-    // whole pipeline step.  The run's length `nr` is then unknown until the counter runs out: it stays kPipeRunOpen until the scalar
+    // whole pipeline step.  Where the launcher asks for it (P.pipe_guided, 8-ray units only) the units SHRINK as the XCD's range runs
+    // out -- 8 rays, then 4, 2, 1 over the last few per cent (pipe_dealing.h: unit index -> start and length, O(1)) -- so that the
+    // XCD's workgroups end within about a ray of each other, not a unit; the scalar wave keeps a running position inside the current
+    // unit (`upos` against deal.len) in place of r % unit, and a one-ray unit fetches its successor while its only ray is proposed.
+    // The run's length `nr` is then unknown until the counter runs out: it stays kPipeRunOpen until the scalar
     // wave meets a unit past the XCD's range, closes the run at that ray and publishes the length through `nr_word`; the shader waves
     // pick it up every third iteration, where both roles decide on the same value whether to go on (it is written between the
     // two barriers of an iteration and read behind the second).  Until they have it they find the run's end in the ray slots:
     // propose_finish marks every ray past the end.  No workgroup waits for another.  The backward stays on static dealing.
     const int64_t total_seq = (P.tiles_per_item > 0 || (BWD && linear_pad(P) > 0)) ? int64_t(P.n_tiles) * 16 : int64_t(P.total_rays);
     const int unit = P.pipe_unit;
-    PipeDeal deal;
-    deal.init(total_seq, kNumXCD, blockIdx.x % kNumXCD, gridDim.x / kNumXCD, blockIdx.x / kNumXCD, unit);
     const bool dyn = !BWD && P.deal_counters != nullptr;        // (uniform over the launch)
+    PipeDeal deal;
+    deal.init(total_seq, kNumXCD, blockIdx.x % kNumXCD, gridDim.x / kNumXCD, blockIdx.x / kNumXCD, unit, dyn ? P.pipe_guided & 255 : 0, P.pipe_guided >> 8);
     constexpr int kPipeRunOpen = 1 << 30;
     int nr = dyn ? (deal.has_unit() ? kPipeRunOpen : 0) : deal.static_units() * unit;      // local rays 0 .. nr - 1; per wave: see above
     unsigned next_unit = 0;                                     // scalar wave, lane 0: what the fetch-add returned
+    int upos = 0;                                               // scalar wave: position of the next proposed ray inside its unit (deal.len: a new unit)
 
 #ifdef GNERF_WG_STAMPS
     const unsigned long long wg_t0 = __builtin_amdgcn_s_memrealtime();       // this workgroup's start, 100 MHz ticks (tools/wg_lifetimes.py)
@@ -192,8 +205,8 @@ __device__ __forceinline__ void render_pipe_body(const Params& P, float* smem, c
     auto propose_issue = [&](int r) {           // P(r), first half: start the global loads (or make the values: GEN).  Called for r = 0, 1, 2, ... in turn
         pre_ray_id = -1;
         if (r < 0 || r >= nr) return;
-        const int pos = r % unit;
-        if (pos == 0 && r > 0) {                // a new unit
+        if (upos == deal.len) {                 // a new unit (never for r = 0: every unit has a ray)
+            upos = 0;
             if constexpr (BWD) deal.advance_static();
             else if (!dyn) deal.advance_static();
             else if (!deal.advance_to(deal.fetched_unit(unsigned(__builtin_amdgcn_readfirstlane(int(next_unit)))))) {
@@ -202,13 +215,14 @@ __device__ __forceinline__ void render_pipe_body(const Params& P, float* smem, c
                 return;
             }
         }
+        const int pos = upos++;
         if constexpr (!BWD) {
-            if (dyn && pos == unit - 1 && lane == 0)
+            if (dyn && pos == deal.len - 1 && lane == 0)
                 next_unit = __hip_atomic_fetch_add(P.deal_counters + (blockIdx.x % kNumXCD) * kDealLineWords, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
         { const int64_t seq = deal.seq(pos); pre_ray_id = seq >= 0 ? pipe_seq_to_ray<BWD>(P, seq) : -1; }
-        if (GEN && p.cam2world && pos == 0 && lane < unit) {
-            // rays of this dealing unit, one lane each (r .. r + unit - 1 are consecutive positions of the sequence)
+        if (GEN && p.cam2world && pos == 0 && lane < deal.len) {
+            // rays of this dealing unit, one lane each (r .. r + len - 1 are consecutive positions of the sequence; len <= kPipeUnit)
             const int64_t seq = deal.seq(lane);
             const int id = seq >= 0 ? pipe_seq_to_ray<BWD>(P, seq) : -1;
             if (id >= 0) {

@@ -17,7 +17,7 @@ for v in "$@"; do
   IFS='+' read -ra parts <<< "$v"
   for p in "${parts[@]}"; do if [ "$p" = STAMPS ]; then defs="$defs -DGNERF_STAMPS"; elif [ "${p#D:}" != "$p" ]; then defs="$defs -D${p#D:}"; elif [ "$p" != base ]; then defs="$defs -DGNERF_ABLATE_$p"; fi; done
   ( compile_unit $unit "$out/${unit}_$v.o" "$defs" > /dev/null
-    others=(); for u in capi bias_act upfirdn2d filtered_lrelu filtered_lrelu_fused grid_sample planes modconv conv3x3 render mesh; do [ $u = $unit ] || others+=("$here/$u.o"); done
+    others=(); for u in capi bias_act upfirdn2d filtered_lrelu filtered_lrelu_fused grid_sample planes modconv conv3x3 render mesh ssim; do [ $u = $unit ] || others+=("$here/$u.o"); done
     $HIPCC -shared -fPIC --offload-arch=gfx950 "${others[@]}" "$out/${unit}_$v.o" -o "$out/libgnerf_$v.so"
     python3 "$root/tools/kernel_resources.py" "$out/${unit}_$v.o" > "$out/resources_$v.txt" 2>/dev/null || true
     rm -f "$out/${unit}_$v.o"; echo "[variant] $v" ) &
