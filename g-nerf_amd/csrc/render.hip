@@ -1179,11 +1179,18 @@ extern "C" size_t gnerf_render_backward_exchange_bytes(const gnerf_render_params
     return size_t(p->n_items) * size_t(p->rays_per_item) * (n_all + 32 * ((n_all + 15) / 16)) * sizeof(float) + 256;
 }
 
+// The three point-query kernels index pts[idx * 3 + k] and 16 * t + j in int.  The largest n_points for which neither overflows
+// (include/gnerf_hip.h states it); checked before anything else of the call, the pointers included.
+constexpr int kMaxQueryPoints = (INT32_MAX - 15) / 3;
+#define GNERF_CHECK_QUERY_POINTS(name_) \
+    if (n_points > kMaxQueryPoints) return gnerf::fail(GNERF_E_ARG, name_ ": too many points (n_points %d > %d)", n_points, kMaxQueryPoints)
+
 extern "C" int gnerf_query_points(const float* planes_nhwc, int n_items, int plane_h, int plane_w,
                                   const float* points, int n_points, float box_warp,
                                   const float* w1, const float* b1, const float* w2, const float* b2,
                                   float* out_sigma, float* out_rgb, int planes_interleaved, gnerf_stream_t stream) {
     using namespace gnerf;
+    GNERF_CHECK_QUERY_POINTS("query_points");
     gnerf_render_params p = {};
     p.planes_interleaved = planes_interleaved;
     p.planes_nhwc = planes_nhwc; p.n_items = n_items; p.plane_h = plane_h; p.plane_w = plane_w;
@@ -1206,6 +1213,7 @@ extern "C" int gnerf_query_points_backward(const float* planes_nhwc, int n_items
                                            float* grad_planes_nhwc, float* grad_w1, float* grad_b1, float* grad_w2, float* grad_b2,
                                            int planes_interleaved, gnerf_stream_t stream) {
     using namespace gnerf;
+    GNERF_CHECK_QUERY_POINTS("query_points_backward");
     Params P = {};
     gnerf_render_params& p = P.p;
     p.planes_interleaved = planes_interleaved;
@@ -1240,6 +1248,7 @@ extern "C" int gnerf_query_points_grad(const float* planes_nhwc, int n_items, in
                                        const float* grad_sigma, const float* grad_rgb, float* grad_points,
                                        int planes_interleaved, gnerf_stream_t stream) {
     using namespace gnerf;
+    GNERF_CHECK_QUERY_POINTS("query_points_grad");
     Params P = {};
     gnerf_render_params& p = P.p;
     p.planes_interleaved = planes_interleaved;

@@ -509,7 +509,9 @@ int gnerf_render_backward(const gnerf_render_params* p, const gnerf_render_grads
  * TriPlaneGenerator.sample / sample_mixed for shape extraction):
  * points [n_items, n_points, 3] -> sigma [n_items, n_points, 1], rgb [n_items, n_points, 32].
  * out_rgb may be NULL: densities only (the 512^3 shape extraction of gen_videos.py:189-224 reads nothing else).
- * planes_interleaved: layout of planes_nhwc, as gnerf_render_params.planes_interleaved. */
+ * planes_interleaved: layout of planes_nhwc, as gnerf_render_params.planes_interleaved.
+ * n_points <= (INT32_MAX - 15) / 3 = 715 827 877 per item, for this call and for the two gradients below: the kernels index a point's
+ * three coordinates and a tile's 16 points in int.  A larger n_points is GNERF_E_ARG ("too many points"), checked before the pointers. */
 int gnerf_query_points(const float* planes_nhwc, int n_items, int plane_h, int plane_w,
                        const float* points, int n_points, float box_warp,
                        const float* w1, const float* b1, const float* w2, const float* b2,
