@@ -788,6 +788,7 @@ __device__ __forceinline__ int choose_mlp(const Params& P, float* smem, bool* so
 #include "render_pipe.inl"
 #include "render_bwd.inl"
 #include "query_grad.inl"
+#include "render_ray_grad.inl"
 
 // (PerDeviceOnce: csrc/common.h)
 
@@ -1027,16 +1028,31 @@ extern "C" int gnerf_render_forward(const gnerf_render_params* p, gnerf_stream_t
     return check_launch("clamp_depth_kernel");
 }
 
-extern "C" int gnerf_render_backward(const gnerf_render_params* p, const gnerf_render_grads* g, gnerf_stream_t stream) {
+// gnerf_render_backward, and with grad_origins / grad_dirs gnerf_render_backward_rays: the same launches, plus render_ray_grad_kernel between
+// the first pass and the scatter.  Without ray outputs nothing differs from the call as it was before the ray gradient existed.
+static int render_backward_impl(const gnerf_render_params* p, const gnerf_render_grads* g_in, float* grad_origins, float* grad_dirs, gnerf_stream_t stream) {
     using namespace gnerf;
     Params P;
     if (int e = fill_params(p, P)) return e;
-    if (!g) return fail(GNERF_E_ARG, "render_backward: grads is null");
+    if (!g_in) return fail(GNERF_E_ARG, "render_backward: grads is null");
+    const bool need_rays = grad_origins != nullptr || grad_dirs != nullptr;
+    const bool want_planes = g_in->grad_planes_nhwc != nullptr;
+    // A ray request needs the dX rows of the staged first pass whether or not a plane gradient is made from them.  The first-pass kernels
+    // only TEST grad_planes_nhwc (the staged forms never write through it), so a ray-only request hands them the staging buffer's address
+    // in its place, and the scatter below is skipped.
+    gnerf_render_grads g_eff = *g_in;
+    if (need_rays && !want_planes) g_eff.grad_planes_nhwc = g_in->scatter_stage;
+    const gnerf_render_grads* g = &g_eff;
     if (p->planes_shared) return fail(GNERF_E_UNSUPPORTED, "render_backward: planes_shared is a forward-only option");
     if (!p->ray_origins || p->rng_mode != GNERF_RNG_TENSORS) return fail(GNERF_E_UNSUPPORTED, "render_backward: in-kernel rays / draws are forward-only options");
     if (p->sigma_noise_coarse || p->sigma_noise_fine) return fail(GNERF_E_UNSUPPORTED, "render_backward: density noise is a forward-only option");
     const int n_dec = (g->grad_w1 != nullptr) + (g->grad_b1 != nullptr) + (g->grad_w2 != nullptr) + (g->grad_b2 != nullptr);
     if (n_dec != 0 && n_dec != 4) return fail(GNERF_E_ARG, "render_backward: the four decoder gradients are given together or not at all");
+    if (need_rays) {
+        // what dL/do = sum dL/dp, dL/dd = sum t dL/dp does not cover, before any launch
+        if (!g->scatter_stage) return fail(GNERF_E_UNSUPPORTED, "render_backward_rays: the ray gradient reads the staged first pass: scatter_stage must hold gnerf_render_backward_stage_bytes(p)");
+        if (p->ray_start_per_ray) return fail(GNERF_E_UNSUPPORTED, "render_backward_rays: per-ray limits ('auto') make the coarse depths depend on the rays; numeric ray_start / ray_end only");
+    }
     if (!g->grad_planes_nhwc && n_dec == 0) return GNERF_OK;
     if (!(int64_t(p->plane_h) * p->plane_w * 3 * 128 < (int64_t(1) << 32))) return fail(GNERF_E_UNSUPPORTED, "render_backward: planes too large for 32-bit tap offsets");
     static_assert(kBwdRaysPerWave == kRaysPerWave, "ray tiles are shared with the forward launcher");
@@ -1054,16 +1070,16 @@ extern "C" int gnerf_render_backward(const gnerf_render_params* p, const gnerf_r
     // not straddle items.  GNERF_BWD_SCATTER=direct|staged forces one route (A/B runs and tests).
     const char* route = getenv("GNERF_BWD_SCATTER");
     bool tiles_ok = P.tiles_per_item > 0 || p->n_items == 1 || p->rays_per_item % kBwdRaysPerWave == 0;
+    const int n_all_r = p->depth_resolution + p->depth_resolution_importance;
+    const bool binned_shape = int64_t(P.total_rays) * n_all_r * 33 < (int64_t(1) << 32) &&
+                              (2 * size_t(3) * ((p->plane_h + kBinTile - 1) / kBinTile) * ((p->plane_w + kBinTile - 1) / kBinTile) + 128) * 4 <= 150 * 1024;
+    const int pad = (p->rays_per_item + kBwdRaysPerWave - 1) / kBwdRaysPerWave * kBwdRaysPerWave;        // an item's rays as whole 16-ray tiles
     {
         // Round 6: a ragged call (several items whose ray count is no multiple of 16) no longer drops to the one-wave-per-ray kernel with
         // float atomics: where the pipelined kernels and the binned scatter cover the shape, the ray SEQUENCE pads every item to whole 16-ray
         // tiles (pipe_seq_to_ray / bin_tile_ray answer -1 for the padding, which every kernel of the path already skips)
         const char* bk = getenv("GNERF_BWD_KERNEL");
-        const int n_all_r = p->depth_resolution + p->depth_resolution_importance;
         const bool piped_shape = P.tiles_c <= 9 && P.tiles_f <= 9 && !(bk && !strcmp(bk, "wave")) && !(route && (!strcmp(route, "direct") || !strcmp(route, "sorted")));
-        const bool binned_shape = int64_t(P.total_rays) * n_all_r * 33 < (int64_t(1) << 32) &&
-                                  (2 * size_t(3) * ((p->plane_h + kBinTile - 1) / kBinTile) * ((p->plane_w + kBinTile - 1) / kBinTile) + 128) * 4 <= 150 * 1024;
-        const int pad = (p->rays_per_item + kBwdRaysPerWave - 1) / kBwdRaysPerWave * kBwdRaysPerWave;
         if (!tiles_ok && g->scatter_stage && g->grad_planes_nhwc && piped_shape && binned_shape && int64_t(p->n_items) * pad < INT32_MAX) {
             P.tiles_y = pad;                                        // (tiles_per_item == 0: linear_pad(P))
             P.n_tiles = p->n_items * (pad / kBwdRaysPerWave);
@@ -1072,6 +1088,21 @@ extern "C" int gnerf_render_backward(const gnerf_render_params* p, const gnerf_r
     }
     bool staged = g->scatter_stage != nullptr && g->grad_planes_nhwc != nullptr && tiles_ok;
     if (route && !strcmp(route, "direct")) staged = false;
+    // A ray request whose ray tiles straddle items on a route that does not pad them (the one-wave-per-ray kernel): the first pass stages
+    // by ray whatever the tiling, so it runs as it is; a plane gradient then takes the binned scatter over the padded ray sequence.
+    Params P_scatter = P;
+    bool scatter_padded = false, unpadded_first_pass = false;
+    if (need_rays && !staged) {
+        if (route && !strcmp(route, "direct")) return fail(GNERF_E_UNSUPPORTED, "render_backward_rays: GNERF_BWD_SCATTER=direct stages no dX rows");
+        if (want_planes) {
+            if (!binned_shape || int64_t(p->n_items) * pad >= INT32_MAX || (route && !strcmp(route, "sorted")))
+                return fail(GNERF_E_UNSUPPORTED, "render_backward_rays: ray tiles straddle items and the binned scatter does not cover this call");
+            P_scatter.tiles_y = pad;
+            P_scatter.n_tiles = p->n_items * (pad / kBwdRaysPerWave);
+            scatter_padded = true;
+        }
+        staged = unpadded_first_pass = true;
+    }
     if (route && !strcmp(route, "staged") && !staged) return fail(GNERF_E_ARG, "render_backward: the staged scatter needs scatter_stage, a plane gradient and whole tiles per item");
     // Pipelined path of the staged form (round 4): the ray-level part on the forward pipeline (render_kernel_pipe_bwd), the per-sample
     // part as a kernel over sample tiles (render_bwd_tiles_kernel).  Shapes the pipelined kernels cover; GNERF_BWD_KERNEL=wave keeps the
@@ -1080,11 +1111,11 @@ extern "C" int gnerf_render_backward(const gnerf_render_params* p, const gnerf_r
     const bool small_planes = int64_t(p->plane_h) * p->plane_w * 3 * 128 < (int64_t(1) << 32);
     // (a decoder-only request with an exchange buffer -- gnerf_render_backward_exchange_bytes -- takes the same two kernels: no dX rows,
     // no second pass)
-    const bool exchange_only = g->scatter_stage != nullptr && g->grad_planes_nhwc == nullptr && n_dec == 4;
+    const bool exchange_only = g->scatter_stage != nullptr && g->grad_planes_nhwc == nullptr && n_dec == 4;      // (never a ray request: g_eff above)
     // (round 6: F = 0 too -- the pipeline's steps and barriers do not depend on the sample counts; a ray without an importance pass shades no
     //  fine tile, merges nothing and marches its coarse samples)
     const bool piped = (staged || exchange_only) && P.tiles_c <= 9 && P.tiles_f <= 9 && small_planes && !(bwd_kernel && !strcmp(bwd_kernel, "wave"))
-                       && !(route && !strcmp(route, "direct"));
+                       && !(route && !strcmp(route, "direct")) && !unpadded_first_pass;
     if (piped) {
         hipStream_t s = as_stream(stream);
         const int64_t total = P.total_rays;
@@ -1143,6 +1174,21 @@ extern "C" int gnerf_render_backward(const gnerf_render_params* p, const gnerf_r
     else        hipLaunchKernelGGL(render_bwd_kernel<false>, dim3(per_xcd * kNumXCD), dim3(kBwdThreads), lds_bytes, as_stream(stream), P, *g, static_cast<float*>(nullptr));
     if (int e = check_launch("render_bwd_kernel")) return e;
     }
+    if (need_rays) {
+        RayGradArgs R;
+        R.planes = p->planes_nhwc; R.origins = p->ray_origins; R.dirs = p->ray_dirs; R.stage = g->scatter_stage;
+        R.grad_origins = grad_origins; R.grad_dirs = grad_dirs;
+        R.plane_floats = int64_t(3) * p->plane_h * p->plane_w * 32;
+        R.H = p->plane_h; R.W = p->plane_w; R.n_all = p->depth_resolution + p->depth_resolution_importance;
+        R.rays_per_item = p->rays_per_item; R.total_rays = P.total_rays;
+        R.tex_pitch = P.tex_pitch; R.row_pitch = P.row_pitch; R.plane_pitch = P.plane_pitch; R.box_scale = P.box_scale;
+        int64_t blocks = (int64_t(P.total_rays) + kRayGradWaves - 1) / kRayGradWaves;
+        if (blocks > int64_t(kNumCU) * 8) blocks = int64_t(kNumCU) * 8;          // eight workgroups of four waves per CU, rays by grid stride
+        hipLaunchKernelGGL(render_ray_grad_kernel, dim3((unsigned)blocks), dim3(kRayGradThreads), 0, as_stream(stream), R);
+        if (int e = check_launch("render_ray_grad_kernel")) return e;
+        if (!want_planes) return GNERF_OK;
+        if (scatter_padded) P = P_scatter;
+    }
     // Second pass of the staged form.  Round 5: bin the rows by plane tile and sum each tile in LDS (scatter_binned.inl: no global float
     // atomics, bit-reproducible); GNERF_BWD_SCATTER=sorted keeps round 2's per-ray-tile sort with one atomic per texel and chunk
     // (plane_scatter_kernel), which also takes the calls the binned form does not cover.
@@ -1162,6 +1208,15 @@ extern "C" int gnerf_render_backward(const gnerf_render_params* p, const gnerf_r
         return check_launch("plane_scatter_kernel");
     }
     return GNERF_OK;
+}
+
+extern "C" int gnerf_render_backward(const gnerf_render_params* p, const gnerf_render_grads* g, gnerf_stream_t stream) {
+    return render_backward_impl(p, g, nullptr, nullptr, stream);
+}
+
+extern "C" int gnerf_render_backward_rays(const gnerf_render_params* p, const gnerf_render_grads* g, float* grad_origins, float* grad_dirs, gnerf_stream_t stream) {
+    if (!grad_origins && !grad_dirs) return gnerf::fail(GNERF_E_ARG, "render_backward_rays: grad_origins and grad_dirs are both null (gnerf_render_backward is that call)");
+    return render_backward_impl(p, g, grad_origins, grad_dirs, stream);
 }
 
 extern "C" size_t gnerf_render_backward_stage_bytes(const gnerf_render_params* p) {

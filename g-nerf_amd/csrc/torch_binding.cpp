@@ -11,7 +11,8 @@
 // cost: a call through ctypes spends 10-12 us marshalling arguments in Python, this path ~3.
 // Also exported: render_forward (the fused renderer has no reference plugin; same C ABI call as gnerf_hip.render_forward) and
 // marching_cubes (gnerf_hip.marching_cubes' count -> read counts -> emit sequence), ssim_forward / ssim_backward (gnerf_hip.ssim_*),
-// modconv_backward (gnerf_hip.scale_channels_backward / modconv_epilogue_backward), query_points_grad (gnerf_hip.query_points_grad).
+// modconv_backward (gnerf_hip.scale_channels_backward / modconv_epilogue_backward), query_points_grad (gnerf_hip.query_points_grad),
+// render_backward_rays (gnerf_hip.render_backward with need_rays).
 //
 // Built ahead of time by csrc/build.sh (g++, no hipcc: there is no device code) into g-nerf_amd/gnerf_hip/gnerf_torch_ext.so.
 
@@ -264,6 +265,70 @@ std::tuple<Tensor, Tensor, Tensor> render_forward(Tensor planes_nhwc, int64_t n_
     return std::make_tuple(rgb, depth, wsum);
 }
 
+// ------------------------------------------------------------------------------------------------ ray gradient of the fused renderer
+
+// gnerf_hip.render_backward(need_rays=True) has converted the tensors (contiguous float32 on one GPU), checked the gradients' sizes and made
+// the buffers the call accumulates into: grad_planes (zeroed, or None), grad_dec = the four zeroed decoder gradients (or an empty list) and
+// stage, uint8 of gnerf_render_backward_stage_bytes.  Absent optional inputs are None.  -> (grad_origins, grad_dirs) [N,M,3].
+std::tuple<Tensor, Tensor> render_backward_rays(Tensor planes_nhwc, int64_t n_items, Tensor w1, Tensor b1, Tensor w2, Tensor b2,
+                                                Tensor ray_origins, Tensor ray_dirs, Tensor noise_coarse, c10::optional<Tensor> noise_fine,
+                                                int64_t depth_resolution, int64_t depth_resolution_importance, double ray_start, double ray_end,
+                                                c10::optional<Tensor> ray_start_t, c10::optional<Tensor> ray_end_t, double box_warp, bool white_back,
+                                                bool disparity_space_sampling, int64_t image_width, c10::optional<Tensor> planes_absmax,
+                                                c10::optional<Tensor> grad_rgb, c10::optional<Tensor> grad_depth, c10::optional<Tensor> grad_wsum,
+                                                c10::optional<Tensor> grad_planes, std::vector<Tensor> grad_dec, c10::optional<Tensor> stage) {
+    auto f32c = [](const Tensor& t, const char* name) {
+        TORCH_CHECK(t.is_cuda() && t.scalar_type() == torch::kFloat32 && t.is_contiguous(), "render_backward_rays: ", name, " must be a contiguous float32 GPU tensor");
+    };
+    auto opt_ptr = [&](const c10::optional<Tensor>& t, const char* name, int64_t numel) -> float* {
+        if (!t.has_value()) return nullptr;
+        f32c(*t, name);
+        TORCH_CHECK(t->numel() == numel, "render_backward_rays: ", name, " has the wrong number of elements");
+        return t->data_ptr<float>();
+    };
+    f32c(planes_nhwc, "planes_nhwc"); f32c(w1, "w1"); f32c(b1, "b1"); f32c(w2, "w2"); f32c(b2, "b2");
+    f32c(ray_origins, "ray_origins"); f32c(ray_dirs, "ray_dirs"); f32c(noise_coarse, "noise_coarse");
+    const bool separate = planes_nhwc.dim() == 4 && planes_nhwc.size(3) == 32 && planes_nhwc.size(0) == 3 * n_items;
+    const bool interleaved = planes_nhwc.dim() == 4 && planes_nhwc.size(3) == 96 && planes_nhwc.size(0) == n_items;
+    TORCH_CHECK(separate || interleaved, "render_backward_rays: planes_nhwc must be [3N,H,W,32] or [N,H,W,96]");
+    TORCH_CHECK(w1.numel() == 64 * 32 && b1.numel() == 64 && w2.numel() == 33 * 64 && b2.numel() == 33, "render_backward_rays: decoder must be the 32->64->33 MLP");
+    TORCH_CHECK(ray_origins.dim() == 3 && ray_origins.size(0) == n_items && ray_origins.size(2) == 3 && ray_dirs.sizes() == ray_origins.sizes(), "render_backward_rays: rays must be [N,M,3]");
+    const int64_t m = ray_origins.size(1), S = depth_resolution, F = depth_resolution_importance, rays = n_items * m;
+    TORCH_CHECK(noise_coarse.numel() == rays * S, "render_backward_rays: noise_coarse must have N*M*S elements");
+    TORCH_CHECK(grad_dec.empty() || grad_dec.size() == 4, "render_backward_rays: grad_dec holds the four decoder gradients or nothing");
+    gnerf_render_params p = {};
+    p.planes_nhwc = planes_nhwc.data_ptr<float>(); p.n_items = int32_t(n_items); p.plane_h = int32_t(planes_nhwc.size(1)); p.plane_w = int32_t(planes_nhwc.size(2));
+    p.ray_origins = ray_origins.data_ptr<float>(); p.ray_dirs = ray_dirs.data_ptr<float>(); p.rays_per_item = int32_t(m); p.image_width = int32_t(image_width);
+    p.w1 = w1.data_ptr<float>(); p.b1 = b1.data_ptr<float>(); p.w2 = w2.data_ptr<float>(); p.b2 = b2.data_ptr<float>();
+    p.depth_resolution = int32_t(S); p.depth_resolution_importance = int32_t(F);
+    p.ray_start = float(ray_start); p.ray_end = float(ray_end);
+    p.ray_start_per_ray = opt_ptr(ray_start_t, "ray_start", rays);
+    p.ray_end_per_ray = opt_ptr(ray_end_t, "ray_end", rays);
+    p.box_warp = float(box_warp); p.white_back = white_back ? 1 : 0; p.disparity_space_sampling = disparity_space_sampling ? 1 : 0;
+    p.noise_coarse = noise_coarse.data_ptr<float>(); p.noise_fine = F > 0 ? opt_ptr(noise_fine, "noise_fine", rays * F) : nullptr;
+    TORCH_CHECK(F == 0 || p.noise_fine, "render_backward_rays: noise_fine required when depth_resolution_importance > 0");
+    p.planes_absmax = opt_ptr(planes_absmax, "planes_absmax", 1);
+    p.planes_interleaved = interleaved ? 1 : 0;
+    gnerf_render_grads g = {};
+    g.grad_rgb = opt_ptr(grad_rgb, "grad_rgb", rays * 32); g.grad_depth = opt_ptr(grad_depth, "grad_depth", rays); g.grad_wsum = opt_ptr(grad_wsum, "grad_wsum", rays);
+    g.grad_planes_nhwc = opt_ptr(grad_planes, "grad_planes", planes_nhwc.numel());
+    if (!grad_dec.empty()) {
+        const int64_t n[4] = {64 * 32, 64, 33 * 64, 33};
+        float* d[4];
+        for (int i = 0; i < 4; i++) d[i] = opt_ptr(grad_dec[i], "grad_dec", n[i]);
+        g.grad_w1 = d[0]; g.grad_b1 = d[1]; g.grad_w2 = d[2]; g.grad_b2 = d[3];
+    }
+    if (stage.has_value()) {
+        TORCH_CHECK(stage->is_cuda() && stage->is_contiguous() && size_t(stage->numel() * stage->element_size()) >= gnerf_render_backward_stage_bytes(&p),
+                    "render_backward_rays: stage is smaller than gnerf_render_backward_stage_bytes");
+        g.scatter_stage = static_cast<float*>(stage->data_ptr());
+    }
+    const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(at::device_of(planes_nhwc));
+    Tensor go = torch::empty({n_items, m, 3}, ray_origins.options()), gd = torch::empty({n_items, m, 3}, ray_origins.options());
+    check_rc(gnerf_render_backward_rays(&p, &g, go.data_ptr<float>(), gd.data_ptr<float>(), current_stream()), "gnerf_render_backward_rays");
+    return std::make_tuple(go, gd);
+}
+
 // ------------------------------------------------------------------------------------------------ position gradient of the point query
 
 // gnerf_hip.query_points_grad has converted the tensors (contiguous float32 on one GPU; planes [3N,H,W,32] or [N,H,W,96], points [N,P,3]) and
@@ -441,6 +506,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("filtered_lrelu", &filtered_lrelu);
     m.def("filtered_lrelu_act_", &filtered_lrelu_act_);
     m.def("render_forward", &render_forward);
+    m.def("render_backward_rays", &render_backward_rays);
     m.def("query_points_grad", &query_points_grad);
     m.def("marching_cubes", &marching_cubes);
     m.def("ssim_forward", &ssim_forward);

@@ -20,10 +20,11 @@ FFHQ_INTRINSICS = ((4.2647, 0.0, 0.5), (0.0, 4.2647, 0.5), (0.0, 0.0, 1.0))
 
 
 def lookat_pose(yaw, pitch, radius, device='cpu'):
-    """cam2world [1,4,4] of a camera on a sphere of `radius` looking at the origin, y up, no roll."""
+    """cam2world [1,4,4] of a camera on a sphere of `radius` looking at the origin, y up, no roll.  yaw / pitch / radius: numbers, or
+    scalar CPU tensors -- the pose is then differentiable by them (fit_camera)."""
     dt = torch.float32
-    theta = torch.tensor([[yaw]], dtype=dt)
-    phi = torch.tensor([[pitch]], dtype=dt)
+    theta = yaw.reshape(1, 1).to(dt) if isinstance(yaw, torch.Tensor) else torch.tensor([[yaw]], dtype=dt)
+    phi = pitch.reshape(1, 1).to(dt) if isinstance(pitch, torch.Tensor) else torch.tensor([[pitch]], dtype=dt)
     org = torch.zeros(1, 3, dtype=dt)
     org[:, 0:1] = radius * torch.sin(phi) * torch.cos(math.pi - theta)
     org[:, 2:3] = radius * torch.sin(phi) * torch.sin(math.pi - theta)
@@ -91,6 +92,51 @@ def to_uint8(img):
         import gnerf_hip
         return gnerf_hip.to_uint8_nhwc(img)             # the same arithmetic in one launch (csrc/planes.hip)
     return (img * 127.5 + 128).clamp(0, 255).to(torch.uint8).permute(0, 2, 3, 1).contiguous()
+
+
+# ---------------------------------------------------------------------------------------------
+# fitting a camera to an image: the user of the renderer's ray gradient
+
+
+def camera_loss(G, ws, target_raw, yaw, pitch, radius, resolution=None):
+    """L1 distance between `target_raw` and G's raw render of `ws` from lookat_pose(yaw, pitch, radius), on the planes G has cached
+    (synthesis(..., cache_backbone=True) made them).  Differentiable by yaw / pitch / radius when they are tensors: the rays come from
+    the ray sampler's torch form, and the renderer takes them on whichever route ImportanceRenderer.fused_ray_grad selects."""
+    c = camera_label(lookat_pose(yaw, pitch, radius).to(ws.device))
+    raw = G.synthesis(ws, c, neural_rendering_resolution=resolution, use_cached_backbone=True, noise_mode='const')['image_raw']
+    return (raw - target_raw).abs().mean()
+
+
+def _camera_setup(G, ws, start, resolution):
+    G.requires_grad_(False)
+    with torch.no_grad():                                    # the planes, once; every step below reads G's cached copy
+        G.synthesis(ws, camera_label(lookat_pose(*[float(v) for v in start]).to(ws.device)), neural_rendering_resolution=resolution,
+                    cache_backbone=True, only_depth=True, noise_mode='const')
+    return [torch.tensor(float(v), dtype=torch.float32, requires_grad=True) for v in start]
+
+
+def camera_loss_gradient(G, ws, target_raw, yaw, pitch, radius, resolution=None):
+    """(loss, d loss / d (yaw, pitch, radius) as a [3] tensor) at one pose, generator frozen."""
+    params = _camera_setup(G, ws, (yaw, pitch, radius), resolution)
+    loss = camera_loss(G, ws, target_raw, *params, resolution=resolution)
+    return float(loss.detach()), torch.stack(torch.autograd.grad(loss, params))
+
+
+def fit_camera(G, ws, target_raw, yaw, pitch, radius, steps=50, lr=0.01, resolution=None):
+    """Adam on the three look-at parameters against the L1 loss on image_raw, from the given start; generator frozen, planes made once.
+    Returns the trajectory: one dict(step, loss, yaw, pitch, radius) per step, the values BEFORE that step's update, plus a last entry
+    for the final pose."""
+    params = _camera_setup(G, ws, (yaw, pitch, radius), resolution)
+    opt = torch.optim.Adam(params, lr=lr)
+    traj = []
+    for step in range(steps + 1):
+        opt.zero_grad()
+        loss = camera_loss(G, ws, target_raw, *params, resolution=resolution)
+        traj.append(dict(step=step, loss=float(loss.detach()), yaw=float(params[0].detach()), pitch=float(params[1].detach()), radius=float(params[2].detach())))
+        if step < steps:
+            loss.backward()
+            opt.step()
+    return traj
 
 
 # ---------------------------------------------------------------------------------------------

@@ -87,6 +87,7 @@ SIGNATURES = {
     'gnerf_render_workspace_bytes': (ctypes.c_size_t, []),
     'gnerf_render_forward': (_c_i, [ctypes.POINTER(RenderParams), _c_p]),
     'gnerf_render_backward': (_c_i, [ctypes.POINTER(RenderParams), ctypes.POINTER(RenderGrads), _c_p]),
+    'gnerf_render_backward_rays': (_c_i, [ctypes.POINTER(RenderParams), ctypes.POINTER(RenderGrads), _c_p, _c_p, _c_p]),
     'gnerf_render_backward_stage_bytes': (ctypes.c_size_t, [ctypes.POINTER(RenderParams)]),
     'gnerf_render_backward_exchange_bytes': (ctypes.c_size_t, [ctypes.POINTER(RenderParams)]),
     'gnerf_query_points': (_c_i, [_c_p, _c_i, _c_i, _c_i, _c_p, _c_i, _c_f, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_i, _c_p]),
@@ -126,8 +127,9 @@ SIGNATURES = {
     'gnerf_modconv_epilogue_backward_nhwc': (_c_i, [_c_p, _c_p, _c_p, _c_p, _c_i, _c_i, _c_i, _c_i, _c_i, _c_i, _c_f, _c_f, _c_f, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p]),
 }
 # exports added WITHOUT a new ABI version: a library of the same version built before them (a variant build behind GNERF_HIP_LIB) loads, and
-# what needs them asks modconv_backward_available()
-OPTIONAL_SYMBOLS = frozenset(n for n in SIGNATURES if n.startswith(('gnerf_modconv_backward_', 'gnerf_scale_channels_backward', 'gnerf_modconv_epilogue_backward')))
+# what needs them asks modconv_backward_available() / render_ray_grad_available()
+OPTIONAL_SYMBOLS = frozenset(n for n in SIGNATURES if n.startswith(('gnerf_modconv_backward_', 'gnerf_scale_channels_backward', 'gnerf_modconv_epilogue_backward',
+                                                                    'gnerf_render_backward_rays')))
 
 
 def profiled(name):

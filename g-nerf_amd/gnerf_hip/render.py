@@ -156,6 +156,38 @@ def render_generated_supported(S, F, ray_start=0.0, ray_end=1.0, disparity_space
     return True
 
 
+def render_ray_grad_available():
+    """Does the loaded library export gnerf_render_backward_rays?  (Added without a new ABI version: a variant build of the same version
+    made before it loads and answers False.)"""
+    return hasattr(load(), 'gnerf_render_backward_rays')
+
+
+def render_ray_grad_refusal(S, F, ray_start=0.0, ray_end=1.0, density_noise=0, views=False, staged_scatter=True):
+    """Why render_backward(need_rays=True) does not cover these options, or None when it does: the host-side form of
+    gnerf_render_backward_rays' refusals (include/gnerf_hip.h), for callers that must choose a route before the forward runs.
+    Covered: numeric ray limits (with tensor limits -- 'auto' -- the coarse depths depend on the rays), no density noise, one set of
+    planes per item of rays, sample counts the renderer takes, the staged two-pass backward."""
+    S, F = int(S), int(F)
+    if isinstance(ray_start, (torch.Tensor, str)) or isinstance(ray_end, (torch.Tensor, str)):
+        return "per-ray ray limits ('auto') make the coarse depths depend on the rays"
+    if density_noise:
+        return 'density_noise is a forward-only option of the kernels'
+    if views:
+        return 'several views of one set of planes (planes_shared) are a forward-only launch'
+    if not (2 <= S <= _native.MAX_SAMPLES and 0 <= F <= _native.MAX_SAMPLES and (F == 0 or S >= 4)):
+        return f'{S}+{F} samples per ray are outside what the renderer takes'
+    if not staged_scatter or os.environ.get('GNERF_BWD_SCATTER') == 'direct':
+        return 'the single-pass backward stages no per-sample gradients'
+    if not render_ray_grad_available():
+        return 'the loaded library has no gnerf_render_backward_rays'
+    return None
+
+
+def render_ray_grad_supported(S, F, ray_start=0.0, ray_end=1.0, density_noise=0, views=False, staged_scatter=True):
+    """render_ray_grad_refusal(...) is None."""
+    return render_ray_grad_refusal(S, F, ray_start, ray_end, density_noise, views, staged_scatter) is None
+
+
 @profiled('gnerf_hip::render_forward')
 def render_forward(planes_nhwc, n_items, decoder, ray_origins, ray_dirs, noise_coarse, noise_fine, *,
                    depth_resolution, depth_resolution_importance, ray_start, ray_end, box_warp,
@@ -221,13 +253,17 @@ def render_forward(planes_nhwc, n_items, decoder, ray_origins, ray_dirs, noise_c
 def render_backward(planes_nhwc, n_items, decoder, ray_origins, ray_dirs, noise_coarse, noise_fine, grad_rgb, grad_depth, grad_wsum, *,
                     depth_resolution, depth_resolution_importance, ray_start, ray_end, box_warp,
                     white_back=False, disparity_space_sampling=False, image_width=0, need_planes=True, need_decoder=True,
-                    staged_scatter=True, planes_absmax=None):
+                    staged_scatter=True, planes_absmax=None, need_rays=False, sigma_noise=None):
     """Gradient of render_forward for the same arguments (the forward pass is recomputed inside the kernel).
     grad_rgb [N,M,32], grad_depth [N,M,1], grad_wsum [N,M,1]; any of them may be None (zeros).
     staged_scatter: make the plane gradient in two passes through a staging buffer (per-texel aggregation in LDS before the
     atomics; see include/gnerf_hip.h) -- the default; False = the single-pass form.
     planes_absmax: max |planes| as for render_forward (the staged form's first pass picks its decoder arithmetic from it on the
     device; measured by the call when None).
+    need_rays: also the gradient with respect to the rays (gnerf_render_backward_rays; render_ray_grad_supported says which calls it
+    covers, anything else raises NativeError with code E_UNSUPPORTED before a launch).  The staging buffer is then made whether or not
+    a plane gradient is asked for, and the return value gains a third element (grad_origins, grad_dirs), both [N,M,3] float32.
+    sigma_noise: as render_forward's; the backward refuses it (E_UNSUPPORTED), so that a forward call's options can be passed on as they are.
     Returns (grad_planes_nhwc [3N,H,W,32] or None, (grad_w1, grad_b1, grad_w2, grad_b2) or None), all float32."""
     p, keep, m = _render_params(planes_nhwc, n_items, decoder, ray_origins, ray_dirs, noise_coarse, noise_fine,
                                 depth_resolution, depth_resolution_importance, ray_start, ray_end, box_warp,
@@ -248,8 +284,14 @@ def render_backward(planes_nhwc, n_items, decoder, ray_origins, ray_dirs, noise_
     if g_dec is not None:
         g.grad_w1, g.grad_b1, g.grad_w2, g.grad_b2 = [t.data_ptr() for t in g_dec]
     g.grad_planes_nhwc = None if g_planes is None else g_planes.data_ptr()
+    if sigma_noise is not None:
+        sc, sf = sigma_noise
+        _require_cuda(sc, sf)
+        sc, sf = _f32c(sc.detach()), None if sf is None else _f32c(sf.detach())
+        p.sigma_noise_coarse, p.sigma_noise_fine = sc.data_ptr(), _ptr(sf)
+        keep = keep + (sc, sf)
     stage = None
-    if g_planes is not None and staged_scatter:
+    if (g_planes is not None or need_rays) and staged_scatter:
         # Staging buffer of the two-pass scatter (gnerf_render_backward_stage_bytes: bounded, the passes run over batches of ray
         # tiles).  Allocated per call on the current stream: torch's caching allocator hands the block back to the rest of the
         # step afterwards (a buffer cached here would be invisible to it).  Out of memory -> the single-pass form, same result.
@@ -266,6 +308,25 @@ def render_backward(planes_nhwc, n_items, decoder, ray_origins, ray_dirs, noise_
             g.scatter_stage = stage.data_ptr()
         except torch.OutOfMemoryError:
             stage = None
+    if need_rays:
+        # an allocation that failed leaves no staging buffer: the call below says so (E_UNSUPPORTED), there is no single-pass ray gradient
+        e = _native.ext()
+        if e is not None and sigma_noise is None and stage is not None and \
+                render_ray_grad_refusal(p.depth_resolution, p.depth_resolution_importance, ray_start, ray_end, staged_scatter=staged_scatter) is None:
+            # the C++ binding: the same C ABI call on the same buffers.  What the call refuses (the host-side predicate knows) goes through
+            # ctypes, whose failures carry the C ABI's return code (NativeError.code)
+            o, d, nc, nf, w1, b1, w2, b2 = keep[1:9]
+            with _on_device(dev):
+                g_rays = e.render_backward_rays(planes_nhwc, n_items, w1, b1, w2, b2, o, d, nc, nf, p.depth_resolution, p.depth_resolution_importance,
+                                                p.ray_start, p.ray_end, None, None, float(box_warp), bool(white_back), bool(disparity_space_sampling),
+                                                int(image_width), planes_absmax, *grads_in, g_planes, list(g_dec or ()), stage)
+        else:
+            g_o = torch.empty([n_items, m, 3], dtype=torch.float32, device=dev)
+            g_d = torch.empty([n_items, m, 3], dtype=torch.float32, device=dev)
+            _launch('gnerf_render_backward_rays', planes_nhwc, ctypes.byref(p), ctypes.byref(g), g_o.data_ptr(), g_d.data_ptr())
+            g_rays = (g_o, g_d)
+        del keep, grads_in, stage
+        return g_planes, g_dec, g_rays
     _launch('gnerf_render_backward', planes_nhwc, ctypes.byref(p), ctypes.byref(g))
     del keep, grads_in, stage
     return g_planes, g_dec

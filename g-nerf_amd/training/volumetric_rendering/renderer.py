@@ -126,10 +126,48 @@ def _osg_decoder_weights(decoder):
     return fc1, fc2
 
 
+def _once_differentiable(message):
+    """torch.autograd.function.once_differentiable with two differences: the error of a double backward is `message`, which says what
+    to do, and it is raised whenever the first backward ran with a graph (create_graph=True) -- torch's decorator looks at the
+    incoming gradients only, and the gradient of `sigma.sum()` requires none: an eikonal term on the fused route would otherwise fail
+    with "does not require grad" or, worse, treat the first-order gradient as a constant."""
+    def deco(fn):
+        @functools.wraps(fn)
+        def wrapper(ctx, *args):
+            with torch.no_grad():
+                outputs = fn(ctx, *args)
+            if not torch.is_grad_enabled():
+                return outputs
+            err_fn = torch._C._functions.DelayedError(message, len(outputs))
+            return err_fn(*[None if v is None else v.detach().requires_grad_(True) for v in outputs])
+        return wrapper
+    return deco
+
+
+_once_differentiable_points = _once_differentiable(
+    b'the fused point query (gnerf_hip.query_points_backward / query_points_grad) is differentiable once: for a second-order '
+    b'gradient (e.g. an eikonal term) set ImportanceRenderer.fused_point_grad = False, which runs run_model as PyTorch ops')
+
+
+def _once_differentiable_render(fn):
+    """_FusedRender.backward: torch's once_differentiable as it always was, and the stricter form above when the rays get a gradient."""
+    lax = torch.autograd.function.once_differentiable(fn)
+    strict = _once_differentiable(
+        b'the fused ray gradient (gnerf_hip.render_backward with need_rays) is differentiable once: for a second-order gradient set '
+        b'ImportanceRenderer.fused_ray_grad = False, which runs the renderer as PyTorch ops')(fn)
+
+    @functools.wraps(fn)
+    def wrapper(ctx, *args):
+        return (strict if (ctx.needs_input_grad[5] or ctx.needs_input_grad[6]) else lax)(ctx, *args)
+    return wrapper
+
+
 class _FusedRender(torch.autograd.Function):
-    """render_forward / render_backward as one differentiable op.  Inputs with a gradient: planes [N,3,32,H,W] and the
-    decoder's effective weights; everything else is constant (importance depths are constants upstream as well,
-    renderer.py:198/211).  `cfg` is the dict of static keyword arguments of gnerf_hip.render_forward."""
+    """render_forward / render_backward as one differentiable op.  Inputs with a gradient: planes [N,3,32,H,W], the
+    decoder's effective weights and -- when the caller hands them in attached, which ImportanceRenderer does only where
+    gnerf_hip.render_ray_grad_supported allows -- the rays (render_backward's need_rays); everything else is constant (importance
+    depths are constants upstream as well, renderer.py:198/211).  `cfg` is the dict of static keyword arguments of
+    gnerf_hip.render_forward.  Differentiable once."""
 
     @staticmethod
     def forward(ctx, planes, w1, b1, w2, b2, ray_origins, ray_dirs, noise_c, noise_f, ray_start, ray_end, cfg):
@@ -160,7 +198,7 @@ class _FusedRender(torch.autograd.Function):
         return out
 
     @staticmethod
-    @torch.autograd.function.once_differentiable
+    @_once_differentiable_render
     def backward(ctx, g_rgb, g_depth, g_wsum):
         saved = list(ctx.saved_tensors)
         planes, w1, b1, w2, b2, ray_origins, ray_dirs, noise_c = saved[:8]
@@ -169,6 +207,7 @@ class _FusedRender(torch.autograd.Function):
         ray_start, ray_end = (rest[0], rest[1]) if ctx.limits_are_tensors else ctx.limits
         need_planes = ctx.needs_input_grad[0]
         need_decoder = any(ctx.needs_input_grad[1:5])
+        need_rays = ctx.needs_input_grad[5] or ctx.needs_input_grad[6]
         N = planes.shape[0]
         if ctx.interleaved:
             nhwc = _interleaved_view(planes.detach())
@@ -176,10 +215,15 @@ class _FusedRender(torch.autograd.Function):
         else:
             nhwc = ctx.nhwc if ctx.nhwc is not None else gnerf_hip.planes_to_nhwc(planes.detach().float())
             amax = ctx.amax
-        g_planes, g_dec = gnerf_hip.render_backward(nhwc, N, (w1, b1, w2, b2), ray_origins, ray_dirs, noise_c, noise_f, g_rgb, g_depth, g_wsum,
-                                                    ray_start=ray_start, ray_end=ray_end, need_planes=need_planes, need_decoder=need_decoder,
-                                                    planes_absmax=amax, **ctx.cfg)
+        extra = dict(need_rays=True) if need_rays else {}
+        g_planes, g_dec, *g_rays = gnerf_hip.render_backward(nhwc, N, (w1, b1, w2, b2), ray_origins, ray_dirs, noise_c, noise_f, g_rgb, g_depth, g_wsum,
+                                                             ray_start=ray_start, ray_end=ray_end, need_planes=need_planes, need_decoder=need_decoder,
+                                                             planes_absmax=amax, **extra, **ctx.cfg)
         grads = [None] * 12
+        if need_rays:
+            for i, (g, t) in enumerate(zip(g_rays[0], (ray_origins, ray_dirs))):
+                if ctx.needs_input_grad[5 + i]:
+                    grads[5 + i] = g.to(t.dtype)
         if need_planes:
             if ctx.interleaved:
                 grads[0] = _planes_from_interleaved(g_planes, planes)                # laid out like the planes themselves: no repack
@@ -199,25 +243,6 @@ def _producer_absmax(planes):
     if tag is not None and not base.is_inference() and tag[0] == base._version:
         return tag[1]
     return None
-
-
-def _once_differentiable_points(fn):
-    """torch.autograd.function.once_differentiable for _FusedQuery.backward, with two differences: the error of a double backward says
-    what to do, and it is raised whenever the first backward ran with a graph (create_graph=True) -- torch's decorator looks at the
-    incoming gradients only, and the gradient of `sigma.sum()` requires none: an eikonal term on the fused route would otherwise fail
-    with "does not require grad" or, worse, treat the first-order gradient as a constant."""
-    @functools.wraps(fn)
-    def wrapper(ctx, *args):
-        with torch.no_grad():
-            outputs = fn(ctx, *args)
-        if not torch.is_grad_enabled():
-            return outputs
-        err_fn = torch._C._functions.DelayedError(
-            b'the fused point query (gnerf_hip.query_points_backward / query_points_grad) is differentiable once: for a second-order '
-            b'gradient (e.g. an eikonal term) set ImportanceRenderer.fused_point_grad = False, which runs run_model as PyTorch ops',
-            len(outputs))
-        return err_fn(*[None if v is None else v.detach().requires_grad_(True) for v in outputs])
-    return wrapper
 
 
 class _FusedQuery(torch.autograd.Function):
@@ -279,6 +304,9 @@ class ImportanceRenderer(torch.nn.Module):
     # run_model with points that require a gradient: True = the fused kernels (first-order gradients only: gnerf_hip.query_points_grad),
     # False = the PyTorch-op form with its warning, which autograd can differentiate twice (an eikonal term needs that)
     fused_point_grad = True
+    # forward() with rays that require a gradient (camera fitting): True = the fused kernels wherever gnerf_hip.render_ray_grad_supported
+    # says so (numeric ray limits, no density noise; first-order gradients only), False = the PyTorch-op form with its warning
+    fused_ray_grad = False
 
     def __init__(self):
         super().__init__()
@@ -301,7 +329,13 @@ class ImportanceRenderer(torch.nn.Module):
             rays_need_grad = torch.is_grad_enabled() and (ray_origins.requires_grad or ray_directions.requires_grad)
             needs_graph = torch.is_grad_enabled() and (planes.requires_grad or any(p.requires_grad for p in decoder.parameters()))
             noisy = rendering_options.get('density_noise', 0) != 0             # renderer.py:146-147: inside the kernels for forward calls (round 6)
-            if fcs is not None and not rays_need_grad and planes.ndim == 5 and planes.shape[1] == 3 and planes.shape[2] == 32 \
+            ray_refusal = None
+            if rays_need_grad:
+                ray_refusal = 'ImportanceRenderer.fused_ray_grad is False' if not self.fused_ray_grad else gnerf_hip.render_ray_grad_refusal(
+                    rendering_options['depth_resolution'], rendering_options['depth_resolution_importance'], rendering_options['ray_start'],
+                    rendering_options['ray_end'], density_noise=noisy)
+                needs_graph = needs_graph or ray_refusal is None
+            if fcs is not None and ray_refusal is None and planes.ndim == 5 and planes.shape[1] == 3 and planes.shape[2] == 32 \
                     and not (noisy and needs_graph):
                 if views and needs_graph:
                     # the several-views launch is forward-only: with a graph, one differentiable call per view (same draws, same order)
@@ -311,7 +345,7 @@ class ImportanceRenderer(torch.nn.Module):
                 return self._forward_hip(planes, fcs, ray_origins, ray_directions, rendering_options, differentiable=needs_graph)
             # A GPU call that leaves the fused kernel says so, once per reason (none of these occurs in gen_videos.py / train.py)
             _warn_gpu_fallback('the decoder is not the OSGDecoder 32->64->33 MLP' if fcs is None else
-                               'the rays need a gradient' if rays_need_grad else
+                               f'the rays need a gradient and {ray_refusal}' if ray_refusal is not None else
                                'density_noise > 0 (renderer.py:146-147) under autograd: the kernels take it for forward calls only' if noisy else
                                f'planes of shape {tuple(planes.shape)} are not [N,3,32,H,W]')
         if views:
@@ -457,7 +491,8 @@ class ImportanceRenderer(torch.nn.Module):
             fc1, fc2 = fcs
             eff = (fc1.weight.float() * fc1.weight_gain, fc1.bias.float() * fc1.bias_gain,          # networks_stylegan2.py:121-127
                    fc2.weight.float() * fc2.weight_gain, fc2.bias.float() * fc2.bias_gain)
-            return _FusedRender.apply(planes, *eff, ray_origins.detach(), ray_directions.detach(), noise_c.reshape(N * M, S), noise_f,
+            # (rays arrive attached only when forward() has decided that the fused ray gradient covers the call)
+            return _FusedRender.apply(planes, *eff, ray_origins, ray_directions, noise_c.reshape(N * M, S), noise_f,
                                       ray_start, ray_end, cfg)
         nhwc, amax = self._planes_nhwc(planes)
         return gnerf_hip.render_forward(nhwc, N, self._decoder_cache(fcs), ray_origins.detach(), ray_directions.detach(),

@@ -505,6 +505,23 @@ size_t gnerf_render_backward_exchange_bytes(const gnerf_render_params* p);
 /* p: the forward call's params (outputs, workspace and debug are ignored). */
 int gnerf_render_backward(const gnerf_render_params* p, const gnerf_render_grads* g, gnerf_stream_t stream);
 
+/* gnerf_render_backward plus the gradient with respect to the RAYS (added without a new ABI version: no existing signature or struct
+ * changes): grad_origins, grad_dirs [n_items, rays_per_item, 3] float32, every element WRITTEN (nothing accumulated); either may be
+ * NULL, not both.  Everything gnerf_render_backward does for (p, g) is done as there, with the same launches.
+ * With numeric ray_start / ray_end the coarse depths do not depend on the rays, the importance depths are constants and the decoder
+ * ignores directions, so the rays act through the sample positions p_k = o + t_k d only:
+ *     dL/do = sum_k dL/dp_k      dL/dd = sum_k t_k dL/dp_k      dL/dp_k = J_k^T dX_k
+ * dX_k = dL/d(mean feature) of sample k (the staged first pass's rows), J_k the position derivative of the three lookups exactly as
+ * in gnerf_query_points_grad above (steps 3 and 4).  One kernel (csrc/render_ray_grad.inl) between the first pass and the scatter, a
+ * wave per ray, no atomics: bit-reproducible, and the same bits with or without the other gradients.
+ * g->scatter_stage must hold gnerf_render_backward_stage_bytes(p) bytes -- also when g->grad_planes_nhwc is NULL (frozen planes: the
+ * rows are staged, the scatter is skipped); the decoder gradients stay optional.
+ * GNERF_E_UNSUPPORTED, before any launch: scatter_stage NULL (the single-pass form stages nothing; GNERF_BWD_SCATTER=direct likewise);
+ * per-ray limits (ray_start_per_ray: the coarse depths then depend on the rays); and what gnerf_render_backward refuses (density
+ * noise, in-kernel rays / draws, planes_shared).  The call cannot tell a buffer of exchange size from one of stage size: the caller
+ * sizes it. */
+int gnerf_render_backward_rays(const gnerf_render_params* p, const gnerf_render_grads* g, float* grad_origins, float* grad_dirs, gnerf_stream_t stream);
+
 /* Density / colour of arbitrary points (run_model, renderer.py:142-148; used by
  * TriPlaneGenerator.sample / sample_mixed for shape extraction):
  * points [n_items, n_points, 3] -> sigma [n_items, n_points, 1], rgb [n_items, n_points, 32].
