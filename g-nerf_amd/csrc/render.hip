@@ -8,11 +8,17 @@
 //   resampling -> fine lookup + MLP -> depth merge -> final composite.
 //
 // This file holds the pieces every kernel shares (depth proposals, importance resampling, the ray march, DPP scans),
-// the GENERIC kernel described below (any sample count up to 256+256), the entry points and the kernel choice.  The
-// kernels that run G-NeRF's actual configurations are in the .inl files included further down:
+// the GENERIC kernel described below (any sample count up to 256+256) and, from check_common down, the host half: the entry points, which
+// choose each call's kernels.  The kernels that run G-NeRF's actual configurations are in the .inl files included further down:
 //   render_pipe.inl   3 shader waves + 1 scalar wave per workgroup, three rays in flight: up to 144+144 samples
 //   render_shade.inl  the 16-sample shade tile, decoder staging and plane taps the pipelined and backward kernels share
 //   render_bwd.inl   the backward pass (plane + decoder gradients) of the renderer and of run_model
+//
+// Host half: fill_params validates a call and derives what every kernel reads; a handful of small helpers behind it hold the facts more
+// than one launcher needs (tiles per wave, the pipelined launch's unit and grid, 32-bit tap offsets, max |planes|, the binned scatter's
+// coverage, the padded ray sequence).  gnerf_render_forward picks generic or pipelined and launches through launch_pipe<TP, FULL, GEN>;
+// render_backward_impl refuses, decides its route once (BwdRoute) and then launches from that decision alone; the three point queries
+// share fill_query.  Every A/B override is an environment variable read once per call, where its launcher starts deciding.
 //
 // Generic kernel: ONE WAVE (a 64-lane workgroup) owns a ray at a time and walks a small tile of rays
 // (4x4 pixels when the rays form an image).  Nothing but the three outputs is ever written to HBM.
@@ -790,8 +796,6 @@ __device__ __forceinline__ int choose_mlp(const Params& P, float* smem, bool* so
 #include "query_grad.inl"
 #include "render_ray_grad.inl"
 
-// (PerDeviceOnce: csrc/common.h)
-
 int check_common(const gnerf_render_params* p) {
     if (!p) return fail(GNERF_E_ARG, "render: params is null");
     if (!p->planes_nhwc || !p->w1 || !p->b1 || !p->w2 || !p->b2) return fail(GNERF_E_ARG, "render: planes and decoder weights must not be null");
@@ -860,7 +864,7 @@ static int fill_params(const gnerf_render_params* p, Params& P) {
     P.tiles_f = (F + 15) / 16;
     P.total_rays = int(total);
     P.split_shift = 0;
-    P.pipe_unit = 8;
+    P.pipe_unit = kPipeUnit;
     P.deal_counters = nullptr;
     P.pipe_guided = 0;
     P.absmax = nullptr;
@@ -889,6 +893,73 @@ static int fill_params(const gnerf_render_params* p, Params& P) {
     return GNERF_OK;
 }
 
+// ---- facts that more than one launcher below needs, each worked out in one place
+// (the pipelined, backward and query-gradient kernels address plane taps with 32-bit byte offsets)
+static bool planes_fit_32bit_taps(const gnerf_render_params* p) { return int64_t(p->plane_h) * p->plane_w * 3 * 128 < (int64_t(1) << 32); }
+// 16-sample tiles per shader wave and pass of the pipelined kernels (render_pipe.inl), 0 where they do not cover the sample counts
+static int pipe_tiles_per_wave(const Params& P) {
+    const int t = P.tiles_c > P.tiles_f ? P.tiles_c : P.tiles_f;
+    return t <= 3 ? 1 : (t <= 6 ? 2 : (t <= 9 ? 3 : 0));
+}
+// resident workgroups per CU for that count (the kernels' __launch_bounds__)
+static int pipe_workgroups_per_cu(int tp) { return tp == 1 ? GNERF_PIPE_WAVES_PER_SIMD : (tp == 2 ? GNERF_PIPE2_WAVES_PER_SIMD : 2); }
+// positions of the ray sequence the pipelined kernels walk: whole 16-ray tiles where the rays are tiled or padded
+static int64_t pipe_seq_len(const Params& P) { return (P.tiles_per_item > 0 || linear_pad(P) > 0) ? int64_t(P.n_tiles) * 16 : int64_t(P.total_rays); }
+// Dealing unit and grid of a pipelined launch (the forward's, the backward's first pass).  One dealing unit per workgroup until the chip
+// is full: a small launch is latency-bound, and the three half-steps of pipeline fill cost less than leaving compute units idle (64x64
+// rays: 167 -> 70 us); the unit shrinks from 8 rays down to what spreads the launch over every resident workgroup slot (a 64x64 frame:
+// 4 rays each on pipe<1>, 6 on pipe<2>).
+struct PipeLaunch { int unit; unsigned grid; bool fills_chip; };
+static PipeLaunch pipe_launch(int tp, int64_t total_seq) {
+    using namespace gnerf;
+    const int64_t capacity = int64_t(pipe_workgroups_per_cu(tp)) * kNumCU;
+    PipeLaunch L;
+    L.fills_chip = total_seq >= capacity * kPipeUnit;
+    L.unit = L.fills_chip ? kPipeUnit : int((total_seq + capacity - 1) / capacity);        // >= 1: total_seq >= 1
+    const int64_t g = ((total_seq + L.unit - 1) / L.unit + kNumXCD - 1) / kNumXCD * kNumXCD;
+    L.grid = unsigned(g < kNumXCD ? kNumXCD : (g > capacity ? capacity : g));
+    return L;
+}
+// max |planes| of this call's planes, measured into `word` (one device float)
+static int measure_absmax(const gnerf_render_params* p, float* word, gnerf_stream_t stream) {
+    return gnerf_planes_absmax(p->planes_nhwc, int64_t(p->planes_shared ? 1 : p->n_items) * 3 * p->plane_h * p->plane_w * 32, word, stream);
+}
+// what choose_mlp reads: the caller's planes_absmax, else measured into `scratch`
+static int absmax_or_measure(const gnerf_render_params* p, float* scratch, gnerf_stream_t stream, const float*& absmax) {
+    absmax = p->planes_absmax ? p->planes_absmax : scratch;
+    return p->planes_absmax ? GNERF_OK : measure_absmax(p, scratch, stream);
+}
+// The binned scatter (scatter_binned.inl) indexes the staging buffer with 32 bits and keeps an item's plane-tile histogram in LDS.
+static bool binned_scatter_covers(const Params& P) {
+    const gnerf_render_params& p = P.p;
+    return int64_t(P.total_rays) * (p.depth_resolution + p.depth_resolution_importance) * 33 < (int64_t(1) << 32) &&
+           (2 * size_t(3) * ((p.plane_h + kBinTile - 1) / kBinTile) * ((p.plane_w + kBinTile - 1) / kBinTile) + 128) * 4 <= 150 * 1024;
+}
+// A ragged call (several items whose ray count is no multiple of 16): the ray SEQUENCE pads every item to whole 16-ray tiles, so that no
+// tile straddles items (linear_pad(P); pipe_seq_to_ray / bin_tile_ray answer -1 for the padding, which every kernel of the path skips).
+static int padded_rays_per_item(const gnerf_render_params& p) { return (p.rays_per_item + kBwdRaysPerWave - 1) / kBwdRaysPerWave * kBwdRaysPerWave; }
+static void pad_ray_sequence(Params& P) {
+    P.tiles_y = padded_rays_per_item(P.p);                      // (tiles_per_item == 0 for such a call)
+    P.n_tiles = P.p.n_items * (P.tiles_y / kBwdRaysPerWave);
+}
+
+// One pipelined forward launch.  These are all the instantiations of render_kernel_pipe: GEN (in-kernel rays / draws) is built with FULL
+// for TP 1 and 2 and for nothing else.  TP = 3 takes 65 KB of LDS, above the default dynamic limit.
+template <int TP, bool FULL, bool GEN>
+static int launch_pipe(int mlp, unsigned grid, hipStream_t s, const Params& P) {
+    static_assert(!GEN || (FULL && TP <= 2), "in-kernel rays / draws: 48+48 and 96+96 samples only");
+    void (*kernel)(Params) = render_kernel_pipe<TP, kMlpAuto, FULL, GEN>;
+    if (mlp == kMlpF16x3) kernel = render_kernel_pipe<TP, kMlpF16x3, FULL, GEN>;
+    if (mlp == kMlpF32) kernel = render_kernel_pipe<TP, kMlpF32, FULL, GEN>;
+    if constexpr (TP == 3) {
+        static_assert(kMlpAuto == 0 && kMlpF16x3 == 1 && kMlpF32 == 2, "once[] is indexed by the MLP mode");
+        static gnerf::PerDeviceOnce once[3];                    // one per kernel of this instantiation (mlp is one of the three: checked by the caller)
+        if (int e = once[mlp].raise_lds(kernel, "render")) return e;
+    }
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(kPipeThreads), pipe_lds_floats(TP, mlp) * sizeof(float), s, P);
+    return gnerf::check_launch("render_kernel_pipe");
+}
+
 extern "C" int gnerf_render_forward(const gnerf_render_params* p, gnerf_stream_t stream) {
     using namespace gnerf;
     Params P;
@@ -901,20 +972,18 @@ extern "C" int gnerf_render_forward(const gnerf_render_params* p, gnerf_stream_t
     // Small launches (one 64x64 frame of gen_videos.py is 256 ray tiles on 256 CUs): a workgroup walking its 16 rays one
     // after the other leaves most of the chip idle and the launch takes 16 ray latencies.  Split each tile over up to four
     // workgroups while that still fits the chip in one wave of workgroups.
-    P.split_shift = 0;
     while (P.split_shift < 2 && (int64_t(P.n_tiles) << (P.split_shift + 1)) <= int64_t(kNumCU) * 4) P.split_shift++;
-    const int per_xcd = ((P.n_tiles << P.split_shift) + kNumXCD - 1) / kNumXCD;
-    const dim3 grid(per_xcd * kNumXCD);
+    const dim3 grid(((P.n_tiles << P.split_shift) + kNumXCD - 1) / kNumXCD * kNumXCD);        // (the generic kernel's: whole XCDs)
     // Kernel choice (GNERF_RENDER_KERNEL=pipe|generic forces one, for A/B runs):
     //   pipe    3 shader waves + 1 scalar wave, three rays in flight: up to 144+144 samples, importance sampling optional (1, 2 or 3 tiles per wave)
     //   generic one wave per ray: everything else (up to 256+256, or planes too large for 32-bit tap offsets)
-    // A/B and test overrides, read per call (the parity tests switch kernels inside one process): two getenv walks of the
+    // A/B and test overrides, read per call (the parity tests switch kernels inside one process): a getenv is a walk of the
     // environment, ~0.1 us against the ~10 us of a launch
     const char* force = getenv("GNERF_RENDER_KERNEL");
     const char* force_mlp = getenv("GNERF_RENDER_MLP");                      // f16x3 | f32: overrides params.mlp_mode
-    const bool small_planes = int64_t(p->plane_h) * p->plane_w * 3 * 128 < (int64_t(1) << 32);
-    bool pipe = P.tiles_c <= 9 && P.tiles_f <= 9 && small_planes;
-    const int pipe_tp = (P.tiles_c <= 3 && P.tiles_f <= 3) ? 1 : ((P.tiles_c <= 6 && P.tiles_f <= 6) ? 2 : 3);   // 16-sample tiles per shader wave and pass
+    const char* verify = getenv("GNERF_VERIFY_ABSMAX");
+    const int pipe_tp = pipe_tiles_per_wave(P);
+    bool pipe = pipe_tp != 0 && planes_fit_32bit_taps(p);
     if (force && !strcmp(force, "generic")) pipe = false;
     if (force && !strcmp(force, "pipe") && !pipe) return fail(GNERF_E_UNSUPPORTED, "render: pipelined kernel does not cover %d+%d samples", S, F);
     // Decoder arithmetic of the pipelined kernel (the generic kernel is fp32 throughout).
@@ -924,38 +993,25 @@ extern "C" int gnerf_render_forward(const gnerf_render_params* p, gnerf_stream_t
     if (mlp != GNERF_MLP_AUTO && mlp != GNERF_MLP_F16X3 && mlp != GNERF_MLP_F32) return fail(GNERF_E_ARG, "render: mlp_mode %d is not one of GNERF_MLP_*", mlp);
     if (pipe && mlp == GNERF_MLP_AUTO) {
         // the choice is made on the device, by every workgroup for itself (no host round trip, graph-capturable): see choose_mlp
-        P.absmax = p->planes_absmax;
+        float* own = reinterpret_cast<float*>(static_cast<int*>(p->workspace) + 5);
         hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;
         (void)hipStreamIsCapturing(s, &capturing);                   // (the check synchronises the stream: not inside a graph capture)
-        if (P.absmax && capturing == hipStreamCaptureStatusNone && getenv("GNERF_VERIFY_ABSMAX") && !strcmp(getenv("GNERF_VERIFY_ABSMAX"), "1")) {
+        if (p->planes_absmax && capturing == hipStreamCaptureStatusNone && verify && !strcmp(verify, "1")) {
             // debug aid (include/gnerf_hip.h, planes_absmax contract): is the caller's value an upper bound of THESE planes?
-            float* own = reinterpret_cast<float*>(static_cast<int*>(p->workspace) + 5);
-            if (int e = gnerf_planes_absmax(p->planes_nhwc, int64_t(p->planes_shared ? 1 : p->n_items) * 3 * p->plane_h * p->plane_w * 32, own, stream)) return e;
+            if (int e = measure_absmax(p, own, stream)) return e;
             float mine = 0.f, theirs = 0.f;
-            if (hipMemcpyAsync(&mine, own, 4, hipMemcpyDeviceToHost, s) != hipSuccess || hipMemcpyAsync(&theirs, P.absmax, 4, hipMemcpyDeviceToHost, s) != hipSuccess ||
+            if (hipMemcpyAsync(&mine, own, 4, hipMemcpyDeviceToHost, s) != hipSuccess || hipMemcpyAsync(&theirs, p->planes_absmax, 4, hipMemcpyDeviceToHost, s) != hipSuccess ||
                 hipStreamSynchronize(s) != hipSuccess)
                 return fail(GNERF_E_LAUNCH, "render: GNERF_VERIFY_ABSMAX could not read the plane statistics back");
             if (theirs < mine)                                  // (NaN on either side compares false: NaN planes / NaN bound both select fp32)
                 return fail(GNERF_E_ARG, "render: planes_absmax = %g is smaller than max |planes| = %g of this call's planes (stale value?)", theirs, mine);
         }
-        if (!P.absmax) {
-            float* own = reinterpret_cast<float*>(static_cast<int*>(p->workspace) + 5);
-            if (int e = gnerf_planes_absmax(p->planes_nhwc, int64_t(p->planes_shared ? 1 : p->n_items) * 3 * p->plane_h * p->plane_w * 32, own, stream)) return e;
-            P.absmax = own;
-        }
+        if (int e = absmax_or_measure(p, own, stream, P.absmax)) return e;
     }
+    const bool gen = !p->ray_origins || p->rng_mode != GNERF_RNG_TENSORS;       // the call makes its rays and / or its draws in the kernel
     if (pipe) {
-        const int64_t total_seq = P.tiles_per_item > 0 ? int64_t(P.n_tiles) * 16 : total;
-        const int per_cu = pipe_tp == 1 ? GNERF_PIPE_WAVES_PER_SIMD : (pipe_tp == 2 ? GNERF_PIPE2_WAVES_PER_SIMD : 2);                         // resident workgroups per CU
-        // one dealing unit per workgroup until the chip is full: a small launch is latency-bound, and the three half-steps of
-        // pipeline fill cost less than leaving compute units idle (64x64 rays: 167 -> 70 us); the unit shrinks from 8 rays down
-        // to what spreads the launch over every resident workgroup slot (a 64x64 frame: 4 rays each on pipe<1>, 6 on pipe<2>)
-        const int64_t capacity = int64_t(per_cu) * kNumCU;
-        P.pipe_unit = kPipeUnit;
-        if (total_seq < capacity * kPipeUnit) P.pipe_unit = int((total_seq + capacity - 1) / capacity);       // >= 1: total_seq >= 1
-        int64_t g = ((total_seq + P.pipe_unit - 1) / P.pipe_unit + kNumXCD - 1) / kNumXCD * kNumXCD;
-        if (g < kNumXCD) g = kNumXCD;
-        if (g > capacity) g = capacity;
+        const PipeLaunch L = pipe_launch(pipe_tp, pipe_seq_len(P));
+        P.pipe_unit = L.unit;
         // Units are dealt on demand where workgroups get more than one (nothing to balance otherwise); clamp_depth_kernel, which
         // follows every forward launch on this stream, returns the counters to zero.  -DGNERF_PIPE_STATIC_DEALING (a variant build) and
         // GNERF_PIPE_DEALING=static (read per call, like the overrides above: the tests compare the two in one process) keep the static form.
@@ -963,7 +1019,7 @@ extern "C" int gnerf_render_forward(const gnerf_render_params* p, gnerf_stream_t
         // level boundaries of its XCD from these two numbers and nothing else); GNERF_PIPE_DEALING=uniform keeps 8-ray units throughout,
         // GNERF_PIPE_DEALING=guided:<c>:<smallest unit, 1 or 2> is the A/B form of the constants.
 #ifndef GNERF_PIPE_STATIC_DEALING
-        if (total_seq >= capacity * kPipeUnit) {
+        if (L.fills_chip) {
             const char* dealing = getenv("GNERF_PIPE_DEALING");
             if (!dealing || strcmp(dealing, "static") != 0) {
                 P.deal_counters = static_cast<unsigned*>(p->workspace) + kDealWord0;
@@ -977,43 +1033,21 @@ extern "C" int gnerf_render_forward(const gnerf_render_params* p, gnerf_stream_t
             }
         }
 #endif
-        const bool gen = !p->ray_origins || p->rng_mode != GNERF_RNG_TENSORS;       // the call makes its rays and / or its draws in the kernel
-        const size_t lds_bytes = pipe_lds_floats(pipe_tp, mlp) * sizeof(float);
-        const dim3 gd((unsigned)g), bd(kPipeThreads);
         // the instantiation with compile-time sample counts (render_pipe_body<.., FULL>) where the call fills the slots exactly
-        bool full = S == 48 * pipe_tp && F == 48 * pipe_tp && !p->disparity_space_sampling && !p->ray_start_per_ray && !p->debug && !p->sigma_noise_coarse;
-#if defined(GNERF_STAMPS) || defined(GNERF_WG_STAMPS)
-        full = full || (S == 48 * pipe_tp && F == 48 * pipe_tp && !p->disparity_space_sampling && !p->ray_start_per_ray && !p->sigma_noise_coarse);     // the timing build's `debug` is its stamp buffer
+        bool full = S == 48 * pipe_tp && F == 48 * pipe_tp && !p->disparity_space_sampling && !p->ray_start_per_ray && !p->sigma_noise_coarse;
+#if !defined(GNERF_STAMPS) && !defined(GNERF_WG_STAMPS)
+        full = full && !p->debug;                               // (the timing builds' `debug` is their stamp buffer)
 #endif
         if (const char* f = getenv("GNERF_PIPE_FULL")) full = full && strcmp(f, "0") != 0;       // A/B runs and the tests' cross-check
-        if (gen) {
-            if (!full || pipe_tp > 2)
-                return fail(GNERF_E_UNSUPPORTED, "render: in-kernel rays / draws are built for 48+48 and 96+96 samples with plain stratified sampling (got %d+%d)", S, F);
-#define GNERF_PIPE_GEN(TP) do { if (mlp == kMlpAuto) hipLaunchKernelGGL((render_kernel_pipe<TP, kMlpAuto, true, true>), gd, bd, lds_bytes, s, P); \
-                                else if (mlp == kMlpF16x3) hipLaunchKernelGGL((render_kernel_pipe<TP, kMlpF16x3, true, true>), gd, bd, lds_bytes, s, P); \
-                                else hipLaunchKernelGGL((render_kernel_pipe<TP, kMlpF32, true, true>), gd, bd, lds_bytes, s, P); } while (0)
-            if (pipe_tp == 1) GNERF_PIPE_GEN(1); else GNERF_PIPE_GEN(2);
-#undef GNERF_PIPE_GEN
-        } else {
-#define GNERF_PIPE2(TP, FULL) do { if (mlp == kMlpAuto) hipLaunchKernelGGL((render_kernel_pipe<TP, kMlpAuto, FULL>), gd, bd, lds_bytes, s, P); \
-                            else if (mlp == kMlpF16x3) hipLaunchKernelGGL((render_kernel_pipe<TP, kMlpF16x3, FULL>), gd, bd, lds_bytes, s, P); \
-                            else hipLaunchKernelGGL((render_kernel_pipe<TP, kMlpF32, FULL>), gd, bd, lds_bytes, s, P); } while (0)
-#define GNERF_PIPE(TP) do { if (full) GNERF_PIPE2(TP, true); else GNERF_PIPE2(TP, false); } while (0)
-        if (pipe_tp == 1) GNERF_PIPE(1);
-        else if (pipe_tp == 2) GNERF_PIPE(2);
-        else {                                              // 65 KB of LDS: above the default dynamic limit
-            static PerDeviceOnce once3[6];
-            if (mlp == kMlpAuto) { if (int e = full ? once3[0].raise_lds(render_kernel_pipe<3, kMlpAuto, true>, "render") : once3[3].raise_lds(render_kernel_pipe<3, kMlpAuto, false>, "render")) return e; }
-            else if (mlp == kMlpF16x3) { if (int e = full ? once3[1].raise_lds(render_kernel_pipe<3, kMlpF16x3, true>, "render") : once3[4].raise_lds(render_kernel_pipe<3, kMlpF16x3, false>, "render")) return e; }
-            else { if (int e = full ? once3[2].raise_lds(render_kernel_pipe<3, kMlpF32, true>, "render") : once3[5].raise_lds(render_kernel_pipe<3, kMlpF32, false>, "render")) return e; }
-            GNERF_PIPE(3);
-        }
-#undef GNERF_PIPE
-#undef GNERF_PIPE2
-        }
-        if (int e = check_launch("render_kernel_pipe")) return e;
-    } else
-    if (!p->ray_origins || p->rng_mode != GNERF_RNG_TENSORS) {
+        if (gen && (!full || pipe_tp > 2))
+            return fail(GNERF_E_UNSUPPORTED, "render: in-kernel rays / draws are built for 48+48 and 96+96 samples with plain stratified sampling (got %d+%d)", S, F);
+        int e;
+        if (gen) e = pipe_tp == 1 ? launch_pipe<1, true, true>(mlp, L.grid, s, P) : launch_pipe<2, true, true>(mlp, L.grid, s, P);
+        else if (pipe_tp == 1) e = full ? launch_pipe<1, true, false>(mlp, L.grid, s, P) : launch_pipe<1, false, false>(mlp, L.grid, s, P);
+        else if (pipe_tp == 2) e = full ? launch_pipe<2, true, false>(mlp, L.grid, s, P) : launch_pipe<2, false, false>(mlp, L.grid, s, P);
+        else e = full ? launch_pipe<3, true, false>(mlp, L.grid, s, P) : launch_pipe<3, false, false>(mlp, L.grid, s, P);
+        if (e) return e;
+    } else if (gen) {
         return fail(GNERF_E_UNSUPPORTED, "render: in-kernel rays / draws need the pipelined kernel (48+48 or 96+96 samples); got %d+%d", S, F);
     } else {
         const size_t lds_bytes = scratch_floats(16 * (P.tiles_c + P.tiles_f), P.tiles_c + P.tiles_f) * sizeof(float);
@@ -1028,10 +1062,23 @@ extern "C" int gnerf_render_forward(const gnerf_render_params* p, gnerf_stream_t
     return check_launch("clamp_depth_kernel");
 }
 
+// What one backward call launches: decided once in render_backward_impl, then only read (DESIGN.md 3.2 has the table of routes).
+struct BwdRoute {
+    // first pass.  Wave: render_bwd_kernel<false / true>, one wave per ray, float atomics into the plane gradient / dX rows into the staging buffer.
+    // Piped: render_kernel_pipe_bwd + render_bwd_tiles_kernel, dX rows into the staging buffer / a decoder-only request's exchange buffer (no dX rows)
+    enum First { kWaveDirect, kWaveStaged, kPipedRows, kPipedExchange } first;
+    enum Second { kNoScatter, kBinned, kSorted } second;       // dX rows -> plane gradient: scatter_binned.inl or plane_scatter_kernel
+    bool padded;            // every kernel of the call walks the padded ray sequence (pad_ray_sequence)
+    bool scatter_padded;    // only the scatter does: the first pass stages by ray whatever the tiling
+    int mlp_first, mlp_tiles;       // decoder arithmetic of the two piped kernels (GNERF_MLP_*)
+};
+
 // gnerf_render_backward, and with grad_origins / grad_dirs gnerf_render_backward_rays: the same launches, plus render_ray_grad_kernel between
-// the first pass and the scatter.  Without ray outputs nothing differs from the call as it was before the ray gradient existed.
+// the first pass and the scatter.  Three parts: (a) what the call refuses, (b) its route, decided once, (c) the launches, which read that
+// decision and nothing else and build each kernel's Params from P and it.
 static int render_backward_impl(const gnerf_render_params* p, const gnerf_render_grads* g_in, float* grad_origins, float* grad_dirs, gnerf_stream_t stream) {
     using namespace gnerf;
+    // ---- (a) refusals
     Params P;
     if (int e = fill_params(p, P)) return e;
     if (!g_in) return fail(GNERF_E_ARG, "render_backward: grads is null");
@@ -1039,7 +1086,7 @@ static int render_backward_impl(const gnerf_render_params* p, const gnerf_render
     const bool want_planes = g_in->grad_planes_nhwc != nullptr;
     // A ray request needs the dX rows of the staged first pass whether or not a plane gradient is made from them.  The first-pass kernels
     // only TEST grad_planes_nhwc (the staged forms never write through it), so a ray-only request hands them the staging buffer's address
-    // in its place, and the scatter below is skipped.
+    // in its place, and there is no scatter.
     gnerf_render_grads g_eff = *g_in;
     if (need_rays && !want_planes) g_eff.grad_planes_nhwc = g_in->scatter_stage;
     const gnerf_render_grads* g = &g_eff;
@@ -1054,160 +1101,124 @@ static int render_backward_impl(const gnerf_render_params* p, const gnerf_render
         if (p->ray_start_per_ray) return fail(GNERF_E_UNSUPPORTED, "render_backward_rays: per-ray limits ('auto') make the coarse depths depend on the rays; numeric ray_start / ray_end only");
     }
     if (!g->grad_planes_nhwc && n_dec == 0) return GNERF_OK;
-    if (!(int64_t(p->plane_h) * p->plane_w * 3 * 128 < (int64_t(1) << 32))) return fail(GNERF_E_UNSUPPORTED, "render_backward: planes too large for 32-bit tap offsets");
+    if (!planes_fit_32bit_taps(p)) return fail(GNERF_E_UNSUPPORTED, "render_backward: planes too large for 32-bit tap offsets");
     static_assert(kBwdRaysPerWave == kRaysPerWave, "ray tiles are shared with the forward launcher");
     const size_t lds_bytes = (kBwdWeightFloats + kBwdWaves * bwd_wave_floats(16 * (P.tiles_c + P.tiles_f))) * sizeof(float);
     if (lds_bytes > 160 * 1024) return fail(GNERF_E_ARG, "render_backward: %d+%d samples need %zu bytes of LDS (> 160 KiB)", p->depth_resolution, p->depth_resolution_importance, lds_bytes);
-    static PerDeviceOnce once;
-    static PerDeviceOnce once_staged;
+    static PerDeviceOnce once, once_staged;
     if (int e = once.raise_lds(render_bwd_kernel<false>, "render_backward")) return e;
     if (int e = once_staged.raise_lds(render_bwd_kernel<true>, "render_backward")) return e;
-    P.split_shift = 0;                                       // up to two workgroups of four waves per CU: share tiles until the chip is full
-    while (P.split_shift < 2 && (int64_t(P.n_tiles) << (P.split_shift + 1)) <= int64_t(kNumCU) * 2 * kBwdWaves) P.split_shift++;
-    const int n_blocks = ((P.n_tiles << P.split_shift) + kBwdWaves - 1) / kBwdWaves;
-    const int per_xcd = (n_blocks + kNumXCD - 1) / kNumXCD;
-    // Staged scatter (see plane_scatter_kernel): needs the caller's staging buffer, a plane gradient to make, and ray tiles that do
-    // not straddle items.  GNERF_BWD_SCATTER=direct|staged forces one route (A/B runs and tests).
-    const char* route = getenv("GNERF_BWD_SCATTER");
-    bool tiles_ok = P.tiles_per_item > 0 || p->n_items == 1 || p->rays_per_item % kBwdRaysPerWave == 0;
-    const int n_all_r = p->depth_resolution + p->depth_resolution_importance;
-    const bool binned_shape = int64_t(P.total_rays) * n_all_r * 33 < (int64_t(1) << 32) &&
-                              (2 * size_t(3) * ((p->plane_h + kBinTile - 1) / kBinTile) * ((p->plane_w + kBinTile - 1) / kBinTile) + 128) * 4 <= 150 * 1024;
-    const int pad = (p->rays_per_item + kBwdRaysPerWave - 1) / kBwdRaysPerWave * kBwdRaysPerWave;        // an item's rays as whole 16-ray tiles
+    // ---- (b) the route.  Overrides for A/B runs and tests, read per call (the tests switch them inside one process):
+    BwdRoute route;
     {
-        // Round 6: a ragged call (several items whose ray count is no multiple of 16) no longer drops to the one-wave-per-ray kernel with
-        // float atomics: where the pipelined kernels and the binned scatter cover the shape, the ray SEQUENCE pads every item to whole 16-ray
-        // tiles (pipe_seq_to_ray / bin_tile_ray answer -1 for the padding, which every kernel of the path already skips)
-        const char* bk = getenv("GNERF_BWD_KERNEL");
-        const bool piped_shape = P.tiles_c <= 9 && P.tiles_f <= 9 && !(bk && !strcmp(bk, "wave")) && !(route && (!strcmp(route, "direct") || !strcmp(route, "sorted")));
-        if (!tiles_ok && g->scatter_stage && g->grad_planes_nhwc && piped_shape && binned_shape && int64_t(p->n_items) * pad < INT32_MAX) {
-            P.tiles_y = pad;                                        // (tiles_per_item == 0: linear_pad(P))
-            P.n_tiles = p->n_items * (pad / kBwdRaysPerWave);
-            tiles_ok = true;
-        }
-    }
-    bool staged = g->scatter_stage != nullptr && g->grad_planes_nhwc != nullptr && tiles_ok;
-    if (route && !strcmp(route, "direct")) staged = false;
-    // A ray request whose ray tiles straddle items on a route that does not pad them (the one-wave-per-ray kernel): the first pass stages
-    // by ray whatever the tiling, so it runs as it is; a plane gradient then takes the binned scatter over the padded ray sequence.
-    Params P_scatter = P;
-    bool scatter_padded = false, unpadded_first_pass = false;
-    if (need_rays && !staged) {
-        if (route && !strcmp(route, "direct")) return fail(GNERF_E_UNSUPPORTED, "render_backward_rays: GNERF_BWD_SCATTER=direct stages no dX rows");
-        if (want_planes) {
-            if (!binned_shape || int64_t(p->n_items) * pad >= INT32_MAX || (route && !strcmp(route, "sorted")))
+        const char* scatter = getenv("GNERF_BWD_SCATTER"), *kernel = getenv("GNERF_BWD_KERNEL");        // direct | staged | sorted;  wave
+        const char* mlp = getenv("GNERF_BWD_MLP"), *mlp_k1 = getenv("GNERF_BWD_MLP_K1"), *mlp_k2 = getenv("GNERF_BWD_MLP_K2");
+        auto is = [](const char* v, const char* word) { return v && !strcmp(v, word); };
+        const bool force_direct = is(scatter, "direct"), force_sorted = is(scatter, "sorted"), force_staged = is(scatter, "staged");
+        // decoder arithmetic of the piped kernels: chosen on the device like the forward's; GNERF_BWD_MLP=f32|f16x3|auto forces both, _K1 / _K2 one
+        auto mode_of = [&](const char* v, int dflt) { return is(v, "f32") ? GNERF_MLP_F32 : is(v, "f16x3") ? GNERF_MLP_F16X3 : is(v, "auto") ? GNERF_MLP_AUTO : dflt; };
+        route.mlp_first = mode_of(mlp_k1, mode_of(mlp, GNERF_MLP_AUTO));
+        route.mlp_tiles = mode_of(mlp_k2, mode_of(mlp, GNERF_MLP_AUTO));
+        // (F = 0 included: the pipeline's steps and barriers do not depend on the sample counts; a ray without an importance pass shades no
+        //  fine tile, merges nothing and marches its coarse samples)
+        const bool pipe_shape = pipe_tiles_per_wave(P) != 0 && !is(kernel, "wave");
+        const bool rows = g->scatter_stage != nullptr && g->grad_planes_nhwc != nullptr;       // dX rows can be staged, and something reads them
+        const bool whole_tiles = P.tiles_per_item > 0 || p->n_items == 1 || p->rays_per_item % kBwdRaysPerWave == 0;    // no 16-ray tile straddles items
+        const bool binned = binned_scatter_covers(P);
+        const bool can_pad = binned && int64_t(p->n_items) * padded_rays_per_item(*p) < INT32_MAX;
+        // a ragged call stays off the one-wave-per-ray kernel and its float atomics where the piped kernels and the binned scatter cover it
+        route.padded = !whole_tiles && rows && pipe_shape && !force_direct && !force_sorted && can_pad;
+        bool staged = rows && (whole_tiles || route.padded) && !force_direct;
+        // A ray request whose ray tiles straddle items on a route that does not pad them: the one-wave-per-ray kernel stages by ray whatever
+        // the tiling, so it runs on the call as it is; a plane gradient then takes the binned scatter over the padded ray sequence.
+        const bool rows_for_rays = need_rays && !staged;
+        route.scatter_padded = rows_for_rays && want_planes;
+        if (rows_for_rays) {
+            if (force_direct) return fail(GNERF_E_UNSUPPORTED, "render_backward_rays: GNERF_BWD_SCATTER=direct stages no dX rows");
+            if (want_planes && (!can_pad || force_sorted))
                 return fail(GNERF_E_UNSUPPORTED, "render_backward_rays: ray tiles straddle items and the binned scatter does not cover this call");
-            P_scatter.tiles_y = pad;
-            P_scatter.n_tiles = p->n_items * (pad / kBwdRaysPerWave);
-            scatter_padded = true;
+            staged = true;
         }
-        staged = unpadded_first_pass = true;
+        if (force_staged && !staged) return fail(GNERF_E_ARG, "render_backward: the staged scatter needs scatter_stage, a plane gradient and whole tiles per item");
+        const bool exchange = g->scatter_stage != nullptr && g->grad_planes_nhwc == nullptr && n_dec == 4;       // (never a ray request: g_eff above)
+        const bool piped = (staged || exchange) && pipe_shape && !force_direct && !rows_for_rays;
+        route.first = piped ? (staged ? BwdRoute::kPipedRows : BwdRoute::kPipedExchange) : (staged ? BwdRoute::kWaveStaged : BwdRoute::kWaveDirect);
+        // (sorted: the per-ray-tile sort with one atomic per texel and chunk; it also takes the calls the binned form does not cover)
+        route.second = !(staged && want_planes) ? BwdRoute::kNoScatter : (binned && !force_sorted ? BwdRoute::kBinned : BwdRoute::kSorted);
     }
-    if (route && !strcmp(route, "staged") && !staged) return fail(GNERF_E_ARG, "render_backward: the staged scatter needs scatter_stage, a plane gradient and whole tiles per item");
-    // Pipelined path of the staged form (round 4): the ray-level part on the forward pipeline (render_kernel_pipe_bwd), the per-sample
-    // part as a kernel over sample tiles (render_bwd_tiles_kernel).  Shapes the pipelined kernels cover; GNERF_BWD_KERNEL=wave keeps the
-    // one-wave-per-ray kernel (A/B runs and the tests' cross-check).
-    const char* bwd_kernel = getenv("GNERF_BWD_KERNEL");
-    const bool small_planes = int64_t(p->plane_h) * p->plane_w * 3 * 128 < (int64_t(1) << 32);
-    // (a decoder-only request with an exchange buffer -- gnerf_render_backward_exchange_bytes -- takes the same two kernels: no dX rows,
-    // no second pass)
-    const bool exchange_only = g->scatter_stage != nullptr && g->grad_planes_nhwc == nullptr && n_dec == 4;      // (never a ray request: g_eff above)
-    // (round 6: F = 0 too -- the pipeline's steps and barriers do not depend on the sample counts; a ray without an importance pass shades no
-    //  fine tile, merges nothing and marches its coarse samples)
-    const bool piped = (staged || exchange_only) && P.tiles_c <= 9 && P.tiles_f <= 9 && small_planes && !(bwd_kernel && !strcmp(bwd_kernel, "wave"))
-                       && !(route && !strcmp(route, "direct")) && !unpadded_first_pass;
-    if (piped) {
-        hipStream_t s = as_stream(stream);
-        const int64_t total = P.total_rays;
-        const int n_all = p->depth_resolution + p->depth_resolution_importance;
-        // decoder arithmetic of the first pass: chosen on the device from max |planes| like the forward's (measured here into the
-        // 256 bytes behind the staged rows when the caller has none)
-        const int tiles_per_ray = (n_all + 15) / 16;
-        P.bwd_ray_stride = staged ? int64_t(n_all) * 33 : int64_t(n_all) + 32 * tiles_per_ray;
-        P.bwd_tile_pitch = staged ? 512 : 32;
-        P.absmax = p->planes_absmax;
-        if (!P.absmax) {
-            float* own = g->scatter_stage + size_t(total) * P.bwd_ray_stride;
-            if (int e = gnerf_planes_absmax(p->planes_nhwc, int64_t(p->n_items) * 3 * p->plane_h * p->plane_w * 32, own, stream)) return e;
-            P.absmax = own;
-        }
-        P.p.workspace = nullptr;                                   // (the backward's params carry no workspace)
-        // Decoder arithmetic: both kernels choose on the device like the forward (f16 hi/lo products when features, weights and
-        // activations are in f16's range, exact fp32 otherwise).  GNERF_BWD_MLP=f32|f16x3|auto forces both, _K1 / _K2 one of them.
-        P.p.mlp_mode = GNERF_MLP_AUTO;
-        Params P2 = P;
-        auto mode_of = [](const char* v, int dflt) { return !v ? dflt : !strcmp(v, "f32") ? GNERF_MLP_F32 : !strcmp(v, "f16x3") ? GNERF_MLP_F16X3 : !strcmp(v, "auto") ? GNERF_MLP_AUTO : dflt; };
-        P.p.mlp_mode = mode_of(getenv("GNERF_BWD_MLP"), P.p.mlp_mode);
-        P2.p.mlp_mode = mode_of(getenv("GNERF_BWD_MLP"), P2.p.mlp_mode);
-        P.p.mlp_mode = mode_of(getenv("GNERF_BWD_MLP_K1"), P.p.mlp_mode);
-        P2.p.mlp_mode = mode_of(getenv("GNERF_BWD_MLP_K2"), P2.p.mlp_mode);
-        const int pipe_tp = (P.tiles_c <= 3 && P.tiles_f <= 3) ? 1 : ((P.tiles_c <= 6 && P.tiles_f <= 6) ? 2 : 3);
-        const int64_t total_seq = (P.tiles_per_item > 0 || linear_pad(P) > 0) ? int64_t(P.n_tiles) * 16 : total;
-        const int per_cu = pipe_tp == 1 ? GNERF_PIPE_WAVES_PER_SIMD : (pipe_tp == 2 ? GNERF_PIPE2_WAVES_PER_SIMD : 2);
-        const int64_t capacity = int64_t(per_cu) * kNumCU;
-        P.pipe_unit = kPipeUnit;
-        if (total_seq < capacity * kPipeUnit) P.pipe_unit = int((total_seq + capacity - 1) / capacity);
-        int64_t gsz = ((total_seq + P.pipe_unit - 1) / P.pipe_unit + kNumXCD - 1) / kNumXCD * kNumXCD;
-        if (gsz < kNumXCD) gsz = kNumXCD;
-        if (gsz > capacity) gsz = capacity;
-        const size_t lds1 = pipe_lds_floats(pipe_tp, kMlpAuto) * sizeof(float);
-        if (pipe_tp == 1) hipLaunchKernelGGL(render_kernel_pipe_bwd<1>, dim3((unsigned)gsz), dim3(kPipeThreads), lds1, s, P, *g, g->scatter_stage);
-        else if (pipe_tp == 2) hipLaunchKernelGGL(render_kernel_pipe_bwd<2>, dim3((unsigned)gsz), dim3(kPipeThreads), lds1, s, P, *g, g->scatter_stage);
+    // ---- (c) launches
+    hipStream_t s = as_stream(stream);
+    const int n_all = p->depth_resolution + p->depth_resolution_importance;
+    Params K = P;                                            // the first pass's
+    // up to two workgroups of four waves per CU: share tiles until the chip is full (read by the one-wave-per-ray kernel only; every route carries it)
+    while (K.split_shift < 2 && (int64_t(K.n_tiles) << (K.split_shift + 1)) <= int64_t(kNumCU) * 2 * kBwdWaves) K.split_shift++;
+    if (route.padded) pad_ray_sequence(K);
+    if (route.first == BwdRoute::kPipedRows || route.first == BwdRoute::kPipedExchange) {
+        // The ray-level part on the forward pipeline (render_kernel_pipe_bwd), the per-sample part as a kernel over sample tiles
+        // (render_bwd_tiles_kernel).  Floats per ray of the staging / exchange buffer and from one 16-rank tile's block to the next:
+        const bool rows = route.first == BwdRoute::kPipedRows;
+        K.bwd_ray_stride = rows ? int64_t(n_all) * 33 : int64_t(n_all) + 32 * ((n_all + 15) / 16);
+        K.bwd_tile_pitch = rows ? 512 : 32;
+        // (max |planes| goes into the 256 bytes behind the rows when the caller has none)
+        if (int e = absmax_or_measure(p, g->scatter_stage + size_t(P.total_rays) * K.bwd_ray_stride, stream, K.absmax)) return e;
+        K.p.workspace = nullptr;                                   // (the backward's params carry no workspace)
+        K.p.mlp_mode = route.mlp_first;
+        const int tp = pipe_tiles_per_wave(K);
+        const int64_t total_seq = pipe_seq_len(K);
+        const PipeLaunch L = pipe_launch(tp, total_seq);
+        K.pipe_unit = L.unit;
+        const size_t lds1 = pipe_lds_floats(tp, kMlpAuto) * sizeof(float);
+        if (tp == 1) hipLaunchKernelGGL(render_kernel_pipe_bwd<1>, dim3(L.grid), dim3(kPipeThreads), lds1, s, K, *g, g->scatter_stage);
+        else if (tp == 2) hipLaunchKernelGGL(render_kernel_pipe_bwd<2>, dim3(L.grid), dim3(kPipeThreads), lds1, s, K, *g, g->scatter_stage);
         else {
             static PerDeviceOnce once3;
             if (int e = once3.raise_lds(render_kernel_pipe_bwd<3>, "render_backward")) return e;
-            hipLaunchKernelGGL(render_kernel_pipe_bwd<3>, dim3((unsigned)gsz), dim3(kPipeThreads), lds1, s, P, *g, g->scatter_stage);
+            hipLaunchKernelGGL(render_kernel_pipe_bwd<3>, dim3(L.grid), dim3(kPipeThreads), lds1, s, K, *g, g->scatter_stage);
         }
         if (int e = check_launch("render_kernel_pipe_bwd")) return e;
+        Params K2 = K;
+        K2.p.mlp_mode = route.mlp_tiles;
         const size_t lds2 = (bwd_tiles_weight_floats() + kTileWaves * bwd_tiles_wave_floats()) * sizeof(float);
         static PerDeviceOnce once_tiles;
         if (int e = once_tiles.raise_lds(render_bwd_tiles_kernel, "render_backward")) return e;
-        const int64_t sample_tiles = total_seq * ((n_all + 15) / 16);
-        int64_t g2 = (sample_tiles + kTileWaves - 1) / kTileWaves;
+        int64_t g2 = (total_seq * ((n_all + 15) / 16) + kTileWaves - 1) / kTileWaves;
         if (g2 > int64_t(kNumCU) * 2) g2 = int64_t(kNumCU) * 2;    // two workgroups of four waves per CU, each walking a contiguous run of tiles
         g2 = (g2 + kNumXCD - 1) / kNumXCD * kNumXCD;
-        P2.pipe_unit = P.pipe_unit;
-        hipLaunchKernelGGL(render_bwd_tiles_kernel, dim3((unsigned)g2), dim3(kTileThreads), lds2, s, P2, *g, g->scatter_stage);
+        hipLaunchKernelGGL(render_bwd_tiles_kernel, dim3((unsigned)g2), dim3(kTileThreads), lds2, s, K2, *g, g->scatter_stage);
         if (int e = check_launch("render_bwd_tiles_kernel")) return e;
     } else {
-    if (staged) hipLaunchKernelGGL(render_bwd_kernel<true>, dim3(per_xcd * kNumXCD), dim3(kBwdThreads), lds_bytes, as_stream(stream), P, *g, g->scatter_stage);
-    else        hipLaunchKernelGGL(render_bwd_kernel<false>, dim3(per_xcd * kNumXCD), dim3(kBwdThreads), lds_bytes, as_stream(stream), P, *g, static_cast<float*>(nullptr));
-    if (int e = check_launch("render_bwd_kernel")) return e;
+        const int n_blocks = ((K.n_tiles << K.split_shift) + kBwdWaves - 1) / kBwdWaves;
+        const dim3 grid((n_blocks + kNumXCD - 1) / kNumXCD * kNumXCD);
+        if (route.first == BwdRoute::kWaveStaged) hipLaunchKernelGGL(render_bwd_kernel<true>, grid, dim3(kBwdThreads), lds_bytes, s, K, *g, g->scatter_stage);
+        else hipLaunchKernelGGL(render_bwd_kernel<false>, grid, dim3(kBwdThreads), lds_bytes, s, K, *g, static_cast<float*>(nullptr));
+        if (int e = check_launch("render_bwd_kernel")) return e;
     }
     if (need_rays) {
         RayGradArgs R;
         R.planes = p->planes_nhwc; R.origins = p->ray_origins; R.dirs = p->ray_dirs; R.stage = g->scatter_stage;
         R.grad_origins = grad_origins; R.grad_dirs = grad_dirs;
         R.plane_floats = int64_t(3) * p->plane_h * p->plane_w * 32;
-        R.H = p->plane_h; R.W = p->plane_w; R.n_all = p->depth_resolution + p->depth_resolution_importance;
+        R.H = p->plane_h; R.W = p->plane_w; R.n_all = n_all;
         R.rays_per_item = p->rays_per_item; R.total_rays = P.total_rays;
         R.tex_pitch = P.tex_pitch; R.row_pitch = P.row_pitch; R.plane_pitch = P.plane_pitch; R.box_scale = P.box_scale;
         int64_t blocks = (int64_t(P.total_rays) + kRayGradWaves - 1) / kRayGradWaves;
         if (blocks > int64_t(kNumCU) * 8) blocks = int64_t(kNumCU) * 8;          // eight workgroups of four waves per CU, rays by grid stride
-        hipLaunchKernelGGL(render_ray_grad_kernel, dim3((unsigned)blocks), dim3(kRayGradThreads), 0, as_stream(stream), R);
+        hipLaunchKernelGGL(render_ray_grad_kernel, dim3((unsigned)blocks), dim3(kRayGradThreads), 0, s, R);
         if (int e = check_launch("render_ray_grad_kernel")) return e;
-        if (!want_planes) return GNERF_OK;
-        if (scatter_padded) P = P_scatter;
     }
-    // Second pass of the staged form.  Round 5: bin the rows by plane tile and sum each tile in LDS (scatter_binned.inl: no global float
-    // atomics, bit-reproducible); GNERF_BWD_SCATTER=sorted keeps round 2's per-ray-tile sort with one atomic per texel and chunk
-    // (plane_scatter_kernel), which also takes the calls the binned form does not cover.
-    if (staged) {
-        const int n_all_s = p->depth_resolution + p->depth_resolution_importance;
-        P.bwd_ray_stride = int64_t(n_all_s) * 33;
-        const bool binned_ok = int64_t(P.total_rays) * n_all_s * 33 < (int64_t(1) << 32) &&
-                               (2 * size_t(3) * ((p->plane_h + kBinTile - 1) / kBinTile) * ((p->plane_w + kBinTile - 1) / kBinTile) + 128) * 4 <= 150 * 1024;
-        if (binned_ok && !(route && !strcmp(route, "sorted"))) {
-            char* ws = reinterpret_cast<char*>(g->scatter_stage) + bin_workspace_offset(P.total_rays, n_all_s);
-            return launch_binned_scatter(P, g->scatter_stage, ws, g->grad_planes_nhwc, as_stream(stream));
-        }
-        static PerDeviceOnce once_scatter;
-        if (int e = once_scatter.raise_lds(plane_scatter_kernel, "render_backward")) return e;
-        hipLaunchKernelGGL(plane_scatter_kernel, dim3(P.n_tiles), dim3(kScatterThreads), scatter_lds_floats() * sizeof(float), as_stream(stream),
-                           P, static_cast<const float*>(g->scatter_stage), g->grad_planes_nhwc);
-        return check_launch("plane_scatter_kernel");
+    if (route.second == BwdRoute::kNoScatter) return GNERF_OK;
+    Params KS = K;                                           // the scatter's
+    if (route.scatter_padded) pad_ray_sequence(KS);
+    KS.bwd_ray_stride = int64_t(n_all) * 33;
+    if (route.second == BwdRoute::kBinned) {
+        char* ws = reinterpret_cast<char*>(g->scatter_stage) + bin_workspace_offset(P.total_rays, n_all);
+        return launch_binned_scatter(KS, g->scatter_stage, ws, g->grad_planes_nhwc, s);
     }
-    return GNERF_OK;
+    static PerDeviceOnce once_scatter;
+    if (int e = once_scatter.raise_lds(plane_scatter_kernel, "render_backward")) return e;
+    hipLaunchKernelGGL(plane_scatter_kernel, dim3(KS.n_tiles), dim3(kScatterThreads), scatter_lds_floats() * sizeof(float), s,
+                       KS, static_cast<const float*>(g->scatter_stage), g->grad_planes_nhwc);
+    return check_launch("plane_scatter_kernel");
 }
 
 extern "C" int gnerf_render_backward(const gnerf_render_params* p, const gnerf_render_grads* g, gnerf_stream_t stream) {
@@ -1237,26 +1248,38 @@ extern "C" size_t gnerf_render_backward_exchange_bytes(const gnerf_render_params
 // The three point-query kernels index pts[idx * 3 + k] and 16 * t + j in int.  The largest n_points for which neither overflows
 // (include/gnerf_hip.h states it); checked before anything else of the call, the pointers included.
 constexpr int kMaxQueryPoints = (INT32_MAX - 15) / 3;
-#define GNERF_CHECK_QUERY_POINTS(name_) \
-    if (n_points > kMaxQueryPoints) return gnerf::fail(GNERF_E_ARG, name_ ": too many points (n_points %d > %d)", n_points, kMaxQueryPoints)
+
+// What the three point-query entry points open with: the n_points cap, the planes and decoder as render params (check_common), the
+// derived fields the kernels read and the tile counts.  `tiles` may still exceed int: the entries refuse that after their own checks.
+static int fill_query(const char* name, const float* planes_nhwc, int n_items, int plane_h, int plane_w, int n_points, float box_warp,
+                      const float* w1, const float* b1, const float* w2, const float* b2, int planes_interleaved,
+                      Params& P, int& tiles_per_item, int64_t& tiles) {
+    if (n_points > kMaxQueryPoints) return gnerf::fail(GNERF_E_ARG, "%s: too many points (n_points %d > %d)", name, n_points, kMaxQueryPoints);
+    P = Params{};
+    gnerf_render_params& p = P.p;
+    p.planes_interleaved = planes_interleaved;
+    p.planes_nhwc = planes_nhwc; p.n_items = n_items; p.plane_h = plane_h; p.plane_w = plane_w;
+    p.w1 = w1; p.b1 = b1; p.w2 = w2; p.b2 = b2; p.box_warp = box_warp;
+    if (int e = check_common(&p)) return e;
+    P.box_scale = float(2.0 / double(box_warp));
+    fill_pitches(P);
+    tiles_per_item = (n_points + 15) / 16;
+    tiles = int64_t(n_items) * tiles_per_item;
+    return GNERF_OK;
+}
 
 extern "C" int gnerf_query_points(const float* planes_nhwc, int n_items, int plane_h, int plane_w,
                                   const float* points, int n_points, float box_warp,
                                   const float* w1, const float* b1, const float* w2, const float* b2,
                                   float* out_sigma, float* out_rgb, int planes_interleaved, gnerf_stream_t stream) {
     using namespace gnerf;
-    GNERF_CHECK_QUERY_POINTS("query_points");
-    gnerf_render_params p = {};
-    p.planes_interleaved = planes_interleaved;
-    p.planes_nhwc = planes_nhwc; p.n_items = n_items; p.plane_h = plane_h; p.plane_w = plane_w;
-    p.w1 = w1; p.b1 = b1; p.w2 = w2; p.b2 = b2; p.box_warp = box_warp;
-    if (int e = check_common(&p)) return e;
+    Params P; int tiles_per_item; int64_t tiles;
+    if (int e = fill_query("query_points", planes_nhwc, n_items, plane_h, plane_w, n_points, box_warp, w1, b1, w2, b2, planes_interleaved, P, tiles_per_item, tiles)) return e;
     if (!points || !out_sigma) return fail(GNERF_E_ARG, "query_points: null pointer");
     if (n_points < 1) return fail(GNERF_E_ARG, "query_points: n_points must be positive");
-    const int64_t tiles = int64_t(n_items) * ((n_points + 15) / 16);
     if (tiles > INT32_MAX) return fail(GNERF_E_ARG, "query_points: too many points");
     const int blocks = int(tiles < int64_t(kNumCU) * 16 ? tiles : int64_t(kNumCU) * 16);
-    hipLaunchKernelGGL(query_kernel, dim3(blocks), dim3(64), 0, as_stream(stream), p, float(2.0 / double(box_warp)), n_points, int(tiles),
+    hipLaunchKernelGGL(query_kernel, dim3(blocks), dim3(64), 0, as_stream(stream), P.p, P.box_scale, n_points, int(tiles),
                        points, out_sigma, out_rgb);
     return check_launch("query_kernel");
 }
@@ -1268,27 +1291,18 @@ extern "C" int gnerf_query_points_backward(const float* planes_nhwc, int n_items
                                            float* grad_planes_nhwc, float* grad_w1, float* grad_b1, float* grad_w2, float* grad_b2,
                                            int planes_interleaved, gnerf_stream_t stream) {
     using namespace gnerf;
-    GNERF_CHECK_QUERY_POINTS("query_points_backward");
-    Params P = {};
-    gnerf_render_params& p = P.p;
-    p.planes_interleaved = planes_interleaved;
-    p.planes_nhwc = planes_nhwc; p.n_items = n_items; p.plane_h = plane_h; p.plane_w = plane_w;
-    p.w1 = w1; p.b1 = b1; p.w2 = w2; p.b2 = b2; p.box_warp = box_warp;
-    if (int e = check_common(&p)) return e;
+    Params P; int tiles_per_item; int64_t tiles;
+    if (int e = fill_query("query_points_backward", planes_nhwc, n_items, plane_h, plane_w, n_points, box_warp, w1, b1, w2, b2, planes_interleaved, P, tiles_per_item, tiles)) return e;
     if (!points) return fail(GNERF_E_ARG, "query_points_backward: points is null");
     if (n_points < 1) return fail(GNERF_E_ARG, "query_points_backward: n_points must be positive");
     const int n_dec = (grad_w1 != nullptr) + (grad_b1 != nullptr) + (grad_w2 != nullptr) + (grad_b2 != nullptr);
     if (n_dec != 0 && n_dec != 4) return fail(GNERF_E_ARG, "query_points_backward: the four decoder gradients are given together or not at all");
     if ((!grad_planes_nhwc && n_dec == 0) || (!grad_sigma && !grad_rgb)) return GNERF_OK;
-    if (!(int64_t(plane_h) * plane_w * 3 * 128 < (int64_t(1) << 32))) return fail(GNERF_E_UNSUPPORTED, "query_points_backward: planes too large for 32-bit tap offsets");
-    P.box_scale = float(2.0 / double(box_warp));
-    fill_pitches(P);
+    if (!planes_fit_32bit_taps(&P.p)) return fail(GNERF_E_UNSUPPORTED, "query_points_backward: planes too large for 32-bit tap offsets");
+    if (tiles > INT32_MAX) return fail(GNERF_E_ARG, "query_points_backward: too many points");
     QueryBwdArgs Q;
     Q.points = points; Q.grad_sigma = grad_sigma; Q.grad_rgb = grad_rgb; Q.n_points = n_points;
-    Q.tiles_per_item = (n_points + 15) / 16;
-    const int64_t tiles = int64_t(n_items) * Q.tiles_per_item;
-    if (tiles > INT32_MAX) return fail(GNERF_E_ARG, "query_points_backward: too many points");
-    Q.n_tiles = int(tiles);
+    Q.tiles_per_item = tiles_per_item; Q.n_tiles = int(tiles);
     Q.grad_planes_nhwc = grad_planes_nhwc; Q.grad_w1 = grad_w1; Q.grad_b1 = grad_b1; Q.grad_w2 = grad_w2; Q.grad_b2 = grad_b2;
     const size_t lds_bytes = (kBwdWeightFloats + kBwdWaves * bwd_wave_floats(0)) * sizeof(float);
     int64_t blocks = (tiles + kBwdWaves - 1) / kBwdWaves;
@@ -1303,25 +1317,16 @@ extern "C" int gnerf_query_points_grad(const float* planes_nhwc, int n_items, in
                                        const float* grad_sigma, const float* grad_rgb, float* grad_points,
                                        int planes_interleaved, gnerf_stream_t stream) {
     using namespace gnerf;
-    GNERF_CHECK_QUERY_POINTS("query_points_grad");
-    Params P = {};
-    gnerf_render_params& p = P.p;
-    p.planes_interleaved = planes_interleaved;
-    p.planes_nhwc = planes_nhwc; p.n_items = n_items; p.plane_h = plane_h; p.plane_w = plane_w;
-    p.w1 = w1; p.b1 = b1; p.w2 = w2; p.b2 = b2; p.box_warp = box_warp;
-    if (int e = check_common(&p)) return e;
+    Params P; int tiles_per_item; int64_t tiles;
+    if (int e = fill_query("query_points_grad", planes_nhwc, n_items, plane_h, plane_w, n_points, box_warp, w1, b1, w2, b2, planes_interleaved, P, tiles_per_item, tiles)) return e;
     if (!points || !grad_points) return fail(GNERF_E_ARG, "query_points_grad: null pointer");
     if (n_points < 1) return fail(GNERF_E_ARG, "query_points_grad: n_points must be positive");
     if (!grad_sigma && !grad_rgb) return fail(GNERF_E_ARG, "query_points_grad: grad_sigma and grad_rgb are both null");
-    if (!(int64_t(plane_h) * plane_w * 3 * 128 < (int64_t(1) << 32))) return fail(GNERF_E_UNSUPPORTED, "query_points_grad: planes too large for 32-bit tap offsets");
-    P.box_scale = float(2.0 / double(box_warp));
-    fill_pitches(P);
+    if (!planes_fit_32bit_taps(&P.p)) return fail(GNERF_E_UNSUPPORTED, "query_points_grad: planes too large for 32-bit tap offsets");
+    if (tiles > INT32_MAX) return fail(GNERF_E_ARG, "query_points_grad: too many points");
     QueryGradArgs Q;
     Q.points = points; Q.grad_sigma = grad_sigma; Q.grad_rgb = grad_rgb; Q.grad_points = grad_points; Q.n_points = n_points;
-    Q.tiles_per_item = (n_points + 15) / 16;
-    const int64_t tiles = int64_t(n_items) * Q.tiles_per_item;
-    if (tiles > INT32_MAX) return fail(GNERF_E_ARG, "query_points_grad: too many points");
-    Q.n_tiles = int(tiles);
+    Q.tiles_per_item = tiles_per_item; Q.n_tiles = int(tiles);
     const size_t lds_bytes = (kBwdWeightFloats + kBwdWaves * query_grad_wave_floats()) * sizeof(float);         // 49.3 KB: three workgroups per CU (the kernel is compiled for three waves per SIMD)
     int64_t blocks = (tiles + kBwdWaves - 1) / kBwdWaves;
     if (blocks > int64_t(kNumCU) * 3) blocks = int64_t(kNumCU) * 3;
