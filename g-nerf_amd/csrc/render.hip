@@ -79,6 +79,7 @@ struct Params {
     // next (33 n_all and 512 when the blocks are the dX rows of the staged scatter; n_all + 32 tiles and 32 for a decoder-only request)
     int64_t bwd_ray_stride;
     int bwd_tile_pitch;
+    const float* decoder_pack;      // pipelined forward: what gnerf_render_pack_decoder made of this call's decoder (statistics + LDS images, render_shade.inl), or null
 };
 __host__ __device__ __forceinline__ int linear_pad(const Params& P) { return P.tiles_per_item == 0 ? P.tiles_y : 0; }
 
@@ -715,7 +716,10 @@ __global__ __launch_bounds__(64) void query_kernel(gnerf_render_params p, float 
 }
 
 // ---- GNERF_MLP_AUTO: which decoder arithmetic may this call use?  Evaluated by every workgroup of the pipelined kernels before
-// it stages the decoder (one wave, a few hundred loads from L2, ~0.1 % of a workgroup's work): no separate launch.
+// it stages the decoder: no separate launch.  Not free, though: stamped (profiles/r14_wg_prologue.json), a workgroup's way from its start to
+// its first shader tile -- this choice, the decoder's way into LDS, the first ray's proposals -- took 12.0 us of a 486 us life at config 2
+// (2.5 %, where a comment here used to say "~0.1 %") and 11.4 of 87 us on a 64x64 frame at 96+96.  With a decoder pack (below) it takes
+// 3.4 and 3.0 us.  Without one (plain C ABI callers, the backward) everything runs as it did.
 // The f16 hi/lo split (render_shade.inl) represents an operand v as hi + lo with |v - hi - lo| <= max(2^-22 |v|, 2^-25): fp32-grade
 // for operands well inside f16's range, but an ABSOLUTE 2^-25 per operand once the low half goes subnormal, and inf/NaN once the high
 // half overflows.  With A = max |planes| (the features are convex combinations of texels, so |x| <= A), W1' = log2(e) W1 and the
@@ -734,13 +738,97 @@ constexpr float kMlpErrLimit = 1.0f / 4096.f;
 // hidden activation -- while no base-2 pre-activation can reach exp2's overflow: |p'| <= max_r ||W1'[r,:]||_1 A + max |b1'| <= 99
 // (config 2: 37; on a random-init generator's planes: 57).  Beyond that the body keeps the form that is safe for any p'.
 constexpr float kSoftplusDirectLimit = 100.f;
+// The decision is made from eight statistics of the decoder and max |planes|.  The statistics depend on the decoder alone: a decoder pack
+// (gnerf_render_pack_decoder, below) holds them ready-made, next to the two LDS images of the weights; without a pack every workgroup
+// reduces them itself (choose_mlp, as it always has).  Either way mlp_decide evaluates the same inequalities on the same numbers.
+constexpr int kStatL1 = 0, kStatSq1 = 1, kStatMx1 = 2, kStatSq2 = 3, kStatMx2 = 4, kStatMb1 = 5, kStatMb2 = 6, kStatBad = 7, kStatBad2 = 8;
+constexpr int kStatFloats = 16;         // the pack's first 64 bytes ([kStatBad]: an int, either wave's flag); in the pack kernel, the LDS words in front of decoder_stats' rows
+struct DecoderStats { float l1, sq1, mx1, sq2, mx2, mb1, mb2; bool bad; };
+__device__ __forceinline__ void mlp_decide(const DecoderStats& s, float A, int& choice, int& direct) {
+    const float R1 = sqrtf(s.sq1), R2 = sqrtf(s.sq2);
+    const float h_hard = s.l1 * A + s.mb1 + 1.f;
+    const float e_p = 0x1p-22f * R1 * A + 0x1p-25f * (R1 + 5.657f * A);
+    const float h = R1 * A + s.mb1 + 1.f;
+    const float e_o = R2 * e_p + 0x1p-22f * R2 * h + 0x1p-25f * (R2 + 8.f * h);
+    const bool ok = !s.bad && A <= kMlpRangeLimit && s.mx1 <= kMlpRangeLimit && s.mx2 <= kMlpRangeLimit && h_hard <= kMlpRangeLimit
+                    && s.mb2 <= kMlpRangeLimit && e_o <= kMlpErrLimit;         // every comparison is false for NaN
+    choice = ok ? 1 : 2;                                                       // kMlpF16x3 : kMlpF32
+    direct = (ok && h_hard <= kSoftplusDirectLimit) ? 1 : 0;
+}
+// The per-row sums, ONE copy for choose_mlp and for the pack kernel: a lane sums its row in column order with every operation pinned --
+// the scaling a multiply of its own, the L1 sum plain adds, the squares fused -- so that no contraction can make two call sites round
+// differently (tests/decoder_pack_ref.py restates exactly this; the GPU test compares the pack's statistics with it bit for bit).
+constexpr int kStatP1 = 33, kStatP2 = 65;      // LDS pitches of the staged rows (odd: the row sums are conflict-free)
+__device__ __forceinline__ void w1_row_stats(const float* s1, int row, float& l1, float& sq1, float& mx1) {
+    constexpr float kL2e = 1.44269504088896341f;
+    l1 = 0.f; sq1 = 0.f; mx1 = 0.f;
+#pragma unroll 8
+    for (int c = 0; c < 32; c++) { const float w = __fmul_rn(fabsf(s1[row * kStatP1 + c]), kL2e); l1 = __fadd_rn(l1, w); sq1 = __fmaf_rn(w, w, sq1); mx1 = fmaxf(mx1, w); }
+}
+__device__ __forceinline__ void w2_row_stats(const float* s2, int row, float& sq2, float& mx2) {
+#pragma unroll 8
+    for (int c = 0; c < 64; c++) { const float w = fabsf(s2[row * kStatP2 + c]); sq2 = __fmaf_rn(w, w, sq2); mx2 = fmaxf(mx2, w); }
+}
+__device__ __forceinline__ float bias_stat(float b) { return __fmul_rn(fabsf(b), 1.44269504088896341f); }
+// The pack kernel's reduction: the eight statistics into smem[0 .. kStatFloats) (all threads of a workgroup of at least two waves; a barrier
+// must follow before they are read).  Wave 0 sums the rows of W1, wave 1 the rows of W2, side by side, with the routines choose_mlp's one
+// wave uses; the maxima over the rows do not depend on an order.
+__device__ __forceinline__ void decoder_stats(const gnerf_render_params& p, float* smem) {
+    constexpr int kP1 = kStatP1, kP2 = kStatP2;
+    float* s1 = smem + kStatFloats;
+    float* s2 = s1 + 64 * kP1;
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    float mb = 0.f;
+    if (wave == 0) mb = bias_stat(p.b1[lane]);
+    else if (wave == 1 && lane < 33) mb = bias_stat(p.b2[lane]);
+    for (int i = threadIdx.x; i < 64 * 32; i += blockDim.x) s1[(i >> 5) * kP1 + (i & 31)] = p.w1[i];
+    for (int i = threadIdx.x; i < 33 * 64; i += blockDim.x) s2[(i >> 6) * kP2 + (i & 63)] = p.w2[i];
+    __syncthreads();
+    if (wave == 0) {                // lane r: row r of W1
+        float l1, sq1, mx1;
+        w1_row_stats(s1, lane, l1, sq1, mx1);
+        // NaN-propagating maxima: fmaxf drops NaNs, so carry "anything not finite" separately
+        bool bad = !(l1 < INFINITY) || !(mb < INFINITY);
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            l1 = fmaxf(l1, __shfl_xor(l1, o)); sq1 = fmaxf(sq1, __shfl_xor(sq1, o)); mx1 = fmaxf(mx1, __shfl_xor(mx1, o));
+            mb = fmaxf(mb, __shfl_xor(mb, o));
+        }
+        bad = __any(bad);
+        if (lane == 0) { smem[kStatL1] = l1; smem[kStatSq1] = sq1; smem[kStatMx1] = mx1; smem[kStatMb1] = mb; reinterpret_cast<int*>(smem)[kStatBad] = bad ? 1 : 0; }
+    } else if (wave == 1) {         // lane r < 33: row r of W2
+        float sq2 = 0.f, mx2 = 0.f;
+        if (lane < 33) w2_row_stats(s2, lane, sq2, mx2);
+        bool bad = !(sq2 < INFINITY) || !(mb < INFINITY);
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            sq2 = fmaxf(sq2, __shfl_xor(sq2, o)); mx2 = fmaxf(mx2, __shfl_xor(mx2, o)); mb = fmaxf(mb, __shfl_xor(mb, o));
+        }
+        bad = __any(bad);
+        if (lane == 0) { smem[kStatSq2] = sq2; smem[kStatMx2] = mx2; smem[kStatMb2] = mb; reinterpret_cast<int*>(smem)[kStatBad2] = bad ? 1 : 0; }
+    }
+}
+// `stats`: the kStatFloats words at the head of a pack (wave-uniform loads); every thread evaluates the decision for itself.
+__device__ __forceinline__ int mlp_choice_from(const float* stats, float A, bool* softplus_direct) {
+    DecoderStats s;
+    s.l1 = stats[kStatL1]; s.sq1 = stats[kStatSq1]; s.mx1 = stats[kStatMx1]; s.sq2 = stats[kStatSq2]; s.mx2 = stats[kStatMx2];
+    s.mb1 = stats[kStatMb1]; s.mb2 = stats[kStatMb2];
+    const int* flags = reinterpret_cast<const int*>(stats);
+    s.bad = flags[kStatBad] != 0;
+    int choice, direct;
+    mlp_decide(s, A, choice, direct);
+    if (softplus_direct) *softplus_direct = __builtin_amdgcn_readfirstlane(direct) != 0;
+    return __builtin_amdgcn_readfirstlane(choice);
+}
+__device__ __forceinline__ void note_mlp_choice(const Params& P, int choice) {         // diagnostics (gnerf_hip.last_mlp_choice)
+    if (blockIdx.x == 0 && threadIdx.x == 0 && P.p.workspace) static_cast<int*>(P.p.workspace)[4] = choice;
+}
 __device__ __forceinline__ int choose_mlp(const Params& P, float* smem, bool* softplus_direct = nullptr) {
     const gnerf_render_params& p = P.p;
-    constexpr float kL2e = 1.44269504088896341f;
     // the decoder into LDS with coalesced loads (rows padded to an odd pitch: the row sums below are conflict-free); a first
     // version read the rows straight from global memory, one row per lane -- 96 uncoalesced load instructions in front of every
     // workgroup's first ray cost 40 us per launch
-    constexpr int kP1 = 33, kP2 = 65;
+    constexpr int kP1 = kStatP1, kP2 = kStatP2;
     float* s1 = smem + 4;
     float* s2 = s1 + 64 * kP1;
     for (int i = threadIdx.x; i < 64 * 32; i += blockDim.x) s1[(i >> 5) * kP1 + (i & 31)] = p.w1[i];
@@ -749,16 +837,12 @@ __device__ __forceinline__ int choose_mlp(const Params& P, float* smem, bool* so
     if (threadIdx.x < 64) {
         const int lane = threadIdx.x;
         // lane r < 64: row r of W1; lane r < 33: row r of W2
-        float l1 = 0.f, sq1 = 0.f, mx1 = 0.f;
-#pragma unroll 8
-        for (int c = 0; c < 32; c++) { const float w = fabsf(s1[lane * kP1 + c]) * kL2e; l1 += w; sq1 = fmaf(w, w, sq1); mx1 = fmaxf(mx1, w); }
+        float l1, sq1, mx1;
+        w1_row_stats(s1, lane, l1, sq1, mx1);
         float sq2 = 0.f, mx2 = 0.f;
-        if (lane < 33) {
-#pragma unroll 8
-            for (int c = 0; c < 64; c++) { const float w = fabsf(s2[lane * kP2 + c]); sq2 = fmaf(w, w, sq2); mx2 = fmaxf(mx2, w); }
-        }
-        float mb1 = fabsf(p.b1[lane]) * kL2e;
-        float mb2 = lane < 33 ? fabsf(p.b2[lane]) * kL2e : 0.f;
+        if (lane < 33) w2_row_stats(s2, lane, sq2, mx2);
+        float mb1 = bias_stat(p.b1[lane]);
+        float mb2 = lane < 33 ? bias_stat(p.b2[lane]) : 0.f;
         // NaN-propagating maxima: fmaxf drops NaNs, so carry "anything not finite" separately
         bool bad = !(l1 < INFINITY) || !(sq2 < INFINITY) || !(mb1 < INFINITY) || !(mb2 < INFINITY);
 #pragma unroll
@@ -769,17 +853,12 @@ __device__ __forceinline__ int choose_mlp(const Params& P, float* smem, bool* so
         }
         bad = __any(bad);
         if (lane == 0) {
-            const float A = *P.absmax;
-            const float R1 = sqrtf(sq1), R2 = sqrtf(sq2);
-            const float h_hard = l1 * A + mb1 + 1.f;
-            const float e_p = 0x1p-22f * R1 * A + 0x1p-25f * (R1 + 5.657f * A);
-            const float h = R1 * A + mb1 + 1.f;
-            const float e_o = R2 * e_p + 0x1p-22f * R2 * h + 0x1p-25f * (R2 + 8.f * h);
-            const bool ok = !bad && A <= kMlpRangeLimit && mx1 <= kMlpRangeLimit && mx2 <= kMlpRangeLimit && h_hard <= kMlpRangeLimit
-                            && mb2 <= kMlpRangeLimit && e_o <= kMlpErrLimit;         // every comparison is false for NaN
-            const int choice = ok ? 1 : 2;                                           // kMlpF16x3 : kMlpF32
+            DecoderStats s;
+            s.l1 = l1; s.sq1 = sq1; s.mx1 = mx1; s.sq2 = sq2; s.mx2 = mx2; s.mb1 = mb1; s.mb2 = mb2; s.bad = bad;
+            int choice, direct;
+            mlp_decide(s, *P.absmax, choice, direct);
             reinterpret_cast<int*>(smem)[0] = choice;
-            reinterpret_cast<int*>(smem)[1] = (ok && h_hard <= kSoftplusDirectLimit) ? 1 : 0;
+            reinterpret_cast<int*>(smem)[1] = direct;
             if (blockIdx.x == 0 && p.workspace) static_cast<int*>(p.workspace)[4] = choice;         // diagnostics (gnerf_hip.last_mlp_choice)
         }
     }
@@ -787,6 +866,12 @@ __device__ __forceinline__ int choose_mlp(const Params& P, float* smem, bool* so
     const int choice = __builtin_amdgcn_readfirstlane(reinterpret_cast<const int*>(smem)[0]);
     if (softplus_direct) *softplus_direct = __builtin_amdgcn_readfirstlane(reinterpret_cast<const int*>(smem)[1]) != 0;
     __syncthreads();                                     // smem is the body's from here on
+    return choice;
+}
+// With a decoder pack there is nothing to stage or reduce: nine wave-uniform words and the inequalities, no LDS, no barrier.
+__device__ __forceinline__ int choose_mlp_packed(const Params& P, bool* softplus_direct) {
+    const int choice = mlp_choice_from(P.decoder_pack, *P.absmax, softplus_direct);
+    note_mlp_choice(P, choice);
     return choice;
 }
 
@@ -868,6 +953,7 @@ static int fill_params(const gnerf_render_params* p, Params& P) {
     P.deal_counters = nullptr;
     P.pipe_guided = 0;
     P.absmax = nullptr;
+    P.decoder_pack = nullptr;
     P.draw_c = P.draw_f = TorchRandDraw{};
     P.draw_item_ctr = 0;
     if (p->rng_mode == GNERF_RNG_TORCH_PHILOX) {
@@ -960,10 +1046,13 @@ static int launch_pipe(int mlp, unsigned grid, hipStream_t s, const Params& P) {
     return gnerf::check_launch("render_kernel_pipe");
 }
 
-extern "C" int gnerf_render_forward(const gnerf_render_params* p, gnerf_stream_t stream) {
+// gnerf_render_forward (pack = null) and gnerf_render_forward_packed.  Only the pipelined kernels read a pack; the generic kernel loads its
+// weight fragments into registers as it always has.
+static int render_forward_impl(const gnerf_render_params* p, const void* pack, gnerf_stream_t stream) {
     using namespace gnerf;
     Params P;
     if (int e = fill_params(p, P)) return e;
+    P.decoder_pack = static_cast<const float*>(pack);
     if (!p->out_rgb || !p->out_depth || !p->out_wsum || !p->workspace)
         return fail(GNERF_E_ARG, "render: outputs and workspace must not be null");
     const int S = p->depth_resolution, F = p->depth_resolution_importance;
@@ -1060,6 +1149,26 @@ extern "C" int gnerf_render_forward(const gnerf_render_params* p, gnerf_stream_t
     hipLaunchKernelGGL(clamp_depth_kernel, dim3((unsigned)((total + 256 * kClampPerThread - 1) / (256 * kClampPerThread))), dim3(256), 0, s,
                        p->out_depth, static_cast<unsigned*>(p->workspace), total, p->rays_per_item, p->depth_clamp_per_item ? p->n_items : 0);
     return check_launch("clamp_depth_kernel");
+}
+
+extern "C" int gnerf_render_forward(const gnerf_render_params* p, gnerf_stream_t stream) { return render_forward_impl(p, nullptr, stream); }
+
+extern "C" int gnerf_render_forward_packed(const gnerf_render_params* p, const void* pack, gnerf_stream_t stream) {
+    if (!pack) return gnerf::fail(GNERF_E_ARG, "render_forward_packed: pack is null (gnerf_render_forward is that call)");
+    if (reinterpret_cast<uintptr_t>(pack) % 16 != 0) return gnerf::fail(GNERF_E_ARG, "render_forward_packed: pack must be 16-byte aligned");
+    return render_forward_impl(p, pack, stream);
+}
+
+extern "C" size_t gnerf_render_decoder_pack_bytes(void) { return size_t(kPackFloats) * sizeof(float); }
+
+extern "C" int gnerf_render_pack_decoder(const float* w1, const float* b1, const float* w2, const float* b2, void* pack, gnerf_stream_t stream) {
+    using namespace gnerf;
+    if (!w1 || !b1 || !w2 || !b2 || !pack) return fail(GNERF_E_ARG, "render_pack_decoder: null pointer");
+    if (reinterpret_cast<uintptr_t>(pack) % 16 != 0) return fail(GNERF_E_ARG, "render_pack_decoder: pack must be 16-byte aligned");
+    gnerf_render_params p = {};
+    p.w1 = w1; p.b1 = b1; p.w2 = w2; p.b2 = b2;
+    hipLaunchKernelGGL(pack_decoder_kernel, dim3(1), dim3(kPipeThreads), 0, as_stream(stream), p, static_cast<float*>(pack));
+    return check_launch("pack_decoder_kernel");
 }
 
 // What one backward call launches: decided once in render_backward_impl, then only read (DESIGN.md 3.2 has the table of routes).

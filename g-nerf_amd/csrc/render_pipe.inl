@@ -132,7 +132,8 @@ __device__ __forceinline__ int pipe_seq_to_ray(const Params& P, int64_t seq) {
 // q = sum_c dL/dcolour[c] colour[c] (all the composite's gradient needs of them); the scalar wave runs the composite's gradient
 // (ray_marcher.py:25-57 backwards) as wave scans right after the merge.  Nothing else of the ray is kept.
 template <int TP, int MLP, bool FULL, bool GEN, bool BWD = false>
-__device__ __forceinline__ void render_pipe_body(const Params& P, float* smem, const gnerf_render_grads* Gr = nullptr, float* bstage = nullptr, bool sp_direct = false) {
+__device__ __forceinline__ void render_pipe_body(const Params& P, float* smem, const gnerf_render_grads* Gr = nullptr, float* bstage = nullptr, bool sp_direct = false,
+                                                 unsigned long long wg_start = 0, const DecoderImage<MLP == kMlpF32 ? kMlpF32 : kMlpF16x3, 256>* early_image = nullptr) {
     typedef PipeDims<TP> D;
     constexpr int kPipeMaxS = D::kMaxS, kPipeSPad = D::kSPad, kSlotFloats = D::kSlotFloats, RND = D::kRounds;
     const gnerf_render_params& p = P.p;
@@ -189,9 +190,8 @@ __device__ __forceinline__ void render_pipe_body(const Params& P, float* smem, c
     int upos = 0;                                               // scalar wave: position of the next proposed ray inside its unit (deal.len: a new unit)
 
 #ifdef GNERF_WG_STAMPS
-    const unsigned long long wg_t0 = __builtin_amdgcn_s_memrealtime();       // this workgroup's start, 100 MHz ticks (tools/wg_lifetimes.py)
+    const unsigned long long wg_t0 = wg_start;       // this workgroup's start (taken by the kernel, in front of choose_mlp), 100 MHz ticks (tools/wg_lifetimes.py)
 #endif
-    stage_decoder<MLP>(L, smem, p, tid, kPipeThreads);
 
     Stamps st;
     // ------------------------------------------------------------------ scalar-wave pieces (lambdas, wave 3 only)
@@ -736,13 +736,41 @@ __device__ __forceinline__ void render_pipe_body(const Params& P, float* smem, c
     // The scalar wave is one instruction stream against three, shares its SIMD's issue port with MFMA-heavy shader
     // waves, and every step ends when it does: give it issue priority (costs the shaders little, it is mostly waiting
     // on LDS round trips).
-    if (wv == 3) __builtin_amdgcn_s_setprio(GNERF_SCALAR_PRIO);
-    __syncthreads();                                            // weights are in LDS
-    if (wv == 3) {
-        if (dyn && lane == 0) *nr_word = nr;
-        propose_issue(0); propose_finish(0);
+    bool packed = false;
+    if constexpr (!BWD) packed = P.decoder_pack != nullptr;     // (uniform over the launch; the backward stages as it always has)
+    if (packed) {
+        // The head with a decoder pack.  The proposals of ray 0 need nothing of the decoder: the scalar wave starts their loads first, so
+        // that their round trip runs beside the one round of 16-byte copies that brings the image gnerf_render_pack_decoder made into
+        // LDS, and ONE barrier publishes the weights, ray 0's slot and the run's length.
+        if (wv == 3) {
+            __builtin_amdgcn_s_setprio(GNERF_SCALAR_PRIO);
+            if (dyn && lane == 0) *nr_word = nr;
+            propose_issue(0);
+        }
+        decoder_lds<MLP>(L, smem);
+        if (early_image) {                                      // (a compile-time fact after inlining: the kernel started these loads at its top)
+            early_image->store(smem, tid);
+        } else {
+            DecoderImage<MLP, kPipeThreads> image;
+            image.load(P.decoder_pack, tid);
+            image.store(smem, tid);
+        }
+        if (wv == 3) propose_finish(0);
+        __syncthreads();                                        // weights, ray 0 and the run's length are in LDS
+    } else {
+        // Without one (plain C ABI callers, the backward): as it always was
+        stage_decoder<MLP>(L, smem, p, tid, kPipeThreads);
+        if (wv == 3) __builtin_amdgcn_s_setprio(GNERF_SCALAR_PRIO);
+        __syncthreads();                                        // weights are in LDS
+        if (wv == 3) {
+            if (dyn && lane == 0) *nr_word = nr;
+            propose_issue(0); propose_finish(0);
+        }
+        __syncthreads();
     }
-    __syncthreads();
+#ifdef GNERF_WG_STAMPS
+    const unsigned long long wg_t1 = __builtin_amdgcn_s_memrealtime();       // the head is over: the first shader tile starts here
+#endif
     auto refresh_nr = [&]() { if (dyn) nr = __builtin_amdgcn_readfirstlane(*nr_word); };
     refresh_nr();
     st.reset();
@@ -847,7 +875,7 @@ __device__ __forceinline__ void render_pipe_body(const Params& P, float* smem, c
     }
 #endif
 #ifdef GNERF_WG_STAMPS
-    // Two stamps per workgroup, nothing inside the loops: where it ran, when it started, when its scalar wave left the last barrier.
+    // Three stamps per workgroup, nothing inside the loops: where it ran, when it started, when its head was over, when its scalar wave left the last barrier.
     if (wv == 3 && lane == 0 && p.debug) {
         unsigned long long* out = reinterpret_cast<unsigned long long*>(p.debug) + size_t(blockIdx.x) * 4;
         unsigned hw, xcc;
@@ -856,7 +884,7 @@ __device__ __forceinline__ void render_pipe_body(const Params& P, float* smem, c
         out[0] = hw | ((unsigned long long)(xcc & 15u) << 32);
         out[1] = wg_t0;
         out[2] = __builtin_amdgcn_s_memrealtime();
-        out[3] = (unsigned long long)nr;
+        out[3] = (unsigned long long)nr | ((wg_t1 - wg_t0) << 32);         // rays | ticks from the workgroup's start to its first shader tile
     }
 #endif
     if (wv == 3 && lane == 0) range.flush(P);
@@ -867,13 +895,60 @@ __device__ __forceinline__ void render_pipe_body(const Params& P, float* smem, c
 template <int TP, int MLP, bool FULL, bool GEN = false>
 __global__ __launch_bounds__(kPipeThreads, TP == 1 ? GNERF_PIPE_WAVES_PER_SIMD : (TP == 2 ? GNERF_PIPE2_WAVES_PER_SIMD : 2)) void render_kernel_pipe(Params P) {
     extern __shared__ __align__(16) float smem[];
+#ifdef GNERF_WG_STAMPS
+    const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
+#else
+    constexpr unsigned long long t0 = 0;
+#endif
     if constexpr (MLP == kMlpAuto) {
         bool sp_direct;
-        if (choose_mlp(P, smem, &sp_direct) == kMlpF32) render_pipe_body<TP, kMlpF32, FULL, GEN>(P, smem);
-        else                                           render_pipe_body<TP, kMlpF16x3, FULL, GEN>(P, smem, nullptr, nullptr, sp_direct);
+        if (P.decoder_pack) {
+            // the f16x3 image's loads leave with the statistics' -- one round trip for both; a decoder that needs fp32 loads the other image
+            // then (and these 20 registers were loaded for nothing: the rare choice pays)
+            DecoderImage<kMlpF16x3, kPipeThreads> image;
+            image.load(P.decoder_pack, threadIdx.x);
+            if (choose_mlp_packed(P, &sp_direct) == kMlpF32) render_pipe_body<TP, kMlpF32, FULL, GEN>(P, smem, nullptr, nullptr, false, t0);
+            else                                             render_pipe_body<TP, kMlpF16x3, FULL, GEN>(P, smem, nullptr, nullptr, sp_direct, t0, &image);
+            return;
+        }
+        // (The packed and the plain launch each get bodies of their own.  Folded into one body per arithmetic that branches on the pack inside
+        //  -- half the code, 100 instead of 155 spilled SGPRs -- the headline step was 0.66 % faster than the parent's instead of 1.5 %, and the
+        //  plain call 0.3 % SLOWER than the parent's: measured, r14 in DESIGN 3.1.)
+        const int choice = choose_mlp(P, smem, &sp_direct);
+        if (choice == kMlpF32) render_pipe_body<TP, kMlpF32, FULL, GEN>(P, smem, nullptr, nullptr, false, t0);
+        else                   render_pipe_body<TP, kMlpF16x3, FULL, GEN>(P, smem, nullptr, nullptr, sp_direct, t0);
     } else {
-        render_pipe_body<TP, MLP, FULL, GEN>(P, smem);
+        render_pipe_body<TP, MLP, FULL, GEN>(P, smem, nullptr, nullptr, false, t0);
     }
+}
+
+// gnerf_render_pack_decoder: one workgroup makes the decoder pack (render_shade.inl has the layout).  The statistics come from
+// decoder_stats, which sums the rows with the routines choose_mlp uses (w1_row_stats, w2_row_stats: render.hip) on two waves; the images
+// are what stage_decoder, the code the render kernels run without a pack, leaves in LDS.
+__global__ __launch_bounds__(kPipeThreads) void pack_decoder_kernel(gnerf_render_params p, float* pack) {
+    constexpr int kLds = kImageFloatsF32 > kImageFloatsF16 ? kImageFloatsF32 : kImageFloatsF16;
+    static_assert(kLds >= kStatFloats + 64 * 33 + 33 * 65, "decoder_stats' rows fit the image area");
+    __shared__ __align__(16) float smem[kLds];
+    const int tid = threadIdx.x;
+    decoder_stats(p, smem);
+    __syncthreads();
+    if (tid < kStatFloats) {
+        const int* words = reinterpret_cast<const int*>(smem);
+        reinterpret_cast<int*>(pack)[tid] = tid < kStatBad ? words[tid] : (tid == kStatBad ? ((words[kStatBad] | words[kStatBad2]) != 0 ? 1 : 0) : 0);
+    }
+    ShadeLds L;
+    __syncthreads();
+    for (int i = tid; i < kLds; i += kPipeThreads) smem[i] = 0.f;
+    __syncthreads();
+    stage_decoder<kMlpF16x3>(L, smem, p, tid, kPipeThreads);
+    __syncthreads();
+    for (int i = tid; i < kImageFloatsF16; i += kPipeThreads) pack[kPackImageF16 + i] = smem[i];
+    __syncthreads();
+    for (int i = tid; i < kLds; i += kPipeThreads) smem[i] = 0.f;
+    __syncthreads();
+    stage_decoder<kMlpF32>(L, smem, p, tid, kPipeThreads);
+    __syncthreads();
+    for (int i = tid; i < kImageFloatsF32; i += kPipeThreads) pack[kPackImageF32 + i] = smem[i];
 }
 
 // First pass of the staged backward: the forward pipeline in its BWD form (see render_pipe_body).  General sample counts (FULL = false:

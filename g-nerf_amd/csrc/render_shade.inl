@@ -187,14 +187,53 @@ struct Stamps { __device__ __forceinline__ void reset() {} };
 #define GNERF_STAMP(st, i) ((void)0)
 #endif
 
-// Copy the decoder into LDS (all threads of the workgroup; a barrier must follow).  base = start of the weight area.
+// Where the pieces of the decoder sit in the weight area that starts at `base` (weights, then b1 [64] and b2 [33 of 36]).
 template <int MLP>
-__device__ __forceinline__ void stage_decoder(ShadeLds& L, float* base, const gnerf_render_params& p, int tid, int nthreads) {
+__device__ __forceinline__ void decoder_lds(ShadeLds& L, float* base) {
     L.w1 = base;
     L.b1 = base + weight_floats(MLP);
     L.b2 = L.b1 + 64;
     if constexpr (MLP == kMlpF32) {
-    L.w2 = L.w1 + 64 * kW1Pitch;
+        L.w2 = L.w1 + 64 * kW1Pitch;
+    } else {
+        L.w2 = base + (2 * kW1FragHalves + 2 * 2048) / 2;              // density row W2[0][:] in fp32
+        L.b2c = L.w2 + 64;
+    }
+}
+
+// The decoder pack (gnerf_render_pack_decoder): what the head of a pipelined workgroup computes from the decoder alone, made once per
+// decoder by one small kernel.  Floats: [0, kStatFloats) the range statistics (choose_mlp, render.hip); then the two LDS IMAGES, byte for
+// byte what stage_decoder<kMlpF16x3> and stage_decoder<kMlpF32> leave in the weight area (bytes they do not write are zero).  An image is
+// a whole number of 16-byte chunks at a 16-byte offset: a workgroup copies it with thread t taking chunks t, t + 256, ... -- consecutive
+// lanes, consecutive chunks, on both sides (global_load_dwordx4, conflict-free ds_write_b128) -- all loads in flight before the first store.
+constexpr int kDecoderTailFloats = 64 + 36;                             // b1, b2 behind the weights (render_pipe.inl: pipe_lds_floats)
+constexpr int kImageFloatsF16 = kWeightFloatsF16 + kDecoderTailFloats, kImageFloatsF32 = kWeightFloatsF32 + kDecoderTailFloats;
+constexpr int kPackImageF16 = kStatFloats, kPackImageF32 = kPackImageF16 + kImageFloatsF16, kPackFloats = kPackImageF32 + kImageFloatsF32;
+static_assert(kStatFloats % 4 == 0 && kImageFloatsF16 % 4 == 0 && kImageFloatsF32 % 4 == 0, "the pack's images are 16-byte chunks");
+// The copy comes in two halves -- the loads into a thread's registers, the stores into LDS -- so that a kernel can start the loads of the
+// image it expects (f16x3) at its very top, beside the loads of the statistics that decide whether that image is the one to use.
+template <int MLP, int THREADS>
+struct DecoderImage {
+    static_assert(MLP == kMlpF32 || MLP == kMlpF16x3, "an image per decoder arithmetic");
+    static constexpr int kChunks = (MLP == kMlpF32 ? kImageFloatsF32 : kImageFloatsF16) / 4, kPer = (kChunks + THREADS - 1) / THREADS;
+    v4f r[kPer];
+    __device__ __forceinline__ void load(const float* pack, int tid) {
+        const v4f* src = reinterpret_cast<const v4f*>(pack + (MLP == kMlpF32 ? kPackImageF32 : kPackImageF16));
+#pragma unroll
+        for (int k = 0; k < kPer; k++) if (tid + k * THREADS < kChunks) r[k] = src[tid + k * THREADS];
+    }
+    __device__ __forceinline__ void store(float* base, int tid) const {
+        v4f* dst = reinterpret_cast<v4f*>(base);
+#pragma unroll
+        for (int k = 0; k < kPer; k++) if (tid + k * THREADS < kChunks) dst[tid + k * THREADS] = r[k];
+    }
+};
+
+// Copy the decoder into LDS (all threads of the workgroup; a barrier must follow).  base = start of the weight area.
+template <int MLP>
+__device__ __forceinline__ void stage_decoder(ShadeLds& L, float* base, const gnerf_render_params& p, int tid, int nthreads) {
+    decoder_lds<MLP>(L, base);
+    if constexpr (MLP == kMlpF32) {
     for (int i = tid; i < 64 * 32; i += nthreads) L.w1[(i >> 5) * kW1Pitch + (i & 31)] = p.w1[i];
     for (int i = tid; i < 33 * 64; i += nthreads) L.w2[(i >> 6) * kW2Pitch + (i & 63)] = p.w2[i];
     for (int i = tid; i < 64; i += nthreads) L.b1[i] = p.b1[i];
@@ -202,7 +241,6 @@ __device__ __forceinline__ void stage_decoder(ShadeLds& L, float* base, const gn
     } else {
     _Float16* w1h = reinterpret_cast<_Float16*>(base);                 // [hi|lo][m=4][lane = 16 g + j][8]: W1[16 m + j][8 g ..]
     _Float16* w2h = w1h + 2 * kW1FragHalves;                           // [hi|lo][n=2][s=2][lane = 16 g + j][8]
-    L.w2 = base + (2 * kW1FragHalves + 2 * 2048) / 2;                  // density row W2[0][:] in fp32
     // The activations run on the hardware's base-2 exp/log, so their scale factors are folded into the weights:
     //   layer 1 produces p' = log2(e) p                      (W1, b1 scaled by log2 e)
     //   softplus becomes h' = log2(1 + 2^p') = h / ln 2       (no multiply on either side)
@@ -228,7 +266,6 @@ __device__ __forceinline__ void stage_decoder(ShadeLds& L, float* base, const gn
         w2h[2048 + dst] = (_Float16)(x - (float)hi);
     }
     for (int i = tid; i < 64; i += nthreads) L.w2[i] = p.w2[i] * kLn2;
-    L.b2c = L.w2 + 64;
     for (int i = tid; i < 128; i += nthreads) L.b2c[i] = p.b2[1 + (i >> 2)] * -kLog2e;
     for (int i = tid; i < 64; i += nthreads) L.b1[i] = p.b1[i] * kLog2e;
     for (int i = tid; i < 33; i += nthreads) L.b2[i] = i == 0 ? p.b2[0] : p.b2[i] * -kLog2e;

@@ -215,12 +215,14 @@ Tensor filtered_lrelu_act_(Tensor x, Tensor si, int sx, int sy, float gain, floa
 // planes_nhwc [3N,H,W,32] (or interleaved [N,H,W,96]) f32 contiguous; w1,b1,w2,b2 effective f32 weights; rays [N,M,3]; noise_coarse [N*M*S]; noise_fine [N*M*F] or
 // empty; ray_start_t / ray_end_t per-ray limits or empty (then the scalars are used); planes_absmax one float or empty; workspace uint8
 // (zeroed once by the caller).  Returns (rgb [N,M,32], depth [N,M,1], wsum [N,M,1]).
-std::tuple<Tensor, Tensor, Tensor> render_forward(Tensor planes_nhwc, int64_t n_items, Tensor w1, Tensor b1, Tensor w2, Tensor b2,
+// render_forward_packed: the same with decoder_pack = what pack_decoder made of these w1, b1, w2, b2 (gnerf_render_forward_packed); an empty
+// decoder_pack is the plain call.
+std::tuple<Tensor, Tensor, Tensor> render_forward_packed(Tensor planes_nhwc, int64_t n_items, Tensor w1, Tensor b1, Tensor w2, Tensor b2,
                                                   Tensor ray_origins, Tensor ray_dirs, Tensor noise_coarse, Tensor noise_fine,
                                                   int64_t depth_resolution, int64_t depth_resolution_importance, double ray_start, double ray_end,
                                                   Tensor ray_start_t, Tensor ray_end_t, double box_warp, bool white_back, bool disparity_space_sampling,
                                                   int64_t image_width, Tensor planes_absmax, int64_t mlp_mode, Tensor workspace,
-                                                  bool planes_shared, bool depth_clamp_per_item) {
+                                                  bool planes_shared, bool depth_clamp_per_item, Tensor decoder_pack) {
     auto f32c = [](const Tensor& t, const char* name) {
         TORCH_CHECK(t.is_cuda() && t.scalar_type() == torch::kFloat32 && t.is_contiguous(), "render_forward: ", name, " must be a contiguous float32 GPU tensor");
     };
@@ -261,8 +263,36 @@ std::tuple<Tensor, Tensor, Tensor> render_forward(Tensor planes_nhwc, int64_t n_
     p.mlp_mode = int32_t(mlp_mode);
     p.planes_interleaved = interleaved ? 1 : 0;
     p.planes_shared = planes_shared ? 1 : 0; p.depth_clamp_per_item = depth_clamp_per_item ? 1 : 0;
-    check_rc(gnerf_render_forward(&p, current_stream()), "gnerf_render_forward");
+    if (present(decoder_pack)) {
+        TORCH_CHECK(decoder_pack.is_cuda() && decoder_pack.is_contiguous() && decoder_pack.get_device() == planes_nhwc.get_device() &&
+                    size_t(decoder_pack.numel() * decoder_pack.element_size()) >= gnerf_render_decoder_pack_bytes(), "render_forward: decoder_pack is not a pack on the planes' device");
+        check_rc(gnerf_render_forward_packed(&p, decoder_pack.data_ptr(), current_stream()), "gnerf_render_forward_packed");
+    } else {
+        check_rc(gnerf_render_forward(&p, current_stream()), "gnerf_render_forward");
+    }
     return std::make_tuple(rgb, depth, wsum);
+}
+
+std::tuple<Tensor, Tensor, Tensor> render_forward(Tensor planes_nhwc, int64_t n_items, Tensor w1, Tensor b1, Tensor w2, Tensor b2,
+                                                  Tensor ray_origins, Tensor ray_dirs, Tensor noise_coarse, Tensor noise_fine,
+                                                  int64_t depth_resolution, int64_t depth_resolution_importance, double ray_start, double ray_end,
+                                                  Tensor ray_start_t, Tensor ray_end_t, double box_warp, bool white_back, bool disparity_space_sampling,
+                                                  int64_t image_width, Tensor planes_absmax, int64_t mlp_mode, Tensor workspace,
+                                                  bool planes_shared, bool depth_clamp_per_item) {
+    return render_forward_packed(planes_nhwc, n_items, w1, b1, w2, b2, ray_origins, ray_dirs, noise_coarse, noise_fine, depth_resolution, depth_resolution_importance,
+                                 ray_start, ray_end, ray_start_t, ray_end_t, box_warp, white_back, disparity_space_sampling, image_width, planes_absmax, mlp_mode,
+                                 workspace, planes_shared, depth_clamp_per_item, Tensor());
+}
+
+// The decoder pack of (w1, b1, w2, b2) -- contiguous float32 on one GPU -- as a uint8 tensor (gnerf_render_pack_decoder, on the current stream).
+Tensor pack_decoder(Tensor w1, Tensor b1, Tensor w2, Tensor b2) {
+    for (const Tensor* t : {&w1, &b1, &w2, &b2})
+        TORCH_CHECK(t->is_cuda() && t->scalar_type() == torch::kFloat32 && t->is_contiguous() && t->get_device() == w1.get_device(), "pack_decoder: the decoder must be contiguous float32 tensors on one GPU");
+    TORCH_CHECK(w1.numel() == 64 * 32 && b1.numel() == 64 && w2.numel() == 33 * 64 && b2.numel() == 33, "pack_decoder: decoder must be the 32->64->33 MLP");
+    const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(at::device_of(w1));
+    Tensor pack = torch::empty({int64_t(gnerf_render_decoder_pack_bytes())}, w1.options().dtype(torch::kUInt8));
+    check_rc(gnerf_render_pack_decoder(w1.data_ptr<float>(), b1.data_ptr<float>(), w2.data_ptr<float>(), b2.data_ptr<float>(), pack.data_ptr(), current_stream()), "gnerf_render_pack_decoder");
+    return pack;
 }
 
 // ------------------------------------------------------------------------------------------------ ray gradient of the fused renderer
@@ -506,6 +536,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("filtered_lrelu", &filtered_lrelu);
     m.def("filtered_lrelu_act_", &filtered_lrelu_act_);
     m.def("render_forward", &render_forward);
+    m.def("render_forward_packed", &render_forward_packed);
+    m.def("pack_decoder", &pack_decoder);
     m.def("render_backward_rays", &render_backward_rays);
     m.def("query_points_grad", &query_points_grad);
     m.def("marching_cubes", &marching_cubes);

@@ -29,7 +29,7 @@ from .conv3x3 import (conv3x3_epilogue, conv3x3_epilogue_supported, conv3x3_epil
                       conv3x3_f32x3_epilogue, conv3x3_f32x3_supported, conv_transpose3x3_s2, conv_transpose3x3_s2_f32x3,
                       conv_transpose3x3_s2_f32x3_supported, conv_transpose3x3_s2_supported, pack_conv3x3_weights, pack_conv3x3_weights_f32x3,
                       pack_conv_transpose3x3_weights, pack_conv_transpose3x3_weights_f32x3, split_f16x3, split_overflow_flag)
-from .render import (last_mlp_choice, planes_layout, query_points, query_points_backward, query_points_grad, render_backward,  # noqa: F401
+from .render import (decoder_pack_available, last_mlp_choice, pack_decoder, planes_layout, query_points, query_points_backward, query_points_grad, render_backward,  # noqa: F401
                      render_forward, render_generated_supported, render_ray_grad_available, render_ray_grad_refusal, render_ray_grad_supported, _render_params)
 from .mesh import marching_cubes, _marching_cubes_ctypes  # noqa: F401
 from .ssim import SSIM_MAX_WIN, ssim_backward, ssim_forward  # noqa: F401

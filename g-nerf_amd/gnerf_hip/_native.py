@@ -1,6 +1,6 @@
 """The native library itself: where it is, its C ABI (signatures and structs), loading it, and what every wrapper needs to hand a
 tensor to it.  ALL mutable state of the package lives in this module (_lib, _ext, _workspaces, _split_overflow, _device_geometry,
-_filter_tap_cache): the sibling modules read it as `_native._ext` and never import those names, which would freeze a copy."""
+_filter_tap_cache, _decoder_packs, _decoder_seen): the sibling modules read it as `_native._ext` and never import those names, which would freeze a copy."""
 
 import ctypes
 import os
@@ -88,6 +88,9 @@ SIGNATURES = {
     'gnerf_render_forward': (_c_i, [ctypes.POINTER(RenderParams), _c_p]),
     'gnerf_render_backward': (_c_i, [ctypes.POINTER(RenderParams), ctypes.POINTER(RenderGrads), _c_p]),
     'gnerf_render_backward_rays': (_c_i, [ctypes.POINTER(RenderParams), ctypes.POINTER(RenderGrads), _c_p, _c_p, _c_p]),
+    'gnerf_render_decoder_pack_bytes': (ctypes.c_size_t, []),
+    'gnerf_render_pack_decoder': (_c_i, [_c_p, _c_p, _c_p, _c_p, _c_p, _c_p]),
+    'gnerf_render_forward_packed': (_c_i, [ctypes.POINTER(RenderParams), _c_p, _c_p]),
     'gnerf_render_backward_stage_bytes': (ctypes.c_size_t, [ctypes.POINTER(RenderParams)]),
     'gnerf_render_backward_exchange_bytes': (ctypes.c_size_t, [ctypes.POINTER(RenderParams)]),
     'gnerf_query_points': (_c_i, [_c_p, _c_i, _c_i, _c_i, _c_p, _c_i, _c_f, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_i, _c_p]),
@@ -127,9 +130,10 @@ SIGNATURES = {
     'gnerf_modconv_epilogue_backward_nhwc': (_c_i, [_c_p, _c_p, _c_p, _c_p, _c_i, _c_i, _c_i, _c_i, _c_i, _c_i, _c_f, _c_f, _c_f, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p]),
 }
 # exports added WITHOUT a new ABI version: a library of the same version built before them (a variant build behind GNERF_HIP_LIB) loads, and
-# what needs them asks modconv_backward_available() / render_ray_grad_available()
+# what needs them asks modconv_backward_available() / render_ray_grad_available() / decoder_pack_available()
 OPTIONAL_SYMBOLS = frozenset(n for n in SIGNATURES if n.startswith(('gnerf_modconv_backward_', 'gnerf_scale_channels_backward', 'gnerf_modconv_epilogue_backward',
-                                                                    'gnerf_render_backward_rays')))
+                                                                    'gnerf_render_backward_rays', 'gnerf_render_decoder_pack_bytes',
+                                                                    'gnerf_render_pack_decoder', 'gnerf_render_forward_packed')))
 
 
 def profiled(name):
@@ -329,6 +333,8 @@ _workspaces = {}                   # (device index, stream) -> the render worksp
 _split_overflow = {}               # device -> conv3x3.split_overflow_flag
 _device_geometry = {}              # device index -> planes.torch_rand_geometry's (CUs, threads per CU)
 _filter_tap_cache = {}             # planes._filter_taps
+_decoder_packs = {}                # render._decoder_pack's cache: key -> (pack, decoder tensors), least recently used first
+_decoder_seen = {}                 # ... and the keys it has seen once: key -> decoder tensors, oldest first
 _EMPTY = torch.empty([0])        # "absent tensor" for the C++ binding, as the reference's _null_tensor (bias_act.py:38)
 
 

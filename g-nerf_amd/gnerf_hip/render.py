@@ -6,7 +6,7 @@ import os
 import torch
 
 from . import _native
-from ._native import DEBUG_SLOTS, MLP_MODES, RenderGrads, RenderParams, _EMPTY, _launch, _on_device, _ptr, _require_cuda, _workspace, load, profiled
+from ._native import DEBUG_SLOTS, MLP_MODES, RenderGrads, RenderParams, _EMPTY, _launch, _on_device, _ptr, _require_cuda, _stream, _workspace, load, profiled
 
 
 def planes_layout(planes_nhwc, n_items, what):
@@ -188,12 +188,95 @@ def render_ray_grad_supported(S, F, ray_start=0.0, ray_end=1.0, density_noise=0,
     return render_ray_grad_refusal(S, F, ray_start, ray_end, density_noise, views, staged_scatter) is None
 
 
+def decoder_pack_available():
+    """Does the loaded library export the decoder pack (gnerf_render_pack_decoder, gnerf_render_forward_packed)?  (Added without a new
+    ABI version: a variant build of the same version made before it loads and answers False; render_forward then makes the plain call.)"""
+    lib = load()
+    return hasattr(lib, 'gnerf_render_pack_decoder') and hasattr(lib, 'gnerf_render_forward_packed')
+
+
+def pack_decoder(decoder):
+    """The decoder pack of decoder = (w1, b1, w2, b2), contiguous float32 on one GPU: a uint8 tensor that holds what the pipelined render
+    kernels otherwise work out of the decoder in every workgroup (range statistics, the weights in their LDS layout), made by one small
+    launch on the current stream.  Valid for the decoder's values at the time of the call.  render_forward makes and caches packs itself;
+    this is for callers of the C ABI and for tests."""
+    w1, b1, w2, b2 = decoder
+    _require_cuda(w1, b1, w2, b2)
+    if any(t.dtype != torch.float32 or not t.is_contiguous() for t in decoder) or \
+            tuple(w1.shape) != (64, 32) or tuple(b1.shape) != (64,) or tuple(w2.shape) != (33, 64) or tuple(b2.shape) != (33,):
+        raise RuntimeError('pack_decoder: decoder must be the 32->64->33 OSGDecoder MLP as contiguous float32 tensors')
+    e = _native.ext()
+    if e is not None:
+        with _on_device(w1.device):
+            return e.pack_decoder(w1, b1, w2, b2)
+    pack = torch.empty([int(load().gnerf_render_decoder_pack_bytes())], dtype=torch.uint8, device=w1.device)
+    _launch('gnerf_render_pack_decoder', w1, w1.data_ptr(), b1.data_ptr(), w2.data_ptr(), b2.data_ptr(), pack.data_ptr())
+    return pack
+
+
+DECODER_PACK_CACHE = 8      # packs render_forward keeps (and, apart from them, as many keys it has seen once)
+
+
+def _decoder_pack(decoder):
+    """The cached pack of `decoder` for a render call on the current stream, or None where the call goes without one.
+    Keyed on the device, the STREAM and each tensor's data_ptr() and _version: an in-place update (an optimizer step) bumps the version
+    and misses -- the contract ImportanceRenderer._decoder_cache already has; a pack is only ever used on the stream that made it (stream
+    order is what says it is complete), so two streams that share a decoder hold a pack each.
+    A pack is made when a key is seen the SECOND time: the launch that makes it (one workgroup, ~10 us in front of the render kernel)
+    costs more than the call it serves gains, so a caller whose weights change before every call (a training loop: measured 0.440 ->
+    0.447 ms per call with a pack made at first sight) goes without and runs as it did before there were packs, and a caller whose
+    decoder stays (inference, an orbit, fit_camera, every call between two optimizer steps) pays one plain call and one tiny launch,
+    then has the pack.  Keys seen once are remembered apart from the packs (_native._decoder_seen, as many, oldest out first) and take
+    no pack's place; the packs are kept least-recently-USED first, so a stream of changing decoders never pushes out the pack of a
+    decoder that is still being rendered.  An entry keeps its four tensors alive, so that an address cannot come back with other values
+    under the same key.
+    Inside a graph capture the answer is always None, whatever the cache holds: a captured launch keeps the ADDRESS of what it was
+    given, the cache may drop any pack before a replay (the block would be handed out again and a replay would copy whatever is there
+    into LDS as weights), and a plain captured call reads w1 .. b2 at replay time, so it follows in-place updates as it always has.  A
+    caller that wants a pack inside a graph passes its own (render_forward's decoder_pack=<tensor>) and owns what that means."""
+    w1, b1, w2, b2 = decoder
+    if any(t.dtype != torch.float32 or not t.is_contiguous() for t in decoder):
+        return None                 # (converted copies are new tensors on every call: nothing to key on)
+    if torch.cuda.is_current_stream_capturing():
+        return None
+    try:
+        key = (w1.device.index, _stream(w1), w1.data_ptr(), w1._version, b1.data_ptr(), b1._version, w2.data_ptr(), w2._version, b2.data_ptr(), b2._version)
+    except RuntimeError:            # inference tensors track no version
+        return None
+    packs, seen = _native._decoder_packs, _native._decoder_seen
+    hit = packs.pop(key, None)
+    if hit is not None:
+        packs[key] = hit            # most recently used: last out
+        return hit[0]
+    if not decoder_pack_available():
+        return None
+    if seen.pop(key, None) is None:             # first sight: remember the key, make nothing
+        while len(seen) >= DECODER_PACK_CACHE:
+            del seen[next(iter(seen))]
+        seen[key] = decoder
+        return None
+    while len(packs) >= DECODER_PACK_CACHE:
+        del packs[next(iter(packs))]            # the least recently used
+    pack = pack_decoder(decoder)                # second sight
+    packs[key] = (pack, decoder)
+    return pack
+
+
 @profiled('gnerf_hip::render_forward')
 def render_forward(planes_nhwc, n_items, decoder, ray_origins, ray_dirs, noise_coarse, noise_fine, *,
                    depth_resolution, depth_resolution_importance, ray_start, ray_end, box_warp,
                    white_back=False, disparity_space_sampling=False, image_width=0, debug=False, planes_absmax=None, mlp='auto',
-                   planes_shared=False, depth_clamp_per_item=False, cameras=None, rng=None, sigma_noise=None):
+                   planes_shared=False, depth_clamp_per_item=False, cameras=None, rng=None, sigma_noise=None, decoder_pack=True):
     """planes_nhwc [3N,H,W,32]; decoder = (w1,b1,w2,b2) effective fp32 weights; rays [N,M,3];
+    decoder_pack: True (the default) = the call hands the kernels the decoder's pack (pack_decoder), cached per stream, decoder tensors
+    and their versions and made when a decoder is seen the second time (_decoder_pack); never inside a graph capture, where the call is
+    the plain one.  False = the plain call, in which every workgroup prepares the decoder itself.  A tensor = a pack the caller made of
+    THESE weights.  Same results bit for bit either way -- PROVIDED the pack is of the weights' current values, which with True is the
+    CALLER'S OBLIGATION in one respect: the cache notices a change of w1 .. b2 by the tensors' version counters alone, so a write that
+    bumps none (through `w.data`, from another library, by a kernel given the raw address) must be followed by decoder_pack=False calls
+    or by any in-place torch operation on the tensor; the plain call reads the tensors every time.  With a pack of the caller's own the
+    weights are FROZEN at pack_decoder's call for as long as that pack is passed -- also in every replay of a graph that captured it,
+    whose owner must keep the pack tensor alive as long as the graph.
     sigma_noise = (coarse [N*M,S], fine [N*M,F] or None): density noise ALREADY multiplied by density_noise, added to the two passes'
     densities before their ray marches (renderer.py:146-147); forward only, tensor rays and draws only.
     cameras = (cam2world [N,4,4], intrinsics [N,3,3], res) with ray_origins = ray_dirs = None: the kernel makes the rays gnerf_make_rays
@@ -206,6 +289,11 @@ def render_forward(planes_nhwc, n_items, decoder, ray_origins, ray_dirs, noise_c
     mlp: decoder arithmetic, 'auto' (decided on the device from planes_absmax -- the one-element tensor planes_to_nhwc(...,
     with_absmax=True) returns; measured by the call itself when None -- and the decoder's weights), 'f16x3' or 'f32'.
     Returns (rgb [N,M,32], depth [N,M,1], wsum [N,M,1][, debug [N*M,8,S+F]])."""
+    if decoder_pack is True:
+        _require_cuda(*decoder)
+        pack = _decoder_pack(tuple(decoder))
+    else:
+        pack = None if decoder_pack is False else decoder_pack
     e = _native.ext()
     if e is not None and not debug and planes_nhwc.dtype == torch.float32 and planes_nhwc.is_contiguous() and cameras is None and rng is None and sigma_noise is None:
         # the C++ binding: same validation and the same C ABI call, without ctypes marshalling.  It takes tensor rays and tensor draws
@@ -215,6 +303,13 @@ def render_forward(planes_nhwc, n_items, decoder, ray_origins, ray_dirs, noise_c
         rs, re, rs_t, re_t = _ray_limits(ray_start, ray_end, n_items, ray_origins.shape[1], dev, 'render_forward')
         w1, b1, w2, b2 = decoder
         with _on_device(dev):
+            if pack is not None:
+                return e.render_forward_packed(planes_nhwc, n_items, _f32c(w1), _f32c(b1), _f32c(w2), _f32c(b2), _f32c(ray_origins), _f32c(ray_dirs),
+                                               _f32c(noise_coarse), _EMPTY if noise_fine is None else _f32c(noise_fine),
+                                               int(depth_resolution), int(depth_resolution_importance), rs, re, _EMPTY if rs_t is None else rs_t,
+                                               _EMPTY if re_t is None else re_t, float(box_warp), bool(white_back), bool(disparity_space_sampling),
+                                               int(image_width), _EMPTY if planes_absmax is None else planes_absmax, mode, _workspace(dev),
+                                               bool(planes_shared), bool(depth_clamp_per_item), pack)
             return e.render_forward(planes_nhwc, n_items, _f32c(w1), _f32c(b1), _f32c(w2), _f32c(b2), _f32c(ray_origins), _f32c(ray_dirs),
                                     _f32c(noise_coarse), _EMPTY if noise_fine is None else _f32c(noise_fine),
                                     int(depth_resolution), int(depth_resolution_importance), rs, re, _EMPTY if rs_t is None else rs_t,
@@ -242,7 +337,12 @@ def render_forward(planes_nhwc, n_items, decoder, ray_origins, ray_dirs, noise_c
             raise RuntimeError('render_forward: sigma_noise must be ([N*M,S], [N*M,F]) tensors')
         p.sigma_noise_coarse, p.sigma_noise_fine = sc.data_ptr(), None if sf is None else sf.data_ptr()
         keep = keep + (sc, sf)
-    _launch('gnerf_render_forward', planes_nhwc, ctypes.byref(p))
+    if pack is not None:
+        if pack.device != dev or pack.dtype != torch.uint8 or not pack.is_contiguous() or pack.numel() < int(load().gnerf_render_decoder_pack_bytes()):
+            raise RuntimeError("render_forward: decoder_pack is not a pack on the planes' device")
+        _launch('gnerf_render_forward_packed', planes_nhwc, ctypes.byref(p), pack.data_ptr())
+    else:
+        _launch('gnerf_render_forward', planes_nhwc, ctypes.byref(p))
     del keep
     if debug:
         return rgb, depth, wsum, dbg

@@ -178,8 +178,10 @@ class _FusedRender(torch.autograd.Function):
             amax = _producer_absmax(planes)                 # None: the launcher measures it
         else:
             nhwc, amax = gnerf_hip.planes_to_nhwc(planes.detach().float(), with_absmax=True)
+        # (decoder_pack=False: the effective weights of a differentiable call are new tensors on every call -- nothing a cached pack
+        #  could be found by, and remembering them would push the packs of inference decoders out of gnerf_hip's small cache)
         out = gnerf_hip.render_forward(nhwc, N, (w1, b1, w2, b2), ray_origins, ray_dirs, noise_c, noise_f,
-                                       ray_start=ray_start, ray_end=ray_end, planes_absmax=amax, **cfg)
+                                       ray_start=ray_start, ray_end=ray_end, planes_absmax=amax, decoder_pack=False, **cfg)
         ctx.amax = amax if not ctx.interleaved else None     # (of the NHWC copy made here; a producer's tag is looked up again in backward)
         tensors = [planes, w1, b1, w2, b2, ray_origins, ray_dirs, noise_c]
         # The NHWC copy is kept for the backward pass (the planes' size again: 25 MB per item) unless GNERF_KEEP_NHWC=0, in

@@ -522,6 +522,25 @@ int gnerf_render_backward(const gnerf_render_params* p, const gnerf_render_grads
  * sizes it. */
 int gnerf_render_backward_rays(const gnerf_render_params* p, const gnerf_render_grads* g, float* grad_origins, float* grad_dirs, gnerf_stream_t stream);
 
+/* The decoder pack (added without a new ABI version, like gnerf_render_backward_rays).
+ * Before its first ray every workgroup of the pipelined render kernels reduces the decoder's range statistics (which pick the decoder
+ * arithmetic under GNERF_MLP_AUTO) and rewrites the weights into their LDS layout.  Both depend on the decoder alone, and a decoder is
+ * the same from call to call between two optimizer steps.  gnerf_render_pack_decoder does that work ONCE, in one small launch (one
+ * workgroup), into `pack`: gnerf_render_decoder_pack_bytes() bytes of device memory, 16-byte aligned, holding the statistics and the LDS
+ * image of either arithmetic.  gnerf_render_forward_packed is gnerf_render_forward for a caller that has a pack of p's CURRENT w1, b1,
+ * w2, b2: a workgroup then evaluates the same inequalities on the stored statistics and copies the image it needs.  Same results bit
+ * for bit, same choice of arithmetic.  A pack made of other weight values than p's gives the other weights' results: the caller remakes
+ * it when the weights change (gnerf_hip.render_forward keeps a small cache keyed on the tensors' versions, and packs a decoder the second
+ * time it sees it: making a pack costs more than one call gains).  p->w1 .. p->b2 must still
+ * be given: kernels that do not read a pack (the generic kernel) use them.  The pack is only read by the call, so one pack serves any
+ * number of calls, streams permitting.  A call captured into a graph keeps the pack's ADDRESS: its owner keeps that memory alive and
+ * unchanged for as long as the graph is replayed, and every replay renders with the weights the pack was made of, whatever w1 .. b2 hold by
+ * then (a captured gnerf_render_forward reads them at replay time).  gnerf_hip.render_forward therefore hands no pack of its cache to a
+ * captured call. */
+size_t gnerf_render_decoder_pack_bytes(void);
+int gnerf_render_pack_decoder(const float* w1, const float* b1, const float* w2, const float* b2, void* pack, gnerf_stream_t stream);
+int gnerf_render_forward_packed(const gnerf_render_params* p, const void* pack, gnerf_stream_t stream);
+
 /* Density / colour of arbitrary points (run_model, renderer.py:142-148; used by
  * TriPlaneGenerator.sample / sample_mixed for shape extraction):
  * points [n_items, n_points, 3] -> sigma [n_items, n_points, 1], rgb [n_items, n_points, 32].
