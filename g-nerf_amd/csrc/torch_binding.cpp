@@ -12,7 +12,7 @@
 // Also exported: render_forward (the fused renderer has no reference plugin; same C ABI call as gnerf_hip.render_forward) and
 // marching_cubes (gnerf_hip.marching_cubes' count -> read counts -> emit sequence), ssim_forward / ssim_backward (gnerf_hip.ssim_*),
 // modconv_backward (gnerf_hip.scale_channels_backward / modconv_epilogue_backward), query_points_grad (gnerf_hip.query_points_grad),
-// render_backward_rays (gnerf_hip.render_backward with need_rays).
+// render_backward_rays (gnerf_hip.render_backward with need_rays), resize_aa (gnerf_hip.resize_aa_forward / _backward).
 //
 // Built ahead of time by csrc/build.sh (g++, no hipcc: there is no device code) into g-nerf_amd/gnerf_hip/gnerf_torch_ext.so.
 
@@ -528,6 +528,28 @@ std::tuple<c10::optional<Tensor>, c10::optional<Tensor>, c10::optional<Tensor>, 
     return std::make_tuple(dx, dscale, dbias, dnoise);
 }
 
+// ------------------------------------------------------------------------------------------------ antialiased resize (csrc/resize.hip)
+// x [N, C, H, W] float32 / float16 on a GPU, any strides.  transposed = false: x is the image, [in_h, in_w] -> [out_h, out_w]; true: x is the
+// gradient w.r.t. the resized image, [out_h, out_w] -> [in_h, in_w].  The result has x's memory format.  -> (result, the C ABI's return code):
+// gnerf_hip.resize_aa_* raises NativeError with the code, so that a caller can tell GNERF_E_UNSUPPORTED apart.
+std::tuple<Tensor, int> resize_aa(Tensor x, int64_t in_h, int64_t in_w, int64_t out_h, int64_t out_w, int mode, double scale_h, double scale_w, bool transposed) {
+    TORCH_CHECK(x.is_cuda() && x.dim() == 4, "resize_aa: x must be a 4-D GPU tensor");
+    TORCH_CHECK(x.scalar_type() == torch::kFloat32 || x.scalar_type() == torch::kFloat16, "resize_aa: the kernel takes float32 and float16 images");
+    const int64_t src_h = transposed ? out_h : in_h, src_w = transposed ? out_w : in_w, dst_h = transposed ? in_h : out_h, dst_w = transposed ? in_w : out_w;
+    TORCH_CHECK(x.size(2) == src_h && x.size(3) == src_w, "resize_aa: x is [", x.size(2), ", ", x.size(3), "], expected [", src_h, ", ", src_w, "]");
+    TORCH_CHECK(x.numel() > 0 && dst_h >= 1 && dst_w >= 1 && x.size(0) <= INT_MAX && x.size(1) <= INT_MAX && in_h <= INT_MAX && in_w <= INT_MAX &&
+                out_h <= INT_MAX && out_w <= INT_MAX, "resize_aa: empty or oversized image");
+    const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(at::device_of(x));
+    Tensor y = torch::empty({x.size(0), x.size(1), dst_h, dst_w}, x.options(), x.suggest_memory_format());
+    int64_t xs[4], ys[4];
+    strides4(x, xs);
+    strides4(y, ys);
+    const auto fn = transposed ? gnerf_resize_aa_backward : gnerf_resize_aa_forward;
+    const int rc = fn(x.data_ptr(), y.data_ptr(), dtype_code(x, "resize_aa"), int(x.size(0)), int(x.size(1)), int(in_h), int(in_w), int(out_h), int(out_w), xs, ys,
+                      mode, scale_h, scale_w, current_stream());
+    return std::make_tuple(y, rc);
+}
+
 }  // namespace
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -544,6 +566,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("ssim_forward", &ssim_forward);
     m.def("ssim_backward", &ssim_backward);
     m.def("modconv_backward", &modconv_backward);
+    m.def("resize_aa", &resize_aa);
     // the header version THIS extension was compiled against (a compile-time constant: gnerf_abi_version() would resolve in
     // libgnerf_hip.so at run time and compare the library with itself); gnerf_hip.ext() checks both against its own
     m.def("abi_version", []() { return int(GNERF_ABI_VERSION); });

@@ -29,6 +29,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from torch_utils.ops import bias_act, conv2d_resample, fma, modconv, upfirdn2d
+from torch_utils.ops import resize as resize_ops
 from training.volumetric_rendering.renderer import ImportanceRenderer
 from training.volumetric_rendering.ray_sampler import RaySampler
 
@@ -690,8 +691,12 @@ class SuperRes8XDC(nn.Module):
             _mark_one_latent(ws)
         x_raw, image_raw = self.block64(x, rgb, ws, noise_mode, **block_kwargs)
         if x.shape[-1] != 128:
-            x = F.interpolate(x_raw, size=(128, 128), mode='bilinear', align_corners=False, antialias=self.antialias)
-            rgb = F.interpolate(image_raw, size=(128, 128), mode='bilinear', align_corners=False, antialias=self.antialias)
+            if self.antialias:                                       # (through the module, so that a test can watch the route)
+                x = resize_ops.interpolate_aa(x_raw, size=(128, 128), mode='bilinear')
+                rgb = resize_ops.interpolate_aa(image_raw, size=(128, 128), mode='bilinear')
+            else:
+                x = F.interpolate(x_raw, size=(128, 128), mode='bilinear', align_corners=False, antialias=False)
+                rgb = F.interpolate(image_raw, size=(128, 128), mode='bilinear', align_corners=False, antialias=False)
         x, rgb = self.block0(x, rgb, ws, noise_mode, **block_kwargs)
         x, rgb = self.block1(x, rgb, ws, noise_mode, discard_x=True, **block_kwargs)
         return rgb, image_raw

@@ -57,7 +57,8 @@ def generator_loss(G, D, batch, res=64, ssim=False, **synthesis_kwargs):
     ws = G.mapping(batch['z'], batch['c'])
     gen = G.synthesis(ws, batch['c'], neural_rendering_resolution=res, **synthesis_kwargs)
     real = batch['loss_image']
-    real_raw = F.interpolate(real, size=(res, res), mode='bilinear', align_corners=False, antialias=True)      # ssim_resize, :180,:337
+    from torch_utils.ops import resize as resize_ops                     # (through the module, so that a test can watch the route)
+    real_raw = resize_ops.interpolate_aa(real, size=(res, res), mode='bilinear')                              # ssim_resize, :180,:337
     l1 = (real - gen['image'].float()).abs().mean((1, 2, 3))
     l1_raw = (real_raw - gen['image_raw'].float()).abs().mean((1, 2, 3))
     factor = batch['factor']

@@ -30,6 +30,8 @@
  *                              shape_mi355x.py; the one family of entry points that needs a host synchronisation in between)
  *   gnerf_ssim_*            <- pytorch_msssim's ssim / ms_ssim as training_loop.py:341-376 calls them (a Python package of grouped
  *                              convolutions there; no native counterpart)
+ *   gnerf_resize_aa_*       <- F.interpolate(mode='bilinear', align_corners=False, antialias=True) as superresolution.py:290-293 and
+ *                              training_loop.py's ssim_resize call it, and its gradient (ATen's kernels there)
  */
 #ifndef GNERF_HIP_H
 #define GNERF_HIP_H
@@ -628,6 +630,32 @@ int gnerf_ssim_backward(const void* x, const void* y, int dtype, int n, int c, i
                         const int64_t* y_strides, const float* window, int win, float C1, float C2, const float* g_ssim,
                         const float* g_cs, void* dx, const int64_t* dx_strides, void* dy, const int64_t* dy_strides,
                         gnerf_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
+ * (ABI 15, added without a new version) Antialiased resize of x [n, c, in_h, in_w] to y [n, c, out_h, out_w] and its transpose --
+ * F.interpolate(mode='bilinear' | 'bicubic', align_corners=False, antialias=True) and its gradient.  float32 or float16; both tensors are
+ * addressed through four element strides (n, c, h, w), so NCHW, channels_last and strided views run without a copy.  Per axis:
+ *   scale = the given scale_h / scale_w (1 / scale_factor of a caller that does not recompute it) or, when that is <= 0, in / out;
+ *   S = 2 (bilinear: f(x) = 1 - |x| on |x| < 1) or 4 (bicubic: Keys' cubic with a = -0.5 on |x| < 2);
+ *   support = S/2 * scale if scale >= 1 else S/2;  invscale = 1 / scale if scale >= 1 else 1;
+ *   for output i: center = scale * (i + 0.5), xmin = max(int(center - support + 0.5), 0), xsize = min(int(center + support + 0.5), in) - xmin,
+ *   w_j = f((j + xmin - center + 0.5) * invscale) for j < xsize, divided by their sum if that is not 0;
+ *   y = W_y x W_x^T per (n, c).
+ * Band edges and weights are evaluated in float64 inside the kernel and each weight is rounded to float32 once; products and sums are float32,
+ * horizontal pass first, the intermediate stays float32 and the result is rounded once, at the store.  No atomics, sums in a fixed order: the
+ * same bits on every run, for every memory layout, and whatever an item is batched with.  No workspace, no host-side table, no synchronisation.
+ *   gnerf_resize_aa_forward:  y = W_y x W_x^T.
+ *   gnerf_resize_aa_backward: dx [n, c, in_h, in_w] = W_y^T dy W_x, dy [n, c, out_h, out_w] (a gather: every element of dx is written once).
+ *     The operator is linear: the backward's own gradient is the forward again.
+ * GNERF_E_UNSUPPORTED, before any launch: more than GNERF_RESIZE_MAX_TAPS taps per output along an axis (scale > 32 bilinear, > 16 bicubic, on an
+ * axis longer than that), more than that many outputs touching one input (scale < 1/32), or 2^31 or more elements in a tensor. */
+#define GNERF_RESIZE_MAX_TAPS 65
+#define GNERF_RESIZE_BILINEAR 0
+#define GNERF_RESIZE_BICUBIC 1
+int gnerf_resize_aa_forward(const void* x, void* y, int dtype, int n, int c, int in_h, int in_w, int out_h, int out_w, const int64_t* x_strides,
+                            const int64_t* y_strides, int mode, double scale_h, double scale_w, gnerf_stream_t stream);
+int gnerf_resize_aa_backward(const void* dy, void* dx, int dtype, int n, int c, int in_h, int in_w, int out_h, int out_w, const int64_t* dy_strides,
+                             const int64_t* dx_strides, int mode, double scale_h, double scale_w, gnerf_stream_t stream);
 
 #ifdef __cplusplus
 }
