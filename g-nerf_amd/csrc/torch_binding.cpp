@@ -12,7 +12,8 @@
 // Also exported: render_forward (the fused renderer has no reference plugin; same C ABI call as gnerf_hip.render_forward) and
 // marching_cubes (gnerf_hip.marching_cubes' count -> read counts -> emit sequence), ssim_forward / ssim_backward (gnerf_hip.ssim_*),
 // modconv_backward (gnerf_hip.scale_channels_backward / modconv_epilogue_backward), query_points_grad (gnerf_hip.query_points_grad),
-// render_backward_rays (gnerf_hip.render_backward with need_rays), resize_aa (gnerf_hip.resize_aa_forward / _backward).
+// render_backward_rays (gnerf_hip.render_backward with need_rays), resize_aa (gnerf_hip.resize_aa_forward / _backward),
+// raster_visibility / raster_resolve (gnerf_hip.rasterize / resolve).
 //
 // Built ahead of time by csrc/build.sh (g++, no hipcc: there is no device code) into g-nerf_amd/gnerf_hip/gnerf_torch_ext.so.
 
@@ -550,6 +551,60 @@ std::tuple<Tensor, int> resize_aa(Tensor x, int64_t in_h, int64_t in_w, int64_t 
     return std::make_tuple(y, rc);
 }
 
+// ------------------------------------------------------------------------------------------------ rasteriser (csrc/raster.hip)
+// gnerf_hip.rasterize / resolve have validated the tensors: verts float32 [V, 3], faces int32 [T, 3], mesh2cam float32 [n, 12], intrinsics
+// float32 [n, 9], all contiguous on one GPU.  workspace / vis: preallocated buffers or None.  -> (vis int64 [n, h, w], counts int64 [4]).
+std::tuple<Tensor, Tensor> raster_visibility(Tensor verts, Tensor faces, Tensor mesh2cam, Tensor intrinsics, int64_t h, int64_t w, double near_z, int cull,
+                                             c10::optional<Tensor> workspace, c10::optional<Tensor> vis) {
+    TORCH_CHECK(verts.is_cuda() && verts.scalar_type() == torch::kFloat32 && verts.is_contiguous() && faces.scalar_type() == torch::kInt32 &&
+                faces.is_contiguous() && mesh2cam.scalar_type() == torch::kFloat32 && mesh2cam.is_contiguous() &&
+                intrinsics.scalar_type() == torch::kFloat32 && intrinsics.is_contiguous(), "raster_visibility: unexpected tensor layout");
+    TORCH_CHECK(verts.size(0) <= INT_MAX && faces.size(0) <= INT_MAX && mesh2cam.size(0) <= INT_MAX && h <= INT_MAX && w <= INT_MAX, "raster_visibility: oversized argument");
+    const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(at::device_of(verts));
+    const int n_verts = int(verts.size(0)), n_tris = int(faces.size(0)), n = int(mesh2cam.size(0));
+    Tensor ws;
+    if (workspace.has_value()) {
+        ws = *workspace;
+    } else {
+        size_t bytes = 0;
+        check_rc(gnerf_raster_workspace_bytes(n_verts, n_tris, n, int(h), int(w), &bytes), "gnerf_raster_workspace_bytes");
+        ws = torch::empty({int64_t(bytes)}, verts.options().dtype(torch::kUInt8));
+    }
+    Tensor v = vis.has_value() ? *vis : torch::empty({n, h, w}, verts.options().dtype(torch::kInt64));
+    Tensor counts = torch::empty({4}, verts.options().dtype(torch::kInt64));
+    check_rc(gnerf_raster_visibility(n_verts ? verts.data_ptr<float>() : nullptr, n_verts, n_tris ? faces.data_ptr<int32_t>() : nullptr, n_tris,
+                                     mesh2cam.data_ptr<float>(), intrinsics.data_ptr<float>(), n, int(h), int(w), float(near_z), cull, ws.data_ptr(),
+                                     reinterpret_cast<uint64_t*>(v.data_ptr<int64_t>()), counts.data_ptr<int64_t>(), current_stream()),
+             "gnerf_raster_visibility");
+    return std::make_tuple(v, counts);
+}
+
+// want: {tri_id, depth, normal, frame}.  -> those four, None where not wanted.
+std::vector<c10::optional<Tensor>> raster_resolve(Tensor vis, Tensor verts, Tensor faces, Tensor mesh2cam, Tensor intrinsics, c10::optional<Tensor> normals,
+                                                  c10::optional<Tensor> normal_mat, c10::optional<Tensor> colors, std::vector<double> shading,
+                                                  std::vector<bool> want) {
+    TORCH_CHECK(vis.is_cuda() && vis.scalar_type() == torch::kInt64 && vis.is_contiguous() && vis.dim() == 3, "raster_resolve: vis must be a contiguous int64 [n, h, w] GPU tensor");
+    TORCH_CHECK(shading.size() == 11 && want.size() == 4, "raster_resolve: shading holds 11 values, want 4");
+    TORCH_CHECK(verts.size(0) <= INT_MAX && faces.size(0) <= INT_MAX, "raster_resolve: oversized argument");
+    const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(at::device_of(vis));
+    const int n = int(vis.size(0)), h = int(vis.size(1)), w = int(vis.size(2)), n_verts = int(verts.size(0)), n_tris = int(faces.size(0));
+    std::vector<c10::optional<Tensor>> out(4);
+    if (want[0]) out[0] = torch::empty({n, h, w}, vis.options().dtype(torch::kInt32));
+    if (want[1]) out[1] = torch::empty({n, h, w}, vis.options().dtype(torch::kFloat32));
+    if (want[2]) out[2] = torch::empty({n, h, w, 3}, vis.options().dtype(torch::kFloat32));
+    if (want[3]) out[3] = torch::empty({n, h, w, 3}, vis.options().dtype(torch::kUInt8));
+    float sh[11];
+    for (int i = 0; i < 11; i++) sh[i] = float(shading[i]);
+    auto p = [](const c10::optional<Tensor>& t) -> void* { return t.has_value() ? t->data_ptr() : nullptr; };
+    check_rc(gnerf_raster_resolve(reinterpret_cast<const uint64_t*>(vis.data_ptr<int64_t>()), n_verts ? verts.data_ptr<float>() : nullptr, n_verts,
+                                  n_tris ? faces.data_ptr<int32_t>() : nullptr, n_tris, mesh2cam.data_ptr<float>(), intrinsics.data_ptr<float>(), n, h, w,
+                                  static_cast<const float*>(p(normals)), static_cast<const float*>(p(normal_mat)), static_cast<const unsigned char*>(p(colors)), sh,
+                                  static_cast<int32_t*>(p(out[0])), static_cast<float*>(p(out[1])), static_cast<float*>(p(out[2])),
+                                  static_cast<unsigned char*>(p(out[3])), current_stream()),
+             "gnerf_raster_resolve");
+    return out;
+}
+
 }  // namespace
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -567,6 +622,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("ssim_backward", &ssim_backward);
     m.def("modconv_backward", &modconv_backward);
     m.def("resize_aa", &resize_aa);
+    m.def("raster_visibility", &raster_visibility);
+    m.def("raster_resolve", &raster_resolve);
     // the header version THIS extension was compiled against (a compile-time constant: gnerf_abi_version() would resolve in
     // libgnerf_hip.so at run time and compare the library with itself); gnerf_hip.ext() checks both against its own
     m.def("abi_version", []() { return int(GNERF_ABI_VERSION); });

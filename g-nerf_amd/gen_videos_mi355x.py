@@ -20,6 +20,8 @@ this repo's inference-only equivalent (gnerf_generator.Generator).  `--graph` re
 HIP graph captured once (FrameProgram); `--shapes out.npy` also extracts the 512^3 density volume of gen_videos.py --shapes,
 `--shapes-mrc out.mrc` writes it as the reference's .mrc, and `--mesh out.ply` meshes it (shape_utils.py's step, shape_mi355x) while it
 is still on the device; `--mesh-attrs normals|colors|all` adds the density field's normals and the decoder's colours per vertex.
+`--geometry-out geo.npy` draws that mesh from every orbit camera with the triangle rasteriser (csrc/raster.hip): shaded geometry frames on
+the renderer's pixel grid, uint8 [F, H, W, 3] at `--geometry-res`, smooth-shaded / coloured with `--mesh-attrs`.
 """
 
 import argparse
@@ -229,6 +231,13 @@ def mesh_to_world_jacobian(resolution, cube_length):
     return size * np.array([[1 / (n * n), 1 / n, -1.0], [1 / n, 1.0, 0.0], [1.0, 0.0, 0.0]])
 
 
+def mesh_to_world_matrix(resolution, cube_length):
+    """The affine map lattice_to_world(mesh_to_lattice(v)) of a mesh vertex v (index space) as a 3x4 [J | b] (float64 numpy): J is
+    mesh_to_world_jacobian, b the world position of v = 0 (lattice point (n - 1, 0, 0))."""
+    half = cube_length / 2
+    return np.concatenate([mesh_to_world_jacobian(resolution, cube_length), np.array([[half], [-half], [-half]])], axis=1)
+
+
 def normals_to_mesh_frame(normals_world, resolution, cube_length):
     """World-space normals [..., 3] -> the mesh's index frame, in which the .ply's vertices stay: a normal is a covector (the gradient
     of a scalar field), so it transforms with the transpose, normalise(J^T n); zero vectors stay zero."""
@@ -329,6 +338,31 @@ def mesh_density_grid(vol, ply_path, level=10.0, attrs=None, G=None, planes=None
     return len(verts), len(faces), dt
 
 
+@torch.no_grad()
+def render_geometry_orbit(verts, faces, n_frames, res, voxel_res, cube_length, radius, rank=0, world=1, frames_per_call=1, normals=None, colors=None,
+                          shading=None):
+    """This rank's shaded geometry frames of the orbit, uint8 [n_local, res, res, 3] on verts' device (None for an empty share): the mesh of a
+    voxel_res^3 density volume (index space; mesh_to_world_matrix puts it into the world) drawn from the orbit's cameras, frames_per_call
+    views per rasteriser call, on the pixel grid of image_raw / image_depth at that resolution.  CUDA tensors take the kernels, CPU tensors
+    the numpy port (shape_mi355x.render_mesh)."""
+    import shape_mi355x
+    lo, hi = H.shard_range(n_frames, rank, world)
+    if hi == lo:
+        return None, (lo, hi)
+    labels = H.orbit_labels(range(lo, hi), n_frames, radius)
+    mesh2world = mesh_to_world_matrix(voxel_res, cube_length)
+    k = max(int(frames_per_call), 1)
+    on_gpu = verts.is_cuda
+    mesh = [t if (t is None or on_gpu) else t.numpy() for t in (verts, faces, normals, colors)]
+    frames = []
+    for j in range(0, hi - lo, k):
+        c = labels[j:j + k]
+        out = shape_mi355x.render_mesh(mesh[0], mesh[1], c[:, :16].reshape(-1, 4, 4), c[:, 16:25].reshape(-1, 3, 3), res, mesh2world=mesh2world,
+                                       normals=mesh[2], colors=mesh[3], shading=shading, outputs=('frame',))
+        frames.append(out['frame'] if on_gpu else torch.from_numpy(out['frame']))
+    return torch.cat(frames), (lo, hi)
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument('--network', help='generator pickle (G_ema)')
@@ -349,6 +383,9 @@ def main():
     ap.add_argument('--mesh-level', type=float, default=10, help='isosurface level of --mesh (shape_utils.py:111)')
     ap.add_argument('--mesh-attrs', choices=MESH_ATTRS, default='none', help='per-vertex attributes of --mesh: normals of the density field and / or the decoder\'s colours')
     ap.add_argument('--voxel-res', type=int, default=512)
+    ap.add_argument('--geometry-out', default=None, help='also draw the mesh of the density volume from every orbit camera (shaded geometry frames, '
+                                                         'uint8 [F, H, W, 3]) and write them to this .npy (rank 0); uses --voxel-res, --mesh-level, --mesh-attrs, --frames-per-call')
+    ap.add_argument('--geometry-res', type=int, default=512, help='resolution of the geometry frames')
     ap.add_argument('--no-solver-search', action='store_true', help='leave torch.backends.cudnn.benchmark off (MIOpen takes its first heuristic pick per shape)')
     args = ap.parse_args()
     H.configure_backend(False if args.no_solver_search else None)
@@ -385,26 +422,60 @@ def main():
               f'(neural rendering {args.res}x{args.res}, {G.rendering_kwargs["depth_resolution"]}+{G.rendering_kwargs["depth_resolution_importance"]} samples)')
         if args.out:
             np.save(args.out, full.cpu().numpy())
-        if args.shapes or args.shapes_mrc or args.mesh:
+    made = {}
+
+    def volume_and_planes():                                             # made once per process, whichever option asks first
+        if 'vol' not in made:
             if device.type == 'cuda':
                 torch.cuda.synchronize()
             t0 = time.perf_counter()
-            vol, planes = extract_density_grid(G, orbit_latents(G, z, device), args.voxel_res, return_planes=True)
+            made['vol'], made['planes'] = extract_density_grid(G, orbit_latents(G, z, device), args.voxel_res, return_planes=True)
             if device.type == 'cuda':
                 torch.cuda.synchronize()
             dt = time.perf_counter() - t0
-            print(f'density volume {args.voxel_res}^3: {dt:.3f} s = {args.voxel_res ** 3 / dt / 1e9:.2f} G points/s')
-            if args.shapes:
-                np.save(args.shapes, vol.cpu().numpy())
-            if args.shapes_mrc:
-                import shape_mi355x
-                shape_mi355x.write_mrc(args.shapes_mrc, vol.cpu().numpy())
-            if args.mesh:
-                t0 = time.perf_counter()
-                nv, nf, dt = mesh_density_grid(vol, args.mesh, args.mesh_level, attrs=args.mesh_attrs, G=G, planes=planes)
-                print(f'mesh at level {args.mesh_level:g}: {dt * 1e3:.2f} ms, {nv} vertices, {nf} triangles -> {args.mesh}'
-                      + (f' (with {args.mesh_attrs}: {(time.perf_counter() - t0) * 1e3:.2f} ms in all, file included)' if args.mesh_attrs != 'none' else ''))
+            if rank == 0:
+                print(f'density volume {args.voxel_res}^3: {dt:.3f} s = {args.voxel_res ** 3 / dt / 1e9:.2f} G points/s')
+        return made['vol'], made['planes']
 
+    if rank == 0 and (args.shapes or args.shapes_mrc or args.mesh):
+        vol, planes = volume_and_planes()
+        if args.shapes:
+            np.save(args.shapes, vol.cpu().numpy())
+        if args.shapes_mrc:
+            import shape_mi355x
+            shape_mi355x.write_mrc(args.shapes_mrc, vol.cpu().numpy())
+        if args.mesh:
+            t0 = time.perf_counter()
+            nv, nf, dt = mesh_density_grid(vol, args.mesh, args.mesh_level, attrs=args.mesh_attrs, G=G, planes=planes)
+            print(f'mesh at level {args.mesh_level:g}: {dt * 1e3:.2f} ms, {nv} vertices, {nf} triangles -> {args.mesh}'
+                  + (f' (with {args.mesh_attrs}: {(time.perf_counter() - t0) * 1e3:.2f} ms in all, file included)' if args.mesh_attrs != 'none' else ''))
+    if args.geometry_out:
+        # every rank meshes the volume itself (the same bits everywhere: no mesh travels between ranks), then draws its share of the cameras
+        import shape_mi355x
+        vol, planes = volume_and_planes()
+        verts, faces = shape_mi355x.marching_cubes(vol.permute(2, 1, 0).contiguous(), args.mesh_level)
+        if not isinstance(verts, torch.Tensor):
+            verts, faces = torch.from_numpy(verts), torch.from_numpy(faces)
+        normals = colors = None
+        if args.mesh_attrs != 'none':
+            normals, colors = mesh_vertex_attributes(G, planes, verts.to(device), args.voxel_res, args.mesh_attrs in ('normals', 'all'), args.mesh_attrs in ('colors', 'all'))
+            if not verts.is_cuda:
+                normals, colors = (None if t is None else t.cpu() for t in (normals, colors))
+        if device.type == 'cuda':
+            torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        geo, _ = render_geometry_orbit(verts, faces, args.frames, args.geometry_res, args.voxel_res, G.rendering_kwargs['box_warp'],
+                                       G.rendering_kwargs['avg_camera_radius'], rank, world, args.frames_per_call, normals=normals, colors=colors)
+        if geo is None:
+            geo = torch.zeros([0, args.geometry_res, args.geometry_res, 3], dtype=torch.uint8, device=verts.device)
+        full_geo = H.gather_frames(geo.to(device), args.frames)
+        if device.type == 'cuda':
+            torch.cuda.synchronize()
+        dt = H.max_over_ranks(time.perf_counter() - t0, device)
+        if rank == 0:
+            print(f'geometry frames: {args.frames} at {args.geometry_res}x{args.geometry_res} of {len(faces)} triangles in {dt:.3f} s = {args.frames / dt:.2f} frames/s '
+                  f'-> {args.geometry_out}')
+            np.save(args.geometry_out, full_geo.cpu().numpy())
 
 if __name__ == '__main__':
     main()

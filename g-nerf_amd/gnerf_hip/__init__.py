@@ -8,7 +8,7 @@ There is NO fallback: if the library is missing or a call fails, a RuntimeError 
 carries the C ABI's return code).
 
 One module per native family, along the lines of csrc/: _native (the library, its ABI, loading, what every wrapper shares, and ALL
-mutable state), plugins, planes, modconv, conv3x3, render, mesh, ssim, resize.  Everything public is re-exported here.
+mutable state), plugins, planes, modconv, conv3x3, render, mesh, ssim, resize, raster.  Everything public is re-exported here.
 """
 
 import ctypes  # noqa: F401  (ctypes, os and torch have always been attributes of the package)
@@ -16,7 +16,7 @@ import os  # noqa: F401
 
 import torch  # noqa: F401
 
-from . import _native, conv3x3, mesh, modconv, planes, plugins, render, resize, ssim  # noqa: F401
+from . import _native, conv3x3, mesh, modconv, planes, plugins, raster, render, resize, ssim  # noqa: F401
 from ._native import (ABI_VERSION, DEBUG_SLOTS, E_UNSUPPORTED, EXT_PATH, F16, F32, F64, LIB_PATH, MAX_SAMPLES, MLP_MODES, OPTIONAL_SYMBOLS, SIGNATURES,  # noqa: F401
                       NativeError, RenderGrads, RenderParams, clock_under_load, ext, is_available, is_channels_last, load, profiled,
                       _activation_layout, _check, _stream, _workspace, _workspaces)
@@ -35,3 +35,5 @@ from .mesh import marching_cubes, _marching_cubes_ctypes  # noqa: F401
 from .ssim import SSIM_MAX_WIN, ssim_backward, ssim_forward  # noqa: F401
 from .resize import (RESIZE_MAX_TAPS, RESIZE_MODES, resize_aa_available, resize_aa_backward, resize_aa_forward, resize_aa_refusal,  # noqa: F401
                      resize_aa_supported)
+from .raster import (RASTER_CULL, RASTER_MAX_SIZE, RASTER_OUTPUTS, RASTER_SHADING, RASTER_SMALL_PIXELS, raster_available, raster_workspace_bytes, rasterize,  # noqa: F401
+                     resolve, shading_vector, _rasterize_ctypes, _resolve_ctypes)

@@ -132,12 +132,17 @@ SIGNATURES = {
                                        ctypes.c_double, ctypes.c_double, _c_p]),
     'gnerf_resize_aa_backward': (_c_i, [_c_p, _c_p, _c_i, _c_i, _c_i, _c_i, _c_i, _c_i, _c_i, ctypes.POINTER(_c_i64), ctypes.POINTER(_c_i64), _c_i,
                                         ctypes.c_double, ctypes.c_double, _c_p]),
+    'gnerf_raster_workspace_bytes': (_c_i, [_c_i, _c_i, _c_i, _c_i, _c_i, ctypes.POINTER(ctypes.c_size_t)]),
+    'gnerf_raster_visibility': (_c_i, [_c_p, _c_i, _c_p, _c_i, _c_p, _c_p, _c_i, _c_i, _c_i, _c_f, _c_i, _c_p, _c_p, _c_p, _c_p]),
+    'gnerf_raster_resolve': (_c_i, [_c_p, _c_p, _c_i, _c_p, _c_i, _c_p, _c_p, _c_i, _c_i, _c_i, _c_p, _c_p, _c_p, ctypes.POINTER(_c_f),
+                                    _c_p, _c_p, _c_p, _c_p, _c_p]),
 }
 # exports added WITHOUT a new ABI version: a library of the same version built before them (a variant build behind GNERF_HIP_LIB) loads, and
-# what needs them asks modconv_backward_available() / render_ray_grad_available() / decoder_pack_available() / resize_aa_available()
+# what needs them asks modconv_backward_available() / render_ray_grad_available() / decoder_pack_available() / resize_aa_available() /
+# raster_available()
 OPTIONAL_SYMBOLS = frozenset(n for n in SIGNATURES if n.startswith(('gnerf_modconv_backward_', 'gnerf_scale_channels_backward', 'gnerf_modconv_epilogue_backward',
                                                                     'gnerf_render_backward_rays', 'gnerf_render_decoder_pack_bytes',
-                                                                    'gnerf_render_pack_decoder', 'gnerf_render_forward_packed', 'gnerf_resize_aa_')))
+                                                                    'gnerf_render_pack_decoder', 'gnerf_render_forward_packed', 'gnerf_resize_aa_', 'gnerf_raster_')))
 
 
 def profiled(name):

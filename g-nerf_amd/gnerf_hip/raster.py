@@ -1,0 +1,184 @@
+"""The triangle rasteriser for extracted meshes (csrc/raster.hip): a visibility buffer per view, then depth / normal / shaded colour."""
+
+import ctypes
+
+import torch
+
+from . import _native
+from ._native import _check, _launch, _on_device, _ptr, _require_cuda, load, profiled
+
+RASTER_SMALL_PIXELS = 64            # GNERF_RASTER_SMALL_PIXELS (include/gnerf_hip.h): the largest bounding box a triangle's own thread walks
+RASTER_MAX_SIZE = 4096              # GNERF_RASTER_MAX_SIZE
+RASTER_CULL = {'none': 0, 'back': 1, 'front': 2}
+RASTER_OUTPUTS = ('tri_id', 'depth', 'normal', 'frame')
+# light: from the surface to the light, in the camera frame (the default is a headlight); colours in [0, 1]
+RASTER_SHADING = dict(light=(0.0, 0.0, -1.0), ambient=0.25, diffuse=0.75, albedo=(0.8, 0.8, 0.8), background=(1.0, 1.0, 1.0))
+
+
+def raster_available():
+    """Whether the loaded library has the rasteriser (a version-15 library built before it does not)."""
+    return all(hasattr(load(), name) for name in ('gnerf_raster_workspace_bytes', 'gnerf_raster_visibility', 'gnerf_raster_resolve'))
+
+
+def _require_raster():
+    if not raster_available():
+        raise RuntimeError('gnerf_hip: this libgnerf_hip.so was built without the rasteriser (gnerf_raster_*): rebuild it (csrc/build.sh)')
+
+
+def _f32(t, shape, what):
+    t = t.detach()
+    if t.numel() % shape[-1] != 0:
+        raise ValueError(f'raster: {what} has shape {tuple(t.shape)}')
+    t = t.reshape(-1, shape[-1])
+    return t if (t.dtype == torch.float32 and t.is_contiguous()) else t.to(torch.float32).contiguous()
+
+
+def _mesh(verts, faces):
+    _require_cuda(verts, faces)
+    if faces.device != verts.device:
+        raise RuntimeError('raster: verts and faces must be on one device')
+    v = _f32(verts, (3,), 'verts')
+    f = faces.detach().reshape(-1, 3)
+    f = f if (f.dtype == torch.int32 and f.is_contiguous()) else f.to(torch.int32).contiguous()
+    return v, f
+
+
+def _cameras(mesh2cam, intrinsics, device):
+    """[n, 12] and [n, 9] float32 on `device`.  Tensors that already are that are passed through untouched, so that a captured graph reads
+    the caller's tensors in place (overwrite them and replay)."""
+    _require_cuda(mesh2cam, intrinsics)
+    if mesh2cam.device != device or intrinsics.device != device:
+        raise RuntimeError('raster: the cameras must be on the mesh\'s device')
+    A, K = _f32(mesh2cam, (12,), 'mesh2cam'), _f32(intrinsics, (9,), 'intrinsics')
+    if len(A) != len(K) or len(A) < 1:
+        raise ValueError(f'raster: {len(A)} mesh2cam for {len(K)} intrinsics')
+    return A, K
+
+
+def _size(size):
+    h, w = (size, size) if isinstance(size, int) else size
+    h, w = int(h), int(w)
+    if not (1 <= h <= RASTER_MAX_SIZE and 1 <= w <= RASTER_MAX_SIZE):
+        raise ValueError(f'raster: the image size must be 1..{RASTER_MAX_SIZE} in each direction (got {h} x {w})')
+    return h, w
+
+
+def shading_vector(shading=None):
+    """The eleven floats gnerf_raster_resolve takes: light [3], ambient, diffuse, albedo [3], background [3] (RASTER_SHADING's keys)."""
+    s = dict(RASTER_SHADING, **(shading or {}))
+    unknown = set(s) - set(RASTER_SHADING)
+    if unknown:
+        raise ValueError(f'raster: unknown shading parameter(s) {sorted(unknown)}')
+    vec = [float(x) for x in (*s['light'], s['ambient'], s['diffuse'], *s['albedo'], *s['background'])]
+    if len(vec) != 11:
+        raise ValueError('raster: light, albedo and background are triples, ambient and diffuse scalars')
+    return vec
+
+
+def _rasterize_ctypes(v, f, A, K, h, w, near, cull, workspace=None, vis=None):
+    """The ctypes route of rasterize (arguments as _mesh / _cameras / _size return them)."""
+    dev, n = v.device, len(A)
+    if workspace is None:
+        nbytes = ctypes.c_size_t()
+        _check(load().gnerf_raster_workspace_bytes(len(v), len(f), n, h, w, ctypes.byref(nbytes)), 'gnerf_raster_workspace_bytes')
+        workspace = torch.empty(nbytes.value, dtype=torch.uint8, device=dev)
+    if vis is None:
+        vis = torch.empty([n, h, w], dtype=torch.int64, device=dev)
+    counts = torch.empty(4, dtype=torch.int64, device=dev)
+    _launch('gnerf_raster_visibility', v, _ptr(v) if len(v) else None, len(v), _ptr(f) if len(f) else None, len(f), _ptr(A), _ptr(K), n, h, w,
+            float(near), cull, _ptr(workspace), _ptr(vis), _ptr(counts))
+    return vis, counts
+
+
+def raster_workspace_bytes(n_verts, n_tris, n_views, size):
+    _require_raster()
+    h, w = _size(size)
+    nbytes = ctypes.c_size_t()
+    _check(load().gnerf_raster_workspace_bytes(int(n_verts), int(n_tris), int(n_views), h, w, ctypes.byref(nbytes)), 'gnerf_raster_workspace_bytes')
+    return int(nbytes.value)
+
+
+@profiled('gnerf_hip::rasterize')
+def rasterize(verts, faces, mesh2cam, intrinsics, size, near=0.01, cull='none', workspace=None, vis=None):
+    """Visibility buffer of a mesh (verts float32 [V, 3], faces int32 [T, 3], CUDA) from n cameras: mesh2cam [n, 3, 4] (mesh frame -> the
+    camera frame of csrc/raygen.h) and normalised intrinsics [n, 3, 3], CUDA tensors; size = (h, w) or one int.  -> (vis int64 [n, h, w]: the
+    bits of the kernel's uint64 keys, float_as_uint(z) << 32 | triangle, -1 where empty; counts int64 [4] on the device = drawn, near, guard,
+    culled).  Rules: include/gnerf_hip.h, gnerf_raster_*; shape_mi355x.rasterize_numpy gives the same bits.  No host read: capturable in a
+    graph (float32 contiguous camera tensors are read in place).  workspace / vis: optional preallocated buffers (uint8 of
+    raster_workspace_bytes, int64 [n, h, w]); neither needs initialising."""
+    _require_raster()
+    v, f = _mesh(verts, faces)
+    A, K = _cameras(mesh2cam, intrinsics, v.device)
+    h, w = _size(size)
+    if cull not in RASTER_CULL:
+        raise ValueError(f'raster: cull must be one of {tuple(RASTER_CULL)}')
+    if not near > 0:
+        raise ValueError('raster: near must be > 0')
+    if vis is not None and (vis.dtype != torch.int64 or tuple(vis.shape) != (len(A), h, w) or not vis.is_contiguous() or vis.device != v.device):
+        raise ValueError('raster: vis must be a contiguous int64 [n_views, h, w] tensor on the mesh\'s device')
+    if workspace is not None and (workspace.dtype != torch.uint8 or workspace.device != v.device or not workspace.is_contiguous()
+                                  or workspace.numel() < raster_workspace_bytes(len(v), len(f), len(A), (h, w))):
+        raise ValueError('raster: workspace must be a contiguous uint8 tensor of raster_workspace_bytes(...) on the mesh\'s device')
+    e = _native.ext()
+    if e is not None and hasattr(e, 'raster_visibility'):
+        with _on_device(v.device):
+            return e.raster_visibility(v, f, A, K, h, w, float(near), RASTER_CULL[cull], workspace, vis)
+    return _rasterize_ctypes(v, f, A, K, h, w, near, RASTER_CULL[cull], workspace, vis)
+
+
+def _resolve_ctypes(vis, v, f, A, K, normals, normal_mat, colors, shading, want):
+    dev = vis.device
+    n, h, w = vis.shape
+    out = {}
+    if 'tri_id' in want:
+        out['tri_id'] = torch.empty([n, h, w], dtype=torch.int32, device=dev)
+    if 'depth' in want:
+        out['depth'] = torch.empty([n, h, w], dtype=torch.float32, device=dev)
+    if 'normal' in want:
+        out['normal'] = torch.empty([n, h, w, 3], dtype=torch.float32, device=dev)
+    if 'frame' in want:
+        out['frame'] = torch.empty([n, h, w, 3], dtype=torch.uint8, device=dev)
+    sh = (ctypes.c_float * 11)(*shading)
+    _launch('gnerf_raster_resolve', vis, _ptr(vis), _ptr(v) if len(v) else None, len(v), _ptr(f) if len(f) else None, len(f), _ptr(A), _ptr(K), n, h, w,
+            _ptr(normals), _ptr(normal_mat), _ptr(colors), sh, _ptr(out.get('tri_id')), _ptr(out.get('depth')), _ptr(out.get('normal')),
+            _ptr(out.get('frame')))
+    return out
+
+
+@profiled('gnerf_hip::raster_resolve')
+def resolve(vis, verts, faces, mesh2cam, intrinsics, normals=None, normal_mat=None, colors=None, shading=None, outputs=RASTER_OUTPUTS):
+    """Per-pixel images of rasterize's visibility buffer, from the same mesh and cameras -> dict over `outputs`: tri_id int32 [n, h, w] (-1:
+    background), depth float32 [n, h, w] (distance along the pixel's ray, what image_depth holds; +inf: background), normal float32
+    [n, h, w, 3] (camera frame, unit, facing the camera), frame uint8 [n, h, w, 3].  normals float32 [V, 3] (mesh frame) need normal_mat
+    [n, 3, 3] (mesh frame -> camera frame); colors uint8 [V, 3]; shading: dict over RASTER_SHADING's keys.  Without normals the face normals
+    shade.  shape_mi355x.resolve_numpy gives the same bits."""
+    _require_raster()
+    v, f = _mesh(verts, faces)
+    A, K = _cameras(mesh2cam, intrinsics, v.device)
+    _require_cuda(vis)
+    if vis.dtype != torch.int64 or vis.ndim != 3 or vis.shape[0] != len(A) or not vis.is_contiguous() or vis.device != v.device:
+        raise ValueError('raster: vis must be rasterize\'s int64 [n_views, h, w] tensor')
+    want = tuple(outputs)
+    if not want or any(o not in RASTER_OUTPUTS for o in want):
+        raise ValueError(f'raster: outputs must be a non-empty subset of {RASTER_OUTPUTS}')
+    if normals is not None:
+        if normal_mat is None:
+            raise ValueError('raster: normals need normal_mat')
+        _require_cuda(normals, normal_mat)
+        normals, normal_mat = _f32(normals, (3,), 'normals'), _f32(normal_mat, (9,), 'normal_mat')
+        if len(normals) != len(v) or len(normal_mat) != len(A) or normals.device != v.device or normal_mat.device != v.device:
+            raise ValueError('raster: normals must be [V, 3] and normal_mat [n_views, 3, 3], on the mesh\'s device')
+    else:
+        normal_mat = None
+    if colors is not None:
+        _require_cuda(colors)
+        if colors.dtype != torch.uint8 or tuple(colors.shape) != (len(v), 3) or colors.device != v.device:
+            raise ValueError('raster: colors must be uint8 [V, 3] on the mesh\'s device')
+        colors = colors.detach().contiguous()
+    sh = shading_vector(shading)
+    e = _native.ext()
+    if e is not None and hasattr(e, 'raster_resolve'):
+        with _on_device(v.device):
+            got = e.raster_resolve(vis, v, f, A, K, normals, normal_mat, colors, sh, [o in want for o in RASTER_OUTPUTS])
+        return {o: t for o, t in zip(RASTER_OUTPUTS, got) if o in want}
+    return _resolve_ctypes(vis, v, f, A, K, normals, normal_mat, colors, sh, want)

@@ -17,6 +17,10 @@ The rules both follow (include/gnerf_hip.h, gnerf_marching_cubes_*):
     on a cube face (a neighbouring cell could draw the same one).  csrc/mesh_tables.h is
     case_table_header()'s output.
 
+render_mesh draws such a mesh from the renderer's cameras on the renderer's pixel grid (triangle ids, depth as image_depth measures it,
+normals, shaded frames): CUDA tensors go to the rasteriser kernels (csrc/raster.hip through gnerf_hip.rasterize / resolve), numpy arrays to
+rasterize_numpy / resolve_numpy below, which state the arithmetic (include/gnerf_hip.h, gnerf_raster_*) and give the same bits.
+
 CLI, as shape_utils.py's (:102-123):  python shape_mi355x.py INPUT [--level 10]   (INPUT: a .mrc / .npy file or a directory of them)
 """
 
@@ -244,6 +248,299 @@ def marching_cubes(volume, level, spacing=1.0, origin=(0.0, 0.0, 0.0)):
     if not identity:
         verts = verts * s + o
     return verts, faces
+
+
+# ---------------------------------------------------------------------------------------------------------------- rasteriser
+# The numpy port of csrc/raster.hip (include/gnerf_hip.h, gnerf_raster_*, states the rules): float32 throughout, one rounding per
+# operation in the kernel's order, integers in int64 -- the kernel's visibility buffer, counts and resolved images bit for bit.
+RASTER_SMALL_PIXELS = 64
+RASTER_CULL = {'none': 0, 'back': 1, 'front': 2}
+RASTER_EMPTY = np.uint64(0xFFFFFFFFFFFFFFFF)
+RASTER_SHADING = dict(light=(0.0, 0.0, -1.0), ambient=0.25, diffuse=0.75, albedo=(0.8, 0.8, 0.8), background=(1.0, 1.0, 1.0))
+_F = np.float32
+
+
+def _raster_cameras(mesh2cam, intrinsics):
+    A = np.ascontiguousarray(np.asarray(mesh2cam), dtype=np.float32)
+    K = np.ascontiguousarray(np.asarray(intrinsics), dtype=np.float32)
+    if A.size == 0 or A.size % 12 or K.size % 9 or A.size // 12 != K.size // 9:
+        raise ValueError('raster: mesh2cam must be [n_views, 3, 4] and intrinsics [n_views, 3, 3] for the same n_views >= 1')
+    return A.reshape(-1, 12), K.reshape(-1, 9)
+
+
+def _raster_mesh(verts, faces):
+    v = np.ascontiguousarray(np.asarray(verts), dtype=np.float32).reshape(-1, 3)
+    f = np.ascontiguousarray(np.asarray(faces), dtype=np.int32).reshape(-1, 3)
+    return v, f
+
+
+def _raster_size(size):
+    h, w = (size, size) if np.isscalar(size) else size
+    h, w = int(h), int(w)
+    if not (1 <= h <= 4096 and 1 <= w <= 4096):
+        raise ValueError(f'raster: the image size must be 1..4096 in each direction (got {h} x {w})')
+    return h, w
+
+
+def _raster_project(v, A, K, h, w, near):
+    """The vertex stage for one view: (cam float32 [V, 3], iz float32 [V], X int64 [V], Y int64 [V], bad uint8 [V]: 1 near, 2 guard)."""
+    x, y, z = v[:, 0], v[:, 1], v[:, 2]
+    with np.errstate(all='ignore'):
+        cam = np.stack([((A[4 * r] * x + A[4 * r + 1] * y) + A[4 * r + 2] * z) + A[4 * r + 3] for r in range(3)], axis=1)
+        near_bad = ~np.isfinite(cam).all(axis=1) | ~(cam[:, 2] > _F(near))
+        iz = np.where(near_bad, _F(0), _F(1) / np.where(near_bad, _F(1), cam[:, 2])).astype(np.float32)
+        xn, yn = cam[:, 0] * iz, cam[:, 1] * iz
+        fx, sk, cx, fy, cy = K[0], K[1], K[2], K[4], K[5]
+        xc = (fx * xn + sk * yn) + cx
+        yc = fy * yn + cy
+        fX = np.rint((xc * _F(w)) * _F(256))
+        fY = np.rint((yc * _F(h)) * _F(256))
+        guard_bad = ~near_bad & (~(np.abs(fX) <= _F(2097152)) | ~(np.abs(fY) <= _F(2097152)))
+    bad = np.where(near_bad, 1, np.where(guard_bad, 2, 0)).astype(np.uint8)
+    ok = bad == 0
+    X = np.where(ok, fX, 0).astype(np.int64)
+    Y = np.where(ok, fY, 0).astype(np.int64)
+    return cam.astype(np.float32), np.where(ok, iz, _F(0)).astype(np.float32), X, Y, bad
+
+
+def _raster_setup(f, n_verts, X, Y, iz, bad, cull, h, w):
+    """Triangle setup for one view over faces f [T, 3] -> dict of arrays [T] (status: 0 drawn, 1 near, 2 guard, 3 culled)."""
+    valid = ((f >= 0) & (f < n_verts)).all(axis=1)
+    g = np.where(valid[:, None], f, 0).astype(np.int64)
+    b = bad[g] if n_verts else np.zeros(g.shape, np.uint8)
+    X3, Y3, iz3 = (X[g], Y[g], iz[g]) if n_verts else (np.zeros(g.shape, np.int64), np.zeros(g.shape, np.int64), np.zeros(g.shape, np.float32))
+    area = (X3[:, 1] - X3[:, 0]) * (Y3[:, 2] - Y3[:, 0]) - (X3[:, 2] - X3[:, 0]) * (Y3[:, 1] - Y3[:, 0])
+    culled = (area == 0) | ((cull == 1) & (area > 0)) | ((cull == 2) & (area < 0))
+    status = np.where(~valid, 3, np.where((b == 1).any(axis=1), 1, np.where((b != 0).any(axis=1), 2, np.where(culled, 3, 0))))
+    flipped = area < 0
+    ib, ic = np.where(flipped, 2, 1), np.where(flipped, 1, 2)
+    rows = np.arange(len(f))
+    t = dict(status=status, flipped=flipped, area=np.abs(area), ia=g[:, 0], ib=g[rows, ib], ic=g[rows, ic],
+             ax=X3[:, 0], ay=Y3[:, 0], iza=iz3[:, 0], bx=X3[rows, ib], by=Y3[rows, ib], izb=iz3[rows, ib],
+             cx=X3[rows, ic], cy=Y3[rows, ic], izc=iz3[rows, ic])
+    c0 = np.maximum((X3.min(axis=1) + 127) >> 8, 0)
+    c1 = np.minimum((X3.max(axis=1) - 128) >> 8, w - 1)
+    r0 = np.maximum((Y3.min(axis=1) + 127) >> 8, 0)
+    r1 = np.minimum((Y3.max(axis=1) - 128) >> 8, h - 1)
+    bw, bh = np.maximum(c1 - c0 + 1, 0), np.maximum(r1 - r0 + 1, 0)
+    t.update(c0=c0, r0=r0, bw=bw, bh=bh, npx=np.where(status == 0, bw * bh, 0))
+    return t
+
+
+def _raster_owns(e, dx, dy):
+    return (e > 0) | ((e == 0) & ((dy < 0) | ((dy == 0) & (dx > 0))))
+
+
+def _raster_cover(t, row, col):
+    """Edge functions at the centres of pixels (row, col) (broadcast against the triangle fields of t) -> (covered, wa, wb, wc)."""
+    px, py = 256 * col + 128, 256 * row + 128
+    wa = (t['cx'] - t['bx']) * (py - t['by']) - (t['cy'] - t['by']) * (px - t['bx'])
+    wb = (t['ax'] - t['cx']) * (py - t['cy']) - (t['ay'] - t['cy']) * (px - t['cx'])
+    wc = (t['bx'] - t['ax']) * (py - t['ay']) - (t['by'] - t['ay']) * (px - t['ax'])
+    covered = (_raster_owns(wa, t['cx'] - t['bx'], t['cy'] - t['by']) & _raster_owns(wb, t['ax'] - t['cx'], t['ay'] - t['cy'])
+               & _raster_owns(wc, t['bx'] - t['ax'], t['by'] - t['ay']))
+    return covered, wa, wb, wc
+
+
+def _raster_iz(t, wa, wb, wc):
+    """(iz, ba, bb, bc): b_i = float32(w_i) / float32(area), iz = (ba iza + bb izb) + bc izc."""
+    fa = np.asarray(t['area']).astype(np.float32)
+    with np.errstate(all='ignore'):
+        ba, bb, bc = (np.asarray(x).astype(np.float32) / fa for x in (wa, wb, wc))
+        return (ba * t['iza'] + bb * t['izb']) + bc * t['izc'], ba, bb, bc
+
+
+def _raster_merge(vis_view, w, t, row, col, tri):
+    """Merge the centres of pixels (row, col) of the triangles t (indices tri; all broadcast against each other) into vis_view [h * w]."""
+    covered, wa, wb, wc = _raster_cover(t, row, col)
+    if not np.any(covered):
+        return
+    with np.errstate(all='ignore'):
+        z = np.asarray(_F(1) / _raster_iz(t, wa, wb, wc)[0], dtype=np.float32)
+    key = (np.ascontiguousarray(z).view(np.uint32).astype(np.uint64) << np.uint64(32)) | np.broadcast_to(np.asarray(tri, dtype=np.uint64), covered.shape)
+    pix = np.broadcast_to(row * w + col, covered.shape)
+    np.minimum.at(vis_view, pix[covered], key[covered])
+
+
+def rasterize_numpy(verts, faces, mesh2cam, intrinsics, size, near=0.01, cull='none'):
+    """The numpy port of gnerf_raster_visibility: (vis uint64 [n_views, h, w], counts int64 [4] = drawn, near, guard, culled)."""
+    v, f = _raster_mesh(verts, faces)
+    A, K = _raster_cameras(mesh2cam, intrinsics)
+    h, w = _raster_size(size)
+    if not near > 0:
+        raise ValueError('raster: near must be > 0')
+    if cull not in RASTER_CULL:
+        raise ValueError(f'raster: cull must be one of {tuple(RASTER_CULL)}')
+    n_views = len(A)
+    vis = np.full((n_views, h * w), RASTER_EMPTY, dtype=np.uint64)
+    counts = np.zeros(4, dtype=np.int64)
+    if len(v) == 0 or len(f) == 0:
+        return vis.reshape(n_views, h, w), counts
+    for view in range(n_views):
+        _, iz, X, Y, bad = _raster_project(v, A[view], K[view], h, w, near)
+        t = _raster_setup(f, len(v), X, Y, iz, bad, RASTER_CULL[cull], h, w)
+        counts += np.bincount(t['status'], minlength=4)[:4]
+        npx = t['npx']
+        small = np.nonzero((npx > 0) & (npx <= RASTER_SMALL_PIXELS))[0]
+        if len(small):                                                   # the thread-per-triangle route: pixel i of every box at once
+            ts = {k: x[small] for k, x in t.items()}
+            for i in range(int(ts['npx'].max())):
+                sel = np.nonzero(i < ts['npx'])[0]
+                sub = {k: x[sel] for k, x in ts.items()}
+                r = i // sub['bw']
+                _raster_merge(vis[view], w, sub, sub['r0'] + r, sub['c0'] + (i - r * sub['bw']), small[sel])
+        for k in np.nonzero(npx > RASTER_SMALL_PIXELS)[0]:               # the queued route: one triangle, its whole box
+            one = {name: x[k] for name, x in t.items()}
+            rr, cc = np.meshgrid(one['r0'] + np.arange(one['bh']), one['c0'] + np.arange(one['bw']), indexing='ij')
+            _raster_merge(vis[view], w, one, rr, cc, k)
+    return vis.reshape(n_views, h, w), counts
+
+
+def _shading_vector(shading):
+    s = dict(RASTER_SHADING, **(shading or {}))
+    unknown = set(s) - set(RASTER_SHADING)
+    if unknown:
+        raise ValueError(f'raster: unknown shading parameter(s) {sorted(unknown)}')
+    vec = np.array([*s['light'], s['ambient'], s['diffuse'], *s['albedo'], *s['background']], dtype=np.float32)
+    if vec.shape != (11,):
+        raise ValueError('raster: light, albedo and background are triples, ambient and diffuse scalars')
+    return vec
+
+
+def _to_u8(x):
+    return np.rint(np.fmin(np.fmax(x, _F(0)), _F(1)) * _F(255)).astype(np.int32).astype(np.uint8)
+
+
+def resolve_numpy(vis, verts, faces, mesh2cam, intrinsics, normals=None, normal_mat=None, colors=None, shading=None,
+                  outputs=('tri_id', 'depth', 'normal', 'frame')):
+    """The numpy port of gnerf_raster_resolve: dict of tri_id int32 [n, h, w], depth float32 [n, h, w], normal float32 [n, h, w, 3],
+    frame uint8 [n, h, w, 3] (those named in `outputs`).  shading: dict over RASTER_SHADING's keys."""
+    v, f = _raster_mesh(verts, faces)
+    A, K = _raster_cameras(mesh2cam, intrinsics)
+    vis = np.asarray(vis)
+    n_views, h, w = vis.shape
+    if len(A) != n_views:
+        raise ValueError('raster: vis and the cameras disagree about n_views')
+    sh = _shading_vector(shading)
+    light, ambient, diffuse, albedo, background = sh[0:3], sh[3], sh[4], sh[5:8], sh[8:11]
+    if normals is not None:
+        normals = np.ascontiguousarray(np.asarray(normals), dtype=np.float32).reshape(-1, 3)
+        N = np.ascontiguousarray(np.asarray(normal_mat), dtype=np.float32).reshape(n_views, 9)
+        if len(normals) != len(v):
+            raise ValueError('raster: normals must be [V, 3]')
+    if colors is not None:
+        colors = np.asarray(colors)
+        if colors.dtype != np.uint8 or colors.shape != (len(v), 3):
+            raise ValueError('raster: colors must be uint8 [V, 3]')
+    tri_id = np.full((n_views, h, w), -1, dtype=np.int32)
+    depth = np.full((n_views, h, w), np.inf, dtype=np.float32)
+    normal = np.zeros((n_views, h, w, 3), dtype=np.float32)
+    frame = np.empty((n_views, h, w, 3), dtype=np.uint8)
+    frame[...] = _to_u8(background)
+    n_tris = len(f) if len(v) else 0
+    for view in range(n_views):
+        key = vis[view].reshape(-1).astype(np.uint64)
+        tri = (key & np.uint64(0xFFFFFFFF)).astype(np.int64)
+        pix = np.nonzero((key != RASTER_EMPTY) & (tri < n_tris))[0]
+        if len(pix) == 0:
+            continue
+        cam, iz_v, X, Y, bad = _raster_project(v, A[view], K[view], h, w, 0.0)
+        t = _raster_setup(f[tri[pix]], len(v), X, Y, iz_v, bad, 0, h, w)
+        keep = t['status'] == 0
+        pix = pix[keep]
+        t = {k: x[keep] for k, x in t.items()}
+        tri = tri[pix]
+        row, col = pix // w, pix % w
+        _, wa, wb, wc = _raster_cover(t, row, col)
+        with np.errstate(all='ignore'):
+            iz, ba, bb, bc = _raster_iz(t, wa, wb, wc)
+            z = _F(1) / iz
+            fx, sk, cx, fy, cy = K[view][0], K[view][1], K[view][2], K[view][4], K[view][5]
+            xc = col.astype(np.float32) * (_F(1) / _F(w)) + (_F(0.5) / _F(w))
+            yc = row.astype(np.float32) * (_F(1) / _F(h)) + (_F(0.5) / _F(h))
+            xl = xc - cx
+            xl = xl + (cy * sk) / fy
+            xl = xl - (sk * yc) / fy
+            xl = xl / fx
+            yl = (yc - cy) / fy
+            tri_id[view].reshape(-1)[pix] = tri
+            depth[view].reshape(-1)[pix] = z * np.sqrt((xl * xl + yl * yl) + _F(1))
+            qa, qb, qc = (ba * t['iza']) / iz, (bb * t['izb']) / iz, (bc * t['izc']) / iz
+            if normals is not None:
+                na, nb, nc = normals[t['ia']], normals[t['ib']], normals[t['ic']]
+                m = (qa[:, None] * na + qb[:, None] * nb) + qc[:, None] * nc
+                Nv = N[view]
+                n = np.stack([(Nv[3 * r] * m[:, 0] + Nv[3 * r + 1] * m[:, 1]) + Nv[3 * r + 2] * m[:, 2] for r in range(3)], axis=1)
+            else:
+                g = f[tri].astype(np.int64)
+                p0, p1, p2 = cam[g[:, 0]], cam[g[:, 1]], cam[g[:, 2]]
+                e1, e2 = p1 - p0, p2 - p0
+                n = np.stack([e1[:, 1] * e2[:, 2] - e1[:, 2] * e2[:, 1], e1[:, 2] * e2[:, 0] - e1[:, 0] * e2[:, 2],
+                              e1[:, 0] * e2[:, 1] - e1[:, 1] * e2[:, 0]], axis=1)
+            length = np.sqrt((n[:, 0] * n[:, 0] + n[:, 1] * n[:, 1]) + n[:, 2] * n[:, 2])
+            ok = length > 0
+            n = np.where(ok[:, None], n / np.where(ok, length, _F(1))[:, None], _F(0)).astype(np.float32)
+            away = ((n[:, 0] * xl + n[:, 1] * yl) + n[:, 2]) > 0
+            n = np.where(away[:, None], -n, n)
+            normal[view].reshape(-1, 3)[pix] = n
+            ndl = np.fmax(_F(0), (n[:, 0] * light[0] + n[:, 1] * light[1]) + n[:, 2] * light[2])
+            shade = ambient + diffuse * ndl
+            if colors is not None:
+                ca, cb, cc = (colors[t[k]].astype(np.float32) for k in ('ia', 'ib', 'ic'))
+                base = ((qa[:, None] * ca + qb[:, None] * cb) + qc[:, None] * cc) / _F(255)
+            else:
+                base = np.broadcast_to(albedo, (len(pix), 3))
+            frame[view].reshape(-1, 3)[pix] = _to_u8(base * shade[:, None])
+    out = dict(tri_id=tri_id, depth=depth, normal=normal, frame=frame)
+    return {k: out[k] for k in outputs}
+
+
+def mesh_to_camera(cam2world, mesh2world=None):
+    """Per-view mesh2cam [n, 3, 4] and normal_mat [n, 3, 3] as float32, made in float64 and rounded once: mesh2cam = inverse(cam2world) @
+    mesh2world (cam2world [n, 4, 4] or [4, 4]; mesh2world a 3x4 / 4x4 affine, identity when None); normal_mat takes a normal of the mesh frame
+    to the camera frame as a covector, inverse(linear part)^T (its scale does not matter: the rasteriser normalises)."""
+    c2w = np.asarray(cam2world, dtype=np.float64).reshape(-1, 4, 4)
+    M = np.eye(4)
+    if mesh2world is not None:
+        mw = np.asarray(mesh2world, dtype=np.float64)
+        M[:3] = mw[:3]
+    full = np.linalg.inv(c2w) @ M
+    lin = full[:, :3, :3]
+    return full[:, :3, :].astype(np.float32), np.linalg.inv(lin).transpose(0, 2, 1).astype(np.float32)
+
+
+def render_mesh(verts, faces, cam2world, intrinsics, size, mesh2world=None, normals=None, colors=None, near=0.01, cull='none', shading=None,
+                outputs=('tri_id', 'depth', 'normal', 'frame')):
+    """Draw a triangle mesh from n cameras (cam2world [n, 4, 4] and normalised intrinsics [n, 3, 3]: what a camera label holds) on the
+    renderer's pixel grid -> dict of `outputs` (tri_id, depth as image_depth measures it, camera-frame normal, shaded uint8 frame) plus
+    'counts'.  CUDA tensors run the gfx950 kernels (gnerf_hip.rasterize / resolve) and return tensors on their device; numpy arrays run
+    the numpy port -- the same bits either way.  normals [V, 3] are in the mesh's frame (mesh_vertex_attributes'), colors uint8 [V, 3]."""
+    try:
+        import torch
+    except ImportError:                                                  # pragma: no cover - torch is part of the stack
+        torch = None
+    on_gpu = torch is not None and isinstance(verts, torch.Tensor) and verts.is_cuda
+
+    def host(x):
+        return x.detach().cpu().numpy() if torch is not None and isinstance(x, torch.Tensor) else np.asarray(x)
+    mesh2cam, normal_mat = mesh_to_camera(host(cam2world), None if mesh2world is None else host(mesh2world))
+    K = np.ascontiguousarray(host(intrinsics), dtype=np.float32).reshape(-1, 9)
+    if on_gpu:
+        import gnerf_hip
+        dev = verts.device
+        A, Kd, Nd = (torch.from_numpy(np.ascontiguousarray(x)).to(dev) for x in (mesh2cam.reshape(-1, 12), K, normal_mat.reshape(-1, 9)))
+        vis, counts = gnerf_hip.rasterize(verts, faces, A, Kd, size, near=near, cull=cull)
+        out = gnerf_hip.resolve(vis, verts, faces, A, Kd, normals=normals, normal_mat=Nd if normals is not None else None, colors=colors,
+                                shading=shading, outputs=outputs)
+        out['counts'] = counts
+        return out
+    if torch is not None:
+        verts, faces, normals, colors = (None if x is None else host(x) for x in (verts, faces, normals, colors))
+    vis, counts = rasterize_numpy(verts, faces, mesh2cam, K, size, near=near, cull=cull)
+    out = resolve_numpy(vis, verts, faces, mesh2cam, K, normals=normals, normal_mat=normal_mat if normals is not None else None, colors=colors,
+                        shading=shading, outputs=outputs)
+    out['counts'] = counts
+    return out
 
 
 # ---------------------------------------------------------------------------------------------------------------- PLY

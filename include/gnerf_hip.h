@@ -657,6 +657,62 @@ int gnerf_resize_aa_forward(const void* x, void* y, int dtype, int n, int c, int
 int gnerf_resize_aa_backward(const void* dy, void* dx, int dtype, int n, int c, int in_h, int in_w, int out_h, int out_w, const int64_t* dy_strides,
                              const int64_t* dx_strides, int mode, double scale_h, double scale_w, gnerf_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * (ABI 15, added without a new version) Triangle rasteriser for the meshes gnerf_marching_cubes_* extracts: a visibility buffer per view,
+ * then depth / normal / shaded colour per pixel.  No gradients, no antialiasing, no textures, no transparency, and NO NEAR-PLANE CLIPPING:
+ * a triangle with a vertex at or behind `near` is dropped whole (the shipped cameras sit 2.7 from a unit box).  Everything is float32 with
+ * every operation rounded on its own, in the order written here (no fused multiply-add); g-nerf_amd/shape_mi355x.py's rasterize_numpy /
+ * resolve_numpy restate it and give the same bits.
+ *   inputs: verts float32 [n_verts, 3] and faces int32 [n_tris, 3] (as marching cubes returns them, in the mesh's own frame); per view a
+ *     3x4 mesh2cam (device float32 [n_views, 12], rows) into the camera frame csrc/raygen.h implies (+z forward, x along columns, y along
+ *     rows) and the camera label's normalised 3x3 intrinsics (device float32 [n_views, 9]); an h x w image (1..GNERF_RASTER_MAX_SIZE each);
+ *     near > 0; n_views * n_tris < 2^31 and n_views * h * w < 2^31.  n_tris == 0 or n_verts == 0 is valid: nothing is drawn.
+ *   vertex: p = ((A0 x + A1 y) + A2 z) + A3 per row; iz = 1 / p.z; xn = p.x iz, yn = p.y iz; xc = (fx xn + sk yn) + cx, yc = fy yn + cy (the
+ *     inverse of ray_sampler.py:51-52); sx = xc w, sy = yc h, so that the centre of pixel (row, col) is (col + 0.5, row + 0.5);
+ *     X = (int)rintf(sx * 256), Y likewise: 1/256-pixel integers.
+ *   dropped, counted and never drawn, tested in this order: a vertex with non-finite p or p.z <= near ("near"); a vertex with |X| or |Y| > 2^21,
+ *     an 8192-pixel guard band ("guard"); area = (X1 - X0)(Y2 - Y0) - (X2 - X0)(Y1 - Y0) == 0, or the culled winding -- GNERF_RASTER_CULL_BACK
+ *     drops area > 0 (with y down that is the winding whose right-hand normal cross(p1 - p0, p2 - p0) points away from the camera),
+ *     GNERF_RASTER_CULL_FRONT drops area < 0 --, or a face that names a vertex outside [0, n_verts) ("culled").  Everything else is "drawn".
+ *   coverage: a triangle with area < 0 is drawn as (0, 2, 1).  Integer edge functions in int64 at pixel centres (256 col + 128, 256 row + 128)
+ *     inside the bounding box clipped to the image; a centre exactly on an edge belongs to the triangle iff that edge runs up (dy < 0, a left
+ *     edge) or is horizontal and runs right (a top edge), so of two triangles sharing an edge or a fan sharing a vertex exactly one owns it.
+ *   depth: b_i = float(w_i) / float(area) (int64 -> float32, round to nearest even), iz = (b_a iz_a + b_b iz_b) + b_c iz_c, z = 1 / iz.
+ *   vis: uint64 [n_views, h, w], key = float_as_uint(z) << 32 | triangle index, merged with a 64-bit atomic minimum; empty = all ones.  The
+ *     nearest wins, equal z: the lowest index; the result does not depend on the order of arrival (the same bits on every run).
+ *   routes: a triangle whose clipped bounding box holds at most GNERF_RASTER_SMALL_PIXELS centres is drawn by its own thread; a larger one is
+ *     appended to a queue in the workspace and drawn by a whole wave of a second, fixed-size launch that reads the queue length on the device.
+ * gnerf_raster_workspace_bytes: *bytes = the workspace of gnerf_raster_visibility (the queue: 4 bytes per (view, triangle) + 256).
+ * gnerf_raster_visibility: initialises vis, counts and the workspace itself (no prepared memory needed), then draws: three launches, no host
+ *   read, capturable.  counts: device int64 [4] = {drawn, near, guard, culled}, which sum to n_views * n_tris.
+ * gnerf_raster_resolve: one thread per pixel, from vis and the same mesh and cameras.  Optional inputs: normals float32 [n_verts, 3] with the
+ *   per-view 3x3 normal_mat (device float32 [n_views, 9]) that takes them to the camera frame; colors uint8 [n_verts, 3].  shading: ELEVEN HOST
+ *   floats {light direction in the camera frame [3] (from the surface to the light, used as given), ambient, diffuse, albedo [3], background [3]},
+ *   needed for `frame`.  Outputs, each optional (NULL = not wanted, not all NULL):
+ *     tri_id int32 [n_views, h, w], -1 for background;
+ *     depth float32 [n_views, h, w]: the distance along the pixel's ray, z * sqrt((xl xl + yl yl) + 1) with (xl, yl) as camera_ray forms them
+ *       from (row, col) (1 / w and 1 / h in place of 1 / res) -- what image_depth holds; background = +inf;
+ *     normal float32 [n_views, h, w, 3]: camera frame, unit length (zero where the length is not > 0), negated where (n . (xl, yl, 1)) > 0 so that
+ *       it faces the camera, zero for background.  With `normals`: normal_mat times the perspective-correct mix (q_a n_a + q_b n_b) + q_c n_c,
+ *       q_i = (b_i iz_i) / iz; without: the face normal cross(p1 - p0, p2 - p0) of the camera-frame positions;
+ *     frame uint8 [n_views, h, w, 3]: rintf(min(max(c * (ambient + diffuse * max(0, n . light)), 0), 1) * 255), c = albedo or the mix of the
+ *       vertex colours / 255; background pixels hold the background colour.
+ *   The barycentrics are those of the depth step, recomputed from the winning triangle (the same bits).
+ * GNERF_E_ARG for null pointers, sizes out of range, near <= 0, an unknown cull mode, normals without normal_mat, frame without shading. */
+#define GNERF_RASTER_SMALL_PIXELS 64
+#define GNERF_RASTER_MAX_SIZE 4096
+#define GNERF_RASTER_CULL_NONE 0
+#define GNERF_RASTER_CULL_BACK 1
+#define GNERF_RASTER_CULL_FRONT 2
+int gnerf_raster_workspace_bytes(int n_verts, int n_tris, int n_views, int h, int w, size_t* bytes);
+int gnerf_raster_visibility(const float* verts, int n_verts, const int32_t* faces, int n_tris, const float* mesh2cam, const float* intrinsics,
+                            int n_views, int h, int w, float near_z, int cull, void* workspace, uint64_t* vis, int64_t* counts,
+                            gnerf_stream_t stream);
+int gnerf_raster_resolve(const uint64_t* vis, const float* verts, int n_verts, const int32_t* faces, int n_tris, const float* mesh2cam,
+                         const float* intrinsics, int n_views, int h, int w, const float* normals, const float* normal_mat,
+                         const unsigned char* colors, const float* shading, int32_t* tri_id, float* depth, float* normal, unsigned char* frame,
+                         gnerf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
