@@ -13,7 +13,7 @@
 // marching_cubes (gnerf_hip.marching_cubes' count -> read counts -> emit sequence), ssim_forward / ssim_backward (gnerf_hip.ssim_*),
 // modconv_backward (gnerf_hip.scale_channels_backward / modconv_epilogue_backward), query_points_grad (gnerf_hip.query_points_grad),
 // render_backward_rays (gnerf_hip.render_backward with need_rays), resize_aa (gnerf_hip.resize_aa_forward / _backward),
-// raster_visibility / raster_resolve (gnerf_hip.rasterize / resolve).
+// raster_visibility / raster_resolve (gnerf_hip.rasterize / resolve), mesh_components / mesh_compact / mesh_smooth (gnerf_hip's of those names).
 //
 // Built ahead of time by csrc/build.sh (g++, no hipcc: there is no device code) into g-nerf_amd/gnerf_hip/gnerf_torch_ext.so.
 
@@ -605,6 +605,72 @@ std::vector<c10::optional<Tensor>> raster_resolve(Tensor vis, Tensor verts, Tens
     return out;
 }
 
+// ------------------------------------------------------------------------------------------------ mesh cleaning (csrc/mesh_clean.hip)
+// gnerf_hip.mesh_components / mesh_compact / mesh_smooth have validated the tensors: verts float32 [V, 3], faces int32 [T, 3], label and
+// faces_of int32 [V], keep uint8 [V], all contiguous on one GPU.
+Tensor mesh_workspace(int n_verts, int n_tris, const Tensor& like) {
+    size_t bytes = 0;
+    check_rc(gnerf_mesh_workspace_bytes(n_verts, n_tris, &bytes), "gnerf_mesh_workspace_bytes");
+    return torch::empty({int64_t(bytes)}, like.options().dtype(torch::kUInt8));
+}
+
+// -> (label [V], faces_of [V], counts int64 [3] on the host: components with a face, vertices in no face, faces out of range)
+std::tuple<Tensor, Tensor, Tensor> mesh_components(Tensor faces, int64_t n_verts) {
+    TORCH_CHECK(faces.is_cuda() && faces.scalar_type() == torch::kInt32 && faces.is_contiguous(), "mesh_components: faces must be a contiguous int32 GPU tensor");
+    TORCH_CHECK(n_verts >= 0 && n_verts <= INT_MAX && faces.size(0) <= INT_MAX, "mesh_components: oversized argument");
+    const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(at::device_of(faces));
+    const int nv = int(n_verts), nt = int(faces.size(0));
+    Tensor ws = mesh_workspace(nv, nt, faces);
+    Tensor label = torch::empty({n_verts}, faces.options()), faces_of = torch::empty({n_verts}, faces.options());
+    Tensor counts = torch::empty({3}, faces.options().dtype(torch::kInt64));
+    check_rc(gnerf_mesh_components(nt ? faces.data_ptr<int32_t>() : nullptr, nv, nt, ws.data_ptr(), nv ? label.data_ptr<int32_t>() : nullptr,
+                                   nv ? faces_of.data_ptr<int32_t>() : nullptr, counts.data_ptr<int64_t>(), current_stream()),
+             "gnerf_mesh_components");
+    return std::make_tuple(label, faces_of, counts.cpu());
+}
+
+// -> (verts' [V', 3], faces' [T', 3], src_vertex [V'], counts int64 [2] on the host: V', T')
+std::tuple<Tensor, Tensor, Tensor, Tensor> mesh_compact(Tensor verts, Tensor faces, Tensor label, Tensor faces_of, Tensor keep) {
+    TORCH_CHECK(verts.is_cuda() && verts.scalar_type() == torch::kFloat32 && verts.is_contiguous() && faces.scalar_type() == torch::kInt32 &&
+                faces.is_contiguous() && label.scalar_type() == torch::kInt32 && label.is_contiguous() && faces_of.scalar_type() == torch::kInt32 &&
+                faces_of.is_contiguous() && keep.scalar_type() == torch::kUInt8 && keep.is_contiguous(), "mesh_compact: unexpected tensor layout");
+    TORCH_CHECK(verts.size(0) <= INT_MAX && faces.size(0) <= INT_MAX && label.numel() == verts.size(0) && faces_of.numel() == verts.size(0) &&
+                keep.numel() == verts.size(0), "mesh_compact: label, faces_of and keep hold one value per vertex");
+    const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(at::device_of(verts));
+    const int nv = int(verts.size(0)), nt = int(faces.size(0));
+    Tensor ws = mesh_workspace(nv, nt, verts);
+    Tensor counts = torch::empty({2}, verts.options().dtype(torch::kInt64));
+    const int32_t* f = nt ? faces.data_ptr<int32_t>() : nullptr;
+    const int32_t* l = nv ? label.data_ptr<int32_t>() : nullptr;
+    const int32_t* fo = nv ? faces_of.data_ptr<int32_t>() : nullptr;
+    const unsigned char* k = nv ? keep.data_ptr<unsigned char>() : nullptr;
+    check_rc(gnerf_mesh_compact_count(f, nv, nt, l, fo, k, ws.data_ptr(), counts.data_ptr<int64_t>(), current_stream()), "gnerf_mesh_compact_count");
+    Tensor host = counts.cpu();                                    // the op's one synchronisation
+    const int64_t* c = host.data_ptr<int64_t>();
+    Tensor out_v = torch::empty({c[0], 3}, verts.options());
+    Tensor out_f = torch::empty({c[1], 3}, verts.options().dtype(torch::kInt32));
+    Tensor src = torch::empty({c[0]}, verts.options().dtype(torch::kInt32));
+    if (c[0] > 0)
+        check_rc(gnerf_mesh_compact_emit(verts.data_ptr<float>(), f, nv, nt, l, fo, k, ws.data_ptr(), out_v.data_ptr<float>(),
+                                         c[1] > 0 ? out_f.data_ptr<int32_t>() : nullptr, src.data_ptr<int32_t>(), current_stream()),
+                 "gnerf_mesh_compact_emit");
+    return std::make_tuple(out_v, out_f, src, host);
+}
+
+Tensor mesh_smooth(Tensor verts, Tensor faces, int64_t iterations, double lam, double mu, bool pin_boundary) {
+    TORCH_CHECK(verts.is_cuda() && verts.scalar_type() == torch::kFloat32 && verts.is_contiguous() && faces.scalar_type() == torch::kInt32 &&
+                faces.is_contiguous(), "mesh_smooth: unexpected tensor layout");
+    TORCH_CHECK(verts.size(0) <= INT_MAX && faces.size(0) <= INT_MAX && iterations >= 0 && iterations <= INT_MAX / 2, "mesh_smooth: argument out of range");
+    const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(at::device_of(verts));
+    const int nv = int(verts.size(0)), nt = int(faces.size(0));
+    Tensor ws = mesh_workspace(nv, nt, verts);
+    Tensor out = torch::empty_like(verts);
+    check_rc(gnerf_mesh_smooth(nv ? verts.data_ptr<float>() : nullptr, nv, nt ? faces.data_ptr<int32_t>() : nullptr, nt, int(iterations), float(lam),
+                               float(mu), pin_boundary ? 1 : 0, ws.data_ptr(), nv ? out.data_ptr<float>() : nullptr, current_stream()),
+             "gnerf_mesh_smooth");
+    return out;
+}
+
 }  // namespace
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -624,6 +690,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("resize_aa", &resize_aa);
     m.def("raster_visibility", &raster_visibility);
     m.def("raster_resolve", &raster_resolve);
+    m.def("mesh_components", &mesh_components);
+    m.def("mesh_compact", &mesh_compact);
+    m.def("mesh_smooth", &mesh_smooth);
     // the header version THIS extension was compiled against (a compile-time constant: gnerf_abi_version() would resolve in
     // libgnerf_hip.so at run time and compare the library with itself); gnerf_hip.ext() checks both against its own
     m.def("abi_version", []() { return int(GNERF_ABI_VERSION); });

@@ -22,6 +22,8 @@ HIP graph captured once (FrameProgram); `--shapes out.npy` also extracts the 512
 is still on the device; `--mesh-attrs normals|colors|all` adds the density field's normals and the decoder's colours per vertex.
 `--geometry-out geo.npy` draws that mesh from every orbit camera with the triangle rasteriser (csrc/raster.hip): shaded geometry frames on
 the renderer's pixel grid, uint8 [F, H, W, 3] at `--geometry-res`, smooth-shaded / coloured with `--mesh-attrs`.
+`--mesh-keep K`, `--mesh-min-faces N` and `--mesh-smooth ITERS` clean the mesh of both first (csrc/mesh_clean.hip): only the K largest connected
+components / those with at least N triangles stay, then ITERS Taubin iterations fair the surface; all 0 by default, which changes nothing.
 """
 
 import argparse
@@ -312,11 +314,38 @@ def mesh_vertex_attributes(G, planes, verts, resolution, want_normals=True, want
     return (torch.cat(normals or [empty]) if want_normals else None), (torch.cat(colors or [empty.to(torch.uint8)]) if want_colors else None)
 
 
-def mesh_density_grid(vol, ply_path, level=10.0, attrs=None, G=None, planes=None):
+def clean_extracted_mesh(verts, faces, clean):
+    """The first half of the --mesh-keep / --mesh-min-faces / --mesh-smooth flags on a mesh marching cubes just made: components, selection
+    and compaction (shape_mi355x.clean_mesh without smoothing), so that vertex attributes are queried at the kept vertices only, at their
+    extracted positions.  clean: shape_mi355x.clean_options' dict or None (nothing runs) -> (verts, faces, report or None)."""
+    if not clean:
+        return verts, faces, None
+    import shape_mi355x
+    cleaned = shape_mi355x.clean_mesh(verts, faces, keep_largest=clean['keep_largest'], min_faces=clean['min_faces'])
+    return cleaned.verts, cleaned.faces, cleaned.report
+
+
+def smooth_extracted_mesh(verts, faces, clean):
+    """The second half: the Taubin iterations, which move positions last (normals and colours stay those of the extracted surface)."""
+    if not clean or not clean['smooth']:
+        return verts
+    import shape_mi355x
+    if isinstance(verts, torch.Tensor) and verts.is_cuda:
+        import gnerf_hip
+        return gnerf_hip.mesh_smooth(verts, faces, clean['smooth'])
+    smoothed = shape_mi355x.mesh_smooth_numpy(verts.numpy() if isinstance(verts, torch.Tensor) else verts, faces.numpy() if isinstance(faces, torch.Tensor) else faces,
+                                              clean['smooth'])
+    return torch.from_numpy(smoothed) if isinstance(verts, torch.Tensor) else smoothed
+
+
+def mesh_density_grid(vol, ply_path, level=10.0, attrs=None, G=None, planes=None, clean=None, report=None):
     """--mesh: the mesh shape_utils.convert_mrc makes of the .mrc of this volume (shape_utils.py:103-105: transpose(2, 1, 0), voxel
     size 1, origin 0), made where the volume lives -- on a GPU the marching-cubes kernel reads it in HBM, only the mesh comes to the host.
     attrs: None / 'none', 'normals', 'colors' or 'all' -- per-vertex attributes (mesh_vertex_attributes) of generator G on `planes`
     (extract_density_grid(..., return_planes=True)), evaluated on the device too; the vertices stay in index space, as the reference's.
+    clean: None or shape_mi355x.clean_options' dict -- marching cubes, then components and compaction, then the attributes (at the kept
+    vertices' extracted positions), then smoothing.  report: a dict that receives clean_mesh's report when the mesh was cleaned (left as
+    it is otherwise).
     Writes `ply_path`; returns (vertex count, triangle count, seconds spent in marching cubes)."""
     import shape_mi355x
     attrs = 'none' if attrs is None else attrs
@@ -327,11 +356,15 @@ def mesh_density_grid(vol, ply_path, level=10.0, attrs=None, G=None, planes=None
     t0 = time.perf_counter()
     verts, faces = shape_mi355x.marching_cubes(vol.permute(2, 1, 0).contiguous(), level)     # (reads its counts: synchronised)
     dt = time.perf_counter() - t0
+    verts, faces, cleaned = clean_extracted_mesh(verts, faces, clean)
+    if report is not None and cleaned is not None:
+        report.update(cleaned)
     normals = colors = None
     if attrs != 'none':
         v = verts if isinstance(verts, torch.Tensor) else torch.from_numpy(verts).to(vol.device)
         normals, colors = mesh_vertex_attributes(G, planes, v, vol.shape[0], attrs in ('normals', 'all'), attrs in ('colors', 'all'))
         normals, colors = (None if t is None else t.cpu().numpy() for t in (normals, colors))
+    verts = smooth_extracted_mesh(verts, faces, clean)
     if isinstance(verts, torch.Tensor):
         verts, faces = verts.cpu().numpy(), faces.cpu().numpy()
     shape_mi355x.write_ply(ply_path, verts, faces, normals=normals, colors=colors)
@@ -382,12 +415,19 @@ def main():
     ap.add_argument('--mesh', default=None, help='also mesh the density volume on the device and write this .ply (shape_utils.py; rank 0)')
     ap.add_argument('--mesh-level', type=float, default=10, help='isosurface level of --mesh (shape_utils.py:111)')
     ap.add_argument('--mesh-attrs', choices=MESH_ATTRS, default='none', help='per-vertex attributes of --mesh: normals of the density field and / or the decoder\'s colours')
+    ap.add_argument('--mesh-keep', type=int, default=0, help='keep only this many of the largest connected components of the mesh (--mesh and --geometry-out; 0: all)')
+    ap.add_argument('--mesh-min-faces', type=int, default=0, help='drop connected components with fewer triangles than this (0: none)')
+    ap.add_argument('--mesh-smooth', type=int, default=0, help='Taubin smoothing iterations of the mesh, applied last (lambda 0.5, mu -0.53, boundaries pinned; 0: none)')
     ap.add_argument('--voxel-res', type=int, default=512)
     ap.add_argument('--geometry-out', default=None, help='also draw the mesh of the density volume from every orbit camera (shaded geometry frames, '
                                                          'uint8 [F, H, W, 3]) and write them to this .npy (rank 0); uses --voxel-res, --mesh-level, --mesh-attrs, --frames-per-call')
     ap.add_argument('--geometry-res', type=int, default=512, help='resolution of the geometry frames')
     ap.add_argument('--no-solver-search', action='store_true', help='leave torch.backends.cudnn.benchmark off (MIOpen takes its first heuristic pick per shape)')
     args = ap.parse_args()
+    if min(args.mesh_keep, args.mesh_min_faces, args.mesh_smooth) < 0:
+        ap.error('--mesh-keep, --mesh-min-faces and --mesh-smooth must be >= 0')
+    import shape_mi355x
+    clean = shape_mi355x.clean_options(args.mesh_keep, args.mesh_min_faces, args.mesh_smooth)
     H.configure_backend(False if args.no_solver_search else None)
 
     rank, world, local_rank = H.init_from_env()
@@ -442,18 +482,22 @@ def main():
         if args.shapes:
             np.save(args.shapes, vol.cpu().numpy())
         if args.shapes_mrc:
-            import shape_mi355x
             shape_mi355x.write_mrc(args.shapes_mrc, vol.cpu().numpy())
         if args.mesh:
             t0 = time.perf_counter()
-            nv, nf, dt = mesh_density_grid(vol, args.mesh, args.mesh_level, attrs=args.mesh_attrs, G=G, planes=planes)
+            report = {}
+            nv, nf, dt = mesh_density_grid(vol, args.mesh, args.mesh_level, attrs=args.mesh_attrs, G=G, planes=planes, clean=clean, report=report)
+            if report:
+                print(shape_mi355x.clean_report_line(report, args.mesh_smooth))
             print(f'mesh at level {args.mesh_level:g}: {dt * 1e3:.2f} ms, {nv} vertices, {nf} triangles -> {args.mesh}'
                   + (f' (with {args.mesh_attrs}: {(time.perf_counter() - t0) * 1e3:.2f} ms in all, file included)' if args.mesh_attrs != 'none' else ''))
     if args.geometry_out:
         # every rank meshes the volume itself (the same bits everywhere: no mesh travels between ranks), then draws its share of the cameras
-        import shape_mi355x
         vol, planes = volume_and_planes()
         verts, faces = shape_mi355x.marching_cubes(vol.permute(2, 1, 0).contiguous(), args.mesh_level)
+        verts, faces, report = clean_extracted_mesh(verts, faces, clean)
+        if report is not None and rank == 0 and not args.mesh:           # (--mesh has printed the same line)
+            print(shape_mi355x.clean_report_line(report, args.mesh_smooth))
         if not isinstance(verts, torch.Tensor):
             verts, faces = torch.from_numpy(verts), torch.from_numpy(faces)
         normals = colors = None
@@ -461,6 +505,7 @@ def main():
             normals, colors = mesh_vertex_attributes(G, planes, verts.to(device), args.voxel_res, args.mesh_attrs in ('normals', 'all'), args.mesh_attrs in ('colors', 'all'))
             if not verts.is_cuda:
                 normals, colors = (None if t is None else t.cpu() for t in (normals, colors))
+        verts = smooth_extracted_mesh(verts, faces, clean)
         if device.type == 'cuda':
             torch.cuda.synchronize()
         t0 = time.perf_counter()

@@ -1,4 +1,4 @@
-"""Marching cubes on the density volume (csrc/marching_cubes.hip)."""
+"""Marching cubes on the density volume (csrc/mesh.hip) and the cleaning of its meshes (csrc/mesh_clean.hip): components, compaction, smoothing."""
 
 import ctypes
 
@@ -58,3 +58,160 @@ def marching_cubes(volume, level):
         with _on_device(vol.device):
             return _marching_cubes_result(*e.marching_cubes(vol, float(level)))
     return _marching_cubes_result(*_marching_cubes_ctypes(vol, level))
+
+
+# ---------------------------------------------------------------------------------------------------------------- cleaning (csrc/mesh_clean.hip)
+_MESH_CLEAN_SYMBOLS = ('gnerf_mesh_workspace_bytes', 'gnerf_mesh_components', 'gnerf_mesh_compact_count', 'gnerf_mesh_compact_emit', 'gnerf_mesh_smooth')
+MESH_SMOOTH_MAX_FACES = 2 ** 32 // 6 - 1            # gnerf_mesh_smooth addresses its 6 T row entries with 32 bits
+
+
+def mesh_clean_available():
+    """Whether the loaded library has the mesh-cleaning kernels (a version-15 library built before them does not)."""
+    return all(hasattr(load(), name) for name in _MESH_CLEAN_SYMBOLS)
+
+
+def _require_mesh_clean():
+    if not mesh_clean_available():
+        raise RuntimeError('gnerf_hip: this libgnerf_hip.so was built without the mesh-cleaning kernels (gnerf_mesh_*): rebuild it (csrc/build.sh)')
+
+
+def _faces_i32(faces, what):
+    _require_cuda(faces)
+    f = faces.detach()
+    if f.numel() % 3 != 0:
+        raise ValueError(f'{what}: faces has shape {tuple(f.shape)}')
+    f = f.reshape(-1, 3)
+    return f if (f.dtype == torch.int32 and f.is_contiguous()) else f.to(torch.int32).contiguous()
+
+
+def _verts_f32(verts, what):
+    _require_cuda(verts)
+    v = verts.detach()
+    if v.numel() % 3 != 0:
+        raise ValueError(f'{what}: verts has shape {tuple(v.shape)}')
+    v = v.reshape(-1, 3)
+    return v if (v.dtype == torch.float32 and v.is_contiguous()) else v.to(torch.float32).contiguous()
+
+
+def _per_vertex(t, n_verts, dtype, dev, what, name):
+    _require_cuda(t)
+    t = t.detach().reshape(-1)
+    if t.numel() != n_verts or t.device != dev:
+        raise ValueError(f'{what}: {name} must hold one value per vertex, on the mesh\'s device')
+    return t if (t.dtype == dtype and t.is_contiguous()) else t.to(dtype).contiguous()
+
+
+def mesh_workspace_bytes(n_verts, n_tris):
+    _require_mesh_clean()
+    nbytes = ctypes.c_size_t()
+    _check(load().gnerf_mesh_workspace_bytes(int(n_verts), int(n_tris), ctypes.byref(nbytes)), 'gnerf_mesh_workspace_bytes')
+    return int(nbytes.value)
+
+
+def _mesh_workspace(n_verts, n_tris, dev):
+    return torch.empty(mesh_workspace_bytes(n_verts, n_tris), dtype=torch.uint8, device=dev)
+
+
+def _mesh_components_ctypes(f, n_verts):
+    """The ctypes route of mesh_components (f: int32 contiguous [T, 3] on a GPU) -> (label, faces_of, counts on the host)."""
+    dev = f.device
+    ws = _mesh_workspace(n_verts, len(f), dev)
+    label = torch.empty(n_verts, dtype=torch.int32, device=dev)
+    faces_of = torch.empty(n_verts, dtype=torch.int32, device=dev)
+    counts = torch.empty(3, dtype=torch.int64, device=dev)
+    _launch('gnerf_mesh_components', f, _ptr(f) if len(f) else None, n_verts, len(f), _ptr(ws), _ptr(label) if n_verts else None,
+            _ptr(faces_of) if n_verts else None, _ptr(counts))
+    return label, faces_of, counts.cpu()
+
+
+def _mesh_components_result(label, faces_of, counts):
+    n_bad = int(counts[2])
+    if n_bad:
+        raise ValueError(f'mesh_components: {n_bad} face(s) name a vertex outside [0, {len(label)})')
+    return label, faces_of, counts
+
+
+@profiled('gnerf_hip::mesh_components')
+def mesh_components(faces, n_verts):
+    """Connected components of a mesh's vertices under its faces (CUDA int32 [T, 3]; n_verts = V) on the gfx950 union-find kernels ->
+    (label int32 [V]: the smallest vertex index of each vertex's component, faces_of int32 [V]: faces per label, counts int64 [3] on the host:
+    components with a face, vertices in no face, faces out of range).  Rules: include/gnerf_hip.h, gnerf_mesh_*;
+    shape_mi355x.mesh_components_numpy gives the same bits.  Raises ValueError when a face names a vertex outside [0, V) (reads the counts)."""
+    _require_mesh_clean()
+    f = _faces_i32(faces, 'mesh_components')
+    n_verts = int(n_verts)
+    if not 0 <= n_verts < 2 ** 31:
+        raise ValueError(f'mesh_components: n_verts must be in [0, 2^31), got {n_verts}')
+    e = _native.ext()
+    if e is not None and hasattr(e, 'mesh_components'):
+        with _on_device(f.device):
+            return _mesh_components_result(*e.mesh_components(f, n_verts))
+    return _mesh_components_result(*_mesh_components_ctypes(f, n_verts))
+
+
+def _mesh_compact_ctypes(v, f, label, faces_of, keep):
+    """The ctypes route of mesh_compact (arguments as mesh_compact prepares them) -> (verts', faces', src_vertex, counts on the host)."""
+    dev, nv, nt = v.device, len(v), len(f)
+    ws = _mesh_workspace(nv, nt, dev)
+    counts = torch.empty(2, dtype=torch.int64, device=dev)
+    mesh = (_ptr(f) if nt else None, nv, nt, _ptr(label) if nv else None, _ptr(faces_of) if nv else None, _ptr(keep) if nv else None, _ptr(ws))
+    _launch('gnerf_mesh_compact_count', v, *mesh, _ptr(counts))
+    host = counts.cpu()                                                      # the op's one synchronisation
+    kv, kt = (int(c) for c in host)
+    out_v = torch.empty([kv, 3], dtype=torch.float32, device=dev)
+    out_f = torch.empty([kt, 3], dtype=torch.int32, device=dev)
+    src = torch.empty(kv, dtype=torch.int32, device=dev)
+    if kv:
+        _launch('gnerf_mesh_compact_emit', v, _ptr(v), *mesh, _ptr(out_v), _ptr(out_f) if kt else None, _ptr(src))
+    return out_v, out_f, src, host
+
+
+@profiled('gnerf_hip::mesh_compact')
+def mesh_compact(verts, faces, label, faces_of, keep):
+    """The mesh of the kept components: verts float32 [V, 3], faces int32 [T, 3], mesh_components' label and faces_of, and keep (bool / uint8
+    [V], INDEXED BY LABEL), all CUDA -> (verts' [V', 3], faces' [T', 3] with remapped ids, src_vertex int32 [V']: the old index of every new
+    vertex).  Order is stable, vertices in no face are dropped, and with everything kept the mesh comes back bit for bit (include/gnerf_hip.h,
+    gnerf_mesh_compact_*; shape_mi355x.mesh_compact_numpy gives the same bits).  Reads two counts to the host between its passes (not
+    graph-capturable)."""
+    _require_mesh_clean()
+    v, f = _verts_f32(verts, 'mesh_compact'), _faces_i32(faces, 'mesh_compact')
+    if f.device != v.device:
+        raise RuntimeError('mesh_compact: verts and faces must be on one device')
+    label = _per_vertex(label, len(v), torch.int32, v.device, 'mesh_compact', 'label')
+    faces_of = _per_vertex(faces_of, len(v), torch.int32, v.device, 'mesh_compact', 'faces_of')
+    keep = _per_vertex(keep, len(v), torch.uint8, v.device, 'mesh_compact', 'keep')
+    e = _native.ext()
+    if e is not None and hasattr(e, 'mesh_compact'):
+        with _on_device(v.device):
+            return tuple(e.mesh_compact(v, f, label, faces_of, keep)[:3])
+    return _mesh_compact_ctypes(v, f, label, faces_of, keep)[:3]
+
+
+def _mesh_smooth_ctypes(v, f, iterations, lam, mu, pin_boundary):
+    """The ctypes route of mesh_smooth (arguments as mesh_smooth prepares them)."""
+    ws = _mesh_workspace(len(v), len(f), v.device)
+    out = torch.empty_like(v)
+    _launch('gnerf_mesh_smooth', v, _ptr(v) if len(v) else None, len(v), _ptr(f) if len(f) else None, len(f), iterations, lam, mu, int(pin_boundary),
+            _ptr(ws), _ptr(out) if len(v) else None)
+    return out
+
+
+@profiled('gnerf_hip::mesh_smooth')
+def mesh_smooth(verts, faces, iterations, lam=0.5, mu=-0.53, pin_boundary=True):
+    """Taubin smoothing with uniform weights of verts float32 [V, 3] under faces int32 [T, 3] (CUDA): `iterations` times a half-step with lam,
+    then one with mu -> the new positions [V, 3].  pin_boundary keeps vertices on boundary or non-manifold edges in place.  Rules:
+    include/gnerf_hip.h, gnerf_mesh_smooth; shape_mi355x.mesh_smooth_numpy gives the same bits.  No host read: capturable."""
+    _require_mesh_clean()
+    v, f = _verts_f32(verts, 'mesh_smooth'), _faces_i32(faces, 'mesh_smooth')
+    if f.device != v.device:
+        raise RuntimeError('mesh_smooth: verts and faces must be on one device')
+    iterations = int(iterations)
+    if iterations < 0:
+        raise ValueError(f'mesh_smooth: iterations must be >= 0, got {iterations}')
+    if len(f) > MESH_SMOOTH_MAX_FACES:
+        raise ValueError(f'mesh_smooth: more than {MESH_SMOOTH_MAX_FACES} faces')
+    e = _native.ext()
+    if e is not None and hasattr(e, 'mesh_smooth'):
+        with _on_device(v.device):
+            return e.mesh_smooth(v, f, iterations, float(lam), float(mu), bool(pin_boundary))
+    return _mesh_smooth_ctypes(v, f, iterations, float(lam), float(mu), bool(pin_boundary))

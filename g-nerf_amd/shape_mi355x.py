@@ -21,10 +21,16 @@ render_mesh draws such a mesh from the renderer's cameras on the renderer's pixe
 normals, shaded frames): CUDA tensors go to the rasteriser kernels (csrc/raster.hip through gnerf_hip.rasterize / resolve), numpy arrays to
 rasterize_numpy / resolve_numpy below, which state the arithmetic (include/gnerf_hip.h, gnerf_raster_*) and give the same bits.
 
+clean_mesh edits such a mesh between extraction and its consumers: connected components, the selection of the large ones, compaction and
+Taubin smoothing.  CUDA tensors go to csrc/mesh_clean.hip (gnerf_hip.mesh_components / mesh_compact / mesh_smooth), numpy arrays to
+mesh_components_numpy / mesh_select / mesh_compact_numpy / mesh_smooth_numpy below (include/gnerf_hip.h, gnerf_mesh_*): the same bits.
+
 CLI, as shape_utils.py's (:102-123):  python shape_mi355x.py INPUT [--level 10]   (INPUT: a .mrc / .npy file or a directory of them)
+  [--mesh-keep K] [--mesh-min-faces N] [--mesh-smooth ITERS] clean the mesh first (all 0 by default: the file is the uncleaned one, byte for byte)
 """
 
 import argparse
+import collections
 import glob
 import os
 import struct
@@ -543,6 +549,206 @@ def render_mesh(verts, faces, cam2world, intrinsics, size, mesh2world=None, norm
     return out
 
 
+# ---------------------------------------------------------------------------------------------------------------- mesh cleaning
+# The numpy ports of csrc/mesh_clean.hip (include/gnerf_hip.h, gnerf_mesh_*, states the rules; restated here).  A mesh is verts float32
+# [V, 3] and faces int32 [T, 3] as marching_cubes returns them; V == 0 or T == 0 is valid.  A face is VALID iff its three ids lie in [0, V)
+# (ids may repeat); an invalid face joins nothing, is counted, dropped by the compaction and ignored by the smoothing.
+#   components: a valid face joins its three vertices.  label[v] = the smallest vertex index of v's component; faces_of[l] = the number of
+#     valid faces whose first vertex has label l; counts = (components with a face, vertices in no face, invalid faces).  Integers, unique.
+#   selection: components with a face by face count descending, then label ascending; kept iff face count >= min_faces and (keep_largest == 0
+#     or rank < keep_largest).
+#   compaction: a vertex is kept iff its component is (vertices in no face never are), a face iff it is valid and its first vertex is kept;
+#     both stay in ascending old index, face ids are remapped, src_vertex holds every new vertex's old index.
+#   smoothing: Taubin lambda | mu with uniform weights.  Corner c of every valid face gives vertex f[c] the two neighbours f[c + 1], f[c + 2]
+#     (cyclically); m_i = the size of that multiset N(i).  A half-step with factor s (a C float), per coordinate, in float64 with one rounding
+#     per operation: c = (sum over N(i) in ascending j, from 0.0, of double(v_j)) / double(m_i); v_i' = float32(double(v_i) + double(s) *
+#     (c - double(v_i))).  All vertices move together; an iteration is a half-step with lam, then one with mu.  m_i == 0 never moves; with
+#     pin_boundary neither does a vertex with a neighbour that does not occur exactly twice in N(i).
+CleanedMesh = collections.namedtuple('CleanedMesh', 'verts faces normals colors src_vertex report')
+
+
+def _mesh_faces(faces, n_verts):
+    """(faces as int64 [T, 3], valid [T])."""
+    f = np.asarray(faces)
+    if f.size % 3 != 0:
+        raise ValueError(f'mesh: faces has shape {f.shape}')
+    f = f.reshape(-1, 3).astype(np.int64)
+    n_verts = int(n_verts)
+    if not 0 <= n_verts < 2 ** 31:
+        raise ValueError(f'mesh: n_verts must be in [0, 2^31), got {n_verts}')
+    return f, np.all((f >= 0) & (f < n_verts), axis=1)
+
+
+def mesh_components_numpy(faces, n_verts, check=True):
+    """The numpy port of gnerf_mesh_components -> (label int32 [V], faces_of int32 [V], counts int64 [3]).  check: raise ValueError when a face
+    names a vertex outside [0, V), as gnerf_hip.mesh_components does (False: such faces are only counted, in counts[2])."""
+    f, ok = _mesh_faces(faces, n_verts)
+    n_verts = int(n_verts)
+    n_bad = int(len(f) - np.count_nonzero(ok))
+    if n_bad and check:
+        raise ValueError(f'mesh_components: {n_bad} face(s) name a vertex outside [0, {n_verts})')
+    g = f[ok]
+    parent = np.arange(n_verts, dtype=np.int64)
+    a, b = np.concatenate([g[:, 0], g[:, 0]]), np.concatenate([g[:, 1], g[:, 2]])
+    while len(a):                                                        # hook the larger root under the smaller, then flatten; an edge whose
+        ra, rb = parent[a], parent[b]                                    # ends share a root is settled for good
+        open_ = ra != rb
+        if not open_.any():
+            break
+        a, b, ra, rb = a[open_], b[open_], ra[open_], rb[open_]
+        np.minimum.at(parent, np.maximum(ra, rb), np.minimum(ra, rb))
+        while True:
+            pp = parent[parent]
+            if np.array_equal(pp, parent):
+                break
+            parent = pp
+    label = parent.astype(np.int32)
+    faces_of = np.bincount(parent[g[:, 0]], minlength=n_verts).astype(np.int32)
+    root = parent == np.arange(n_verts)
+    counts = np.array([np.count_nonzero(root & (faces_of > 0)), np.count_nonzero(root & (faces_of == 0)), n_bad], dtype=np.int64)
+    return label, faces_of, counts
+
+
+def mesh_select(faces_of, keep_largest=0, min_faces=0, labels=None):
+    """The labels of the kept components, int64, in rank order (face count descending, then label ascending).  faces_of: mesh_components'
+    array [V] -- or, with `labels` given, the face counts of just those labels (what a caller that holds faces_of on a GPU sends over)."""
+    keep_largest, min_faces = int(keep_largest), int(min_faces)
+    if keep_largest < 0 or min_faces < 0:
+        raise ValueError('mesh_select: keep_largest and min_faces must be >= 0')
+    n = np.asarray(faces_of).astype(np.int64).reshape(-1)
+    if labels is None:
+        labels = np.nonzero(n)[0]
+        n = n[labels]
+    else:
+        labels = np.asarray(labels).astype(np.int64).reshape(-1)
+        if labels.shape != n.shape:
+            raise ValueError('mesh_select: one face count per label')
+        labels, n = labels[n > 0], n[n > 0]
+    order = np.lexsort((labels, -n))
+    labels, n = labels[order], n[order]
+    kept = n >= min_faces
+    if keep_largest > 0:
+        kept &= np.arange(len(n)) < keep_largest
+    return labels[kept]
+
+
+def mesh_compact_numpy(verts, faces, label, faces_of, keep):
+    """The numpy port of gnerf_mesh_compact_*: keep is bool / uint8 [V], INDEXED BY LABEL -> (verts' float32 [V', 3], faces' int32 [T', 3],
+    src_vertex int32 [V'])."""
+    v = np.ascontiguousarray(np.asarray(verts), dtype=np.float32).reshape(-1, 3)
+    f, ok = _mesh_faces(faces, len(v))
+    label, faces_of, keep = (np.asarray(x).reshape(-1) for x in (label, faces_of, keep))
+    if not len(label) == len(faces_of) == len(keep) == len(v):
+        raise ValueError('mesh_compact: label, faces_of and keep hold one value per vertex')
+    label = label.astype(np.int64)
+    vkeep = (keep[label] != 0) & (faces_of[label] > 0)
+    fkeep = ok.copy()
+    fkeep[ok] = vkeep[f[ok, 0]]
+    newid = np.cumsum(vkeep) - 1
+    return v[vkeep], newid[f[fkeep]].astype(np.int32).reshape(-1, 3), np.nonzero(vkeep)[0].astype(np.int32)
+
+
+def _mesh_rows(faces, n_verts):
+    """The sorted neighbour rows: (nbr int64 [6 T'] row after row, each ascending; deg int64 [V]; start int64 [V]; odd bool [V]: some neighbour
+    does not occur exactly twice)."""
+    f, ok = _mesh_faces(faces, n_verts)
+    g = f[ok]
+    owner = np.concatenate([g[:, c] for c in range(3) for _ in range(2)])
+    nbr = np.concatenate([g[:, (c + k) % 3] for c in range(3) for k in (1, 2)])
+    order = np.lexsort((nbr, owner))
+    owner, nbr = owner[order], nbr[order]
+    deg = np.bincount(owner, minlength=n_verts).astype(np.int64)
+    odd = np.zeros(n_verts, dtype=bool)
+    pairs, times = np.unique(owner << 32 | nbr, return_counts=True)
+    odd[pairs[times != 2] >> 32] = True
+    return nbr, deg, np.cumsum(deg) - deg, odd
+
+
+def mesh_smooth_numpy(verts, faces, iterations, lam=0.5, mu=-0.53, pin_boundary=True):
+    """The numpy port of gnerf_mesh_smooth -> the new positions, float32 [V, 3], the kernel's bits."""
+    cur = np.array(np.asarray(verts), dtype=np.float32).reshape(-1, 3)
+    iterations = int(iterations)
+    if iterations < 0:
+        raise ValueError(f'mesh_smooth: iterations must be >= 0, got {iterations}')
+    if iterations == 0 or len(cur) == 0:
+        return cur
+    nbr, deg, start, odd = _mesh_rows(faces, len(cur))
+    move = np.nonzero((deg > 0) & ~(odd & bool(pin_boundary)))[0]
+    m, first = deg[move], start[move]
+    m64 = m.astype(np.float64)[:, None]
+    for step in range(2 * iterations):
+        s = np.float64(np.float32(mu if step & 1 else lam))
+        x = cur.astype(np.float64)
+        acc = np.zeros((len(move), 3), dtype=np.float64)
+        for k in range(int(m.max()) if len(m) else 0):                  # the k-th neighbour of every row that has one: ascending j per row
+            sel = m > k
+            acc[sel] += x[nbr[first[sel] + k]]
+        xm = x[move]
+        nxt = cur.copy()
+        nxt[move] = (xm + s * (acc / m64 - xm)).astype(np.float32)
+        cur = nxt
+    return cur
+
+
+def clean_mesh(verts, faces, keep_largest=0, min_faces=0, smooth=0, lam=0.5, mu=-0.53, pin_boundary=True, normals=None, colors=None):
+    """Keep the large pieces of a mesh, drop the rest, fair the surface: components -> selection (keep_largest: at most that many components,
+    0 = no limit; min_faces: only components with at least that many faces) -> compaction -> `smooth` Taubin iterations.  CUDA tensors run the
+    gfx950 kernels (gnerf_hip.mesh_components / mesh_compact / mesh_smooth) and return tensors on their device; numpy arrays and CPU tensors
+    run the numpy ports and return numpy arrays -- the same bits either way.  -> CleanedMesh(verts, faces, normals, colors, src_vertex, report):
+    normals / colors are the given per-vertex arrays gathered at the kept vertices (None when not given; smoothing does not touch them), src_vertex
+    the old index of every new vertex, report a dict: components, kept, faces, kept_faces, share (kept_faces / faces), vertices, kept_vertices."""
+    try:
+        import torch
+    except ImportError:                                                  # pragma: no cover - torch is part of the stack
+        torch = None
+    on_gpu = torch is not None and isinstance(verts, torch.Tensor) and verts.is_cuda
+    if on_gpu:
+        import gnerf_hip
+        dev = verts.device
+        label, faces_of, counts = gnerf_hip.mesh_components(faces, len(verts))
+        roots = torch.nonzero(faces_of).reshape(-1)                      # only the labels and their face counts travel to the host
+        sizes = faces_of[roots].cpu().numpy()
+        kept = mesh_select(sizes, keep_largest, min_faces, labels=roots.cpu().numpy())
+        keep = torch.zeros(len(verts), dtype=torch.uint8, device=dev)
+        keep[torch.from_numpy(kept).to(dev)] = 1
+        v, f, src = gnerf_hip.mesh_compact(verts, faces, label, faces_of, keep)
+        index = src.long()
+        normals, colors = (None if t is None else t.to(dev)[index] for t in (normals, colors))
+        if smooth:
+            v = gnerf_hip.mesh_smooth(v, f, smooth, lam, mu, pin_boundary)
+        kept_faces, n_faces = int(sizes[np.isin(roots.cpu().numpy(), kept)].sum()), int(sizes.sum())
+    else:
+        if torch is not None:
+            verts, faces, normals, colors = (t.detach().cpu().numpy() if isinstance(t, torch.Tensor) else t for t in (verts, faces, normals, colors))
+        verts = np.asarray(verts, dtype=np.float32).reshape(-1, 3)
+        label, faces_of, counts = mesh_components_numpy(faces, len(verts))
+        kept = mesh_select(faces_of, keep_largest, min_faces)
+        keep = np.zeros(len(verts), dtype=np.uint8)
+        keep[kept] = 1
+        v, f, src = mesh_compact_numpy(verts, faces, label, faces_of, keep)
+        normals, colors = (None if t is None else np.asarray(t)[src] for t in (normals, colors))
+        if smooth:
+            v = mesh_smooth_numpy(v, f, smooth, lam, mu, pin_boundary)
+        kept_faces, n_faces = int(faces_of[kept].sum()), int(faces_of.sum(dtype=np.int64))
+    report = dict(components=int(counts[0]), kept=int(len(kept)), faces=n_faces, kept_faces=kept_faces, share=kept_faces / n_faces if n_faces else 1.0,
+                  vertices=int(len(verts)), kept_vertices=int(len(v)))
+    return CleanedMesh(v, f, normals, colors, src, report)
+
+
+def clean_report_line(report, smooth=0):
+    """The one stdout line of the CLIs about a clean_mesh report."""
+    return (f'mesh cleaning: kept {report["kept"]} of {report["components"]} component(s), {report["kept_faces"]} of {report["faces"]} triangles '
+            f'({100 * report["share"]:.2f} %), {report["kept_vertices"]} of {report["vertices"]} vertices' + (f'; {smooth} Taubin iteration(s)' if smooth else ''))
+
+
+def clean_options(keep_largest=0, min_faces=0, smooth=0):
+    """The CLIs' three flags (--mesh-keep, --mesh-min-faces, --mesh-smooth) as clean_mesh keywords, or None when all are 0 (nothing runs)."""
+    opts = dict(keep_largest=int(keep_largest), min_faces=int(min_faces), smooth=int(smooth))
+    if min(opts.values()) < 0:
+        raise ValueError('--mesh-keep, --mesh-min-faces and --mesh-smooth must be >= 0')
+    return opts if any(opts.values()) else None
+
+
 # ---------------------------------------------------------------------------------------------------------------- PLY
 def write_ply(path, verts, faces, normals=None, colors=None):
     """Binary little-endian PLY with the layout plyfile writes for shape_utils.py's two elements (vertex x/y/z float, face
@@ -641,11 +847,17 @@ def read_ply_attrs(path):
     return {k: v for k, v in found.items() if v is not None}
 
 
-def convert_sdf_samples_to_ply(volume, voxel_grid_origin, voxel_size, ply_filename_out, offset=None, scale=None, level=0.0):
+def convert_sdf_samples_to_ply(volume, voxel_grid_origin, voxel_size, ply_filename_out, offset=None, scale=None, level=0.0, clean=None, report=None):
     """shape_utils.py:40-100: mesh `volume` at `level` with spacing voxel_size, move the vertices by voxel_grid_origin, then
     / scale and - offset when given, and write the .ply.  `volume` may be a CUDA tensor (the kernel) or a CPU array (the numpy port).
-    Returns (vertex count, face count)."""
+    clean: None, or clean_mesh's keywords (clean_options) -- the mesh is cleaned where it was extracted, before it is moved; report: a dict
+    that then receives clean_mesh's report.  Returns (vertex count, face count)."""
     verts, faces = marching_cubes(volume, level, spacing=voxel_size)
+    if clean:
+        cleaned = clean_mesh(verts, faces, **clean)
+        verts, faces = cleaned.verts, cleaned.faces
+        if report is not None:
+            report.update(cleaned.report)
     if not isinstance(verts, np.ndarray):
         verts, faces = verts.cpu().numpy(), faces.cpu().numpy()
     mesh_points = np.zeros_like(verts)
@@ -723,14 +935,14 @@ def load_volume(path):
     return read_mrc(path) if path.lower().endswith('.mrc') else np.load(path).astype(np.float32, copy=False)
 
 
-def convert_mrc(input_filename, output_filename, level=10.0, device=None):
+def convert_mrc(input_filename, output_filename, level=10.0, device=None, clean=None, report=None):
     """shape_utils.py:103-105: mesh transpose(2, 1, 0) of the file's data (.mrc or .npy), voxel size 1, origin 0.  `device`: a torch
-    device to run the kernel on (None: the numpy port).  Returns (vertex count, face count)."""
+    device to run the kernel on (None: the numpy port).  clean, report: as convert_sdf_samples_to_ply's.  Returns (vertex count, face count)."""
     vol = np.ascontiguousarray(np.transpose(load_volume(input_filename), (2, 1, 0)))
     if device is not None:
         import torch
         vol = torch.from_numpy(vol).to(device)
-    return convert_sdf_samples_to_ply(vol, [0, 0, 0], 1, output_filename, level=level)
+    return convert_sdf_samples_to_ply(vol, [0, 0, 0], 1, output_filename, level=level, clean=clean, report=report)
 
 
 def main(argv=None):
@@ -738,7 +950,13 @@ def main(argv=None):
     ap.add_argument('input', help='a .mrc / .npy volume, or a directory of them (each gets a .ply next to it)')
     ap.add_argument('--level', type=float, default=10, help='the isosurface level (shape_utils.py:111)')
     ap.add_argument('--device', default=None, help="'cuda' runs the gfx950 kernel (default: cuda when available, else the numpy port)")
+    ap.add_argument('--mesh-keep', type=int, default=0, help='keep only this many of the largest connected components (0: all)')
+    ap.add_argument('--mesh-min-faces', type=int, default=0, help='drop connected components with fewer triangles than this (0: none)')
+    ap.add_argument('--mesh-smooth', type=int, default=0, help='Taubin smoothing iterations (lambda 0.5, mu -0.53, boundaries pinned; 0: none)')
     args = ap.parse_args(argv)
+    if min(args.mesh_keep, args.mesh_min_faces, args.mesh_smooth) < 0:
+        ap.error('--mesh-keep, --mesh-min-faces and --mesh-smooth must be >= 0')
+    clean = clean_options(args.mesh_keep, args.mesh_min_faces, args.mesh_smooth)
     device = args.device
     if device is None:
         try:
@@ -757,7 +975,10 @@ def main(argv=None):
     for path in paths:                                                   # --level is honoured for a single file too (the reference's
         t0 = time.perf_counter()                                         # single-file branch ignores it, shape_utils.py:114-116)
         out = os.path.splitext(path)[0] + '.ply'
-        nv, nf = convert_mrc(path, out, level=args.level, device=device)
+        report = {}
+        nv, nf = convert_mrc(path, out, level=args.level, device=device, clean=clean, report=report)
+        if report:
+            print(clean_report_line(report, args.mesh_smooth))
         print(f'wrote {out}: {nv} vertices, {nf} triangles ({time.perf_counter() - t0:.3f} s)')
     return 0
 

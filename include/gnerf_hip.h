@@ -32,6 +32,8 @@
  *                              convolutions there; no native counterpart)
  *   gnerf_resize_aa_*       <- F.interpolate(mode='bilinear', align_corners=False, antialias=True) as superresolution.py:290-293 and
  *                              training_loop.py's ssim_resize call it, and its gradient (ATen's kernels there)
+ *   gnerf_mesh_*            <- (no counterpart: the reference only zeroes fixed borders of the volume, gen_videos.py:214-221; the compaction,
+ *                              like marching cubes, needs a host read between its two passes)
  */
 #ifndef GNERF_HIP_H
 #define GNERF_HIP_H
@@ -712,6 +714,54 @@ int gnerf_raster_resolve(const uint64_t* vis, const float* verts, int n_verts, c
                          const float* intrinsics, int n_views, int h, int w, const float* normals, const float* normal_mat,
                          const unsigned char* colors, const float* shading, int32_t* tri_id, float* depth, float* normal, unsigned char* frame,
                          gnerf_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
+ * (ABI 15, added without a new version) Cleaning the meshes gnerf_marching_cubes_* extracts: connected components, compaction to the kept
+ * components, Taubin smoothing (csrc/mesh_clean.hip).  g-nerf_amd/shape_mi355x.py restates the rules and holds numpy ports
+ * (mesh_components_numpy, mesh_select, mesh_compact_numpy, mesh_smooth_numpy) that give the same bits.
+ *   a mesh: verts float32 [V, 3] and faces int32 [T, 3] as marching cubes returns them; V == 0 or T == 0 is valid (the pointer of an empty
+ *   array may be NULL).  A face is VALID iff its three ids lie in [0, V); ids may repeat.  An invalid face joins nothing, is counted, is dropped
+ *   by the compaction and ignored by the smoothing; the Python layer raises ValueError when the count is not 0.
+ * COMPONENTS (gnerf_mesh_components): a valid face joins its three vertices.
+ *   label int32 [V]: the smallest vertex index of v's connected component (label[v] <= v, label[label[v]] == label[v]; a vertex in no face:
+ *     label[v] == v);
+ *   faces_of int32 [V]: faces_of[l] = the number of valid faces whose first vertex has label l (0 where l is no label);
+ *   counts (device int64 [3]) = {components with at least one face, vertices in no valid face, invalid faces}.
+ *   All integers and unique: the same bits on every run and for every order of the faces.  Six launches, no host read, capturable.
+ * SELECTION (integers only, on the host; shape_mi355x.mesh_select): the components with at least one face, ordered by face count descending,
+ *   then label ascending; a component is kept iff its face count >= min_faces and (keep_largest == 0 or its rank < keep_largest).
+ * COMPACTION (gnerf_mesh_compact_count, then _emit): keep uint8 [V] is indexed by LABEL.  A vertex is kept iff keep[label[v]] != 0 and
+ *   faces_of[label[v]] > 0 (vertices in no face are always dropped); a face iff it is valid and its first vertex is kept.  Kept vertices stay in
+ *   ascending old index, kept faces in ascending old face index with their ids remapped; src_vertex int32 [V'] = the old index of every new
+ *   vertex (gather normals and colours with it).  If everything is kept the output equals the input bit for bit.
+ *   _count: counts (device int64 [2]) = {V', T'}; the caller reads them (the op's one synchronisation, so it is not capturable), sizes
+ *   out_verts [V', 3], out_faces [T', 3], src_vertex [V'] and calls _emit with the same inputs and workspace -- not at all when V' == 0.
+ *   out_faces may be NULL when the counted T' is 0 (the face pass is then skipped): label and faces_of that do not belong together can give V' > 0 with T' == 0.
+ *   Positions come from a block scan plus a scan of the block totals, never from the order of arrival.
+ * SMOOTHING (gnerf_mesh_smooth): Taubin lambda | mu smoothing with uniform weights; positions change, faces do not.
+ *   N(i), the neighbour multiset of vertex i: corner c (0, 1, 2) of every valid face gives vertex f[c] the two ids f[c + 1], f[c + 2]
+ *   (cyclically), so a neighbour j occurs once per face that contains the edge {i, j}; m_i = |N(i)|.
+ *   One half-step with factor s (a C float), per coordinate: c = (sum of double(v_j)) / double(m_i), summed over N(i) in ascending j
+ *   (duplicates adjacent, starting from 0.0), sum and division in float64; v_i' = float32(double(v_i) + double(s) * (c - double(v_i))).  Every
+ *   operation is rounded on its own, no contraction.  All vertices move together from the previous positions; one iteration = a half-step
+ *   with lam, then one with mu.  A vertex with m_i == 0 never moves; with pin_boundary != 0 neither does a vertex some neighbour of which
+ *   does not occur exactly twice in N(i) (a boundary or non-manifold edge).  The ascending order makes the result independent of the order of
+ *   the faces and of the rotation of a face's ids.  iterations == 0 copies verts to out (out may be verts).  The neighbour rows are built
+ *   once per call (counts, row starts by a scan, fill, one sort per row, any length); the 2 * iterations half-steps are pure gathers.
+ *   No host read: capturable.
+ * gnerf_mesh_workspace_bytes: *bytes = a workspace large enough for each of the calls on a mesh of that size (the smoothing's is the
+ *   largest: 24 bytes per face + 37 per vertex); no initialisation needed.
+ * GNERF_E_ARG for null pointers, negative sizes, negative iterations, or more than 2^32 / 6 - 1 faces in gnerf_mesh_smooth. */
+int gnerf_mesh_workspace_bytes(int n_verts, int n_tris, size_t* bytes);
+int gnerf_mesh_components(const int32_t* faces, int n_verts, int n_tris, void* workspace, int32_t* label, int32_t* faces_of,
+                          int64_t* counts, gnerf_stream_t stream);
+int gnerf_mesh_compact_count(const int32_t* faces, int n_verts, int n_tris, const int32_t* label, const int32_t* faces_of,
+                             const unsigned char* keep, void* workspace, int64_t* counts, gnerf_stream_t stream);
+int gnerf_mesh_compact_emit(const float* verts, const int32_t* faces, int n_verts, int n_tris, const int32_t* label,
+                            const int32_t* faces_of, const unsigned char* keep, void* workspace, float* out_verts, int32_t* out_faces,
+                            int32_t* src_vertex, gnerf_stream_t stream);
+int gnerf_mesh_smooth(const float* verts, int n_verts, const int32_t* faces, int n_tris, int iterations, float lam, float mu,
+                      int pin_boundary, void* workspace, float* out, gnerf_stream_t stream);
 
 #ifdef __cplusplus
 }
