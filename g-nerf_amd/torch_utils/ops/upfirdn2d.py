@@ -118,10 +118,17 @@ _Config = collections.namedtuple('_Config', 'upx upy downx downy padx0 padx1 pad
 
 def _run(x, f, c):
     """Forward computation on the plugin: one 2-D pass, or a row pass then a column pass for a separable filter."""
+    # The plugin takes the gain as a float32 (as the reference's does).  A float64 result would carry that rounding, 3e-8 relative for
+    # gain = 1.7, so a float64 call whose gain is not exact in float32 runs unscaled and is scaled here, in double.
+    gain, late = c.gain, 1.0
+    if x.dtype == torch.float64 and float(np.float32(gain)) != float(gain):
+        gain, late = 1.0, float(c.gain)
     if f.ndim == 2:
-        return _plugin.upfirdn2d(x, f, c.upx, c.upy, c.downx, c.downy, c.padx0, c.padx1, c.pady0, c.pady1, c.flip, c.gain)
-    y = _plugin.upfirdn2d(x, f.unsqueeze(0), c.upx, 1, c.downx, 1, c.padx0, c.padx1, 0, 0, c.flip, 1.0)
-    return _plugin.upfirdn2d(y, f.unsqueeze(1), 1, c.upy, 1, c.downy, 0, 0, c.pady0, c.pady1, c.flip, c.gain)
+        y = _plugin.upfirdn2d(x, f, c.upx, c.upy, c.downx, c.downy, c.padx0, c.padx1, c.pady0, c.pady1, c.flip, gain)
+    else:
+        y = _plugin.upfirdn2d(x, f.unsqueeze(0), c.upx, 1, c.downx, 1, c.padx0, c.padx1, 0, 0, c.flip, 1.0)
+        y = _plugin.upfirdn2d(y, f.unsqueeze(1), 1, c.upy, 1, c.downy, 0, 0, c.pady0, c.pady1, c.flip, gain)
+    return y if late == 1.0 else y.mul_(late)
 
 
 def _transposed(c, f, in_hw, out_hw):
