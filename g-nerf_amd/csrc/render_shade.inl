@@ -354,13 +354,25 @@ __device__ __forceinline__ void shade_tile(const Params& P, const ShadeLds& L, c
     // round trip overlaps the first instead of following it.  Measured alternatives (tools/ablate.py, config 2): all 24
     // in flight (96 VGPRs) halves the lookup time but costs a wave per SIMD and is slower overall; one step after the
     // other (the previous default) exposes two full round trips.
-    // One fused multiply-add per tap, chained through the sample's 12 taps (the first tap of the first plane starts the accumulator).
-    // History: round 1 had this form and dropped it -- with hipcc 7.2's code for it (v_pk_fma_f32 chains whose weight operand is the
-    // high register of a pair, selected on src1) lanes 48-63 of ~3 % of the rays differed from run to run; round 3's inline-asm op_sel
-    // broadcast reproduced that.  Round 4 found the mechanism (csrc/pk_opsel_fixup.py: that operand form reads 0.0 in lanes 48-63 now and
-    // then while another wave of the SIMD runs v_mfma_f32_16x16x32_f16); with the build exchanging the sources of every such
-    // instruction (2 550 of them in this form) the chain is bit-stable (tools/determinism.py: 0 of 10 x 65 536 rays) and 1 % faster
-    // than four products summed per plane (24 instead of 28 packed instructions per sample pair).
+    // One fused multiply-add per tap and channel, chained through the sample's 12 taps (the first tap of the first plane starts the
+    // accumulator with a multiply) -- as SCALAR instructions: v_mul_f32 / v_fmac_f32 from inline asm, which neither instruction selection
+    // nor the SLP vectoriser can pair up again.  Rounds 4-17 ran this chain as v_pk_fma_f32 (one per tap and channel pair, what
+    // __builtin_elementwise_fma on v4f gives), priced from a stream of its own at 4.5 SIMD cycles = no dearer than two scalar FMAs.  Beside
+    // matrix work it is: tools/probes/valu_issue_probe --beside-mfma (profiles/r18_valu_beside_mfma_probe.json) has one v_pk_fma_f32 in a
+    // wave's own MFMA gap at +16 cycles where two v_fma_f32 cost +1, and a wave of packed FMAs at 6-15 times its price while one or two other waves
+    // of the SIMD stream v_mfma_f32_16x16x32_f16 (scalar FMAs: 3 times).  The same FMAs in the same order per lane: bit-identical outputs.
+    // Which registers the three sources sit in decides what a scalar FMA costs (same probe, `scalar_operand_banks`): all three in even or
+    // all three in odd registers = 4.3-4.6 cycles, any other placement 2.3-2.4.  The accumulator and a texel are 128-bit tuples, which
+    // start on even registers, so channel c of both would always share a parity and the tap weight w[k] would make it three of a kind
+    // for half of the 96 FMAs of a sample (k and c both even or both odd) -- measured: the scalar chain in that placement is NO faster
+    // than the packed one (profiles/r18_blend_scalar_ab.jsonl, arm scalar0).  So channel c accumulates in element (c + 1) & 3 of the
+    // accumulator (kBlendRot): an odd register for an even texel register, never three of a kind; the quad goes to its staging row
+    // rotated as it is, and the rows' one reader below names the elements back (f[]), which costs nothing.
+    // History of the packed form: round 1 dropped it -- with hipcc 7.2's code for it (v_pk_fma_f32 chains whose weight operand is the
+    // high register of a pair, selected on src1) lanes 48-63 of ~3 % of the rays differed from run to run; round 4 found the mechanism
+    // (csrc/pk_opsel_fixup.py: that operand form reads 0.0 in lanes 48-63 now and then while another wave of the SIMD runs
+    // v_mfma_f32_16x16x32_f16) and the build has exchanged the sources of every such instruction since: 6 911 of them in render.hip with
+    // the packed blend, 143 without it.
     v4f acc0, acc1;
     float* const row0 = stage + b * kFwdStagePitch + (((lane & 7) ^ stage_swz(b)) * 4);
     float* const row1 = stage + (8 + b) * kFwdStagePitch + (((lane & 7) ^ stage_swz(8 + b)) * 4);
@@ -373,7 +385,18 @@ __device__ __forceinline__ void shade_tile(const Params& P, const ShadeLds& L, c
     // its blend): with both steps' records held in registers (48) next to the window (48) and the colours (32) the pinned order spills.
     const float* const rec0 = taps + b * kFwdTapStride;
     const float* const rec1 = taps + (8 + b) * kFwdTapStride;
-    auto bc = [](float w) { return (v4f){w, w, w, w}; };
+    // a plane's four taps into the accumulator: channel c (= | +=) t[k][c] * w[k], k = 0..3
+    constexpr int kBlendRot = 1;
+    auto blend4 = [](v4f& acc, const v4f (&t)[4], const v4f& w, bool first) {
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+#pragma unroll
+            for (int c = 0; c < 4; c++) {
+                if (first && k == 0) asm("v_mul_f32 %0, %1, %2" : "=v"(acc[(c + kBlendRot) & 3]) : "v"(t[0][c]), "v"(w[0]));
+                else asm("v_fmac_f32 %0, %1, %2" : "+v"(acc[(c + kBlendRot) & 3]) : "v"(t[k][c]), "v"(w[k]));
+            }
+        }
+    };
     auto load4 = [&](v4f (&t)[4], uint4 o) {
 #ifdef GNERF_ABLATE_GATHER      // timing-only build: no texel loads (outputs are wrong): what a perfect load latency could return
         t[0] = (v4f){float(o.x + cq16), 1.f, 2.f, 3.f}; t[1] = (v4f){float(o.y), 1.f, 2.f, 3.f};
@@ -394,10 +417,7 @@ __device__ __forceinline__ void shade_tile(const Params& P, const ShadeLds& L, c
 #pragma unroll
     for (int pl = 0; pl < 3; pl++) {            // a plane's four taps at a time
         const uint4 o1 = *reinterpret_cast<const uint4*>(rec1 + pl * 8);
-        acc0 = pl == 0 ? win[pl][0] * w0[pl][0] : __builtin_elementwise_fma(win[pl][0], bc(w0[pl][0]), acc0);
-        acc0 = __builtin_elementwise_fma(win[pl][1], bc(w0[pl][1]), acc0);
-        acc0 = __builtin_elementwise_fma(win[pl][2], bc(w0[pl][2]), acc0);
-        acc0 = __builtin_elementwise_fma(win[pl][3], bc(w0[pl][3]), acc0);
+        blend4(acc0, win[pl], w0[pl], pl == 0);
         pin(acc0);
         load4(win[pl], o1);
         pin(acc0);
@@ -410,10 +430,7 @@ __device__ __forceinline__ void shade_tile(const Params& P, const ShadeLds& L, c
     *reinterpret_cast<v4f*>(row0) = acc0;
 #pragma unroll
     for (int pl = 0; pl < 3; pl++) {
-        acc1 = pl == 0 ? win[pl][0] * w1[pl][0] : __builtin_elementwise_fma(win[pl][0], bc(w1[pl][0]), acc1);
-        acc1 = __builtin_elementwise_fma(win[pl][1], bc(w1[pl][1]), acc1);
-        acc1 = __builtin_elementwise_fma(win[pl][2], bc(w1[pl][2]), acc1);
-        acc1 = __builtin_elementwise_fma(win[pl][3], bc(w1[pl][3]), acc1);
+        blend4(acc1, win[pl], w1[pl], pl == 0);
     }
     *reinterpret_cast<v4f*>(row1) = acc1;
     lds_wave_sync();
@@ -421,7 +438,8 @@ __device__ __forceinline__ void shade_tile(const Params& P, const ShadeLds& L, c
     const int j = lane & 15, g = lane >> 4;
     const v4f f_lo = *reinterpret_cast<const v4f*>(stage + j * kFwdStagePitch + (((2 * g) ^ stage_swz(j)) * 4));
     const v4f f_hi = *reinterpret_cast<const v4f*>(stage + j * kFwdStagePitch + (((2 * g + 1) ^ stage_swz(j)) * 4));
-    const float f[8] = {f_lo[0], f_lo[1], f_lo[2], f_lo[3], f_hi[0], f_hi[1], f_hi[2], f_hi[3]};
+    constexpr int r0 = (0 + kBlendRot) & 3, r1 = (1 + kBlendRot) & 3, r2 = (2 + kBlendRot) & 3, r3 = (3 + kBlendRot) & 3;      // (the staged quads are rotated: see the blend)
+    const float f[8] = {f_lo[r0], f_lo[r1], f_lo[r2], f_lo[r3], f_hi[r0], f_hi[r1], f_hi[r2], f_hi[r3]};
     float sig = 0.f;
     v4f o[2];
     if constexpr (MLP == kMlpF32) {

@@ -11,6 +11,8 @@
 //   simd_cyc_per_inst  = slowest wave of the SIMD / waves on that SIMD (what the SIMD sustains: the price the roofline needs)
 // plus the SIMD each wave landed on (HW_ID) so that the waves-per-SIMD assumption is checked, not assumed.
 // build + run: tools/probes/valu_issue_probe.sh  ->  gpurun_out/valu_issue_probe.json  (committed as profiles/r03_valu_issue_probe.json)
+// `valu_issue_probe --beside-mfma OUT.json` runs only the packed-fp32-beside-MFMA rows (probe_beside below; random operands)
+//   -> profiles/r18_valu_beside_mfma_probe.json
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <cstdlib>
@@ -350,7 +352,228 @@ __global__ __launch_bounds__(1024) void gather_probe(const char* table, unsigned
     if (acc[0] + acc[1] + acc[2] + acc[3] == 12345.678f) out[0] = 1.f;
 }
 
+// ---- packed fp32 beside MFMAs (round 18).  The rows above time v_pk_fma_f32 in a stream of its own and mix only SCALAR fillers into the
+// MFMA stream; the render kernel runs its packed blend while other waves of the SIMD are in their matrix phases.  Two kinds of stream:
+//   within one wave:  per v_mfma_f32_16x16x32_f16, N v_pk_fma_f32 | 2N v_fma_f32 | N v_pk_mul_f32 | N v_pk_add_f32 (N = 1, 2, 4)
+//   scalar_operand_banks: v_fmac_f32 D, A, B with the three registers even / odd / 2 mod 4 / 0 mod 4 (what a SCALAR FMA costs depends
+//     on them: three sources of one parity = about twice the price; the scalar reference streams here avoid that placement)
+//   between waves (4 per SIMD): M = 1 or 2 waves of every SIMD run the bare MFMA stream, the others a pure v_pk_fma_f32 stream or a
+//     v_fma_f32 stream of twice the length (the same FMAs).  A wave learns its role from its arrival rank on its SIMD (HW_ID + an LDS
+//     counter), so the split holds whatever SIMD the hardware gives a wave.  Each role is timed in a launch of its own in which the OTHER
+//     role runs 8x the iterations, so the timed waves have their partners beside them from start to end (checked: `covered`).
+// Operands are random and non-zero (a per-lane table in LDS, read into the registers in front of the loop): zeros clock higher.
+// Chains stay finite: x <- a x + b with 0.5 <= |a| < 0.9; products of constants for v_pk_mul_f32; sums grow linearly.
+#define CLOB_B CLOB_V, "v58", "v59", "v60", "v61", "v62"
+#define TIMED_LOOP_B(BODY)                                                                                       \
+    asm volatile("s_mov_b32 s20, %2\n\t"                                                                         \
+                 "s_barrier\n\t"                                                                                 \
+                 "s_memtime %0\n\t"                                                                              \
+                 "s_waitcnt lgkmcnt(0)\n\t"                                                                      \
+                 "1:\n\t" BODY                                                                                   \
+                 "s_sub_u32 s20, s20, 1\n\t"                                                                     \
+                 "s_cmp_lg_u32 s20, 0\n\t"                                                                       \
+                 "s_cbranch_scc1 1b\n\t"                                                                         \
+                 "s_nop 7\n\t"                                                                                   \
+                 "s_memtime %1\n\t"                                                                              \
+                 "s_waitcnt lgkmcnt(0)\n\t"                                                                      \
+                 : "=s"(t0), "=s"(t1) : "s"(iters) : "s20", "scc", "vcc", "memory", CLOB_B)
+// fillers write v50..v57; multiplier a = v[58:59], addend b = v[60:61]
+#define PF(a, b)  "v_pk_fma_f32 v[" #a ":" #b "], v[" #a ":" #b "], v[58:59], v[60:61]\n\t"
+#define SF(a, b)  "v_fma_f32 v" #a ", v" #a ", v58, v61\n\tv_fma_f32 v" #b ", v" #b ", v59, v60\n\t"      /* never three sources of one parity: see X16E */
+#define PM(a, b)  "v_pk_mul_f32 v[" #a ":" #b "], v[58:59], v[60:61]\n\t"
+#define PA(a, b)  "v_pk_add_f32 v[" #a ":" #b "], v[" #a ":" #b "], v[60:61]\n\t"
+#define N1(OP) OP(50, 51)
+#define N2(OP) OP(50, 51) OP(52, 53)
+#define N4(OP) OP(50, 51) OP(52, 53) OP(54, 55) OP(56, 57)
+#define I_FMA_B(n) "v_fma_f32 v" #n ", v" #n ", v58, v60\n\t"
+#define I_FMA_C(n) "v_fma_f32 v" #n ", v" #n ", v58, v59\n\t"
+// which registers the three sources of a scalar FMA sit in: v_fmac_f32 D, A, B (D += A * B) with D in even registers (X16E) or in
+// registers 2 mod 4 (X8Q), A and B even (v58 = 2 mod 4, v60 = 0 mod 4, v62 = 2 mod 4) or odd (v59, v61)
+#define X16E(A, B) FM(10, A, B) FM(12, A, B) FM(14, A, B) FM(16, A, B) FM(18, A, B) FM(20, A, B) FM(22, A, B) FM(24, A, B) \
+                   FM(26, A, B) FM(28, A, B) FM(30, A, B) FM(32, A, B) FM(34, A, B) FM(36, A, B) FM(38, A, B) FM(40, A, B)
+#define X8Q(A, B)  FM(10, A, B) FM(14, A, B) FM(18, A, B) FM(22, A, B) FM(26, A, B) FM(30, A, B) FM(34, A, B) FM(38, A, B)
+#define FM(d, A, B) "v_fmac_f32 v" #d ", " A ", " B "\n\t"
+constexpr int kBesideRegs = 52;         // v10..v61
+struct BesideStream { const char* name; int insts_per_iter; int fma_per_iter; const char* what; };
+static const BesideStream kBeside[] = {
+    {"mfma_f16_16x16x32", 8, 0, "8 independent v_mfma_f32_16x16x32_f16, random operands"},
+    {"mfma_f16+1pk_fma", 16, 16, "per MFMA: 1 v_pk_fma_f32"},   {"mfma_f16+2fma", 24, 16, "per MFMA: 2 v_fma_f32"},
+    {"mfma_f16+2pk_fma", 24, 32, "per MFMA: 2 v_pk_fma_f32"},   {"mfma_f16+4fma", 40, 32, "per MFMA: 4 v_fma_f32"},
+    {"mfma_f16+4pk_fma", 40, 64, "per MFMA: 4 v_pk_fma_f32"},   {"mfma_f16+8fma", 72, 64, "per MFMA: 8 v_fma_f32"},
+    {"mfma_f16+1pk_mul", 16, 16, "per MFMA: 1 v_pk_mul_f32"},   {"mfma_f16+2pk_mul", 24, 32, "per MFMA: 2 v_pk_mul_f32"},   {"mfma_f16+4pk_mul", 40, 64, "per MFMA: 4 v_pk_mul_f32"},
+    {"mfma_f16+1pk_add", 16, 16, "per MFMA: 1 v_pk_add_f32"},   {"mfma_f16+2pk_add", 24, 32, "per MFMA: 2 v_pk_add_f32"},   {"mfma_f16+4pk_add", 40, 64, "per MFMA: 4 v_pk_add_f32"},
+    {"v_pk_fma_f32", 16, 32, "16 independent v_pk_fma_f32, random operands"},
+    {"v_fma_f32", 32, 32, "32 independent v_fma_f32, random operands (multiplier in an even, addend in an odd register)"},
+    {"v_fma_f32 both sources even", 32, 32, "the same with multiplier and addend both in even registers: half of the 32 read three even registers"},
+    {"v_fmac D even, A even, B even", 32, 32, ""}, {"v_fmac D even, A even, B odd", 32, 32, ""}, {"v_fmac D even, A odd, B even", 32, 32, ""}, {"v_fmac D even, A odd, B odd", 32, 32, ""},
+    {"v_fmac D 2mod4, A 2mod4, B 2mod4", 32, 32, ""}, {"v_fmac D 2mod4, A 2mod4, B 0mod4", 32, 32, ""}, {"v_fmac D 2mod4, A 0mod4, B 0mod4", 32, 32, ""},
+};
+constexpr int kNumBeside = sizeof(kBeside) / sizeof(kBeside[0]);
+constexpr int kBesidePk = 13, kBesideFma = 14;
+
+// stream: index into kBeside (the VALU role's stream when mfma_waves > 0); mfma_waves: how many waves of each SIMD run the bare MFMA stream
+__global__ __launch_bounds__(1024) void probe_beside(int stream, int mfma_waves, int iters_valu, int iters_mfma, unsigned long long* cyc,
+                                                     unsigned long long* t_end, unsigned* hwid, unsigned* role_out) {
+    extern __shared__ __align__(16) float lds[];
+    unsigned* cnt = reinterpret_cast<unsigned*>(lds + 64 * kBesideRegs);
+    if (threadIdx.x < 4) cnt[threadIdx.x] = 0;
+    for (unsigned i = threadIdx.x; i < 64 * kBesideRegs; i += blockDim.x) {
+        const unsigned k = i % kBesideRegs;
+        unsigned h = (i + 1 + blockIdx.x * 4099u) * 2654435761u; h ^= h >> 15; h *= 2246822519u; h ^= h >> 13; h *= 3266489917u; h ^= h >> 16;
+        const float u = float(h & 0xffff) * (1.0f / 65536.0f), sgn = (h & 0x10000) ? -1.f : 1.f;
+        float v;
+        if (k >= 32 && k < 40) {        // two f16 in [0.25, 1) with random signs: A / B of the matrix instruction
+            const unsigned lo = 0x3400u + (h & 0x7ffu) + ((h >> 11) & 1u) * 0x8000u, hi = 0x3400u + ((h >> 12) & 0x7ffu) + ((h >> 23) & 1u) * 0x8000u;
+            v = __uint_as_float(lo | (hi << 16));
+        } else if (k == 48 || k == 49) v = sgn * (0.5f + 0.4f * u);     // a
+        else v = sgn * (0.5f + u);                                     // accumulators, filler chains, b
+        lds[i] = v;
+    }
+    __syncthreads();
+    unsigned id;
+    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(id));
+    unsigned rank = 0;
+    if ((threadIdx.x & 63) == 0) rank = atomicAdd(&cnt[(id >> 4) & 3], 1u);
+    rank = __builtin_amdgcn_readfirstlane(rank);
+    const bool is_mfma = int(rank) < mfma_waves;
+    const int iters = __builtin_amdgcn_readfirstlane(is_mfma ? iters_mfma : iters_valu);
+    const unsigned addr = (threadIdx.x & 63) * (kBesideRegs * 4);
+    unsigned long long t0 = 0, t1 = 0;
+    asm volatile("v_mov_b32 v62, %0\n\t"
+                 "ds_read_b128 v[10:13], v62\n\tds_read_b128 v[14:17], v62 offset:16\n\tds_read_b128 v[18:21], v62 offset:32\n\t"
+                 "ds_read_b128 v[22:25], v62 offset:48\n\tds_read_b128 v[26:29], v62 offset:64\n\tds_read_b128 v[30:33], v62 offset:80\n\t"
+                 "ds_read_b128 v[34:37], v62 offset:96\n\tds_read_b128 v[38:41], v62 offset:112\n\tds_read_b128 v[42:45], v62 offset:128\n\t"
+                 "ds_read_b128 v[46:49], v62 offset:144\n\tds_read_b128 v[50:53], v62 offset:160\n\tds_read_b128 v[54:57], v62 offset:176\n\t"
+                 "ds_read_b128 v[58:61], v62 offset:192\n\ts_waitcnt lgkmcnt(0)\n\tv_mov_b32 v62, v58\n\t" :: "v"(addr) : "memory", CLOB_B);
+    switch (is_mfma ? 0 : stream) {
+        case 0: TIMED_LOOP_B(X8M(I_MFMA16)); break;
+        case 1: TIMED_LOOP_B(PER_MFMA(N1(PF))); break;
+        case 2: TIMED_LOOP_B(PER_MFMA(N1(SF))); break;
+        case 3: TIMED_LOOP_B(PER_MFMA(N2(PF))); break;
+        case 4: TIMED_LOOP_B(PER_MFMA(N2(SF))); break;
+        case 5: TIMED_LOOP_B(PER_MFMA(N4(PF))); break;
+        case 6: TIMED_LOOP_B(PER_MFMA(N4(SF))); break;
+        case 7: TIMED_LOOP_B(PER_MFMA(N1(PM))); break;
+        case 8: TIMED_LOOP_B(PER_MFMA(N2(PM))); break;
+        case 9: TIMED_LOOP_B(PER_MFMA(N4(PM))); break;
+        case 10: TIMED_LOOP_B(PER_MFMA(N1(PA))); break;
+        case 11: TIMED_LOOP_B(PER_MFMA(N2(PA))); break;
+        case 12: TIMED_LOOP_B(PER_MFMA(N4(PA))); break;
+        case 13: TIMED_LOOP_B(X16P(PF)); break;
+        case 14: TIMED_LOOP_B(X32(I_FMA_C)); break;
+        case 15: TIMED_LOOP_B(X32(I_FMA_B)); break;
+        case 16: TIMED_LOOP_B(X16E("v58", "v60") X16E("v58", "v60")); break;
+        case 17: TIMED_LOOP_B(X16E("v58", "v59") X16E("v58", "v59")); break;
+        case 18: TIMED_LOOP_B(X16E("v59", "v58") X16E("v59", "v58")); break;
+        case 19: TIMED_LOOP_B(X16E("v59", "v61") X16E("v59", "v61")); break;
+        case 20: TIMED_LOOP_B(X8Q("v58", "v62") X8Q("v58", "v62") X8Q("v58", "v62") X8Q("v58", "v62")); break;
+        case 21: TIMED_LOOP_B(X8Q("v58", "v60") X8Q("v58", "v60") X8Q("v58", "v60") X8Q("v58", "v60")); break;
+        default: TIMED_LOOP_B(X8Q("v60", "v56") X8Q("v60", "v56") X8Q("v60", "v56") X8Q("v60", "v56")); break;
+    }
+    if ((threadIdx.x & 63) == 0) {
+        const int w = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+        cyc[w] = t1 - t0;
+        t_end[w] = t1;
+        hwid[w] = id;
+        role_out[w] = is_mfma ? 1u : 0u;
+    }
+}
+
+static int run_beside(const char* out_path) {
+    const int iters = 20000;
+    hipDeviceProp_t prop;
+    hipGetDeviceProperties(&prop, 0);
+    const int n_cu = prop.multiProcessorCount, max_waves = n_cu * 16;
+    unsigned long long *d_cyc, *d_end; unsigned *d_id, *d_role;
+    hipMalloc(&d_cyc, max_waves * sizeof(unsigned long long)); hipMalloc(&d_end, max_waves * sizeof(unsigned long long));
+    hipMalloc(&d_id, max_waves * sizeof(unsigned)); hipMalloc(&d_role, max_waves * sizeof(unsigned));
+    hipFuncSetAttribute(reinterpret_cast<const void*>(probe_beside), hipFuncAttributeMaxDynamicSharedMemorySize, 100 * 1024);
+    std::vector<unsigned long long> cyc(max_waves), tend(max_waves); std::vector<unsigned> id(max_waves), role(max_waves);
+    auto launch = [&](int s, int W, int M, int it_valu, int it_mfma) -> bool {
+        const int waves = n_cu * 4 * W;
+        hipMemset(d_cyc, 0, waves * sizeof(unsigned long long));
+        hipLaunchKernelGGL(probe_beside, dim3(n_cu), dim3(256 * W), 100 * 1024, 0, s, M, 200, 200, d_cyc, d_end, d_id, d_role);     // warm-up
+        hipLaunchKernelGGL(probe_beside, dim3(n_cu), dim3(256 * W), 100 * 1024, 0, s, M, it_valu, it_mfma, d_cyc, d_end, d_id, d_role);
+        if (hipDeviceSynchronize() != hipSuccess) { fprintf(stderr, "launch failed: %s\n", hipGetErrorString(hipGetLastError())); return false; }
+        hipMemcpy(cyc.data(), d_cyc, waves * sizeof(unsigned long long), hipMemcpyDeviceToHost);
+        hipMemcpy(tend.data(), d_end, waves * sizeof(unsigned long long), hipMemcpyDeviceToHost);
+        hipMemcpy(id.data(), d_id, waves * sizeof(unsigned), hipMemcpyDeviceToHost);
+        hipMemcpy(role.data(), d_role, waves * sizeof(unsigned), hipMemcpyDeviceToHost);
+        return true;
+    };
+    FILE* fo = fopen(out_path, "w");
+    fprintf(fo, "{\"device\": \"%s\", \"compute_units\": %d, \"iters\": %d,\n \"how\": \"tools/probes/valu_issue_probe --beside-mfma: one workgroup of 256 x W lanes per CU, "
+                "independent instructions, s_memtime per wave, random non-zero operands. within_wave: simd_cyc_per_group = slowest wave of a SIMD / (W x MFMA groups), "
+                "averaged over SIMDs; extra_cyc_per_fma = (that - the bare MFMA stream's at the same W) / FMAs per lane and group. between_waves (4 waves per SIMD): "
+                "M waves of each SIMD run the bare MFMA stream, 4 - M the VALU stream; each role timed while the other runs 8x the iterations; "
+                "valu_simd_cyc_per_fma = slowest VALU wave of a SIMD / (FMAs per lane and wave x VALU waves)\",\n \"within_wave\": [\n", prop.gcnArchName, n_cu, iters);
+    double bare[5] = {0, 0, 0, 0, 0};
+    bool first = true;
+    for (int s = 0; s < kNumBeside; s++) {
+        for (int W : {1, 2, 4}) {
+            if (!launch(s, W, 0, iters, iters)) return 1;
+            int wps_min = 1 << 30, wps_max = 0;
+            double simd_sum = 0; int simd_n = 0;
+            for (int b = 0; b < n_cu; b++) {
+                int cnt[4] = {0, 0, 0, 0}; double worst[4] = {0, 0, 0, 0};
+                for (int w = 0; w < 4 * W; w++) { const int q = (id[b * 4 * W + w] >> 4) & 3; cnt[q]++; worst[q] = std::max(worst[q], double(cyc[b * 4 * W + w])); }
+                for (int q = 0; q < 4; q++) { wps_min = std::min(wps_min, cnt[q]); wps_max = std::max(wps_max, cnt[q]); if (worst[q] > 0) { simd_sum += worst[q]; simd_n++; } }
+            }
+            const double simd_iter = simd_sum / simd_n / W / iters;     // SIMD cycles per loop iteration of one wave
+            const bool mixed = s >= 1 && s <= 12;
+            if (s == 0) bare[W] = simd_iter / 8;
+            const int fma_per_group = kBeside[s].fma_per_iter / 8;
+            if (s == kBesideFma + 1 && W == 1) { fprintf(fo, "\n ],\n \"scalar_operand_banks\": [\n"); first = true; }
+            fprintf(fo, "%s  {\"stream\": \"%s\", \"what\": \"%s\", \"waves_per_simd\": %d, \"waves_per_simd_by_hw_id\": [%d, %d], \"simd_cyc_per_inst\": %.3f",
+                    first ? "" : ",\n", kBeside[s].name, kBeside[s].what, W, wps_min, wps_max, simd_iter / kBeside[s].insts_per_iter);
+            if (mixed) fprintf(fo, ", \"simd_cyc_per_group\": %.3f, \"fma_per_lane_and_group\": %d, \"extra_cyc_per_fma\": %.3f", simd_iter / 8, fma_per_group, (simd_iter / 8 - bare[W]) / fma_per_group);
+            else if (s > 0) fprintf(fo, ", \"simd_cyc_per_fma\": %.3f", simd_iter / kBeside[s].fma_per_iter);
+            fprintf(fo, "}");
+            first = false;
+            printf("%-34s W=%d  simd %.3f cyc/inst  %.3f cyc/iteration  (hw_id waves/SIMD %d..%d)\n", kBeside[s].name, W, simd_iter / kBeside[s].insts_per_iter, simd_iter, wps_min, wps_max);
+            fflush(stdout);
+        }
+    }
+    fprintf(fo, "\n ],\n \"between_waves\": [\n");
+    first = true;
+    for (int s : {kBesidePk, kBesideFma}) {
+        for (int M : {0, 1, 2}) {
+            const int W = 4, n_valu = W - M;
+            // timed role: 0 = the VALU waves (MFMA waves run 8x), 1 = the MFMA waves (VALU waves run 8x)
+            double valu_cyc_per_fma = 0, valu_wave_cyc_per_inst = 0, mfma_cyc_per_inst = 0; bool covered = true, split_ok = true;
+            for (int timed = 0; timed < (M ? 2 : 1); timed++) {
+                if (!launch(s, W, M, timed == 0 ? iters : 8 * iters, timed == 1 ? iters : 8 * iters)) return 1;
+                double sum = 0, wsum = 0; int n = 0, wn = 0;
+                for (int b = 0; b < n_cu; b++) {
+                    double worst[4] = {0, 0, 0, 0}; unsigned long long end_timed[4] = {0, 0, 0, 0}, end_other[4]; int n_m[4] = {0, 0, 0, 0};
+                    for (int q = 0; q < 4; q++) end_other[q] = ~0ull;
+                    for (int w = 0; w < 4 * W; w++) {
+                        const int i = b * 4 * W + w, q = (id[i] >> 4) & 3;
+                        n_m[q] += role[i];
+                        if (int(role[i]) == timed) { worst[q] = std::max(worst[q], double(cyc[i])); end_timed[q] = std::max(end_timed[q], tend[i]); wsum += double(cyc[i]); wn++; }
+                        else end_other[q] = std::min(end_other[q], tend[i]);
+                    }
+                    for (int q = 0; q < 4; q++) { sum += worst[q]; n++; if (M && end_other[q] < end_timed[q]) covered = false; if (n_m[q] != M) split_ok = false; }
+                }
+                if (timed == 0) { valu_cyc_per_fma = sum / n / (double(iters) * kBeside[s].fma_per_iter * n_valu); valu_wave_cyc_per_inst = wsum / wn / (double(iters) * kBeside[s].insts_per_iter); }
+                else mfma_cyc_per_inst = sum / n / (double(iters) * 8 * M);
+            }
+            fprintf(fo, "%s  {\"valu_stream\": \"%s\", \"mfma_waves_per_simd\": %d, \"valu_waves_per_simd\": %d, \"valu_simd_cyc_per_fma\": %.3f, \"valu_wave_cyc_per_inst_mean\": %.3f, "
+                        "\"mfma_simd_cyc_per_inst\": %.3f, \"covered\": %s, \"split_as_asked\": %s}", first ? "" : ",\n", kBeside[s].name, M, n_valu, valu_cyc_per_fma, valu_wave_cyc_per_inst,
+                    mfma_cyc_per_inst, covered ? "true" : "false", split_ok ? "true" : "false");
+            first = false;
+            printf("between waves: %-14s M=%d  VALU %.3f SIMD cyc/FMA (wave %.3f cyc/inst)  MFMA %.3f SIMD cyc/inst  covered %d split %d\n", kBeside[s].name, M, valu_cyc_per_fma,
+                   valu_wave_cyc_per_inst, mfma_cyc_per_inst, int(covered), int(split_ok));
+            fflush(stdout);
+        }
+    }
+    fprintf(fo, "\n ]}\n");
+    fclose(fo);
+    return 0;
+}
+
 int main(int argc, char** argv) {
+    if (argc > 1 && !strcmp(argv[1], "--beside-mfma")) return run_beside(argc > 2 ? argv[2] : "valu_beside_mfma_probe.json");
     const char* out_path = argc > 1 ? argv[1] : "valu_issue_probe.json";
     const int iters = 20000;
     hipDeviceProp_t prop;
