@@ -7,12 +7,18 @@ from . import _native
 from ._native import _clamp_arg, _launch, _ptr, _require_cuda, is_channels_last, profiled
 
 
+def _nhwc_memory(x):
+    """Is the MEMORY of the 4-D tensor x [N,H,W,C]?  is_channels_last -- or one pixel per image (H = W = 1), whose dense memory is [N,C] in
+    either layout and which is_channels_last, made to tell the two layouts apart, counts as NCHW."""
+    return is_channels_last(x) or (x.ndim == 4 and x.shape[1] > 1 and x.shape[2] == 1 and x.shape[3] == 1 and x.is_contiguous())
+
+
 def _operands(x, w, name, w_name, channels='C', c_out=None):
     """Check the two operands every kernel here takes -- x (x3 for the split form) channels_last float16 [N,C,H,W], w contiguous float16
     [9,O,C padded to a multiple of 64], O == c_out when given -- and return (N, C, H, W, O)."""
     n, c, h, wd = x.shape
     o = w.shape[1]
-    if not is_channels_last(x) or x.dtype != torch.float16 or tuple(w.shape) != (9, c_out or o, -(-c // 64) * 64) or w.dtype != torch.float16 or not w.is_contiguous():
+    if not _nhwc_memory(x) or x.dtype != torch.float16 or tuple(w.shape) != (9, c_out or o, -(-c // 64) * 64) or w.dtype != torch.float16 or not w.is_contiguous():
         raise RuntimeError(f"{name}: {'x3' if channels == '3C' else 'x'} must be channels_last float16 [N,{channels},H,W] and {w_name} contiguous float16 "
                            f"[9,{c_out or 'O'},{channels}]")
     return n, c, h, wd, o
@@ -189,7 +195,7 @@ def pack_conv_transpose3x3_weights(weight, dtype=torch.float16):
 def conv_transpose3x3_s2_supported(x, c_out):
     """Does the phase-decomposed transposed convolution take this activation tensor?  (float16, channels_last, input channels in
     multiples of 8, output channels in blocks of 128; any height and width.)"""
-    return (x.is_cuda and x.dtype == torch.float16 and x.ndim == 4 and is_channels_last(x) and x.shape[1] % 8 == 0 and c_out % 128 == 0
+    return (x.is_cuda and x.dtype == torch.float16 and x.ndim == 4 and _nhwc_memory(x) and x.shape[1] % 8 == 0 and c_out % 128 == 0
             and x.shape[1] * x.shape[2] * x.shape[3] * 2 < (1 << 31))
 
 
