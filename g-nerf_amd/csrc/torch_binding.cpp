@@ -13,7 +13,8 @@
 // marching_cubes (gnerf_hip.marching_cubes' count -> read counts -> emit sequence), ssim_forward / ssim_backward (gnerf_hip.ssim_*),
 // modconv_backward (gnerf_hip.scale_channels_backward / modconv_epilogue_backward), query_points_grad (gnerf_hip.query_points_grad),
 // render_backward_rays (gnerf_hip.render_backward with need_rays), resize_aa (gnerf_hip.resize_aa_forward / _backward),
-// raster_visibility / raster_resolve (gnerf_hip.rasterize / resolve), mesh_components / mesh_compact / mesh_smooth (gnerf_hip's of those names).
+// raster_visibility / raster_resolve (gnerf_hip.rasterize / resolve), mesh_components / mesh_compact / mesh_smooth /
+// mesh_simplify / mesh_simplify_count (gnerf_hip's of those names).
 //
 // Built ahead of time by csrc/build.sh (g++, no hipcc: there is no device code) into g-nerf_amd/gnerf_hip/gnerf_torch_ext.so.
 
@@ -671,6 +672,58 @@ Tensor mesh_smooth(Tensor verts, Tensor faces, int64_t iterations, double lam, d
     return out;
 }
 
+// ------------------------------------------------------------------------------------------------ mesh simplification (csrc/mesh_simplify.hip)
+// gnerf_hip.mesh_simplify / mesh_simplify_count have validated the tensors (verts float32 [V, 3], faces int32 [T, 3], contiguous on one GPU),
+// cell and origin (three values that are exact floats).
+struct SimplifyCall {
+    int nv, nt;
+    const float* v;
+    const int32_t* f;
+    float origin[3];
+    Tensor ws, counts;
+};
+
+SimplifyCall mesh_simplify_counted(const Tensor& verts, const Tensor& faces, double cell, const std::vector<double>& origin) {
+    TORCH_CHECK(verts.is_cuda() && verts.scalar_type() == torch::kFloat32 && verts.is_contiguous() && faces.scalar_type() == torch::kInt32 &&
+                faces.is_contiguous() && faces.device() == verts.device(), "mesh_simplify: unexpected tensor layout");
+    TORCH_CHECK(verts.size(0) <= INT_MAX && faces.size(0) <= INT_MAX && origin.size() == 3, "mesh_simplify: argument out of range");
+    SimplifyCall c;
+    c.nv = int(verts.size(0));
+    c.nt = int(faces.size(0));
+    c.v = c.nv ? verts.data_ptr<float>() : nullptr;
+    c.f = c.nt ? faces.data_ptr<int32_t>() : nullptr;
+    for (int a = 0; a < 3; a++) c.origin[a] = float(origin[a]);
+    size_t bytes = 0;
+    check_rc(gnerf_mesh_simplify_workspace_bytes(c.nv, c.nt, &bytes), "gnerf_mesh_simplify_workspace_bytes");
+    c.ws = torch::empty({int64_t(bytes)}, verts.options().dtype(torch::kUInt8));
+    c.counts = torch::empty({8}, verts.options().dtype(torch::kInt64));
+    check_rc(gnerf_mesh_simplify_count(c.v, c.f, c.nv, c.nt, float(cell), c.origin, c.ws.data_ptr(), c.counts.data_ptr<int64_t>(), current_stream()),
+             "gnerf_mesh_simplify_count");
+    return c;
+}
+
+// -> counts int64 [8] on the host
+Tensor mesh_simplify_count(Tensor verts, Tensor faces, double cell, std::vector<double> origin) {
+    const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(at::device_of(verts));
+    return mesh_simplify_counted(verts, faces, cell, origin).counts.cpu();
+}
+
+// -> (verts' [V', 3], faces' [T', 3], src_vertex [V'], vertex_map [V], counts int64 [8] on the host)
+std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor> mesh_simplify(Tensor verts, Tensor faces, double cell, std::vector<double> origin) {
+    const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(at::device_of(verts));
+    SimplifyCall c = mesh_simplify_counted(verts, faces, cell, origin);
+    Tensor host = c.counts.cpu();                                  // the op's one synchronisation
+    const int64_t* n = host.data_ptr<int64_t>();
+    const auto ints = verts.options().dtype(torch::kInt32);
+    Tensor out_v = torch::empty({n[0], 3}, verts.options()), out_f = torch::empty({n[1], 3}, ints), src = torch::empty({n[0]}, ints);
+    Tensor vmap = n[0] > 0 ? torch::empty({int64_t(c.nv)}, ints) : torch::full({int64_t(c.nv)}, -1, ints);
+    if (n[0] > 0)
+        check_rc(gnerf_mesh_simplify_emit(c.v, c.f, c.nv, c.nt, float(cell), c.origin, c.ws.data_ptr(), out_v.data_ptr<float>(),
+                                          n[1] > 0 ? out_f.data_ptr<int32_t>() : nullptr, src.data_ptr<int32_t>(), vmap.data_ptr<int32_t>(), current_stream()),
+                 "gnerf_mesh_simplify_emit");
+    return std::make_tuple(out_v, out_f, src, vmap, host);
+}
+
 }  // namespace
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -693,6 +746,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("mesh_components", &mesh_components);
     m.def("mesh_compact", &mesh_compact);
     m.def("mesh_smooth", &mesh_smooth);
+    m.def("mesh_simplify", &mesh_simplify);
+    m.def("mesh_simplify_count", &mesh_simplify_count);
     // the header version THIS extension was compiled against (a compile-time constant: gnerf_abi_version() would resolve in
     // libgnerf_hip.so at run time and compare the library with itself); gnerf_hip.ext() checks both against its own
     m.def("abi_version", []() { return int(GNERF_ABI_VERSION); });

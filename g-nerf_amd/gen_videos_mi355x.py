@@ -24,6 +24,8 @@ is still on the device; `--mesh-attrs normals|colors|all` adds the density field
 the renderer's pixel grid, uint8 [F, H, W, 3] at `--geometry-res`, smooth-shaded / coloured with `--mesh-attrs`.
 `--mesh-keep K`, `--mesh-min-faces N` and `--mesh-smooth ITERS` clean the mesh of both first (csrc/mesh_clean.hip): only the K largest connected
 components / those with at least N triangles stay, then ITERS Taubin iterations fair the surface; all 0 by default, which changes nothing.
+`--mesh-simplify CELL` (voxels) and `--mesh-target-faces N` simplify it in between (csrc/mesh_simplify.hip): one vertex per occupied cell of a
+uniform grid, placed by the cell's quadric; both 0 by default, which changes nothing.
 """
 
 import argparse
@@ -325,6 +327,17 @@ def clean_extracted_mesh(verts, faces, clean):
     return cleaned.verts, cleaned.faces, cleaned.report
 
 
+def simplify_extracted_mesh(verts, faces, simplify):
+    """--mesh-simplify / --mesh-target-faces on the mesh the compaction left (shape_mi355x.simplify_mesh), before the vertex attributes are
+    queried -- at the simplified vertices -- and before the smoothing.  simplify: shape_mi355x.simplify_options' dict or None (nothing runs)
+    -> (verts, faces, report or None)."""
+    if not simplify:
+        return verts, faces, None
+    import shape_mi355x
+    simplified = shape_mi355x.simplify_mesh(verts, faces, **simplify)
+    return simplified.verts, simplified.faces, simplified.report
+
+
 def smooth_extracted_mesh(verts, faces, clean):
     """The second half: the Taubin iterations, which move positions last (normals and colours stay those of the extracted surface)."""
     if not clean or not clean['smooth']:
@@ -338,14 +351,15 @@ def smooth_extracted_mesh(verts, faces, clean):
     return torch.from_numpy(smoothed) if isinstance(verts, torch.Tensor) else smoothed
 
 
-def mesh_density_grid(vol, ply_path, level=10.0, attrs=None, G=None, planes=None, clean=None, report=None):
+def mesh_density_grid(vol, ply_path, level=10.0, attrs=None, G=None, planes=None, clean=None, report=None, simplify=None, simplify_report=None):
     """--mesh: the mesh shape_utils.convert_mrc makes of the .mrc of this volume (shape_utils.py:103-105: transpose(2, 1, 0), voxel
     size 1, origin 0), made where the volume lives -- on a GPU the marching-cubes kernel reads it in HBM, only the mesh comes to the host.
     attrs: None / 'none', 'normals', 'colors' or 'all' -- per-vertex attributes (mesh_vertex_attributes) of generator G on `planes`
     (extract_density_grid(..., return_planes=True)), evaluated on the device too; the vertices stay in index space, as the reference's.
     clean: None or shape_mi355x.clean_options' dict -- marching cubes, then components and compaction, then the attributes (at the kept
     vertices' extracted positions), then smoothing.  report: a dict that receives clean_mesh's report when the mesh was cleaned (left as
-    it is otherwise).
+    it is otherwise).  simplify: None or shape_mi355x.simplify_options' dict -- the mesh is simplified between the compaction and the
+    attributes; simplify_report: a dict that then receives simplify_mesh's report.
     Writes `ply_path`; returns (vertex count, triangle count, seconds spent in marching cubes)."""
     import shape_mi355x
     attrs = 'none' if attrs is None else attrs
@@ -359,6 +373,9 @@ def mesh_density_grid(vol, ply_path, level=10.0, attrs=None, G=None, planes=None
     verts, faces, cleaned = clean_extracted_mesh(verts, faces, clean)
     if report is not None and cleaned is not None:
         report.update(cleaned)
+    verts, faces, simplified = simplify_extracted_mesh(verts, faces, simplify)
+    if simplify_report is not None and simplified is not None:
+        simplify_report.update(simplified)
     normals = colors = None
     if attrs != 'none':
         v = verts if isinstance(verts, torch.Tensor) else torch.from_numpy(verts).to(vol.device)
@@ -418,6 +435,10 @@ def main():
     ap.add_argument('--mesh-keep', type=int, default=0, help='keep only this many of the largest connected components of the mesh (--mesh and --geometry-out; 0: all)')
     ap.add_argument('--mesh-min-faces', type=int, default=0, help='drop connected components with fewer triangles than this (0: none)')
     ap.add_argument('--mesh-smooth', type=int, default=0, help='Taubin smoothing iterations of the mesh, applied last (lambda 0.5, mu -0.53, boundaries pinned; 0: none)')
+    ap.add_argument('--mesh-simplify', type=float, default=0, metavar='CELL',
+                    help='simplify the mesh by vertex clustering on a grid of cells this many voxels wide, after the components, before the attributes and the smoothing (0: off)')
+    ap.add_argument('--mesh-target-faces', type=int, default=0, metavar='N',
+                    help='pick the cell instead: the smallest of CELL (or one voxel) * 2^(j / 4), j = 0 .. 40, that leaves at most N triangles (0: off)')
     ap.add_argument('--voxel-res', type=int, default=512)
     ap.add_argument('--geometry-out', default=None, help='also draw the mesh of the density volume from every orbit camera (shaded geometry frames, '
                                                          'uint8 [F, H, W, 3]) and write them to this .npy (rank 0); uses --voxel-res, --mesh-level, --mesh-attrs, --frames-per-call')
@@ -426,8 +447,11 @@ def main():
     args = ap.parse_args()
     if min(args.mesh_keep, args.mesh_min_faces, args.mesh_smooth) < 0:
         ap.error('--mesh-keep, --mesh-min-faces and --mesh-smooth must be >= 0')
+    if not args.mesh_simplify >= 0 or args.mesh_simplify == float('inf') or args.mesh_target_faces < 0:
+        ap.error('--mesh-simplify and --mesh-target-faces must be >= 0')
     import shape_mi355x
     clean = shape_mi355x.clean_options(args.mesh_keep, args.mesh_min_faces, args.mesh_smooth)
+    simplify = shape_mi355x.simplify_options(args.mesh_simplify, args.mesh_target_faces)
     H.configure_backend(False if args.no_solver_search else None)
 
     rank, world, local_rank = H.init_from_env()
@@ -485,10 +509,13 @@ def main():
             shape_mi355x.write_mrc(args.shapes_mrc, vol.cpu().numpy())
         if args.mesh:
             t0 = time.perf_counter()
-            report = {}
-            nv, nf, dt = mesh_density_grid(vol, args.mesh, args.mesh_level, attrs=args.mesh_attrs, G=G, planes=planes, clean=clean, report=report)
+            report, simplify_report = {}, {}
+            nv, nf, dt = mesh_density_grid(vol, args.mesh, args.mesh_level, attrs=args.mesh_attrs, G=G, planes=planes, clean=clean, report=report,
+                                           simplify=simplify, simplify_report=simplify_report)
             if report:
                 print(shape_mi355x.clean_report_line(report, args.mesh_smooth))
+            if simplify_report:
+                print(shape_mi355x.simplify_report_line(simplify_report))
             print(f'mesh at level {args.mesh_level:g}: {dt * 1e3:.2f} ms, {nv} vertices, {nf} triangles -> {args.mesh}'
                   + (f' (with {args.mesh_attrs}: {(time.perf_counter() - t0) * 1e3:.2f} ms in all, file included)' if args.mesh_attrs != 'none' else ''))
     if args.geometry_out:
@@ -498,6 +525,9 @@ def main():
         verts, faces, report = clean_extracted_mesh(verts, faces, clean)
         if report is not None and rank == 0 and not args.mesh:           # (--mesh has printed the same line)
             print(shape_mi355x.clean_report_line(report, args.mesh_smooth))
+        verts, faces, report = simplify_extracted_mesh(verts, faces, simplify)
+        if report is not None and rank == 0 and not args.mesh:
+            print(shape_mi355x.simplify_report_line(report))
         if not isinstance(verts, torch.Tensor):
             verts, faces = torch.from_numpy(verts), torch.from_numpy(faces)
         normals = colors = None

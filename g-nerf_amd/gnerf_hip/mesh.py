@@ -1,4 +1,5 @@
-"""Marching cubes on the density volume (csrc/mesh.hip) and the cleaning of its meshes (csrc/mesh_clean.hip): components, compaction, smoothing."""
+"""Marching cubes on the density volume (csrc/mesh.hip) the cleaning of its meshes (csrc/mesh_clean.hip): components, compaction, smoothing, and
+their simplification (csrc/mesh_simplify.hip): vertex clustering with quadrics."""
 
 import ctypes
 
@@ -215,3 +216,100 @@ def mesh_smooth(verts, faces, iterations, lam=0.5, mu=-0.53, pin_boundary=True):
         with _on_device(v.device):
             return e.mesh_smooth(v, f, iterations, float(lam), float(mu), bool(pin_boundary))
     return _mesh_smooth_ctypes(v, f, iterations, float(lam), float(mu), bool(pin_boundary))
+
+
+# ---------------------------------------------------------------------------------------------------------------- simplification (csrc/mesh_simplify.hip)
+_MESH_SIMPLIFY_SYMBOLS = ('gnerf_mesh_simplify_workspace_bytes', 'gnerf_mesh_simplify_count', 'gnerf_mesh_simplify_emit')
+
+
+def mesh_simplify_available():
+    """Whether the loaded library has the mesh-simplification kernels (a version-15 library built before them does not)."""
+    return all(hasattr(load(), name) for name in _MESH_SIMPLIFY_SYMBOLS)
+
+
+def _require_mesh_simplify():
+    if not mesh_simplify_available():
+        raise RuntimeError('gnerf_hip: this libgnerf_hip.so was built without the mesh-simplification kernels (gnerf_mesh_simplify_*): rebuild it (csrc/build.sh)')
+
+
+def mesh_simplify_workspace_bytes(n_verts, n_tris):
+    _require_mesh_simplify()
+    nbytes = ctypes.c_size_t()
+    _check(load().gnerf_mesh_simplify_workspace_bytes(int(n_verts), int(n_tris), ctypes.byref(nbytes)), 'gnerf_mesh_simplify_workspace_bytes')
+    return int(nbytes.value)
+
+
+def _mesh_simplify_args(verts, faces, cell, origin, what):
+    """(verts float32 [V, 3], faces int32 [T, 3], cell and origin as Python floats that are exact C floats)."""
+    _require_mesh_simplify()
+    v, f = _verts_f32(verts, what), _faces_i32(faces, what)
+    if f.device != v.device:
+        raise RuntimeError(f'{what}: verts and faces must be on one device')
+    cell = float(torch.tensor(float(cell), dtype=torch.float32))
+    if not (0 < cell < float('inf')):
+        raise ValueError(f'{what}: cell must be a finite float32 > 0, got {cell}')
+    origin = [float(x) for x in torch.as_tensor(origin, dtype=torch.float64).reshape(-1).to(torch.float32).cpu()]
+    if len(origin) != 3 or not all(abs(x) < float('inf') for x in origin):
+        raise ValueError(f'{what}: origin must be three finite floats')
+    return v, f, cell, origin
+
+
+def _mesh_simplify_count_launch(v, f, cell, origin):
+    """gnerf_mesh_simplify_count through ctypes -> (the mesh's arguments for the emit call, workspace, counts on the device)."""
+    dev, nv, nt = v.device, len(v), len(f)
+    ws = torch.empty(mesh_simplify_workspace_bytes(nv, nt), dtype=torch.uint8, device=dev)
+    counts = torch.empty(8, dtype=torch.int64, device=dev)
+    mesh = (_ptr(v) if nv else None, _ptr(f) if nt else None, nv, nt, cell, (ctypes.c_float * 3)(*origin), _ptr(ws))
+    _launch('gnerf_mesh_simplify_count', v, *mesh, _ptr(counts))
+    return mesh, ws, counts
+
+
+def _mesh_simplify_ctypes(v, f, cell, origin):
+    """The ctypes route of mesh_simplify (arguments as _mesh_simplify_args prepares them) -> (verts', faces', src_vertex, vertex_map, counts on
+    the host)."""
+    dev = v.device
+    mesh, ws, counts = _mesh_simplify_count_launch(v, f, cell, origin)
+    host = counts.cpu()                                                      # the op's one synchronisation
+    kv, kt = int(host[0]), int(host[1])
+    out_v = torch.empty([kv, 3], dtype=torch.float32, device=dev)
+    out_f = torch.empty([kt, 3], dtype=torch.int32, device=dev)
+    src = torch.empty(kv, dtype=torch.int32, device=dev)
+    vmap = torch.empty(len(v), dtype=torch.int32, device=dev) if kv else torch.full([len(v)], -1, dtype=torch.int32, device=dev)
+    if kv:
+        _launch('gnerf_mesh_simplify_emit', v, *mesh, _ptr(out_v), _ptr(out_f) if kt else None, _ptr(src), _ptr(vmap))
+    return out_v, out_f, src, vmap, host
+
+
+def _mesh_simplify_result(*result):
+    counts = result[-1]
+    if int(counts[6]):
+        raise RuntimeError('mesh_simplify: internal error (a hash table of the kernels ran full)')
+    return result if len(result) > 1 else counts
+
+
+@profiled('gnerf_hip::mesh_simplify_count')
+def mesh_simplify_count(verts, faces, cell, origin):
+    """The counts of mesh_simplify alone (tables, ids and face grouping, no quadrics): int64 [8] on the host = V', T', invalid faces, collapsed
+    faces, faces absorbed by grouping, groups with |sigma| >= 2, internal error, 0.  What a search for a cell calls."""
+    v, f, cell, origin = _mesh_simplify_args(verts, faces, cell, origin, 'mesh_simplify_count')
+    e = _native.ext()
+    if e is not None and hasattr(e, 'mesh_simplify_count'):
+        with _on_device(v.device):
+            return _mesh_simplify_result(e.mesh_simplify_count(v, f, cell, origin))
+    return _mesh_simplify_result(_mesh_simplify_count_launch(v, f, cell, origin)[2].cpu())
+
+
+@profiled('gnerf_hip::mesh_simplify')
+def mesh_simplify(verts, faces, cell, origin):
+    """Vertex clustering with quadrics on the gfx950 kernels: verts float32 [V, 3], faces int32 [T, 3] (CUDA), cell (a float > 0: the edge of
+    the grid's cells) and origin (three floats: the grid's corner) -> (verts' [V', 3]: one vertex per occupied cell, at the minimum of its
+    cluster's quadric inside the cell; faces' [T', 3]; src_vertex int32 [V']: the old index of every new vertex's representative; vertex_map
+    int32 [V]: the new id of every old vertex or -1; counts int64 [8] on the host, as mesh_simplify_count's).  Rules: include/gnerf_hip.h,
+    gnerf_mesh_simplify_*; shape_mi355x.mesh_simplify_numpy gives the same bits.  Reads the counts to the host between its two passes (not
+    graph-capturable; each pass alone is)."""
+    v, f, cell, origin = _mesh_simplify_args(verts, faces, cell, origin, 'mesh_simplify')
+    e = _native.ext()
+    if e is not None and hasattr(e, 'mesh_simplify'):
+        with _on_device(v.device):
+            return _mesh_simplify_result(*e.mesh_simplify(v, f, cell, origin))
+    return _mesh_simplify_result(*_mesh_simplify_ctypes(v, f, cell, origin))

@@ -25,8 +25,13 @@ clean_mesh edits such a mesh between extraction and its consumers: connected com
 Taubin smoothing.  CUDA tensors go to csrc/mesh_clean.hip (gnerf_hip.mesh_components / mesh_compact / mesh_smooth), numpy arrays to
 mesh_components_numpy / mesh_select / mesh_compact_numpy / mesh_smooth_numpy below (include/gnerf_hip.h, gnerf_mesh_*): the same bits.
 
+simplify_mesh shrinks such a mesh: vertex clustering on a uniform grid with a quadric-error representative per cell, for a given cell or a
+target face count.  CUDA tensors go to csrc/mesh_simplify.hip (gnerf_hip.mesh_simplify / mesh_simplify_count), numpy arrays to
+mesh_simplify_numpy below (include/gnerf_hip.h, gnerf_mesh_simplify_*): the same bits.
+
 CLI, as shape_utils.py's (:102-123):  python shape_mi355x.py INPUT [--level 10]   (INPUT: a .mrc / .npy file or a directory of them)
   [--mesh-keep K] [--mesh-min-faces N] [--mesh-smooth ITERS] clean the mesh first (all 0 by default: the file is the uncleaned one, byte for byte)
+  [--mesh-simplify CELL] [--mesh-target-faces N] simplify it between the compaction and the smoothing (both 0 by default: nothing runs)
 """
 
 import argparse
@@ -749,6 +754,285 @@ def clean_options(keep_largest=0, min_faces=0, smooth=0):
     return opts if any(opts.values()) else None
 
 
+# ---------------------------------------------------------------------------------------------------------------- mesh simplification
+# The numpy port of csrc/mesh_simplify.hip (include/gnerf_hip.h, gnerf_mesh_simplify_*, states the rules; restated here): vertex clustering on
+# a uniform grid with a quadric-error representative per cell.  Parameters: cell (a C float > 0) and origin (three C floats).  Every float64
+# operation is rounded on its own (no contraction); only + - * /, floor, comparisons and integer conversion occur, so the kernels give these bits.
+#   1 valid faces: a face is VALID iff its three ids lie in [0, V) and its three vertices are finite; invalid faces are counted and ignored.  A
+#     vertex is USED iff a valid face names it; unused vertices are dropped.
+#   2 cells: per axis p = (double(v) - double(origin)) / double(cell), k = floor(p) clamped to [0, 2^21 - 1]; key = kx 2^42 + ky 2^21 + kz.  A
+#     cluster = the used vertices of one key, its representative = its smallest vertex index; new ids number the representatives in ascending
+#     old index (src_vertex).  u = p - (k + 0.5), clamped to [-0.5, 0.5] (which only a vertex outside the 2^21-cell grid feels).
+#   3 accumulation in int64 fixed point, q(x) = llrint(x 2^32) (sums wrap modulo 2^64), so any order gives the same bits:
+#     per used vertex into its cluster: q(u) per axis and a member count;
+#     per valid face, read from its corner with the smallest id (rotated, never reflected: 0, 1, 2 below are that order): e1 = p1 - p0,
+#     e2 = p2 - p0, n = e1 x e2 (n0 = e1y e2z - e1z e2y, ...), s = (n0 n0 + n1 n1) + n2 n2; the face is skipped unless 0 < s < inf;
+#     f = 16 / s if s > 16 else 1; per corner c into the cluster of its vertex: d = (n0 u0 + n1 u1) + n2 u2 with u of that vertex, the six
+#     q((f n_a) n_b), a <= b, and the three q(n_a (f d)).
+#   4 position: A, b = the sums / 2^32 as doubles; cen = (the u sums / 2^32) / members; tr = (A00 + A11) + A22, mu = tr / 256.  If tr > 0,
+#     x solves (A + mu I) x = b + mu cen by the elimination written out in _simplify_solve (no pivoting; x = cen if a pivot is not > 0 or x is not finite),
+#     else x = cen; x is clamped to [-0.5, 0.5]; the vertex is float32(double(origin) + ((k + 0.5) + x) double(cell)).
+#   5 faces: a valid face mapped through the new ids is COLLAPSED when two ids coincide, and dropped; the others are grouped by their id set.
+#     sigma = the sum over the group of +1 for a rotation of the ascending triple, -1 otherwise; the group gives one face iff sigma is odd:
+#     (a, b, c) ascending when sigma > 0, else (a, c, b); output faces are ordered by their group's smallest old face index.
+#   6 counts int64 [8] = V', T', invalid faces, collapsed faces, faces absorbed by grouping, groups with |sigma| >= 2, internal error, 0.
+SimplifiedMesh = collections.namedtuple('SimplifiedMesh', 'verts faces normals colors src_vertex vertex_map report')
+MESH_SIMPLIFY_GRID = 2 ** 21                                             # cells per axis that a key holds
+MESH_SIMPLIFY_CANDIDATES = 41                                            # the target search's cells: base * 2^(j / 4), j = 0 .. 40
+_Q32 = 4294967296.0
+
+
+def _simplify_params(cell, origin):
+    cell = np.float32(cell)
+    if not (np.isfinite(cell) and cell > 0):
+        raise ValueError(f'mesh_simplify: cell must be a finite float32 > 0, got {cell}')
+    origin = np.asarray(origin, dtype=np.float32).reshape(-1)
+    if origin.shape != (3,) or not np.all(np.isfinite(origin)):
+        raise ValueError('mesh_simplify: origin must be three finite floats')
+    return cell, origin
+
+
+def _simplify_q(x):
+    return np.rint(x * _Q32).astype(np.int64)
+
+
+def _simplify_solve(A, b, cen, members):
+    """Rule 4 for every cluster at once: A [6, C] (00 01 02 11 12 22), b [3, C], cen [3, C] -> x [3, C] in [-0.5, 0.5]."""
+    m00, m01, m02, m11, m12, m22 = A
+    tr = (m00 + m11) + m22
+    mu = tr / 256.0
+    with np.errstate(all='ignore'):
+        m00, m11, m22 = m00 + mu, m11 + mu, m22 + mu
+        r0, r1, r2 = b[0] + mu * cen[0], b[1] + mu * cen[1], b[2] + mu * cen[2]
+        l10, l20 = m01 / m00, m02 / m00
+        m11, m12b, m22 = m11 - l10 * m01, m12 - l10 * m02, m22 - l20 * m02
+        r1, r2 = r1 - l10 * r0, r2 - l20 * r0
+        l21 = m12b / m11
+        m22, r2 = m22 - l21 * m12b, r2 - l21 * r1
+        x2 = r2 / m22
+        x1 = (r1 - m12b * x2) / m11
+        x0 = ((r0 - m01 * x1) - m02 * x2) / m00
+        solved = (tr > 0) & (m00 > 0) & (m11 > 0) & (m22 > 0) & np.isfinite(x0) & np.isfinite(x1) & np.isfinite(x2)
+    x = np.where(solved, np.stack([x0, x1, x2]), cen)
+    return np.minimum(np.maximum(x, -0.5), 0.5)
+
+
+def mesh_simplify_numpy(verts, faces, cell, origin, count_only=False):
+    """The numpy port of gnerf_mesh_simplify_count / _emit -> (verts' float32 [V', 3], faces' int32 [T', 3], src_vertex int32 [V'], vertex_map
+    int32 [V]: the new id of every old vertex or -1, counts int64 [8]); count_only: just the counts (no quadrics, as the count call)."""
+    v = np.ascontiguousarray(np.asarray(verts), dtype=np.float32).reshape(-1, 3)
+    f, ok = _mesh_faces(faces, len(v))
+    cell, origin = _simplify_params(cell, origin)
+    nv, nt = len(v), len(f)
+    finite = np.all(np.isfinite(v), axis=1)
+    ok = ok.copy()
+    ok[ok] = np.all(finite[f[ok]], axis=1)
+    g = f[ok]                                                            # the valid faces, in order
+    used = np.zeros(nv, dtype=bool)
+    used[g.reshape(-1)] = True
+    old = np.nonzero(used)[0]                                            # used vertices, ascending
+    with np.errstate(all='ignore'):
+        p = (v[old].astype(np.float64) - origin.astype(np.float64)) / np.float64(cell)
+    k = np.minimum(np.maximum(np.floor(p), 0.0), float(MESH_SIMPLIFY_GRID - 1)).astype(np.int64)
+    key = (k[:, 0] << 42) | (k[:, 1] << 21) | k[:, 2]
+    _, first, inverse = np.unique(key, return_index=True, return_inverse=True)       # first: the first (smallest) member of every key
+    rank = np.argsort(np.argsort(first))                                 # unique-key number -> new id (representatives in ascending old index)
+    src = old[np.sort(first)].astype(np.int32)
+    cluster = rank[inverse.reshape(-1)]                                  # new id of every used vertex
+    vmap = np.full(nv, -1, dtype=np.int32)
+    vmap[old] = cluster
+    # faces: collapse, group, parity
+    h = vmap[g].astype(np.int64).reshape(-1, 3)
+    a, b, c = h[:, 0], h[:, 1], h[:, 2]
+    alive = (a != b) & (b != c) & (a != c)
+    n_collapsed = int(len(g) - np.count_nonzero(alive))
+    h = h[alive]
+    a, b, c = h[:, 0], h[:, 1], h[:, 2]
+    sign = np.where((a < b).astype(np.int64) + (b < c) + (c < a) == 2, 1, -1)
+    tri = np.sort(h, axis=1)
+    order = np.lexsort((np.arange(len(tri)), tri[:, 2], tri[:, 1], tri[:, 0]))
+    ts = tri[order]
+    head = np.ones(len(ts), dtype=bool)
+    head[1:] = np.any(ts[1:] != ts[:-1], axis=1)
+    group = np.cumsum(head) - 1                                          # group number of every sorted face
+    sigma = np.bincount(group, weights=sign[order], minlength=int(head.sum())).astype(np.int64)
+    leader = order[head]                                                 # the smallest face of every group (the sort is by face last)
+    out = sigma % 2 != 0
+    by_leader = np.argsort(leader[out])
+    tri_out, sig_out = ts[head][out][by_leader], sigma[out][by_leader]
+    new_faces = np.where((sig_out > 0)[:, None], tri_out, tri_out[:, [0, 2, 1]]).astype(np.int32).reshape(-1, 3)
+    counts = np.array([len(src), len(new_faces), nt - len(g), n_collapsed, len(h) - len(new_faces), np.count_nonzero(np.abs(sigma) >= 2), 0, 0], dtype=np.int64)
+    if count_only:
+        return counts
+    # quadrics
+    n_new = len(src)
+    u = np.minimum(np.maximum(p - (k.astype(np.float64) + 0.5), -0.5), 0.5)
+    acc = np.zeros((13, n_new), dtype=np.int64)                          # u sums, members, the six of A, the three of b
+    qu = _simplify_q(u)
+    for axis in range(3):
+        np.add.at(acc[axis], cluster, qu[:, axis])
+    np.add.at(acc[3], cluster, 1)
+    where = np.full(nv, -1, dtype=np.int64)
+    where[old] = np.arange(len(old))
+    lowest = np.argmin(g, axis=1) if len(g) else np.zeros(0, dtype=np.int64)
+    rows = np.arange(len(g))
+    g = np.stack([g[rows, (lowest + j) % 3] for j in range(3)], axis=1) if len(g) else g
+    w = where[g].reshape(-1, 3)                                          # rows of p / u / cluster of the three corners
+    with np.errstate(all='ignore'):
+        e1, e2 = p[w[:, 1]] - p[w[:, 0]], p[w[:, 2]] - p[w[:, 0]]
+        n = np.stack([e1[:, 1] * e2[:, 2] - e1[:, 2] * e2[:, 1], e1[:, 2] * e2[:, 0] - e1[:, 0] * e2[:, 2], e1[:, 0] * e2[:, 1] - e1[:, 1] * e2[:, 0]], axis=1)
+        s = (n[:, 0] * n[:, 0] + n[:, 1] * n[:, 1]) + n[:, 2] * n[:, 2]
+        take = (s > 0) & (s < np.inf)
+    n, s, w = n[take], s[take], w[take]
+    scale = np.ones(len(s))
+    scale[s > 16.0] = 16.0 / s[s > 16.0]
+    fn = scale[:, None] * n
+    quad = [_simplify_q(fn[:, i] * n[:, j]) for i, j in ((0, 0), (0, 1), (0, 2), (1, 1), (1, 2), (2, 2))]
+    for corner in range(3):
+        uc, target = u[w[:, corner]], cluster[w[:, corner]]
+        d = (n[:, 0] * uc[:, 0] + n[:, 1] * uc[:, 1]) + n[:, 2] * uc[:, 2]
+        fd = scale * d
+        for i in range(6):
+            np.add.at(acc[4 + i], target, quad[i])
+        for axis in range(3):
+            np.add.at(acc[10 + axis], target, _simplify_q(n[:, axis] * fd))
+    members = acc[3].astype(np.float64)
+    cen = (acc[0:3].astype(np.float64) / _Q32) / members
+    x = _simplify_solve(acc[4:10].astype(np.float64) / _Q32, acc[10:13].astype(np.float64) / _Q32, cen, members)
+    krep = k[where[src.astype(np.int64)]].astype(np.float64).T           # [3, V']
+    pos = origin.astype(np.float64)[:, None] + ((krep + 0.5) + x) * np.float64(cell)
+    return np.ascontiguousarray(pos.T.astype(np.float32)).reshape(-1, 3), np.ascontiguousarray(new_faces), src, vmap, counts
+
+
+def simplify_candidates(base):
+    """The cells the target search may choose: float32(base * 2^(j / 4)), j = 0 .. 40 (a factor of 1024 in all)."""
+    return [float(np.float32(float(base) * 2.0 ** (j / 4))) for j in range(MESH_SIMPLIFY_CANDIDATES)]
+
+
+def simplify_search(count_faces, target_faces, n=MESH_SIMPLIFY_CANDIDATES):
+    """Bisect j in [0, n) for the smallest candidate whose face count count_faces(j) is <= target_faces, taking the count to fall as the cell
+    grows -> (j, calls, met): at most ceil(log2 n) + 1 calls; met is False when even the coarsest candidate leaves more faces (j = n - 1)."""
+    seen = {}
+
+    def passes(j):
+        if j not in seen:
+            seen[j] = count_faces(j) <= target_faces
+        return seen[j]
+    lo, hi = 0, n - 1
+    while lo < hi:
+        mid = (lo + hi) // 2
+        if passes(mid):
+            hi = mid
+        else:
+            lo = mid + 1
+    met = passes(lo)
+    return lo, len(seen), met
+
+
+def simplify_mesh(verts, faces, cell=None, target_faces=0, origin=None, normals=None, colors=None):
+    """Simplify a mesh by vertex clustering with quadrics: one vertex per occupied cell of a grid of edge `cell` with its corner at `origin`
+    (default: the per-axis minimum of the finite vertices).  target_faces > 0 picks the cell instead: the smallest of simplify_candidates(cell
+    or 1.0) that leaves at most that many faces, found by bisection on the count call alone.  CUDA tensors run the gfx950 kernels
+    (gnerf_hip.mesh_simplify / mesh_simplify_count) and return tensors on their device; numpy arrays and CPU tensors run mesh_simplify_numpy and
+    return numpy arrays -- the same bits either way.  -> SimplifiedMesh(verts, faces, normals, colors, src_vertex, vertex_map, report): normals /
+    colors are the given per-vertex arrays gathered at src_vertex (None when not given), report a dict: cell, origin, target_faces, j and
+    count_calls (None / 0 without a target), met, vertices, faces, new_vertices, new_faces, invalid, collapsed, absorbed, multi."""
+    try:
+        import torch
+    except ImportError:                                                  # pragma: no cover - torch is part of the stack
+        torch = None
+    target_faces = int(target_faces)
+    if target_faces < 0:
+        raise ValueError(f'simplify_mesh: target_faces must be >= 0, got {target_faces}')
+    if cell is None and target_faces == 0:
+        raise ValueError('simplify_mesh: give a cell, a target_faces > 0, or both')
+    on_gpu = torch is not None and isinstance(verts, torch.Tensor) and verts.is_cuda
+    if on_gpu:
+        import gnerf_hip
+        dev = verts.device
+        verts = verts.detach().reshape(-1, 3).to(torch.float32)
+        finite = verts[torch.isfinite(verts).all(dim=1)]
+        lo_hi = torch.stack([finite.min(dim=0).values, finite.max(dim=0).values]).cpu().numpy() if len(finite) else np.zeros((2, 3), np.float32)
+        count = lambda c, o: gnerf_hip.mesh_simplify_count(verts, faces, c, o).numpy()
+    else:
+        if torch is not None:
+            verts, faces, normals, colors = (t.detach().cpu().numpy() if isinstance(t, torch.Tensor) else t for t in (verts, faces, normals, colors))
+        verts = np.asarray(verts, dtype=np.float32).reshape(-1, 3)
+        finite = verts[np.all(np.isfinite(verts), axis=1)]
+        lo_hi = np.stack([finite.min(axis=0), finite.max(axis=0)]) if len(finite) else np.zeros((2, 3), np.float32)
+        count = lambda c, o: mesh_simplify_numpy(verts, faces, c, o, count_only=True)
+    origin = lo_hi[0] if origin is None else origin
+    base, origin = _simplify_params(1.0 if cell is None else cell, origin)
+    if np.any((lo_hi[1].astype(np.float64) - origin.astype(np.float64)) / np.float64(base) >= MESH_SIMPLIFY_GRID):
+        raise ValueError(f'simplify_mesh: the mesh spans {MESH_SIMPLIFY_GRID} cells or more of edge {base} along an axis')
+    j, calls, met = None, 0, True
+    if target_faces:
+        cells = simplify_candidates(base)
+        j, calls, met = simplify_search(lambda i: int(count(cells[i], origin)[1]), target_faces)
+        base = np.float32(cells[j])
+    if on_gpu:
+        v, f, src, vmap, counts = gnerf_hip.mesh_simplify(verts, faces, float(base), origin)
+        index = src.long()
+        normals, colors = (None if t is None else t.to(dev)[index] for t in (normals, colors))
+    else:
+        v, f, src, vmap, counts = mesh_simplify_numpy(verts, faces, base, origin)
+        normals, colors = (None if t is None else np.asarray(t)[src] for t in (normals, colors))
+    c = [int(x) for x in counts]
+    report = dict(cell=float(base), origin=tuple(float(x) for x in origin), target_faces=target_faces, j=j, count_calls=calls, met=bool(met),
+                  vertices=int(len(verts)), faces=int(c[1] + c[2] + c[3] + c[4]), new_vertices=c[0], new_faces=c[1], invalid=c[2], collapsed=c[3], absorbed=c[4],
+                  multi=c[5])
+    return SimplifiedMesh(v, f, normals, colors, src, vmap, report)
+
+
+def simplify_report_line(report):
+    """The one stdout line of the CLIs about a simplify_mesh report."""
+    search = (f', candidate {report["j"]} for at most {report["target_faces"]} faces after {report["count_calls"]} count call(s)'
+              + ('' if report['met'] else ' (not met)')) if report['target_faces'] else ''
+    return (f'mesh simplification: cell {report["cell"]:g}{search}: {report["new_faces"]} of {report["faces"]} triangles, {report["new_vertices"]} of '
+            f'{report["vertices"]} vertices ({report["collapsed"]} collapsed, {report["absorbed"]} absorbed, {report["invalid"]} invalid)')
+
+
+def simplify_options(cell=0.0, target_faces=0, voxel=1.0):
+    """The CLIs' two flags (--mesh-simplify CELL, in voxels of edge `voxel`, and --mesh-target-faces N) as simplify_mesh keywords, or None when
+    both are 0 (nothing runs)."""
+    cell, target_faces = float(cell), int(target_faces)
+    if cell < 0 or target_faces < 0 or cell != cell:
+        raise ValueError('--mesh-simplify and --mesh-target-faces must be >= 0')
+    if not cell and not target_faces:
+        return None
+    return dict(cell=(cell if cell else 1.0) * float(voxel), target_faces=target_faces)
+
+
+def process_mesh(verts, faces, clean=None, simplify=None):
+    """What the CLIs do to a mesh marching cubes just made, up to the smoothing: components and compaction (clean: clean_options' dict or
+    None), then simplification (simplify: simplify_options' dict or None).  -> (verts, faces, clean report or None, simplify report or None);
+    smoothing (smooth_mesh) comes after the vertex attributes have been evaluated, at the final vertices."""
+    clean_report = simplify_report = None
+    if clean:
+        cleaned = clean_mesh(verts, faces, keep_largest=clean['keep_largest'], min_faces=clean['min_faces'])
+        verts, faces, clean_report = cleaned.verts, cleaned.faces, cleaned.report
+    if simplify:
+        simplified = simplify_mesh(verts, faces, **simplify)
+        verts, faces, simplify_report = simplified.verts, simplified.faces, simplified.report
+    return verts, faces, clean_report, simplify_report
+
+
+def smooth_mesh(verts, faces, clean=None):
+    """The Taubin iterations of clean_options' dict (None or smooth == 0: nothing) on a mesh of either route; positions only."""
+    if not clean or not clean['smooth']:
+        return verts
+    try:
+        import torch
+    except ImportError:                                                  # pragma: no cover - torch is part of the stack
+        torch = None
+    if torch is not None and isinstance(verts, torch.Tensor):
+        if verts.is_cuda:
+            import gnerf_hip
+            return gnerf_hip.mesh_smooth(verts, faces, clean['smooth'])
+        return torch.from_numpy(mesh_smooth_numpy(verts.numpy(), faces.numpy() if isinstance(faces, torch.Tensor) else faces, clean['smooth']))
+    return mesh_smooth_numpy(verts, faces, clean['smooth'])
+
+
 # ---------------------------------------------------------------------------------------------------------------- PLY
 def write_ply(path, verts, faces, normals=None, colors=None):
     """Binary little-endian PLY with the layout plyfile writes for shape_utils.py's two elements (vertex x/y/z float, face
@@ -847,13 +1131,23 @@ def read_ply_attrs(path):
     return {k: v for k, v in found.items() if v is not None}
 
 
-def convert_sdf_samples_to_ply(volume, voxel_grid_origin, voxel_size, ply_filename_out, offset=None, scale=None, level=0.0, clean=None, report=None):
+def convert_sdf_samples_to_ply(volume, voxel_grid_origin, voxel_size, ply_filename_out, offset=None, scale=None, level=0.0, clean=None, report=None,
+                               simplify=None, simplify_report=None):
     """shape_utils.py:40-100: mesh `volume` at `level` with spacing voxel_size, move the vertices by voxel_grid_origin, then
     / scale and - offset when given, and write the .ply.  `volume` may be a CUDA tensor (the kernel) or a CPU array (the numpy port).
     clean: None, or clean_mesh's keywords (clean_options) -- the mesh is cleaned where it was extracted, before it is moved; report: a dict
-    that then receives clean_mesh's report.  Returns (vertex count, face count)."""
+    that then receives clean_mesh's report.  simplify: None, or simplify_mesh's keywords (simplify_options; the cell in the mesh's units) --
+    the mesh is simplified between the compaction and the smoothing; simplify_report: a dict that then receives simplify_mesh's report.
+    Returns (vertex count, face count)."""
     verts, faces = marching_cubes(volume, level, spacing=voxel_size)
-    if clean:
+    if simplify:
+        verts, faces, cleaned, simplified = process_mesh(verts, faces, clean, simplify)
+        verts = smooth_mesh(verts, faces, clean)
+        if report is not None and cleaned is not None:
+            report.update(cleaned)
+        if simplify_report is not None:
+            simplify_report.update(simplified)
+    elif clean:
         cleaned = clean_mesh(verts, faces, **clean)
         verts, faces = cleaned.verts, cleaned.faces
         if report is not None:
@@ -935,14 +1229,16 @@ def load_volume(path):
     return read_mrc(path) if path.lower().endswith('.mrc') else np.load(path).astype(np.float32, copy=False)
 
 
-def convert_mrc(input_filename, output_filename, level=10.0, device=None, clean=None, report=None):
+def convert_mrc(input_filename, output_filename, level=10.0, device=None, clean=None, report=None, simplify=None, simplify_report=None):
     """shape_utils.py:103-105: mesh transpose(2, 1, 0) of the file's data (.mrc or .npy), voxel size 1, origin 0.  `device`: a torch
-    device to run the kernel on (None: the numpy port).  clean, report: as convert_sdf_samples_to_ply's.  Returns (vertex count, face count)."""
+    device to run the kernel on (None: the numpy port).  clean, report, simplify, simplify_report: as convert_sdf_samples_to_ply's.  Returns
+    (vertex count, face count)."""
     vol = np.ascontiguousarray(np.transpose(load_volume(input_filename), (2, 1, 0)))
     if device is not None:
         import torch
         vol = torch.from_numpy(vol).to(device)
-    return convert_sdf_samples_to_ply(vol, [0, 0, 0], 1, output_filename, level=level, clean=clean, report=report)
+    return convert_sdf_samples_to_ply(vol, [0, 0, 0], 1, output_filename, level=level, clean=clean, report=report, simplify=simplify,
+                                      simplify_report=simplify_report)
 
 
 def main(argv=None):
@@ -953,10 +1249,17 @@ def main(argv=None):
     ap.add_argument('--mesh-keep', type=int, default=0, help='keep only this many of the largest connected components (0: all)')
     ap.add_argument('--mesh-min-faces', type=int, default=0, help='drop connected components with fewer triangles than this (0: none)')
     ap.add_argument('--mesh-smooth', type=int, default=0, help='Taubin smoothing iterations (lambda 0.5, mu -0.53, boundaries pinned; 0: none)')
+    ap.add_argument('--mesh-simplify', type=float, default=0, metavar='CELL',
+                    help='simplify the mesh by vertex clustering on a grid of cells this many voxels wide, after the components, before the smoothing (0: off)')
+    ap.add_argument('--mesh-target-faces', type=int, default=0, metavar='N',
+                    help='pick the cell instead: the smallest of CELL (or one voxel) * 2^(j / 4), j = 0 .. 40, that leaves at most N triangles (0: off)')
     args = ap.parse_args(argv)
     if min(args.mesh_keep, args.mesh_min_faces, args.mesh_smooth) < 0:
         ap.error('--mesh-keep, --mesh-min-faces and --mesh-smooth must be >= 0')
+    if not args.mesh_simplify >= 0 or args.mesh_simplify == float('inf') or args.mesh_target_faces < 0:
+        ap.error('--mesh-simplify and --mesh-target-faces must be >= 0')
     clean = clean_options(args.mesh_keep, args.mesh_min_faces, args.mesh_smooth)
+    simplify = simplify_options(args.mesh_simplify, args.mesh_target_faces)
     device = args.device
     if device is None:
         try:
@@ -975,10 +1278,12 @@ def main(argv=None):
     for path in paths:                                                   # --level is honoured for a single file too (the reference's
         t0 = time.perf_counter()                                         # single-file branch ignores it, shape_utils.py:114-116)
         out = os.path.splitext(path)[0] + '.ply'
-        report = {}
-        nv, nf = convert_mrc(path, out, level=args.level, device=device, clean=clean, report=report)
+        report, simplify_report = {}, {}
+        nv, nf = convert_mrc(path, out, level=args.level, device=device, clean=clean, report=report, simplify=simplify, simplify_report=simplify_report)
         if report:
             print(clean_report_line(report, args.mesh_smooth))
+        if simplify_report:
+            print(simplify_report_line(simplify_report))
         print(f'wrote {out}: {nv} vertices, {nf} triangles ({time.perf_counter() - t0:.3f} s)')
     return 0
 

@@ -763,6 +763,58 @@ int gnerf_mesh_compact_emit(const float* verts, const int32_t* faces, int n_vert
 int gnerf_mesh_smooth(const float* verts, int n_verts, const int32_t* faces, int n_tris, int iterations, float lam, float mu,
                       int pin_boundary, void* workspace, float* out, gnerf_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * (ABI 15, added without a new version) Simplifying such a mesh between the compaction and the smoothing: vertex clustering on a uniform grid
+ * with a quadric-error representative per cell (Lindstrom's out-of-core simplification; csrc/mesh_simplify.hip).  One pass over vertices and
+ * faces, order-independent and bit-reproducible (integer accumulation), and no vertex leaves its cell.  g-nerf_amd/shape_mi355x.py restates
+ * the rules and holds the numpy port (mesh_simplify_numpy) that gives the same bits.  Every float64 operation is rounded on its own, no
+ * contraction; only + - * /, floor, comparisons and integer conversion occur.
+ *   a mesh as above (V == 0 or T == 0 is valid); cell: a C float > 0, finite; origin: three finite C floats ON THE HOST.
+ * 1 VALID FACES: a face is valid iff its three ids lie in [0, V) and its three vertices are finite (ids are range-checked before they index
+ *   anything).  Invalid faces are counted and otherwise ignored.  A vertex is USED iff a valid face names it; unused vertices are dropped.
+ * 2 CELLS: for a used vertex, per axis p = (double(v) - double(origin)) / double(cell), k = floor(p) clamped to [0, 2^21 - 1];
+ *   key = kx 2^42 + ky 2^21 + kz.  A CLUSTER is the set of used vertices of one key, its representative its smallest vertex index
+ *   (cluster[v] <= v, cluster[cluster[v]] == cluster[v]).  New vertex ids number the representatives in ascending old index; src_vertex [V']
+ *   holds those old indices (gather normals and colours with it).  u = p - (k + 0.5), clamped to [-0.5, 0.5] per axis (the clamp is felt
+ *   only by a vertex outside the grid's 2^21 cells).
+ * 3 ACCUMULATION in int64 fixed point, q(x) = llrint(x 2^32), sums modulo 2^64, so any order gives the same bits:
+ *   per used vertex, into its cluster: q(u) per axis and a member count;
+ *   per valid face, read from its corner with the smallest vertex id (the first of them; the face is rotated, never reflected, which makes
+ *   the result independent of the rotation of a face's ids) -- corners 0, 1, 2 in that order: e1 = p1 - p0, e2 = p2 - p0, n = e1 x e2
+ *   (n0 = e1y e2z - e1z e2y, n1 = e1z e2x - e1x e2z, n2 = e1x e2y - e1y e2x), s = (n0 n0 + n1 n1) + n2 n2 in grid units.  The face is
+ *   skipped unless 0 < s < inf.  Its scale is f = 16 / s if s > 16, else 1: area-squared weighting, which mutes marching-cubes slivers; the
+ *   cap only bounds oversized triangles so that the fixed point stays small.
+ *   per corner c of such a face, into the cluster of that corner's vertex, with d = (n0 u0 + n1 u1) + n2 u2 for u of that vertex: the six
+ *   q((f n_a) n_b), a <= b, and the three q(n_a (f d)).
+ * 4 POSITION: A and b are the sums / 2^32 as doubles, cen = (the u sums / 2^32) / members, tr = (A00 + A11) + A22, mu = tr / 256.
+ *   If tr > 0, x solves (A + mu I) x = b + mu cen by this elimination (M = A + mu I, r = b + mu cen; no pivoting):
+ *     l10 = M01 / M00, l20 = M02 / M00; M11 -= l10 M01, M12 -= l10 M02, M22 -= l20 M02; r1 -= l10 r0, r2 -= l20 r0;
+ *     l21 = M12 / M11; M22 -= l21 M12, r2 -= l21 r1; x2 = r2 / M22, x1 = (r1 - M12 x2) / M11, x0 = ((r0 - M01 x1) - M02 x2) / M00;
+ *   x = cen instead if tr is not > 0, if one of the pivots M00, M11, M22 (as eliminated) is not > 0 or if x is not finite.  x is clamped to
+ *   [-0.5, 0.5] per axis; the new vertex is float32(double(origin) + ((k + 0.5) + x) double(cell)) with k of the representative.  The mu
+ *   term pulls flat regions to the centroid's foot on their plane and leaves corners alone.
+ * 5 FACES: a valid face mapped through the new ids is COLLAPSED if two ids coincide, and dropped.  The rest are grouped by their unordered id
+ *   set; sigma of a group = the sum over its members of +1 for a rotation of the ascending triple and -1 otherwise.  The group yields one
+ *   face iff sigma is odd: the ascending triple (a, b, c) when sigma > 0, (a, c, b) otherwise.  Output faces are ordered by their group's
+ *   smallest old face index.  This is the mod-2 image of the input chain: a closed input gives an output every edge of which lies in an even
+ *   number of faces.
+ * 6 counts (device int64 [8]) = {V', T', invalid faces, collapsed faces, faces absorbed by grouping (T - T' - invalid - collapsed), groups
+ *   with |sigma| >= 2, internal error (a probe ran through a whole table: cannot happen, the Python layer raises), 0}.
+ * gnerf_mesh_simplify_count does the tables, the ids and the face grouping, no quadrics; the caller reads the counts (the op's one
+ *   synchronisation), sizes out_verts [V', 3], out_faces [T', 3], src_vertex [V'] and calls _emit with the same inputs and workspace -- not at
+ *   all when V' == 0.  out_faces may be NULL when T' == 0; vertex_map int32 [V] (the new id of every old vertex, or -1) may be NULL.
+ *   Neither call reads on the host, allocates or synchronises.  New positions of vertices and faces come from a block scan plus a scan of
+ *   the block totals, never from the order of arrival.
+ * gnerf_mesh_simplify_workspace_bytes: a workspace for both calls on a mesh of that size (about 137 bytes per vertex and 28 per face); no
+ *   initialisation needed.  At most 2^30 vertices and 2^30 faces.
+ * GNERF_E_ARG for null pointers, negative or oversized sizes, cell not > 0 or not finite, origin not finite, or _emit on an empty mesh. */
+int gnerf_mesh_simplify_workspace_bytes(int n_verts, int n_tris, size_t* bytes);
+int gnerf_mesh_simplify_count(const float* verts, const int32_t* faces, int n_verts, int n_tris, float cell, const float* origin,
+                              void* workspace, int64_t* counts, gnerf_stream_t stream);
+int gnerf_mesh_simplify_emit(const float* verts, const int32_t* faces, int n_verts, int n_tris, float cell, const float* origin,
+                             void* workspace, float* out_verts, int32_t* out_faces, int32_t* src_vertex, int32_t* vertex_map,
+                             gnerf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
