@@ -29,6 +29,8 @@
 //     block offset), rows filled through a returning add per vertex, then every row sorted ascending by its own thread (insertion sort for
 //     short rows, heapsort beyond) and the pin flag read off the sorted row (some neighbour not exactly twice).  A half-step is then a pure
 //     gather, one thread per vertex, no atomics, float64 sums in ascending-neighbour order, between ping-pong buffers.
+// flip guard  (gnerf_mesh_flip_guard; port: mesh_flip_guard_numpy) behind a move of the vertices, such as the projection onto the level set
+//     (csrc/project_level.inl): rounds of two launches, faces -> marks in status[] and one count per block, vertices -> marked ones set back.
 #include "common.h"
 
 #pragma clang fp contract(off)
@@ -436,6 +438,61 @@ __global__ __launch_bounds__(kThreads) void smooth_step_kernel(const float* __re
     dst[size_t(v) * 3 + 2] = y2;
 }
 
+// ---------------------------------------------------------------------------------------------------------------- flip guard
+// (include/gnerf_hip.h, gnerf_mesh_flip_guard, states the rules.)  The marks live in status[] itself: 3 = reverted.  A round is two launches,
+// one over the faces (reads positions, writes status and one count per block) and one over the vertices (reads status, writes positions), so
+// neither kernel reads what it writes.  `prev` is the count of the round before (null for the first): zero there means nothing moved since
+// that round looked, and the whole launch leaves -- a device-side read, the launch sequence is the same whatever the data.
+struct D3 { double x, y, z; };
+
+__device__ __forceinline__ D3 face_normal(const float* __restrict__ v, const int32_t (&f)[3]) {
+    const double ax = double(v[size_t(f[0]) * 3]), ay = double(v[size_t(f[0]) * 3 + 1]), az = double(v[size_t(f[0]) * 3 + 2]);
+    const double e1x = double(v[size_t(f[1]) * 3]) - ax, e1y = double(v[size_t(f[1]) * 3 + 1]) - ay, e1z = double(v[size_t(f[1]) * 3 + 2]) - az;
+    const double e2x = double(v[size_t(f[2]) * 3]) - ax, e2y = double(v[size_t(f[2]) * 3 + 1]) - ay, e2z = double(v[size_t(f[2]) * 3 + 2]) - az;
+    return D3{e1y * e2z - e1z * e2y, e1z * e2x - e1x * e2z, e1x * e2y - e1y * e2x};
+}
+
+__device__ __forceinline__ double dot3(const D3& a, const D3& b) { return (a.x * b.x + a.y * b.y) + a.z * b.z; }
+
+template <bool MARK>
+__global__ __launch_bounds__(kThreads) void flip_faces_kernel(const float* __restrict__ verts_in, const float* __restrict__ cur,
+                                                              const int32_t* __restrict__ faces, uint32_t nv, uint32_t nt,
+                                                              unsigned char* status, const int32_t* prev, int32_t* count) {
+    __shared__ uint32_t s_n[kThreads / 64];
+    if (prev && *prev == 0) return;
+    uint32_t n = 0;                                      // wave-uniform: flipped faces this wave has seen
+    const uint32_t first = blockIdx.x * uint32_t(kItems);
+    for (int j = 0; j < kChunks; j++) {
+        const uint32_t t = first + uint32_t(j * kThreads) + threadIdx.x;
+        bool flipped = false;
+        int32_t f[3];
+        if (t < nt && load_face(faces, t, nv, f)) {
+            const D3 n0 = face_normal(verts_in, f), n1 = face_normal(cur, f);
+            flipped = dot3(n0, n1) < 0.0 || (dot3(n1, n1) == 0.0 && dot3(n0, n0) > 0.0);
+            if (MARK && flipped) status[f[0]] = status[f[1]] = status[f[2]] = 3;
+        }
+        n += uint32_t(__popcll(__ballot(flipped)));
+    }
+    if ((threadIdx.x & 63) == 0) s_n[threadIdx.x >> 6] = n;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        uint32_t all = 0;
+        for (int w = 0; w < kThreads / 64; w++) all += s_n[w];
+        if (all) atomicAdd(count, int32_t(all));         // one add per block
+    }
+}
+
+__global__ __launch_bounds__(kThreads) void flip_revert_kernel(const float* __restrict__ verts_in, float* __restrict__ cur,
+                                                               const unsigned char* __restrict__ status, uint32_t nv, const int32_t* count) {
+    if (*count == 0) return;                             // this round marked nothing
+    const uint32_t v = blockIdx.x * uint32_t(kThreads) + threadIdx.x;
+    if (v < nv && status[v] == 3) {
+        cur[size_t(v) * 3] = verts_in[size_t(v) * 3];
+        cur[size_t(v) * 3 + 1] = verts_in[size_t(v) * 3 + 1];
+        cur[size_t(v) * 3 + 2] = verts_in[size_t(v) * 3 + 2];
+    }
+}
+
 int check_sizes(int n_verts, int n_tris, const char* what) {
     using namespace gnerf;
     if (n_verts < 0 || n_tris < 0) return fail(GNERF_E_ARG, "%s: negative size (%d vertices, %d faces)", what, n_verts, n_tris);
@@ -568,4 +625,31 @@ extern "C" int gnerf_mesh_smooth(const float* verts, int n_verts, const int32_t*
         src = dst;
     }
     return GNERF_OK;
+}
+
+extern "C" int gnerf_mesh_flip_guard(const float* verts_in, const float* verts_moved, const int32_t* faces, int n_verts, int n_tris, int max_rounds,
+                                     float* verts_out, unsigned char* status, int32_t* counts, gnerf_stream_t stream) {
+    using namespace gnerf;
+    if (int rc = check_sizes(n_verts, n_tris, "mesh_flip_guard")) return rc;
+    if (max_rounds < 1) return fail(GNERF_E_ARG, "mesh_flip_guard: max_rounds must be >= 1 (got %d)", max_rounds);
+    if (!counts || (n_tris && !faces) || (n_verts && (!verts_in || !verts_moved || !verts_out || !status)))
+        return fail(GNERF_E_ARG, "mesh_flip_guard: null pointer");
+    if (n_verts && verts_out == verts_in) return fail(GNERF_E_ARG, "mesh_flip_guard: verts_out must not be verts_in");
+    const uint32_t nv = uint32_t(n_verts), nt = uint32_t(n_tris);
+    hipStream_t s = as_stream(stream);
+    if (hipMemsetAsync(counts, 0, size_t(max_rounds + 1) * 4, s) != hipSuccess) return fail(GNERF_E_LAUNCH, "mesh_flip_guard: memset failed");
+    if (nv && verts_out != verts_moved && hipMemcpyAsync(verts_out, verts_moved, size_t(nv) * 12, hipMemcpyDeviceToDevice, s) != hipSuccess)
+        return fail(GNERF_E_LAUNCH, "mesh_flip_guard: copy failed");
+    if (nv == 0 || nt == 0) return GNERF_OK;
+    for (int j = 0; j < max_rounds; j++) {
+        hipLaunchKernelGGL(flip_faces_kernel<true>, dim3(blocks_of(nt)), dim3(kThreads), 0, s, verts_in, (const float*)verts_out, faces, nv, nt, status,
+                           (const int32_t*)(j ? counts + j - 1 : nullptr), counts + j);
+        if (int rc = check_launch("mesh_flip_guard (faces)")) return rc;
+        hipLaunchKernelGGL(flip_revert_kernel, dim3(grid_of(nv)), dim3(kThreads), 0, s, verts_in, verts_out, (const unsigned char*)status, nv,
+                           (const int32_t*)(counts + j));
+        if (int rc = check_launch("mesh_flip_guard (revert)")) return rc;
+    }
+    hipLaunchKernelGGL(flip_faces_kernel<false>, dim3(blocks_of(nt)), dim3(kThreads), 0, s, verts_in, (const float*)verts_out, faces, nv, nt, status,
+                       (const int32_t*)(counts + max_rounds - 1), counts + max_rounds);
+    return check_launch("mesh_flip_guard (check)");
 }

@@ -41,6 +41,7 @@
 #include "common.h"
 #include "raygen.h"
 #include "pipe_dealing.h"
+#include <cmath>
 #include <cstdlib>
 #include <cstring>
 
@@ -879,6 +880,7 @@ __device__ __forceinline__ int choose_mlp_packed(const Params& P, bool* softplus
 #include "render_pipe.inl"
 #include "render_bwd.inl"
 #include "query_grad.inl"
+#include "project_level.inl"
 #include "render_ray_grad.inl"
 
 int check_common(const gnerf_render_params* p) {
@@ -1442,4 +1444,33 @@ extern "C" int gnerf_query_points_grad(const float* planes_nhwc, int n_items, in
     if (grad_rgb) hipLaunchKernelGGL(query_grad_kernel<true>, dim3((unsigned)blocks), dim3(kBwdThreads), lds_bytes, as_stream(stream), P, Q);
     else          hipLaunchKernelGGL(query_grad_kernel<false>, dim3((unsigned)blocks), dim3(kBwdThreads), lds_bytes, as_stream(stream), P, Q);
     return check_launch("query_grad_kernel");
+}
+
+extern "C" int gnerf_project_points_to_level(const float* planes_nhwc, int n_items, int plane_h, int plane_w,
+                                             const float* points, int n_points, float box_warp,
+                                             const float* w1, const float* b1, const float* w2, const float* b2,
+                                             float level, const float* affine, int max_steps, float radius, float tol,
+                                             float* points_out, float* residual_in, float* residual_out, unsigned char* status,
+                                             int planes_interleaved, gnerf_stream_t stream) {
+    using namespace gnerf;
+    Params P; int tiles_per_item; int64_t tiles;
+    if (int e = fill_query("project_points_to_level", planes_nhwc, n_items, plane_h, plane_w, n_points, box_warp, w1, b1, w2, b2, planes_interleaved, P, tiles_per_item, tiles)) return e;
+    if (!points || !points_out || !residual_in || !residual_out || !status) return fail(GNERF_E_ARG, "project_points_to_level: null pointer");
+    if (n_points < 1) return fail(GNERF_E_ARG, "project_points_to_level: n_points must be positive");
+    if (max_steps < 0) return fail(GNERF_E_ARG, "project_points_to_level: max_steps must be >= 0 (got %d)", max_steps);
+    if (!(radius >= 0.f) || !std::isfinite(radius)) return fail(GNERF_E_ARG, "project_points_to_level: radius must be finite and >= 0");
+    if (!(tol > 0.f) || !std::isfinite(tol)) return fail(GNERF_E_ARG, "project_points_to_level: tol must be finite and > 0");
+    if (!planes_fit_32bit_taps(&P.p)) return fail(GNERF_E_UNSUPPORTED, "project_points_to_level: planes too large for 32-bit tap offsets");
+    if (tiles > INT32_MAX) return fail(GNERF_E_ARG, "project_points_to_level: too many points");
+    ProjectArgs Q = {};
+    Q.points = points; Q.points_out = points_out; Q.residual_in = residual_in; Q.residual_out = residual_out; Q.status = status;
+    Q.has_affine = affine != nullptr;
+    if (affine) for (int i = 0; i < 12; i++) Q.a[i] = affine[i];
+    Q.level = level; Q.radius = radius; Q.tol = tol; Q.max_steps = max_steps;
+    Q.n_points = n_points; Q.tiles_per_item = tiles_per_item; Q.n_tiles = int(tiles);
+    const size_t lds_bytes = (kBwdWeightFloats + kBwdWaves * query_grad_wave_floats()) * sizeof(float);         // as query_grad_kernel: three workgroups per CU
+    int64_t blocks = (tiles + kBwdWaves - 1) / kBwdWaves;
+    if (blocks > int64_t(kNumCU) * 3) blocks = int64_t(kNumCU) * 3;
+    hipLaunchKernelGGL(project_level_kernel, dim3((unsigned)blocks), dim3(kBwdThreads), lds_bytes, as_stream(stream), P, Q);
+    return check_launch("project_level_kernel");
 }

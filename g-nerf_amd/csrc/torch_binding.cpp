@@ -14,7 +14,7 @@
 // modconv_backward (gnerf_hip.scale_channels_backward / modconv_epilogue_backward), query_points_grad (gnerf_hip.query_points_grad),
 // render_backward_rays (gnerf_hip.render_backward with need_rays), resize_aa (gnerf_hip.resize_aa_forward / _backward),
 // raster_visibility / raster_resolve (gnerf_hip.rasterize / resolve), mesh_components / mesh_compact / mesh_smooth /
-// mesh_simplify / mesh_simplify_count (gnerf_hip's of those names).
+// mesh_simplify / mesh_simplify_count / project_points_to_level / mesh_flip_guard (gnerf_hip's of those names).
 //
 // Built ahead of time by csrc/build.sh (g++, no hipcc: there is no device code) into g-nerf_amd/gnerf_hip/gnerf_torch_ext.so.
 
@@ -390,6 +390,38 @@ Tensor query_points_grad(Tensor planes_nhwc, int64_t n_items, Tensor w1, Tensor 
     return out;
 }
 
+// gnerf_hip.project_points_to_level has converted the tensors as for query_points_grad and validated steps, radius and tol; affine: twelve
+// values (row-major [A | b]) or empty for the identity.  -> (points_out [N,P,3], status uint8 [N,P], residual_in [N,P], residual_out [N,P]).
+std::tuple<Tensor, Tensor, Tensor, Tensor> project_points_to_level(Tensor planes_nhwc, int64_t n_items, Tensor w1, Tensor b1, Tensor w2, Tensor b2,
+                                                                   Tensor points, double box_warp, double level, std::vector<double> affine,
+                                                                   int64_t steps, double radius, double tol) {
+    auto f32c = [](const Tensor& t, const char* name) {
+        TORCH_CHECK(t.is_cuda() && t.scalar_type() == torch::kFloat32 && t.is_contiguous(), "project_points_to_level: ", name, " must be a contiguous float32 GPU tensor");
+    };
+    f32c(planes_nhwc, "planes_nhwc"); f32c(w1, "w1"); f32c(b1, "b1"); f32c(w2, "w2"); f32c(b2, "b2"); f32c(points, "points");
+    const bool separate = planes_nhwc.dim() == 4 && planes_nhwc.size(3) == 32 && planes_nhwc.size(0) == 3 * n_items;
+    const bool interleaved = planes_nhwc.dim() == 4 && planes_nhwc.size(3) == 96 && planes_nhwc.size(0) == n_items;
+    TORCH_CHECK(separate || interleaved, "project_points_to_level: planes_nhwc must be [3N,H,W,32] or [N,H,W,96]");
+    TORCH_CHECK(w1.numel() == 64 * 32 && b1.numel() == 64 && w2.numel() == 33 * 64 && b2.numel() == 33, "project_points_to_level: decoder must be the 32->64->33 MLP");
+    TORCH_CHECK(points.dim() == 3 && points.size(0) == n_items && points.size(2) == 3 && points.size(1) <= INT_MAX, "project_points_to_level: points must be [N,P,3]");
+    TORCH_CHECK(affine.empty() || affine.size() == 12, "project_points_to_level: affine holds twelve values or none");
+    TORCH_CHECK(steps >= 0 && steps <= INT_MAX, "project_points_to_level: steps out of range");
+    const int64_t n_pts = points.size(1);
+    float a[12];
+    for (size_t i = 0; i < affine.size(); i++) a[i] = float(affine[i]);
+    const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(at::device_of(points));
+    Tensor out = torch::empty({n_items, n_pts, 3}, points.options());
+    Tensor res_in = torch::empty({n_items, n_pts}, points.options()), res_out = torch::empty({n_items, n_pts}, points.options());
+    Tensor status = torch::empty({n_items, n_pts}, points.options().dtype(torch::kUInt8));
+    check_rc(gnerf_project_points_to_level(planes_nhwc.data_ptr<float>(), int(n_items), int(planes_nhwc.size(1)), int(planes_nhwc.size(2)),
+                                           points.data_ptr<float>(), int(n_pts), float(box_warp), w1.data_ptr<float>(), b1.data_ptr<float>(),
+                                           w2.data_ptr<float>(), b2.data_ptr<float>(), float(level), affine.empty() ? nullptr : a, int(steps),
+                                           float(radius), float(tol), out.data_ptr<float>(), res_in.data_ptr<float>(), res_out.data_ptr<float>(),
+                                           status.data_ptr<uint8_t>(), interleaved ? 1 : 0, current_stream()),
+             "gnerf_project_points_to_level");
+    return std::make_tuple(out, status, res_in, res_out);
+}
+
 // ------------------------------------------------------------------------------------------------ marching cubes (shape_utils.py:58-61)
 
 // volume: contiguous float32 [d0, d1, d2] on a GPU.  Returns (verts [V,3] float32, faces [T,3] int32, counts int64 [3] on the host:
@@ -672,6 +704,27 @@ Tensor mesh_smooth(Tensor verts, Tensor faces, int64_t iterations, double lam, d
     return out;
 }
 
+// gnerf_hip.mesh_flip_guard has validated the tensors (verts float32 [V, 3] twice, faces int32 [T, 3], status uint8 [V], contiguous on one GPU)
+// and rounds >= 1.  -> (verts_out [V, 3], status' [V], counts int32 [rounds + 1] ON THE DEVICE: no host read, capturable).
+std::tuple<Tensor, Tensor, Tensor> mesh_flip_guard(Tensor verts_in, Tensor verts_moved, Tensor faces, Tensor status, int64_t rounds) {
+    TORCH_CHECK(verts_in.is_cuda() && verts_in.scalar_type() == torch::kFloat32 && verts_in.is_contiguous() && verts_moved.scalar_type() == torch::kFloat32 &&
+                verts_moved.is_contiguous() && verts_moved.sizes() == verts_in.sizes() && verts_moved.device() == verts_in.device() &&
+                faces.scalar_type() == torch::kInt32 && faces.is_contiguous() && faces.device() == verts_in.device() &&
+                status.scalar_type() == torch::kUInt8 && status.is_contiguous() && status.numel() == verts_in.size(0) && status.device() == verts_in.device(),
+                "mesh_flip_guard: unexpected tensor layout");
+    TORCH_CHECK(verts_in.size(0) <= INT_MAX && faces.size(0) <= INT_MAX && rounds >= 1 && rounds < INT_MAX, "mesh_flip_guard: argument out of range");
+    const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(at::device_of(verts_in));
+    const int nv = int(verts_in.size(0)), nt = int(faces.size(0));
+    Tensor out = torch::empty_like(verts_in);
+    Tensor st = status.clone();
+    Tensor counts = torch::empty({rounds + 1}, faces.options());
+    check_rc(gnerf_mesh_flip_guard(nv ? verts_in.data_ptr<float>() : nullptr, nv ? verts_moved.data_ptr<float>() : nullptr,
+                                   nt ? faces.data_ptr<int32_t>() : nullptr, nv, nt, int(rounds), nv ? out.data_ptr<float>() : nullptr,
+                                   nv ? st.data_ptr<uint8_t>() : nullptr, counts.data_ptr<int32_t>(), current_stream()),
+             "gnerf_mesh_flip_guard");
+    return std::make_tuple(out, st, counts);
+}
+
 // ------------------------------------------------------------------------------------------------ mesh simplification (csrc/mesh_simplify.hip)
 // gnerf_hip.mesh_simplify / mesh_simplify_count have validated the tensors (verts float32 [V, 3], faces int32 [T, 3], contiguous on one GPU),
 // cell and origin (three values that are exact floats).
@@ -748,6 +801,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("mesh_smooth", &mesh_smooth);
     m.def("mesh_simplify", &mesh_simplify);
     m.def("mesh_simplify_count", &mesh_simplify_count);
+    m.def("project_points_to_level", &project_points_to_level);
+    m.def("mesh_flip_guard", &mesh_flip_guard);
     // the header version THIS extension was compiled against (a compile-time constant: gnerf_abi_version() would resolve in
     // libgnerf_hip.so at run time and compare the library with itself); gnerf_hip.ext() checks both against its own
     m.def("abi_version", []() { return int(GNERF_ABI_VERSION); });

@@ -26,6 +26,10 @@ the renderer's pixel grid, uint8 [F, H, W, 3] at `--geometry-res`, smooth-shaded
 components / those with at least N triangles stay, then ITERS Taubin iterations fair the surface; all 0 by default, which changes nothing.
 `--mesh-simplify CELL` (voxels) and `--mesh-target-faces N` simplify it in between (csrc/mesh_simplify.hip): one vertex per occupied cell of a
 uniform grid, placed by the cell's quadric; both 0 by default, which changes nothing.
+`--mesh-snap R` (voxels; `--mesh-snap-steps`, `--mesh-snap-tol`) comes last, after the smoothing: every vertex goes onto the level set of the
+density itself by Newton steps along its gradient, at most R voxels per axis from where it stood (csrc/project_level.inl), faces that this
+turns over get their vertices back (the flip guard of csrc/mesh_clean.hip), and the attributes are evaluated at the final positions; 0 by
+default, which changes nothing.
 """
 
 import argparse
@@ -351,7 +355,56 @@ def smooth_extracted_mesh(verts, faces, clean):
     return torch.from_numpy(smoothed) if isinstance(verts, torch.Tensor) else smoothed
 
 
-def mesh_density_grid(vol, ply_path, level=10.0, attrs=None, G=None, planes=None, clean=None, report=None, simplify=None, simplify_report=None):
+@torch.no_grad()
+def snap_extracted_mesh(G, planes, verts, faces, resolution, snap, level=10.0):
+    """--mesh-snap: the last stage, after the smoothing.  Every vertex (index space) goes back onto the level set sigma = level of generator
+    G's own density on `planes`: Newton steps along the density's gradient inside a box of snap['radius'] voxels around where it stood
+    (ImportanceRenderer.project_to_level with mesh_to_world_matrix as the affine: one kernel launch on a GPU), then the flip guard
+    (gnerf_hip.mesh_flip_guard / shape_mi355x.mesh_flip_guard_numpy) sets back the vertices of every face the move turned over.  A vertex
+    that does not converge keeps its position -- by design those on the walls that extract_density_grid's crop cuts into the volume and that
+    lie farther than the radius from the true surface.  snap: shape_mi355x.snap_options' dict or None (nothing runs) -> (verts, report or None);
+    report: vertices, converged, not_converged, flat, reverted, median_before / max_before / median_after / max_after of |sigma - level|,
+    flips (per guard round), flips_left, tol."""
+    if not snap:
+        return verts, None
+    import shape_mi355x
+    kw = G.rendering_kwargs
+    dev = planes.device
+    v = (verts if isinstance(verts, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(verts))).to(dev).float().reshape(-1, 3)
+    f = faces if isinstance(faces, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(faces))
+    rounds = snap['guard_rounds']
+    tol = snap['tol'] if snap['tol'] is not None else 2.0 ** -10 * max(1.0, abs(float(level)))
+    if len(v) == 0:
+        return verts, dict(vertices=0, converged=0, not_converged=0, flat=0, reverted=0, median_before=0.0, max_before=0.0, median_after=0.0,
+                           max_after=0.0, flips=[0] * rounds, flips_left=0, tol=tol)
+    moved, status, res_in, res_out = G.renderer.project_to_level(planes[:1], G.decoder, v.unsqueeze(0), level, kw, affine=mesh_to_world_matrix(resolution, kw['box_warp']),
+                                                                 steps=snap['steps'], radius=snap['radius'], tol=tol)
+    moved, status, res_in, res_out = moved[0].float(), status[0], res_in[0].float(), res_out[0].float()
+    if v.is_cuda:
+        import gnerf_hip
+        out, status, counts = gnerf_hip.mesh_flip_guard(v, moved, f.to(dev), status, rounds)
+        counts = counts.cpu().numpy()
+    else:
+        out, status, counts = shape_mi355x.mesh_flip_guard_numpy(v.numpy(), moved.numpy(), f.numpy(), status.numpy(), rounds)
+        out, status = torch.from_numpy(out), torch.from_numpy(status)
+    res_out = torch.where(status == 3, res_in, res_out)
+    before, after = res_in.abs(), res_out.abs()
+
+    def stats(x):
+        x = x[torch.isfinite(x)]
+        return (float(x.median()), float(x.max())) if len(x) else (float('nan'), float('nan'))
+
+    (m0, x0), (m1, x1) = stats(before), stats(after)
+    tally = torch.bincount(status.long().cpu(), minlength=4)
+    report = dict(vertices=len(v), converged=int(tally[0]), not_converged=int(tally[1]), flat=int(tally[2]), reverted=int(tally[3]), median_before=m0,
+                  max_before=x0, median_after=m1, max_after=x1, flips=[int(c) for c in counts[:rounds]], flips_left=int(counts[rounds]), tol=tol)
+    if isinstance(verts, torch.Tensor):
+        return out.to(verts.device), report
+    return out.cpu().numpy(), report
+
+
+def mesh_density_grid(vol, ply_path, level=10.0, attrs=None, G=None, planes=None, clean=None, report=None, simplify=None, simplify_report=None,
+                      snap=None, snap_report=None):
     """--mesh: the mesh shape_utils.convert_mrc makes of the .mrc of this volume (shape_utils.py:103-105: transpose(2, 1, 0), voxel
     size 1, origin 0), made where the volume lives -- on a GPU the marching-cubes kernel reads it in HBM, only the mesh comes to the host.
     attrs: None / 'none', 'normals', 'colors' or 'all' -- per-vertex attributes (mesh_vertex_attributes) of generator G on `planes`
@@ -359,14 +412,16 @@ def mesh_density_grid(vol, ply_path, level=10.0, attrs=None, G=None, planes=None
     clean: None or shape_mi355x.clean_options' dict -- marching cubes, then components and compaction, then the attributes (at the kept
     vertices' extracted positions), then smoothing.  report: a dict that receives clean_mesh's report when the mesh was cleaned (left as
     it is otherwise).  simplify: None or shape_mi355x.simplify_options' dict -- the mesh is simplified between the compaction and the
-    attributes; simplify_report: a dict that then receives simplify_mesh's report.
+    attributes; simplify_report: a dict that then receives simplify_mesh's report.  snap: None or shape_mi355x.snap_options' dict -- the order
+    becomes marching cubes, compaction, simplification, smoothing, snap_extracted_mesh (snap_report receives its report), and the attributes
+    are evaluated at the snapped positions; with snap None the order and the file's bytes are those of a call without it.
     Writes `ply_path`; returns (vertex count, triangle count, seconds spent in marching cubes)."""
     import shape_mi355x
     attrs = 'none' if attrs is None else attrs
     if attrs not in MESH_ATTRS:
         raise ValueError(f'mesh_density_grid: attrs must be one of {MESH_ATTRS}')
-    if attrs != 'none' and (G is None or planes is None):
-        raise ValueError('mesh_density_grid: vertex attributes need the generator G and the planes the volume was made from')
+    if (attrs != 'none' or snap) and (G is None or planes is None):
+        raise ValueError('mesh_density_grid: vertex attributes and the snap need the generator G and the planes the volume was made from')
     t0 = time.perf_counter()
     verts, faces = shape_mi355x.marching_cubes(vol.permute(2, 1, 0).contiguous(), level)     # (reads its counts: synchronised)
     dt = time.perf_counter() - t0
@@ -377,11 +432,17 @@ def mesh_density_grid(vol, ply_path, level=10.0, attrs=None, G=None, planes=None
     if simplify_report is not None and simplified is not None:
         simplify_report.update(simplified)
     normals = colors = None
+    if snap:                                                 # smoothing, then the snap, then the attributes: at the final positions
+        verts = smooth_extracted_mesh(verts, faces, clean)
+        verts, snapped = snap_extracted_mesh(G, planes, verts, faces, vol.shape[0], snap, level=level)
+        if snap_report is not None and snapped is not None:
+            snap_report.update(snapped)
     if attrs != 'none':
         v = verts if isinstance(verts, torch.Tensor) else torch.from_numpy(verts).to(vol.device)
         normals, colors = mesh_vertex_attributes(G, planes, v, vol.shape[0], attrs in ('normals', 'all'), attrs in ('colors', 'all'))
         normals, colors = (None if t is None else t.cpu().numpy() for t in (normals, colors))
-    verts = smooth_extracted_mesh(verts, faces, clean)
+    if not snap:
+        verts = smooth_extracted_mesh(verts, faces, clean)
     if isinstance(verts, torch.Tensor):
         verts, faces = verts.cpu().numpy(), faces.cpu().numpy()
     shape_mi355x.write_ply(ply_path, verts, faces, normals=normals, colors=colors)
@@ -439,6 +500,11 @@ def main():
                     help='simplify the mesh by vertex clustering on a grid of cells this many voxels wide, after the components, before the attributes and the smoothing (0: off)')
     ap.add_argument('--mesh-target-faces', type=int, default=0, metavar='N',
                     help='pick the cell instead: the smallest of CELL (or one voxel) * 2^(j / 4), j = 0 .. 40, that leaves at most N triangles (0: off)')
+    ap.add_argument('--mesh-snap', type=float, default=0, metavar='R',
+                    help='last, after the smoothing: move every vertex onto the level set of the density itself (Newton steps along its gradient), at most '
+                         'R voxels per axis from where it stood; faces that this turns over get their vertices back (--mesh and --geometry-out; 0: off)')
+    ap.add_argument('--mesh-snap-steps', type=int, default=6, help='Newton steps of --mesh-snap at the most')
+    ap.add_argument('--mesh-snap-tol', type=float, default=None, help='|sigma - level| at which a vertex of --mesh-snap is done (default: 2^-10 max(1, |level|))')
     ap.add_argument('--voxel-res', type=int, default=512)
     ap.add_argument('--geometry-out', default=None, help='also draw the mesh of the density volume from every orbit camera (shaded geometry frames, '
                                                          'uint8 [F, H, W, 3]) and write them to this .npy (rank 0); uses --voxel-res, --mesh-level, --mesh-attrs, --frames-per-call')
@@ -452,6 +518,10 @@ def main():
     import shape_mi355x
     clean = shape_mi355x.clean_options(args.mesh_keep, args.mesh_min_faces, args.mesh_smooth)
     simplify = shape_mi355x.simplify_options(args.mesh_simplify, args.mesh_target_faces)
+    try:
+        snap = shape_mi355x.snap_options(args.mesh_snap, args.mesh_snap_steps, args.mesh_snap_tol)
+    except ValueError as err:
+        ap.error(str(err))
     H.configure_backend(False if args.no_solver_search else None)
 
     rank, world, local_rank = H.init_from_env()
@@ -509,13 +579,15 @@ def main():
             shape_mi355x.write_mrc(args.shapes_mrc, vol.cpu().numpy())
         if args.mesh:
             t0 = time.perf_counter()
-            report, simplify_report = {}, {}
+            report, simplify_report, snap_report = {}, {}, {}
             nv, nf, dt = mesh_density_grid(vol, args.mesh, args.mesh_level, attrs=args.mesh_attrs, G=G, planes=planes, clean=clean, report=report,
-                                           simplify=simplify, simplify_report=simplify_report)
+                                           simplify=simplify, simplify_report=simplify_report, snap=snap, snap_report=snap_report)
             if report:
                 print(shape_mi355x.clean_report_line(report, args.mesh_smooth))
             if simplify_report:
                 print(shape_mi355x.simplify_report_line(simplify_report))
+            if snap_report:
+                print(shape_mi355x.snap_report_line(snap_report))
             print(f'mesh at level {args.mesh_level:g}: {dt * 1e3:.2f} ms, {nv} vertices, {nf} triangles -> {args.mesh}'
                   + (f' (with {args.mesh_attrs}: {(time.perf_counter() - t0) * 1e3:.2f} ms in all, file included)' if args.mesh_attrs != 'none' else ''))
     if args.geometry_out:
@@ -531,11 +603,17 @@ def main():
         if not isinstance(verts, torch.Tensor):
             verts, faces = torch.from_numpy(verts), torch.from_numpy(faces)
         normals = colors = None
+        if snap:                                                         # smoothing, then the snap, then the attributes: at the final positions
+            verts = smooth_extracted_mesh(verts, faces, clean)
+            verts, report = snap_extracted_mesh(G, planes, verts, faces, args.voxel_res, snap, level=args.mesh_level)
+            if report is not None and rank == 0 and not args.mesh:
+                print(shape_mi355x.snap_report_line(report))
         if args.mesh_attrs != 'none':
             normals, colors = mesh_vertex_attributes(G, planes, verts.to(device), args.voxel_res, args.mesh_attrs in ('normals', 'all'), args.mesh_attrs in ('colors', 'all'))
             if not verts.is_cuda:
                 normals, colors = (None if t is None else t.cpu() for t in (normals, colors))
-        verts = smooth_extracted_mesh(verts, faces, clean)
+        if not snap:
+            verts = smooth_extracted_mesh(verts, faces, clean)
         if device.type == 'cuda':
             torch.cuda.synchronize()
         t0 = time.perf_counter()

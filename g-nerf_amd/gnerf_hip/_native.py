@@ -97,7 +97,9 @@ SIGNATURES = {
     'gnerf_query_points_backward': (_c_i, [_c_p, _c_i, _c_i, _c_i, _c_p, _c_i, _c_f, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p,
                                            _c_p, _c_p, _c_p, _c_p, _c_p, _c_i, _c_p]),
     'gnerf_query_points_grad': (_c_i, [_c_p, _c_i, _c_i, _c_i, _c_p, _c_i, _c_f, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _c_i, _c_p]),
-    'gnerf_modulate_weights': (_c_i, [_c_p, _c_p, _c_p, _c_i, _c_p, _c_i, _c_i, _c_i, _c_i, _c_i, _c_i, _c_i, _c_p]),
+    'gnerf_project_points_to_level': (_c_i, [_c_p, _c_i, _c_i, _c_i, _c_p, _c_i, _c_f, _c_p, _c_p, _c_p, _c_p, _c_f, ctypes.POINTER(_c_f), _c_i, _c_f, _c_f,
+                                             _c_p, _c_p, _c_p, _c_p, _c_i, _c_p]),
+    'gnerf_modulate_weights':(_c_i, [_c_p, _c_p, _c_p, _c_i, _c_p, _c_i, _c_i, _c_i, _c_i, _c_i, _c_i, _c_i, _c_p]),
     'gnerf_normalise_styles': (_c_i, [_c_p, _c_p, _c_i, _c_i, _c_p]),
     'gnerf_scale_channels': (_c_i, [_c_p, _c_p, _c_p, _c_i, _c_i, _c_i, _c_p]),
     'gnerf_modconv_epilogue': (_c_i, [_c_p, _c_p, _c_i, _c_i, _c_i, _c_i, _c_p, _c_p, _c_i, _c_i, _c_p, _c_i, _c_f, _c_f, _c_f, _c_p]),
@@ -144,11 +146,12 @@ SIGNATURES = {
     'gnerf_mesh_simplify_workspace_bytes': (_c_i, [_c_i, _c_i, ctypes.POINTER(ctypes.c_size_t)]),
     'gnerf_mesh_simplify_count': (_c_i, [_c_p, _c_p, _c_i, _c_i, _c_f, ctypes.POINTER(_c_f), _c_p, _c_p, _c_p]),
     'gnerf_mesh_simplify_emit': (_c_i, [_c_p, _c_p, _c_i, _c_i, _c_f, ctypes.POINTER(_c_f), _c_p, _c_p, _c_p, _c_p, _c_p, _c_p]),
+    'gnerf_mesh_flip_guard': (_c_i, [_c_p, _c_p, _c_p, _c_i, _c_i, _c_i, _c_p, _c_p, _c_p, _c_p]),
 }
 # exports added WITHOUT a new ABI version: a library of the same version built before them (a variant build behind GNERF_HIP_LIB) loads, and
 # what needs them asks modconv_backward_available() / render_ray_grad_available() / decoder_pack_available() / resize_aa_available() /
-# raster_available() / mesh_clean_available() / mesh_simplify_available()
-OPTIONAL_SYMBOLS = frozenset(n for n in SIGNATURES if n.startswith(('gnerf_modconv_backward_', 'gnerf_scale_channels_backward', 'gnerf_modconv_epilogue_backward',
+# raster_available() / mesh_clean_available() / mesh_simplify_available() / project_to_level_available() / mesh_flip_guard_available()
+OPTIONAL_SYMBOLS = frozenset(n for n in SIGNATURES if n.startswith(('gnerf_project_points_to_level', 'gnerf_modconv_backward_','gnerf_scale_channels_backward', 'gnerf_modconv_epilogue_backward',
                                                                     'gnerf_render_backward_rays', 'gnerf_render_decoder_pack_bytes',
                                                                     'gnerf_render_pack_decoder', 'gnerf_render_forward_packed', 'gnerf_resize_aa_', 'gnerf_raster_', 'gnerf_mesh_')))
 

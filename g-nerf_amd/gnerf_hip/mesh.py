@@ -218,6 +218,47 @@ def mesh_smooth(verts, faces, iterations, lam=0.5, mu=-0.53, pin_boundary=True):
     return _mesh_smooth_ctypes(v, f, iterations, float(lam), float(mu), bool(pin_boundary))
 
 
+# ---------------------------------------------------------------------------------------------------------------- flip guard (csrc/mesh_clean.hip)
+def mesh_flip_guard_available():
+    """Whether the loaded library has the flip guard (a version-15 library built before it does not)."""
+    return hasattr(load(), 'gnerf_mesh_flip_guard')
+
+
+def _mesh_flip_guard_ctypes(v0, v1, f, status, rounds):
+    """The ctypes route of mesh_flip_guard (arguments as mesh_flip_guard prepares them)."""
+    nv, nt, dev = len(v0), len(f), v0.device
+    out = torch.empty_like(v0)
+    st = status.clone()
+    counts = torch.empty(rounds + 1, dtype=torch.int32, device=dev)
+    _launch('gnerf_mesh_flip_guard', v0, _ptr(v0) if nv else None, _ptr(v1) if nv else None, _ptr(f) if nt else None, nv, nt, rounds,
+            _ptr(out) if nv else None, _ptr(st) if nv else None, _ptr(counts))
+    return out, st, counts
+
+
+@profiled('gnerf_hip::mesh_flip_guard')
+def mesh_flip_guard(verts_in, verts_moved, faces, status=None, rounds=4):
+    """Set back the vertices of every face that a move of the vertices turned over: verts_in and verts_moved float32 [V, 3], faces int32
+    [T, 3], status uint8 [V] (the projection's 0 / 1 / 2; None: zeros), all CUDA -> (verts_out [V, 3]: verts_moved with the vertices of
+    flipped faces back at verts_in, status' [V]: 3 for those, counts int32 [rounds + 1] ON THE DEVICE: faces flipped at the start of each of
+    the `rounds` rounds, then those left).  Rules: include/gnerf_hip.h, gnerf_mesh_flip_guard; shape_mi355x.mesh_flip_guard_numpy gives the
+    same bits.  No host read: capturable."""
+    if not mesh_flip_guard_available():
+        raise RuntimeError('gnerf_hip: this libgnerf_hip.so was built without gnerf_mesh_flip_guard: rebuild it (csrc/build.sh)')
+    v0, v1, f = _verts_f32(verts_in, 'mesh_flip_guard'), _verts_f32(verts_moved, 'mesh_flip_guard'), _faces_i32(faces, 'mesh_flip_guard')
+    if v1.shape != v0.shape or v1.device != v0.device or f.device != v0.device:
+        raise ValueError('mesh_flip_guard: verts_in, verts_moved and faces must describe one mesh on one device')
+    rounds = int(rounds)
+    if not 1 <= rounds < 2 ** 31 - 1:
+        raise ValueError(f'mesh_flip_guard: rounds must be >= 1, got {rounds}')
+    status = torch.zeros(len(v0), dtype=torch.uint8, device=v0.device) if status is None else _per_vertex(status, len(v0), torch.uint8, v0.device,
+                                                                                                        'mesh_flip_guard', 'status')
+    e = _native.ext()
+    if e is not None and hasattr(e, 'mesh_flip_guard'):
+        with _on_device(v0.device):
+            return tuple(e.mesh_flip_guard(v0, v1, f, status, rounds))
+    return _mesh_flip_guard_ctypes(v0, v1, f, status, rounds)
+
+
 # ---------------------------------------------------------------------------------------------------------------- simplification (csrc/mesh_simplify.hip)
 _MESH_SIMPLIFY_SYMBOLS = ('gnerf_mesh_simplify_workspace_bytes', 'gnerf_mesh_simplify_count', 'gnerf_mesh_simplify_emit')
 

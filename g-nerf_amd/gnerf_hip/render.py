@@ -495,3 +495,68 @@ def query_points_grad(planes_nhwc, n_items, decoder, points, box_warp, grad_sigm
     _launch('gnerf_query_points_grad', pts, _ptr(planes_nhwc), n_items, planes_nhwc.shape[1], planes_nhwc.shape[2], _ptr(pts), n_pts, float(box_warp),
             _ptr(w1), _ptr(b1), _ptr(w2), _ptr(b2), _ptr(gs), _ptr(gc), _ptr(g_pts), interleaved)
     return g_pts
+
+
+def project_to_level_available():
+    """Whether the loaded library has the level-set projection kernel (a version-15 library built before it does not)."""
+    return hasattr(load(), 'gnerf_project_points_to_level')
+
+
+def _project_affine(affine):
+    """affine as twelve Python floats that are exact C floats (row-major 3x4 [A | b]), or None."""
+    if affine is None:
+        return None
+    a = torch.as_tensor(affine, dtype=torch.float64).detach().cpu().reshape(-1)
+    if a.numel() == 16:                                                      # a 4x4 whose last row is 0 0 0 1
+        if a[12:].tolist() != [0.0, 0.0, 0.0, 1.0]:
+            raise ValueError('project_points_to_level: a 4x4 affine must end in the row 0 0 0 1')
+        a = a[:12]
+    if a.numel() != 12 or not bool(torch.isfinite(a).all()):
+        raise ValueError('project_points_to_level: affine must hold twelve finite values (3x4 [A | b]) or be None')
+    return [float(x) for x in a.to(torch.float32)]
+
+
+def _project_points_to_level_ctypes(planes_nhwc, n_items, dec, pts, box_warp, level, affine, steps, radius, tol, interleaved):
+    """The ctypes route of project_points_to_level (arguments as project_points_to_level prepares them)."""
+    w1, b1, w2, b2 = dec
+    n_pts, dev = pts.shape[1], pts.device
+    out = torch.empty([n_items, n_pts, 3], dtype=torch.float32, device=dev)
+    res_in = torch.empty([n_items, n_pts], dtype=torch.float32, device=dev)
+    res_out = torch.empty([n_items, n_pts], dtype=torch.float32, device=dev)
+    status = torch.empty([n_items, n_pts], dtype=torch.uint8, device=dev)
+    _launch('gnerf_project_points_to_level', pts, _ptr(planes_nhwc), n_items, planes_nhwc.shape[1], planes_nhwc.shape[2], _ptr(pts), n_pts, float(box_warp),
+            _ptr(w1), _ptr(b1), _ptr(w2), _ptr(b2), level, None if affine is None else (ctypes.c_float * 12)(*affine), steps, radius, tol,
+            _ptr(out), _ptr(res_in), _ptr(res_out), _ptr(status), interleaved)
+    return out, status, res_in, res_out
+
+
+@profiled('gnerf_hip::project_points_to_level')
+def project_points_to_level(planes_nhwc, n_items, decoder, points, box_warp, level, affine=None, steps=6, radius=1.0, tol=2.0 ** -10):
+    """Newton projection of points [N,P,3] onto the level set sigma = level of query_points' density, in one launch (include/gnerf_hip.h,
+    gnerf_project_points_to_level, states the rules): at most `steps` steps along the gradient, never more than `radius` per axis from the
+    start, done when |sigma - level| <= tol.  affine: None, or a 3x4 (or 4x4) [A | b] with world = A p + b for points in another frame
+    (radius is in the points' frame).  -> (points_out [N,P,3] float32: the input's bits unless converged; status uint8 [N,P]: 0 converged,
+    1 not converged, 2 flat or not finite; residual_in, residual_out float32 [N,P]: sigma - level before and after).  No atomics: the same
+    bits on every run and through either binding."""
+    if not project_to_level_available():
+        raise RuntimeError('gnerf_hip: this libgnerf_hip.so was built without gnerf_project_points_to_level: rebuild it (csrc/build.sh)')
+    dec = [_f32c(t) for t in decoder]
+    _require_cuda(planes_nhwc, points, dec[0])
+    interleaved = planes_layout(planes_nhwc, n_items, 'project_points_to_level')
+    pts = _points(points, n_items, 'project_points_to_level')
+    affine = _project_affine(affine)
+    steps = int(steps)
+    level, radius, tol = (float(torch.tensor(float(x), dtype=torch.float32)) for x in (level, radius, tol))
+    if steps < 0:
+        raise ValueError(f'project_points_to_level: steps must be >= 0, got {steps}')
+    if not 0 <= radius < float('inf'):
+        raise ValueError(f'project_points_to_level: radius must be finite and >= 0, got {radius}')
+    if not 0 < tol < float('inf'):
+        raise ValueError(f'project_points_to_level: tol must be a finite float32 > 0, got {tol}')
+    if level != level or abs(level) == float('inf'):
+        raise ValueError(f'project_points_to_level: level must be finite, got {level}')
+    e = _native.ext()
+    if e is not None and hasattr(e, 'project_points_to_level'):
+        with _on_device(pts.device):
+            return tuple(e.project_points_to_level(planes_nhwc, n_items, *dec, pts, float(box_warp), level, affine or [], steps, radius, tol))
+    return _project_points_to_level_ctypes(planes_nhwc, n_items, dec, pts, box_warp, level, affine, steps, radius, tol, interleaved)

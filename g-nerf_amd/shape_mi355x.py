@@ -1003,6 +1003,91 @@ def simplify_options(cell=0.0, target_faces=0, voxel=1.0):
     return dict(cell=(cell if cell else 1.0) * float(voxel), target_faces=target_faces)
 
 
+# ---------------------------------------------------------------------------------------------------------------- snapping to the level set
+# The last stage, after the smoothing: gen_videos_mi355x.snap_extracted_mesh projects the vertices onto sigma = level with the generator's own
+# density and gradient (gnerf_hip.project_points_to_level) and then runs the flip guard below, the numpy port of gnerf_mesh_flip_guard
+# (include/gnerf_hip.h states the rules; restated here).  The normal of a face (a, b, c) is n = (b - a) x (c - a) in float64 from the float32
+# coordinates, a dot product (x0 y0 + x1 y1) + x2 y2, every operation rounded on its own.  With n0 at verts_in and n1 at the current positions a
+# face is FLIPPED iff n0.n1 < 0, or n1.n1 == 0 and n0.n0 > 0 (an input face of zero area is never flipped); faces with an id outside [0, V)
+# are skipped.  Round j: the vertices of all faces flipped at the start of the round get status 3 and counts[j] = the number of those faces;
+# then every vertex of status 3 is set back to verts_in.  A round whose predecessor counted 0 does nothing.  counts[R] = the flips left.
+def _face_normals64(v, g):
+    a, b, c = (v[g[:, k]].astype(np.float64) for k in range(3))
+    e1, e2 = b - a, c - a
+    return np.stack([e1[:, 1] * e2[:, 2] - e1[:, 2] * e2[:, 1], e1[:, 2] * e2[:, 0] - e1[:, 0] * e2[:, 2], e1[:, 0] * e2[:, 1] - e1[:, 1] * e2[:, 0]], axis=1)
+
+
+def _dot3(a, b):
+    return (a[:, 0] * b[:, 0] + a[:, 1] * b[:, 1]) + a[:, 2] * b[:, 2]
+
+
+def mesh_flipped_faces(verts_in, verts_now, faces):
+    """bool [T]: the faces the move verts_in -> verts_now turned over, by the rule above (False for a face with an id out of range)."""
+    v0 = np.ascontiguousarray(np.asarray(verts_in), dtype=np.float32).reshape(-1, 3)
+    v1 = np.ascontiguousarray(np.asarray(verts_now), dtype=np.float32).reshape(-1, 3)
+    f, ok = _mesh_faces(faces, len(v0))
+    flipped = np.zeros(len(f), dtype=bool)
+    g = f[ok]
+    with np.errstate(all='ignore'):
+        n0, n1 = _face_normals64(v0, g), _face_normals64(v1, g)
+        flipped[ok] = (_dot3(n0, n1) < 0) | ((_dot3(n1, n1) == 0) & (_dot3(n0, n0) > 0))
+    return flipped
+
+
+def mesh_flip_guard_numpy(verts_in, verts_moved, faces, status=None, rounds=4):
+    """The numpy port of gnerf_mesh_flip_guard -> (verts_out float32 [V, 3], status uint8 [V], counts int32 [rounds + 1]), the kernels' bits."""
+    v0 = np.ascontiguousarray(np.asarray(verts_in), dtype=np.float32).reshape(-1, 3)
+    cur = np.array(np.asarray(verts_moved), dtype=np.float32).reshape(-1, 3)
+    if cur.shape != v0.shape:
+        raise ValueError('mesh_flip_guard: verts_in and verts_moved must have one shape')
+    rounds = int(rounds)
+    if rounds < 1:
+        raise ValueError(f'mesh_flip_guard: rounds must be >= 1, got {rounds}')
+    st = np.zeros(len(v0), dtype=np.uint8) if status is None else np.array(np.asarray(status), dtype=np.uint8).reshape(-1)
+    if len(st) != len(v0):
+        raise ValueError('mesh_flip_guard: status must hold one value per vertex')
+    if (st == 3).any():
+        raise ValueError('mesh_flip_guard: status 3 (reverted) is the guard\'s to set')
+    f, _ = _mesh_faces(faces, len(v0))
+    counts = np.zeros(rounds + 1, dtype=np.int32)
+    for j in range(rounds + 1):
+        if j and counts[j - 1] == 0:
+            break
+        flipped = mesh_flipped_faces(v0, cur, f)
+        counts[j] = np.count_nonzero(flipped)
+        if j < rounds and counts[j]:
+            st[f[flipped].reshape(-1)] = 3
+            back = st == 3
+            cur[back] = v0[back]
+    return cur, st, counts
+
+
+def snap_options(radius=0.0, steps=6, tol=None, guard_rounds=4):
+    """The CLI's flags (--mesh-snap R in voxels, --mesh-snap-steps, --mesh-snap-tol) as snap_extracted_mesh's dict, or None when R is 0
+    (nothing runs).  tol None: 2^-10 max(1, |level|), chosen where the level is known."""
+    radius, steps, guard_rounds = float(radius), int(steps), int(guard_rounds)
+    if not 0 <= radius < float('inf'):
+        raise ValueError('--mesh-snap must be a finite number of voxels >= 0')
+    if steps < 0:
+        raise ValueError('--mesh-snap-steps must be >= 0')
+    if tol is not None and not 0 < float(tol) < float('inf'):
+        raise ValueError('--mesh-snap-tol must be finite and > 0')
+    if guard_rounds < 1:
+        raise ValueError('the flip guard needs at least one round')
+    if not radius:
+        return None
+    return dict(radius=radius, steps=steps, tol=None if tol is None else float(tol), guard_rounds=guard_rounds)
+
+
+def snap_report_line(report):
+    """The one stdout line of the CLIs about a snap_extracted_mesh report."""
+    left = report['flips_left']
+    return (f'mesh snap: {report["converged"]} of {report["vertices"]} vertices on the level set, {report["not_converged"]} not converged, '
+            f'{report["flat"]} flat, {report["reverted"]} reverted by the flip guard (flips per round {report["flips"]}, '
+            + (f'{left} LEFT' if left else 'none left') + f'); |sigma - level| median {report["median_before"]:.3g} -> {report["median_after"]:.3g}, '
+            f'max {report["max_before"]:.3g} -> {report["max_after"]:.3g}')
+
+
 def process_mesh(verts, faces, clean=None, simplify=None):
     """What the CLIs do to a mesh marching cubes just made, up to the smoothing: components and compaction (clean: clean_options' dict or
     None), then simplification (simplify: simplify_options' dict or None).  -> (verts, faces, clean report or None, simplify report or None);
@@ -1242,7 +1327,9 @@ def convert_mrc(input_filename, output_filename, level=10.0, device=None, clean=
 
 
 def main(argv=None):
-    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter,
+                                 epilog='Snapping the vertices onto the density\'s level set (--mesh-snap of gen_videos_mi355x.py) needs the generator the '
+                                        'volume came from: this tool works from the volume alone and has no such flag.')
     ap.add_argument('input', help='a .mrc / .npy volume, or a directory of them (each gets a .ply next to it)')
     ap.add_argument('--level', type=float, default=10, help='the isosurface level (shape_utils.py:111)')
     ap.add_argument('--device', default=None, help="'cuda' runs the gfx950 kernel (default: cuda when available, else the numpy port)")

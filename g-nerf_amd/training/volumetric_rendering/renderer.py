@@ -291,6 +291,70 @@ class _FusedQuery(torch.autograd.Function):
         return tuple(grads)
 
 
+def _affine_3x4(affine, like):
+    """affine (3x4 or 4x4 [A | b], anything torch.as_tensor takes) -> (A [3,3], b [3]) in `like`'s dtype on its device, or (None, None)."""
+    if affine is None:
+        return None, None
+    if isinstance(affine, torch.Tensor) and affine.device == like.device and affine.numel() == 12:      # already there: no host round trip
+        m = affine.detach().reshape(3, 4).to(like.dtype)
+        return m[:, :3], m[:, 3]
+    a = torch.as_tensor(affine).detach().to(torch.float64).cpu().reshape(-1)
+    if a.numel() == 16:
+        a = a[:12]
+    if a.numel() != 12:
+        raise ValueError('project_to_level: affine must be a 3x4 or 4x4 [A | b]')
+    m = a.reshape(3, 4).to(device=like.device, dtype=like.dtype)
+    return m[:, :3], m[:, 3]
+
+
+def project_to_level_rules(field, points, level, steps=6, radius=1.0, tol=2.0 ** -10, affine=None, early_exit=True):
+    """The rules of gnerf_project_points_to_level (include/gnerf_hip.h) as tensor operations in the points' own dtype, for any field:
+    field(world [..., 3]) -> (s [...], g_world [..., 3]), the field and its gradient at world = A p + b.  Per point, independently:
+        p = p0
+        for k = 0 .. steps:
+            e = s(A p + b) - level;  k == 0: residual_in = e
+            e not finite -> status 2, stop;  |e| <= tol -> status 0, stop;  k == steps -> status 1, stop
+            g = A^T g_world;  gg = g.g;  gg not > 0 or not finite -> status 2, stop
+            p = clamp(p - (e / gg) g, p0 - radius, p0 + radius)         (a NaN coordinate takes the box's lower face)
+    -> (points_out: p where status == 0, else p0's bits; status uint8; residual_in; residual_out: e where status == 0, else residual_in).
+    The float64 port the kernel's tests compare against, and ImportanceRenderer.project_to_level off the kernel's path.  early_exit False
+    never reads a tensor on the host (all steps run, the same result): the form a HIP graph can capture."""
+    steps = int(steps)
+    if steps < 0 or not 0 <= float(radius) < float('inf') or not 0 < float(tol) < float('inf'):
+        raise ValueError('project_to_level: steps >= 0, a finite radius >= 0 and a finite tol > 0 are needed')
+    p0 = points.detach()
+    A, b = _affine_3x4(affine, p0)
+    p = p0.clone()
+    lo, hi = p0 - radius, p0 + radius
+    status = torch.full(p0.shape[:-1], 255, dtype=torch.uint8, device=p0.device)
+    e_last = torch.zeros(p0.shape[:-1], dtype=p0.dtype, device=p0.device)
+    res_in = e_last
+    for k in range(steps + 1):
+        active = status == 255
+        if early_exit and not bool(active.any()):
+            break
+        world = p if A is None else p @ A.t() + b
+        s, g_world = field(world)
+        e = torch.where(torch.isfinite(world).all(-1), s.to(p0.dtype) - level, torch.full_like(e_last, float('nan')))
+        if k == 0:
+            res_in = e.clone()
+        e_last = torch.where(active, e, e_last)
+        status = torch.where(active & ~torch.isfinite(e), torch.full_like(status, 2), status)
+        status = torch.where((status == 255) & (e.abs() <= tol), torch.zeros_like(status), status)
+        if k == steps:
+            status = torch.where(status == 255, torch.ones_like(status), status)
+            break
+        g = g_world.to(p0.dtype) if A is None else g_world.to(p0.dtype) @ A
+        gg = (g * g).sum(-1)
+        status = torch.where((status == 255) & ~((gg > 0) & torch.isfinite(gg)), torch.full_like(status, 2), status)
+        move = status == 255
+        q = p - (e / gg)[..., None] * g
+        q = torch.where(torch.isnan(q), lo, q)
+        p = torch.where(move[..., None], torch.minimum(torch.maximum(q, lo), hi), p)
+    done = status == 0
+    return torch.where(done[..., None], p, p0), status, res_in, torch.where(done, e_last, res_in)
+
+
 _warned_fallbacks = set()
 
 
@@ -603,6 +667,30 @@ class ImportanceRenderer(torch.nn.Module):
             sigma = sigma.detach()
         length = grad.norm(dim=-1, keepdim=True)
         return sigma, torch.where(length > 0, -grad / length, torch.zeros_like(grad))
+
+    def project_to_level(self, planes, decoder, points, level, options, affine=None, steps=6, radius=1.0, tol=None):
+        """Newton projection of points [N,P,3] onto the density's level set sigma = level -> (points_out [N,P,3], status uint8 [N,P]: 0
+        converged / 1 not converged / 2 flat or not finite, residual_in [N,P], residual_out [N,P]: sigma - level before and after).  At most
+        `steps` steps, never more than `radius` per axis from the start (in the points' frame), done when |sigma - level| <= tol (None:
+        2^-10 max(1, |level|)); a point that does not converge keeps its input's bits.  affine: a 3x4 (or 4x4) [A | b], world = A p + b,
+        for points in another frame (a mesh in its index frame).  On a GPU with the OSG decoder and [N,3,32,H,W] planes one launch of
+        gnerf_hip.project_points_to_level; otherwise (CPU tensors, float64, another decoder) project_to_level_rules on autograd through
+        the PyTorch-op form, as query_normals falls back.  density_noise is not applied.  Not part of the reference's interface."""
+        tol = 2.0 ** -10 * max(1.0, abs(float(level))) if tol is None else float(tol)
+        fcs = _osg_decoder_weights(decoder) if planes.device.type == 'cuda' else None
+        if fcs is not None and planes.ndim == 5 and planes.shape[1] == 3 and planes.shape[2] == 32 and points.dtype != torch.float64:
+            return gnerf_hip.project_points_to_level(self._planes_nhwc(planes)[0], planes.shape[0], self._decoder_cache(fcs), points.detach(),
+                                                     options['box_warp'], level, affine=affine, steps=steps, radius=radius, tol=tol)
+        opts = dict(options, density_noise=0)
+
+        def field(world):
+            with torch.enable_grad():
+                pts = world.detach().to(planes.dtype).requires_grad_(True)         # the field in the planes' dtype, the rules in the points'
+                sigma = self._run_model(planes.detach(), decoder, pts, torch.zeros_like(pts), opts, fused_points=False)['sigma']      # (GPU tensors here: the fallback warning)
+                grad, = torch.autograd.grad(sigma.sum(), pts)
+            return sigma.detach()[..., 0], grad
+
+        return project_to_level_rules(field, points.detach(), level, steps=steps, radius=radius, tol=tol, affine=affine)
 
     def sort_samples(self, all_depths, all_colors, all_densities):
         _, order = torch.sort(all_depths, dim=-2)

@@ -587,6 +587,35 @@ int gnerf_query_points_grad(const float* planes_nhwc, int n_items, int plane_h, 
                             const float* grad_sigma, const float* grad_rgb, float* grad_points,
                             int planes_interleaved, gnerf_stream_t stream);
 
+/* (ABI 15, added without a new version) Newton projection of points onto the level set sigma = level of gnerf_query_points' density, with
+ * the gradient of gnerf_query_points_grad (grad_sigma = 1, no colour half) -- one launch (csrc/project_level.inl) for all steps.
+ *   points [n_items, n_points, 3] float32; affine: float32 [12] ON THE HOST (read during the call), a row-major 3x4 [A | b] with world = A p + b (b = affine[3], [7],
+ *   [11]), or NULL for the identity (no arithmetic at all then); max_steps K >= 0; radius r >= 0 in the points' own frame; tol > 0 in
+ *   sigma units.  Per point, independent of every other point (tile, batch and position do not matter), all in float32:
+ *     p = p0
+ *     for k = 0 .. K:
+ *         s, g_world = sigma and grad sigma at A p + b
+ *         e = s - level (NaN when A p + b has a non-finite coordinate);  if k == 0: residual_in = e
+ *         if e is not finite:  status = 2; break
+ *         if |e| <= tol:       status = 0; break            (converged; the point takes no further step)
+ *         if k == K:           status = 1; break            (not converged)
+ *         g = A^T g_world                                   (a covector)
+ *         gg = (g0 g0 + g1 g1) + g2 g2;  if gg is not > 0 or not finite: status = 2; break       (flat)
+ *         q = p - (e / gg) g                                (the nearest point of the linearised level set)
+ *         p = min(max(q, p0 - r), p0 + r) per axis          (a trust box around the START; a NaN q takes the box's lower face)
+ *     points_out   = status == 0 ? p : p0                   (the input's bits when not converged)
+ *     residual_out = status == 0 ? e : residual_in
+ *   points_out [n_items, n_points, 3], residual_in / residual_out float32 [n_items, n_points], status uint8 [n_items, n_points]: every
+ *   element WRITTEN.  points_out may be points.  Plain stores, no atomics: bit-reproducible.
+ * GNERF_E_ARG for null pointers (affine excepted), n_points < 1 or beyond gnerf_query_points' cap, K < 0, r < 0 or not finite, tol <= 0 or
+ * not finite; GNERF_E_UNSUPPORTED when one item's planes exceed 32-bit tap offsets (as gnerf_query_points_grad). */
+int gnerf_project_points_to_level(const float* planes_nhwc, int n_items, int plane_h, int plane_w,
+                                  const float* points, int n_points, float box_warp,
+                                  const float* w1, const float* b1, const float* w2, const float* b2,
+                                  float level, const float* affine, int max_steps, float radius, float tol,
+                                  float* points_out, float* residual_in, float* residual_out, unsigned char* status,
+                                  int planes_interleaved, gnerf_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------
  * (ABI 13) Marching cubes: the triangle mesh of a level set of a dense float32 volume [d0, d1, d2] (axis 2 fastest, contiguous,
  * every d >= 2, d0 * d1 * d2 < 2^31) -- what shape_utils.py:58-61 asks skimage.measure.marching_cubes for, with this project's own rules
@@ -814,6 +843,26 @@ int gnerf_mesh_simplify_count(const float* verts, const int32_t* faces, int n_ve
 int gnerf_mesh_simplify_emit(const float* verts, const int32_t* faces, int n_verts, int n_tris, float cell, const float* origin,
                              void* workspace, float* out_verts, int32_t* out_faces, int32_t* src_vertex, int32_t* vertex_map,
                              gnerf_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
+ * (ABI 15, added without a new version) Flip guard: after the vertices of a mesh have been moved (gnerf_project_points_to_level), set back the
+ * vertices of every face that the move turned over (csrc/mesh_clean.hip; shape_mi355x.mesh_flip_guard_numpy gives the same bits).
+ *   verts_in, verts_moved float32 [V, 3]; faces int32 [T, 3]; max_rounds R >= 1; verts_out float32 [V, 3] (written; may be verts_moved, not
+ *   verts_in); status uint8 [V], IN AND OUT; counts int32 [R + 1] on the device, written.
+ *   The normal of a face (a, b, c) at given positions is n = (b - a) x (c - a) = (e1y e2z - e1z e2y, e1z e2x - e1x e2z, e1x e2y - e1y e2x),
+ *   formed in float64 from the float32 coordinates; a dot product is (x0 y0 + x1 y1) + x2 y2; every operation is rounded on its own, no
+ *   contraction.  With n0 at verts_in and n1 at the current positions a face is FLIPPED iff n0.n1 < 0, or n1.n1 == 0 and n0.n0 > 0: an
+ *   input face of zero area is never flipped.  A face is valid iff its three ids lie in [0, V); the others are skipped.
+ *   The current positions start as verts_moved.  Status 3 means REVERTED; status comes in with other values only (the
+ *   projection's 0, 1, 2), which the vertices that are not reverted keep.
+ *   Round j = 0 .. R - 1: status = 3 for the three vertices of every face flipped at the positions of the start of the round (plain stores
+ *   of the same value), the number of those faces -> counts[j] (one integer add per block); then every vertex of status 3 is set to verts_in.
+ *   A round whose predecessor counted 0 does nothing and counts 0 (a device-side read of counts[j - 1]).  A last pass writes the number of
+ *   faces still flipped into counts[R].  The reverted set only grows and a fully reverted mesh has no flip, so the counts reach 0.
+ *   No workspace, no host read, no allocation: capturable.  Integer adds only: the same bits for every order of the faces.
+ * GNERF_E_ARG for null pointers, negative sizes, R < 1 or verts_out == verts_in. */
+int gnerf_mesh_flip_guard(const float* verts_in, const float* verts_moved, const int32_t* faces, int n_verts, int n_tris, int max_rounds,
+                          float* verts_out, unsigned char* status, int32_t* counts, gnerf_stream_t stream);
 
 #ifdef __cplusplus
 }
