@@ -9,6 +9,8 @@
 #include "common.h"
 #include "raygen.h"
 
+#include <cstdlib>
+
 namespace {
 
 using namespace gnerf;
@@ -110,48 +112,89 @@ __global__ __launch_bounds__(256) void nchw_to_nhwc_kernel(const float* __restri
 // The form for 32k channels, h w % 4 == 0 and 16-byte aligned tensors (the renderer's planes): no LDS, 16-byte accesses on both
 // sides.  Lane cg + 8 xg of a wave holds the 4 x 4 block channels 4 cg .. 4 cg + 3 x pixels 4 xg .. 4 xg + 3: it loads four rows
 // along x and stores four channel quads, one per pixel.  A wave's load instruction reads eight whole 128-byte lines (32 pixels of
-// eight channels); a store instruction writes eight whole texels.  Workgroup: 32 channels x kV4Px pixels, two 16-byte loads of each
-// channel row in flight per lane.
+// eight channels); a store instruction writes eight whole texels.  A workgroup's unit: 32 channels x kV4UnitPx pixels, one 16-byte
+// load of each of a lane's four channel rows.
 // In the step (profiles/r07_step_*_kernel_stats.csv, same box): 38.3 us where the dword form took 53.0 plus 4.3 for its fill launch;
 // the step 0.520 against 0.536 ms alternating (profiles/r07_repack_ab.jsonl), render kernel unchanged.  (Round 3's 16-byte form, which
 // went through an LDS tile, was faster alone but slowed the step; that code is gone and was not re-measured.)
-constexpr int kV4Trips = 2, kV4Px = 4 * 32 * kV4Trips;
-template <bool STATS>
-__global__ __launch_bounds__(256) void nchw_to_nhwc_v4_kernel(const float* __restrict__ src, float* __restrict__ dst,
-                                                              int c, int64_t hw, int tiles_p, int tiles_c, unsigned* ws, float* absmax) {
-    int64_t t = blockIdx.x;
-    const int tp = int(t % tiles_p); t /= tiles_p;
-    const int tc = int(t % tiles_c); t /= tiles_c;
-    const int64_t plane = t;
+//
+// Round 20 (profiles/r20_step_edges_ab.jsonl, r20_step_*_kernel_stats.csv): the grid is what is resident, balanced over the walks, and a
+// workgroup keeps the NEXT walk's loads in flight while it stores this one: 37.2 -> 32.7 us in the step, where 201 MB at the 6.29 TB/s of
+// a float4 copy are 32.0.  One workgroup per 256 pixels made 3 072 of them for the headline's planes on a chip that holds 2 048 (a round
+// and a half), each with its loads drained before its stores began.  Resident grids of the unpipelined body took 35-36 us whatever the
+// walk order (strided or adjacent walks per workgroup, one to three units per walk, 1 024-2 048 workgroups); with the next walk's eight
+// loads issued ahead of the stores 33.2-34.1 us.  The two walks in registers cost 100 VGPRs = 4 workgroups per CU, 16 loads of 16 bytes in
+// flight per lane: 256 KB per CU where HBM's latency wants about 50.  Measured and left out: lanes taking two adjacent vectors of a row
+// (256-byte runs per wave load; 35-36 us), three units per walk (no faster at 140 VGPRs), write-through stores (no change: this pass
+// evicts its dirty lines as it goes).
+constexpr int kV4Trips = 2, kV4UnitPx = 4 * 32;
+// One walk of a workgroup: kV4Trips adjacent units of 32 channels x kV4UnitPx pixels, every load issued before the first store.
+struct V4Walk {
+    float4 v[kV4Trips][4];
+    int64_t px[kV4Trips];           // this lane's first pixel of each unit; hw for a unit past the end (nothing loaded, nothing stored)
+    float* d[kV4Trips];
+};
+
+__device__ __forceinline__ void v4_load(V4Walk& k, unsigned w, const float* __restrict__ src, float* __restrict__ dst, int c, int64_t hw,
+                                        unsigned units_p, unsigned tiles_c, unsigned units) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int cg = lane & 7, xg = lane >> 3;
-    const int ch0 = tc * CT + 4 * cg;
-    const float* s = src + (plane * c + ch0) * hw;
-    float* d = dst + plane * hw * c + ch0;
-    float4 v[kV4Trips][4];
-    int64_t px[kV4Trips];
 #pragma unroll
     for (int j = 0; j < kV4Trips; j++) {
-        px[j] = int64_t(tp) * kV4Px + (j * 4 + wave) * 32 + 4 * xg;        // hw % 4 == 0: the four pixels are all in or all out
-        const int64_t pl = px[j] < hw ? px[j] : hw - 4;                     // past the end: a duplicate load, not a branch per load
+        const unsigned u = w * kV4Trips + j;                                    // wave-uniform
+        k.px[j] = hw;
+        k.d[j] = dst;
 #pragma unroll
-        for (int k = 0; k < 4; k++) v[j][k] = *reinterpret_cast<const float4*>(s + k * hw + pl);
+        for (int q = 0; q < 4; q++) k.v[j][q] = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (u < units) {
+            const unsigned up = u % units_p, t = u / units_p, tc = t % tiles_c, plane = t / tiles_c;
+            const int ch0 = int(tc) * CT + 4 * cg;
+            const float* s = src + (int64_t(plane) * c + ch0) * hw;
+            k.d[j] = dst + int64_t(plane) * hw * c + ch0;
+            k.px[j] = int64_t(up) * kV4UnitPx + wave * 32 + 4 * xg;             // hw % 4 == 0: the four pixels are all in or all out
+            const int64_t pl = k.px[j] < hw ? k.px[j] : hw - 4;                 // past the end: a duplicate load, not a branch per load
+#pragma unroll
+            for (int q = 0; q < 4; q++) k.v[j][q] = *reinterpret_cast<const float4*>(s + q * hw + pl);
+        }
     }
-    unsigned amax = 0u;
+}
+
+template <bool STATS>
+__device__ __forceinline__ void v4_store(const V4Walk& k, int c, int64_t hw, unsigned& amax) {
 #pragma unroll
     for (int j = 0; j < kV4Trips; j++) {
-        if (px[j] < hw) {
-            float* o = d + px[j] * c;
-            *reinterpret_cast<float4*>(o)         = make_float4(v[j][0].x, v[j][1].x, v[j][2].x, v[j][3].x);
-            *reinterpret_cast<float4*>(o + c)     = make_float4(v[j][0].y, v[j][1].y, v[j][2].y, v[j][3].y);
-            *reinterpret_cast<float4*>(o + 2 * c) = make_float4(v[j][0].z, v[j][1].z, v[j][2].z, v[j][3].z);
-            *reinterpret_cast<float4*>(o + 3 * c) = make_float4(v[j][0].w, v[j][1].w, v[j][2].w, v[j][3].w);
+        const float4* q = k.v[j];
+        if (k.px[j] < hw) {
+            float* o = k.d[j] + k.px[j] * c;
+            *reinterpret_cast<float4*>(o)         = make_float4(q[0].x, q[1].x, q[2].x, q[3].x);
+            *reinterpret_cast<float4*>(o + c)     = make_float4(q[0].y, q[1].y, q[2].y, q[3].y);
+            *reinterpret_cast<float4*>(o + 2 * c) = make_float4(q[0].z, q[1].z, q[2].z, q[3].z);
+            *reinterpret_cast<float4*>(o + 3 * c) = make_float4(q[0].w, q[1].w, q[2].w, q[3].w);
         }
-        if (STATS) {                                                        // (a duplicate cannot raise the maximum)
+        if (STATS) {                                                            // (a duplicate cannot raise the maximum)
 #pragma unroll
-            for (int k = 0; k < 4; k++)
-                amax = max(max(amax, abs_bits(v[j][k].x)), max(max(abs_bits(v[j][k].y), abs_bits(v[j][k].z)), abs_bits(v[j][k].w)));
+            for (int i = 0; i < 4; i++)
+                amax = max(max(amax, abs_bits(q[i].x)), max(max(abs_bits(q[i].y), abs_bits(q[i].z)), abs_bits(q[i].w)));
         }
+    }
+}
+
+// Workgroup b takes walks b, b + grid, b + 2 grid, ...: at any moment the resident workgroups read and write one moving window of
+// the planes.  One absmax ticket per workgroup.
+template <bool STATS>
+__global__ __launch_bounds__(256) void nchw_to_nhwc_v4_kernel(const float* __restrict__ src, float* __restrict__ dst, int c, int64_t hw,
+                                                              unsigned units_p, unsigned tiles_c, unsigned units, unsigned walks,
+                                                              unsigned* ws, float* absmax) {
+    unsigned amax = 0u;
+    const unsigned step = gridDim.x;
+    V4Walk a, b;
+    v4_load(a, blockIdx.x, src, dst, c, hw, units_p, tiles_c, units);           // (grid <= walks)
+    for (unsigned w = blockIdx.x; w < walks; w += 2 * step) {
+        if (w + step < walks) v4_load(b, w + step, src, dst, c, hw, units_p, tiles_c, units);
+        v4_store<STATS>(a, c, hw, amax);
+        if (w + step >= walks) break;
+        if (w + 2 * step < walks) v4_load(a, w + 2 * step, src, dst, c, hw, units_p, tiles_c, units);
+        v4_store<STATS>(b, c, hw, amax);
     }
     if (STATS) publish_absmax_ticket(amax, ws, absmax);
 }
@@ -283,11 +326,12 @@ __global__ __launch_bounds__(256) void nhwc_to_nchw_kernel(const float* __restri
     }
 }
 
-// One lane per ray; the arithmetic is camera_ray's (raygen.h), shared with the render kernels' in-kernel form.
-__global__ __launch_bounds__(256) void make_rays_kernel(const float* __restrict__ c2w, const float* __restrict__ intr,
-                                                        int n, int res, float* __restrict__ origins, float* __restrict__ dirs) {
+// One lane per ray; the arithmetic is camera_ray's (raygen.h), shared with the render kernels' in-kernel form.  ONE compiled body for
+// both launches that make ray tensors (not inlined): where the compiler contracts a multiply and an add of camera_ray into an FMA depends
+// on the code around it, and gnerf_make_rays and gnerf_make_rays_and_draws promise the same bits.
+__device__ __noinline__ void ray_lane(const float* __restrict__ c2w, const float* __restrict__ intr, int n, int res, int64_t i,
+                                      float* __restrict__ origins, float* __restrict__ dirs) {
     const int64_t m_total = int64_t(res) * res;
-    const int64_t i = int64_t(blockIdx.x) * 256 + threadIdx.x;
     if (i >= m_total * n) return;
     const int item = int(i / m_total);
     const int m = int(i % m_total);
@@ -301,48 +345,86 @@ __global__ __launch_bounds__(256) void make_rays_kernel(const float* __restrict_
     }
 }
 
+__global__ __launch_bounds__(256) void make_rays_kernel(const float* __restrict__ c2w, const float* __restrict__ intr,
+                                                        int n, int res, float* __restrict__ origins, float* __restrict__ dirs) {
+    ray_lane(c2w, intr, n, res, int64_t(blockIdx.x) * 256 + threadIdx.x, origins, dirs);
+}
+
+// A 16-byte store that is written through the L2 (sc1) instead of staying dirty in it.  The draws are 25 MB that fit the L2s whole: stored
+// plainly they all wait there for the write-back at the end of the launch, 2 us during which nothing else runs (9.8 -> 7.8 us in the step,
+// the render kernel unchanged: it finds them in the Infinity Cache either way; non-temporal stores, which bypass that too, cost the render
+// kernel 8 us).  The compiler does not model the statement: the s_nop keeps its next instruction off the data registers until the store
+// has read them, and nothing in the launch waits for these stores but its end.
+typedef float f4_t __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ void store16_through(float* p, float a, float b, float c, float d) {
+    const f4_t v = {a, b, c, d};
+    asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" :: "v"(p), "v"(v) : "memory");
+}
+
 // Round 6: what a render step needs in front of the fused kernel -- the rays of n cameras and the reference's two uniform draws (renderer.py:
 // 190 `rand_like([N,M,S,1])`, :241 `rand(N*M, F)`) -- in ONE launch instead of three (gnerf_make_rays + two torch.rand).  The draws are
 // torch.rand's, bit for bit: thread t of a draw evaluates the Philox block of (counter ctr + call, subsequence t) and stores its four words
 // at elements t + threads * (4 call + word), exactly as ATen's grid-stride kernel does (raygen.h: torch_rand_element is the per-element view of
 // the same map) -- one block per four elements, where the stand-alone gnerf_torch_rand evaluates one per element.
-__global__ __launch_bounds__(256) void rays_and_draws_kernel(const float* __restrict__ c2w, const float* __restrict__ intr, int n, int res,
-                                                             float* __restrict__ origins, float* __restrict__ dirs,
-                                                             float* __restrict__ out_a, int64_t numel_a, TorchRandDraw da, uint32_t threads_a,
-                                                             float* __restrict__ out_b, int64_t numel_b, TorchRandDraw db, uint32_t threads_b) {
-    const int64_t i = int64_t(blockIdx.x) * 256 + threadIdx.x;
-    const int64_t m_total = int64_t(res) * res;
-    if (i < m_total * n) {
-        const int item = int(i / m_total);
-        const int m = int(i % m_total);
-        const float* M = c2w + item * 16;
-        float d[3];
-        camera_ray(M, intr + item * 9, res, m / res, m % res, d);
+//
+// Round 20.  The three parts have workgroups of their own (rays, draw a, draw b, in that order of blockIdx): until then every lane made its
+// ray first and then both draws, and since the whole grid is resident at once the launch lasted as long as its longest lane.  A draw lane
+// owns kDrawQuad ADJACENT threads of ATen's grid: their Philox blocks are independent (the ten-round multiply chains interleave), and word k
+// of the four blocks lies at four adjacent elements, so it leaves as one 16-byte store -- a wave instruction writes 1 KB where one lane per
+// thread wrote 256 bytes.  The number of calls is the launch's (the host's ceil(numel / 4 threads)), not a 64-bit division per lane; I is
+// uint32_t wherever every index of the launch fits (the host decides), int64_t otherwise.
+constexpr int kDrawQuad = 4;
+struct DrawPart {
+    float* out;
+    TorchRandDraw d;
+    uint64_t calls;                 // Philox blocks per thread of ATen's grid
+    uint32_t threads;               // ATen's grid in threads
+    uint32_t vec;                   // out is 16-byte aligned and threads % 4 == 0: element t + threads * j is 16-byte aligned for t % 4 == 0
+};
+
+template <typename I>
+__device__ __forceinline__ void draw_quads(const DrawPart& p, I numel, I g) {
+    const I threads = I(p.threads), t0 = g * kDrawQuad;
+    if (t0 >= threads) return;
+    float* __restrict__ out = p.out;
+    for (uint64_t call = 0; call < p.calls; call++) {
+        const uint64_t c = p.d.ctr + call;
+        uint32_t w[kDrawQuad][4];
 #pragma unroll
-        for (int r = 0; r < 3; r++) {
-            dirs[i * 3 + r] = d[r];
-            origins[i * 3 + r] = M[r * 4 + 3];
-        }
-    }
-    auto draw = [&](float* __restrict__ out, int64_t numel, const TorchRandDraw& d, uint32_t threads) {
-        if (!out || i >= int64_t(threads)) return;
-        const int64_t per_thread = (numel - i + int64_t(threads) - 1) / int64_t(threads);      // elements of this thread: i, i + threads, ...
-        for (int64_t call = 0; 4 * call < per_thread; call++) {
-            const uint64_t c = d.ctr + uint64_t(call);
-            uint32_t w[4];
-            philox4x32_10_block(uint32_t(c), uint32_t(c >> 32), uint32_t(i), 0u, d.k0, d.k1, w);
+        for (int q = 0; q < kDrawQuad; q++) philox4x32_10_block(uint32_t(c), uint32_t(c >> 32), uint32_t(t0) + q, 0u, p.d.k0, p.d.k1, w[q]);
 #pragma unroll
-            for (int k = 0; k < 4; k++) {
-                const int64_t li = i + int64_t(threads) * (4 * call + k);
-                if (li < numel) {
-                    const float u = __fmaf_rn(float(w[k]), 0x1p-32f, 0x1p-32f);
-                    out[li] = u == 1.0f ? 0.0f : u;
-                }
+        for (int k = 0; k < 4; k++) {
+            const I li = t0 + threads * I(4 * call + k);                     // element of thread t0; thread t0 + q has li + q
+            float u[kDrawQuad];
+#pragma unroll
+            for (int q = 0; q < kDrawQuad; q++) {
+                const float x = __fmaf_rn(float(w[q][k]), 0x1p-32f, 0x1p-32f);
+                u[q] = x == 1.0f ? 0.0f : x;
+            }
+            if (p.vec && li + (kDrawQuad - 1) < numel) {
+                store16_through(out + li, u[0], u[1], u[2], u[3]);
+            } else {
+#pragma unroll
+                for (int q = 0; q < kDrawQuad; q++)
+                    if (t0 + q < threads && li + q < numel) out[li + q] = u[q];
             }
         }
-    };
-    draw(out_a, numel_a, da, threads_a);
-    draw(out_b, numel_b, db, threads_b);
+    }
+}
+
+template <typename I>
+__global__ __launch_bounds__(256) void rays_and_draws_kernel(const float* __restrict__ c2w, const float* __restrict__ intr, int n, int res,
+                                                             float* __restrict__ origins, float* __restrict__ dirs, unsigned ray_blocks,
+                                                             DrawPart a, I numel_a, unsigned blocks_a, DrawPart b, I numel_b) {
+    unsigned blk = blockIdx.x;
+    if (blk < ray_blocks) {
+        ray_lane(c2w, intr, n, res, int64_t(blk) * 256 + threadIdx.x, origins, dirs);
+        return;
+    }
+    blk -= ray_blocks;
+    if (blk < blocks_a) { draw_quads<I>(a, numel_a, I(blk) * 256 + threadIdx.x); return; }
+    blk -= blocks_a;
+    draw_quads<I>(b, numel_b, I(blk) * 256 + threadIdx.x);
 }
 
 // torch.rand(numel) at (seed, offset) as a stand-alone kernel: one element per lane, grid-stride free (numel <= 2^32 checked by the host)
@@ -381,6 +463,22 @@ extern "C" int gnerf_to_uint8_nhwc(const float* img, unsigned char* out, int n, 
     return check_launch("to_uint8_nhwc");
 }
 
+// Workgroups of 256 threads of `kernel` that the current device holds at once (occupancy x CUs), asked once per device and kernel
+// (`slot`); the chip's nominal 4 per CU where the runtime does not answer.
+template <class K> static unsigned resident_workgroups(K kernel, int slot) {
+    static unsigned cache[2][64] = {};
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = -1;
+    if (dev >= 0 && cache[slot][dev]) return cache[slot][dev];
+    int per_cu = 0, cus = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, 256, 0) != hipSuccess || per_cu < 1) per_cu = 4;
+    if (dev < 0 || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1) cus = gnerf::kNumCU;
+    (void)hipGetLastError();
+    const unsigned r = unsigned(per_cu) * unsigned(cus);
+    if (dev >= 0) cache[slot][dev] = r;
+    return r;
+}
+
 static int planes_to_nhwc_impl(const float* planes_nchw, float* planes_nhwc, int np, int c, int h, int w, float* absmax, void* workspace,
                                bool stats, gnerf_stream_t stream) {
     using namespace gnerf;
@@ -388,15 +486,27 @@ static int planes_to_nhwc_impl(const float* planes_nchw, float* planes_nhwc, int
     if (np < 1 || c < 1 || h < 1 || w < 1) return fail(GNERF_E_ARG, "planes_to_nhwc: empty tensor");
     const int64_t hw = int64_t(h) * w;
     const bool v4 = c % CT == 0 && hw % 4 == 0 && !(reinterpret_cast<uintptr_t>(planes_nchw) & 15) && !(reinterpret_cast<uintptr_t>(planes_nhwc) & 15);
-    const int px_tile = v4 ? kV4Px : PT;
+    const int px_tile = v4 ? kV4UnitPx : PT;
     const int tiles_p = int((hw + px_tile - 1) / px_tile), tiles_c = (c + CT - 1) / CT;
     const int64_t blocks = int64_t(tiles_p) * tiles_c * np;
     if (blocks > INT32_MAX) return fail(GNERF_E_ARG, "planes_to_nhwc: tensor too large");
     unsigned* ws = static_cast<unsigned*>(workspace);
-    const dim3 grid((unsigned)blocks), block(256);
-    if (v4 && stats) hipLaunchKernelGGL(nchw_to_nhwc_v4_kernel<true>, grid, block, 0, as_stream(stream), planes_nchw, planes_nhwc, c, hw, tiles_p, tiles_c, ws, absmax);
-    else if (v4) hipLaunchKernelGGL(nchw_to_nhwc_v4_kernel<false>, grid, block, 0, as_stream(stream), planes_nchw, planes_nhwc, c, hw, tiles_p, tiles_c, ws, absmax);
-    else if (stats) hipLaunchKernelGGL(nchw_to_nhwc_kernel<true>, grid, block, 0, as_stream(stream), planes_nchw, planes_nhwc, c, hw, tiles_p, tiles_c, ws, absmax);
+    const dim3 block(256);
+    if (v4) {
+        const unsigned units = unsigned(blocks), walks = (units + kV4Trips - 1) / kV4Trips;
+        // the grid: what is resident, and the same number of walks for every workgroup where that divides (3 072 walks on 1 024 resident
+        // workgroups, the headline: three each).  GNERF_REPACK_GRID caps it, for the tests only: a small tensor on a grid of a few
+        // workgroups reaches every branch of the walk loop.  (Read per call, so that a test can set it in its own process; 0.1 us.)
+        unsigned resident = stats ? resident_workgroups(nchw_to_nhwc_v4_kernel<true>, 0) : resident_workgroups(nchw_to_nhwc_v4_kernel<false>, 1);
+        if (const char* e = getenv("GNERF_REPACK_GRID")) { const long cap = atol(e); if (cap > 0 && cap < long(resident)) resident = unsigned(cap); }
+        const unsigned rounds = (walks + resident - 1) / resident;
+        const dim3 grid((walks + rounds - 1) / rounds);
+        if (stats) hipLaunchKernelGGL(nchw_to_nhwc_v4_kernel<true>, grid, block, 0, as_stream(stream), planes_nchw, planes_nhwc, c, hw, unsigned(tiles_p), unsigned(tiles_c), units, walks, ws, absmax);
+        else hipLaunchKernelGGL(nchw_to_nhwc_v4_kernel<false>, grid, block, 0, as_stream(stream), planes_nchw, planes_nhwc, c, hw, unsigned(tiles_p), unsigned(tiles_c), units, walks, ws, absmax);
+        return check_launch("planes_to_nhwc");
+    }
+    const dim3 grid((unsigned)blocks);
+    if (stats) hipLaunchKernelGGL(nchw_to_nhwc_kernel<true>, grid, block, 0, as_stream(stream), planes_nchw, planes_nhwc, c, hw, tiles_p, tiles_c, ws, absmax);
     else hipLaunchKernelGGL(nchw_to_nhwc_kernel<false>, grid, block, 0, as_stream(stream), planes_nchw, planes_nhwc, c, hw, tiles_p, tiles_c, ws, absmax);
     return check_launch("planes_to_nhwc");
 }
@@ -498,11 +608,31 @@ extern "C" int gnerf_make_rays_and_draws(const float* cam2world, const float* in
     if (!torch_rand_draw(seed, offset_a, threads_a, numel_a, da) || (draw_b && !torch_rand_draw(seed, offset_b, threads_b, numel_b, db)))
         return fail(GNERF_E_UNSUPPORTED, "make_rays_and_draws: the generator geometry (threads %u / %u at offsets %llu / %llu) is not one these kernels reproduce",
                     threads_a, threads_b, (unsigned long long)offset_a, (unsigned long long)offset_b);
-    int64_t lanes = int64_t(n) * res * res;
-    if (int64_t(threads_a) > lanes) lanes = threads_a;
-    if (draw_b && int64_t(threads_b) > lanes) lanes = threads_b;
-    hipLaunchKernelGGL(rays_and_draws_kernel, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, as_stream(stream), cam2world, intrinsics, n, res, origins, dirs,
-                       draw_a, numel_a, da, threads_a, draw_b, draw_b ? numel_b : 0, db, draw_b ? threads_b : 0u);
+    if (!draw_b) { numel_b = 0; threads_b = 0; }
+    // a thread of ATen's grid makes ceil(numel / (4 threads)) Philox blocks; no index of the launch reaches `bound`
+    auto part = [](float* out, const TorchRandDraw& d, int64_t numel, uint32_t threads, uint64_t& bound) {
+        DrawPart p{out, d, 0u, threads, 0u};
+        if (!out) return p;
+        p.calls = (uint64_t(numel) + 4 * uint64_t(threads) - 1) / (4 * uint64_t(threads));
+        p.vec = threads % kDrawQuad == 0 && !(reinterpret_cast<uintptr_t>(out) & 15);
+        bound = uint64_t(threads) * 4 * p.calls + kDrawQuad;
+        return p;
+    };
+    uint64_t bound_a = 0, bound_b = 0;
+    const DrawPart pa = part(draw_a, da, numel_a, threads_a, bound_a), pb = part(draw_b, db, numel_b, threads_b, bound_b);
+    const int64_t rays = int64_t(n) * res * res;
+    const uint64_t ray_blocks = uint64_t(rays + 255) / 256;
+    const uint64_t blocks_a = (uint64_t(threads_a) + 256 * kDrawQuad - 1) / (256 * kDrawQuad), blocks_b = (uint64_t(threads_b) + 256 * kDrawQuad - 1) / (256 * kDrawQuad);
+    const uint64_t blocks = ray_blocks + blocks_a + blocks_b;
+    if (blocks > uint64_t(INT32_MAX)) return fail(GNERF_E_ARG, "make_rays_and_draws: too many rays");
+    const dim3 grid((unsigned)blocks), block(256);
+    const uint64_t lim = uint64_t(1) << 31;
+    if (bound_a < lim && bound_b < lim)
+        hipLaunchKernelGGL(rays_and_draws_kernel<uint32_t>, grid, block, 0, as_stream(stream), cam2world, intrinsics, n, res, origins, dirs, unsigned(ray_blocks),
+                           pa, uint32_t(numel_a), unsigned(blocks_a), pb, uint32_t(numel_b));
+    else
+        hipLaunchKernelGGL(rays_and_draws_kernel<int64_t>, grid, block, 0, as_stream(stream), cam2world, intrinsics, n, res, origins, dirs, unsigned(ray_blocks),
+                           pa, numel_a, unsigned(blocks_a), pb, numel_b);
     return check_launch("make_rays_and_draws");
 }
 
