@@ -1,5 +1,5 @@
 // Newton projection of points onto the level set sigma = level (gnerf_project_points_to_level; include/gnerf_hip.h states the rules per
-// point).  Included by render.hip after query_grad.inl, whose tile body this is -- tap records, lookup, bwd_mlp_forward, the sigma-only
+// point).  Included by render_query.hip alone (it holds a kernel).  It is the tile body of query_grad.inl -- tap records, lookup, bwd_mlp_forward, the sigma-only
 // decoder backward on the exact fp32 MFMA, the derivative lookup -- inside a wave-uniform loop over the steps:
 //   every lane keeps the state of point j = lane & 15 of its tile in registers (start, position, status, residuals; the four lanes of a point
 //   hold the same values, computed from the same operands), so the record lanes (lane < 48) read their point's position without a hand-off;
@@ -9,6 +9,10 @@
 //   gradient) and once after the move, so every lds_wave_sync is reached by the whole wave.  A point that has stopped keeps its state: it
 //   rides along with frozen operands.  The pad points of a partial last tile repeat the last point (they stop when it does) and are never stored.
 // Plain stores, no atomics: the same bits on every run, in every tile and batch position.
+#pragma once
+#include "query_grad.inl"
+
+namespace {
 
 struct ProjectArgs {
     const float* points;
@@ -189,3 +193,5 @@ __global__ __launch_bounds__(kBwdThreads, 3) void project_level_kernel(Params P,
         }
     }
 }
+
+}  // namespace

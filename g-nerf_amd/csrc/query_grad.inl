@@ -1,5 +1,5 @@
-// Position gradient of run_model (renderer.py:142-148): dL/dpoints from dL/dsigma and / or dL/drgb.  Included by render.hip after
-// render_bwd.inl, whose decoder staging, MLP forward and MFMA conventions it shares (D layout col = lane & 15, rows = 4 * (lane >> 4) + r).
+// Position gradient of run_model (renderer.py:142-148): dL/dpoints from dL/dsigma and / or dL/drgb.  Included by render_query.hip
+// alone (it holds a kernel); it shares the decoder staging, MLP forward and MFMA conventions of render_bwd_tile.inl (D layout col = lane & 15, rows = 4 * (lane >> 4) + r).
 //
 // Upstream this is autograd through grid_sample's coordinate gradient (zero padding, align_corners=False) and the decoder.  Here a wave
 // takes 16-point tiles through
@@ -13,6 +13,12 @@
 //        dL/dpoint = (2 / box_warp) * (gu_0 + gu_1 + gv_2,  gv_0,  gv_1 + gu_2)            planes read (x,y), (x,z), (z,x).
 // Every point owns its three outputs: plain stores, no atomics, the same bits on every run.
 
+#pragma once
+#include "render_bwd_tile.inl"
+#include "plane_taps_grad.inl"
+
+namespace {
+
 constexpr int kGradRecDwords = 16;      // per (point, plane): 4 byte offsets, 4 blend weights, 4 d/du weights, 4 d/dv weights
 __host__ __device__ inline size_t query_grad_wave_floats() { return 16 * kStagePitch + 16 * kTPitch + 16 * 3 * kGradRecDwords; }
 
@@ -21,35 +27,6 @@ struct QueryGradArgs {
     float* grad_points;
     int n_points, tiles_per_item, n_tiles;
 };
-
-// plane_taps (render_shade.inl) with the derivative of the blend: a tap outside the image is a zero texel, so with the taps
-// (t00 t10 / t01 t11) and fractions (fx, fy)   df/dix = (t10 - t00)(1 - fy) + (t11 - t01) fy,   df/diy = (t01 - t00)(1 - fx) + (t11 - t10) fx
-// and dix/du = W / 2, diy/dv = H / 2 (u, v in [-1, 1], align_corners=False).  floor's derivative is the one-sided one, as grid_sample's.
-__device__ __forceinline__ void plane_taps_grad(int H, int W, float u, float v, unsigned tex_pitch, unsigned row_pitch, unsigned plane_bytes_off,
-                                                uint4& off, v4f& wgt, v4f& du, v4f& dv) {
-    float ix = ((u + 1.f) * float(W) - 1.f) * 0.5f;
-    float iy = ((v + 1.f) * float(H) - 1.f) * 0.5f;
-    ix = clamp_nn(ix, -1.5f, float(W) + 0.5f);           // beyond the clamp every tap is outside: weights and derivatives are all zero
-    iy = clamp_nn(iy, -1.5f, float(H) + 0.5f);
-    const float x0f = floorf(ix), y0f = floorf(iy);
-    const float fx = ix - x0f, fy = iy - y0f;
-    const int x0 = int(x0f), y0 = int(y0f), x1 = x0 + 1, y1 = y0 + 1;
-    auto inside = [](int i, int n) { return unsigned(i) < unsigned(n); };
-    auto clamp0 = [](int i, int last) { return min(max(i, 0), last); };
-    const bool in_x0 = inside(x0, W), in_x1 = inside(x1, W), in_y0 = inside(y0, H), in_y1 = inside(y1, H);
-    const float wx0 = in_x0 ? 1.f - fx : 0.f, wx1 = in_x1 ? fx : 0.f;
-    const float wy0 = in_y0 ? (1.f - fy) * (1.f / 3.f) : 0.f, wy1 = in_y1 ? fy * (1.f / 3.f) : 0.f;
-    const float sx = 0.5f * float(W), sy = 0.5f * float(H) * (1.f / 3.f);
-    const float dx0 = in_x0 ? -sx : 0.f, dx1 = in_x1 ? sx : 0.f;
-    const float dy0 = in_y0 ? -sy : 0.f, dy1 = in_y1 ? sy : 0.f;
-    const unsigned cx0 = __umul24(unsigned(clamp0(x0, W - 1)), tex_pitch), cx1 = __umul24(unsigned(clamp0(x1, W - 1)), tex_pitch);
-    const unsigned cy0 = __umul24(unsigned(clamp0(y0, H - 1)), row_pitch) + plane_bytes_off;
-    const unsigned cy1 = __umul24(unsigned(clamp0(y1, H - 1)), row_pitch) + plane_bytes_off;
-    off = make_uint4(cy0 + cx0, cy0 + cx1, cy1 + cx0, cy1 + cx1);
-    wgt = (v4f){wx0 * wy0, wx1 * wy0, wx0 * wy1, wx1 * wy1};
-    du = (v4f){dx0 * wy0, dx1 * wy0, dx0 * wy1, dx1 * wy1};
-    dv = (v4f){wx0 * dy0, wx1 * dy0, wx0 * dy1, wx1 * dy1};
-}
 
 // sum over the 8 lanes that share a point (lanes 8b .. 8b+7); every lane gets the total
 __device__ __forceinline__ float group8_total(float v) {
@@ -197,3 +174,5 @@ __global__ __launch_bounds__(kBwdThreads, 3) void query_grad_kernel(Params P, Qu
         lds_wave_sync();                                                         // the records and dX are the next tile's to overwrite
     }
 }
+
+}  // namespace

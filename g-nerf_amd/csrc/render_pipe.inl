@@ -1,5 +1,5 @@
 // Pipelined render kernel: 3 SHADER WAVES + 1 SCALAR WAVE per workgroup, three rays in flight.
-// Included by render.hip (inside its anonymous namespace) after render_shade.inl.
+// Included by render_pipe.hip alone: kernel templates, instantiated by its launch functions.
 //
 // A ray alternates between work that uses all three shader waves (tri-plane lookups + MLP) and work only one wave
 // can do (ray march, cdf, inverse-cdf, merge).  With all waves on one ray and a workgroup barrier between such phases,
@@ -20,100 +20,20 @@
 // default), 96+96 (gen_videos.py's doubled counts, the ShapeNet config's 64+64) and 144+144.  Importance sampling is optional
 // (F = 0: the fine pass finds no tiles).  Other shapes use the generic kernel.
 
+#pragma once
+#include "render_pipe_layout.inl"
+#include "pipe_dealing.h"
+
+namespace {
+
 #if defined(GNERF_STAMPS) || defined(GNERF_WG_STAMPS)      // (these builds' `debug` is their stamp buffer)
 #define GNERF_DBG_PTR(x) ((float*)nullptr)
 #else
 #define GNERF_DBG_PTR(x) (x)
 #endif
 
-#ifndef GNERF_PIPE_UNIT
-#define GNERF_PIPE_UNIT 8
-#endif
-constexpr int kPipeUnit = GNERF_PIPE_UNIT;      // rays dealt to a workgroup at a time (see render_kernel_pipe)
-// guided dealing (pipe_dealing.h): each shrinking level covers kPipeGuidedC x (workgroups of the XCD) units; the smallest unit, 1 or 2 rays
-#ifndef GNERF_PIPE_GUIDED_C
-#define GNERF_PIPE_GUIDED_C 1
-#endif
-#ifndef GNERF_PIPE_GUIDED_MIN
-#define GNERF_PIPE_GUIDED_MIN 1
-#endif
-constexpr int kPipeGuidedC = GNERF_PIPE_GUIDED_C, kPipeGuidedMin = GNERF_PIPE_GUIDED_MIN;
-constexpr int kPipeThreads = 256;
-constexpr int kPipeSlots = 4;
-// TP = 16-sample tiles per shader wave and pass: 1 covers up to 48+48 samples (the reference's default), 2 up to 96+96, 3 up to 144+144
-// (gen_videos.py doubles the ShapeNet configuration's 64+64 to 128+128)
-// (gen_videos.py doubles the counts, gen_videos.py:127-128; the ShapeNet config uses 64+64).
-template <int TP> struct PipeDims {
-    static constexpr int kMaxS = 48 * TP;                  // samples per pass
-    static constexpr int kSPad = 2 * kMaxS;                // coarse [0, kMaxS) + fine [kMaxS, 2 kMaxS)
-    static constexpr int kRounds = (kMaxS + 63) / 64;      // lanes x rounds cover the samples of a pass
-    static constexpr int kSlotFloats = 7 * kSPad + 2 * kMaxS + 96 + 16;        // seven per-sample arrays, cdf + fine noise (per pass), partials, ray
-};
-
-struct PipeSlot {
-    float* t_e; float* sig_e; float* v_e; int* rank_e; float* s_t; float* s_sig; float* w_s; float* cdf;
-    float* nf;      // [kMaxS] fine noise of this ray
-    float* part;    // [3][32] colour partial sums of the shader waves
-    float* misc;    // [0..11] the ray per plane: (ou, du, ov, dv) x 3 (ShadeRay, render_shade.inl)  [12] item (int)  [13] ray (int)  [14] w_sum  [15] wt_sum
-};
-constexpr int kMiscItem = 12, kMiscRay = 13, kMiscWsum = 14, kMiscWtsum = 15;
-// lane l < 12 of the scalar wave carries component misc_comp(l) of (origin xyz, direction xyz): plane l / 4, then ou, du, ov, dv
-__device__ __forceinline__ int misc_comp(int l) {
-    const int pl = l >> 2, q = l & 3;
-    const int axis = q < 2 ? (pl == 2 ? 2 : 0) : (pl == 0 ? 1 : (pl == 1 ? 2 : 0));       // u: x, x, z   v: y, z, x
-    return (q & 1) * 3 + axis;
-}
-
-template <int TP>
-__device__ __forceinline__ PipeSlot pipe_slot(float* base, int slot) {
-    typedef PipeDims<TP> D;
-    float* p = base + slot * D::kSlotFloats;
-    PipeSlot s;
-    s.t_e = p; s.sig_e = p + D::kSPad; s.v_e = p + 2 * D::kSPad; s.rank_e = reinterpret_cast<int*>(p + 3 * D::kSPad);
-    s.s_t = p + 4 * D::kSPad; s.s_sig = p + 5 * D::kSPad; s.w_s = p + 6 * D::kSPad; s.cdf = p + 7 * D::kSPad;
-    s.nf = s.cdf + D::kMaxS; s.part = s.nf + D::kMaxS; s.misc = s.part + 96;       // cdf: kMaxS entries (n_w + 1 <= S - 2 used, the rest +inf / histogram)
-    return s;
-}
-
-__host__ __device__ inline size_t pipe_lds_floats(int tp, int mlp) {
-    const size_t slot_floats = tp == 1 ? PipeDims<1>::kSlotFloats : (tp == 2 ? PipeDims<2>::kSlotFloats : PipeDims<3>::kSlotFloats);
-    return size_t(weight_floats(mlp)) + 64 + 36 + size_t(kPipeSlots) * slot_floats + 3 * 16 * kStagePitch       // (tap records live in the staging rows)
-           + kPipeUnit * 8                                                                                         // GEN: the dealing unit's rays
-           + 4;                                                                                                    // on-demand dealing: the run's length
-}
-// Four TP = 1 workgroups share a CU's 160 KiB of LDS (GNERF_PIPE_WAVES_PER_SIMD): growth past that would silently drop to three.
-static_assert(4 * sizeof(float) * (size_t(weight_floats(kMlpF32) > weight_floats(kMlpF16x3) ? weight_floats(kMlpF32) : weight_floats(kMlpF16x3)) + 64 + 36
-                                   + size_t(kPipeSlots) * PipeDims<1>::kSlotFloats + 3 * 16 * kStagePitch + kPipeUnit * 8 + 4) <= 160 * 1024,
-              "a TP = 1 workgroup of the pipelined render kernel must fit a CU's LDS four times");
-
-// position `seq` of the locality-ordered ray sequence -> ray index (or -1 past the end)
-// PADDED: instantiations of the backward only (linear_pad(P) is never set on a forward call: the forward kernels do not carry the branch)
-template <bool PADDED = false>
-__device__ __forceinline__ int pipe_seq_to_ray(const Params& P, int64_t seq) {
-    const gnerf_render_params& p = P.p;
-    if (P.tiles_per_item > 0) {
-        const int tile = int(seq >> 4), rr = int(seq & 15);
-        const int item = tile / P.tiles_per_item, tt = tile % P.tiles_per_item;
-        const int tx = tt / P.tiles_y, ty = tt % P.tiles_y;
-        return item * p.rays_per_item + (ty * 4 + (rr >> 2)) * p.image_width + tx * 4 + (rr & 3);
-    }
-    if constexpr (PADDED) {
-        if (const int pad = linear_pad(P); pad > 0) {         // (the staged backward of ragged calls: items padded to whole 16-ray tiles)
-            const int item = int(unsigned(seq) / unsigned(pad)), local = int(unsigned(seq) - unsigned(item) * unsigned(pad));     // (seq < 2^31: checked by the launcher)
-            return (item < p.n_items && local < p.rays_per_item) ? item * p.rays_per_item + local : -1;
-        }
-    }
-    return seq < P.total_rays ? int(seq) : -1;
-}
-
 #ifndef GNERF_SCALAR_PRIO
 #define GNERF_SCALAR_PRIO 3
-#endif
-#ifndef GNERF_PIPE2_WAVES_PER_SIMD
-#define GNERF_PIPE2_WAVES_PER_SIMD 3
-#endif
-#ifndef GNERF_PIPE_WAVES_PER_SIMD
-#define GNERF_PIPE_WAVES_PER_SIMD 4
 #endif
 // FULL: the call fills the kernel's sample slots exactly (depth_resolution = depth_resolution_importance = 48 TP: the reference's 48+48
 // default, gen_videos.py's doubled 96+96) with plain stratified sampling (no disparity spacing, no per-ray limits) and no stage dump.
@@ -890,7 +810,7 @@ __device__ __forceinline__ void render_pipe_body(const Params& P, float* smem, c
     if (wv == 3 && lane == 0) range.flush(P);
 }
 
-// GNERF_MLP_AUTO: every workgroup evaluates the (cheap, deterministic) range bounds itself -- choose_mlp in render.hip -- and runs
+// GNERF_MLP_AUTO: every workgroup evaluates the (cheap, deterministic) range bounds itself -- choose_mlp in decoder_choice.inl -- and runs
 // the body of the arithmetic they allow: one launch, no select kernel, no second grid that returns at once.
 template <int TP, int MLP, bool FULL, bool GEN = false>
 __global__ __launch_bounds__(kPipeThreads, TP == 1 ? GNERF_PIPE_WAVES_PER_SIMD : (TP == 2 ? GNERF_PIPE2_WAVES_PER_SIMD : 2)) void render_kernel_pipe(Params P) {
@@ -922,35 +842,6 @@ __global__ __launch_bounds__(kPipeThreads, TP == 1 ? GNERF_PIPE_WAVES_PER_SIMD :
     }
 }
 
-// gnerf_render_pack_decoder: one workgroup makes the decoder pack (render_shade.inl has the layout).  The statistics come from
-// decoder_stats, which sums the rows with the routines choose_mlp uses (w1_row_stats, w2_row_stats: render.hip) on two waves; the images
-// are what stage_decoder, the code the render kernels run without a pack, leaves in LDS.
-__global__ __launch_bounds__(kPipeThreads) void pack_decoder_kernel(gnerf_render_params p, float* pack) {
-    constexpr int kLds = kImageFloatsF32 > kImageFloatsF16 ? kImageFloatsF32 : kImageFloatsF16;
-    static_assert(kLds >= kStatFloats + 64 * 33 + 33 * 65, "decoder_stats' rows fit the image area");
-    __shared__ __align__(16) float smem[kLds];
-    const int tid = threadIdx.x;
-    decoder_stats(p, smem);
-    __syncthreads();
-    if (tid < kStatFloats) {
-        const int* words = reinterpret_cast<const int*>(smem);
-        reinterpret_cast<int*>(pack)[tid] = tid < kStatBad ? words[tid] : (tid == kStatBad ? ((words[kStatBad] | words[kStatBad2]) != 0 ? 1 : 0) : 0);
-    }
-    ShadeLds L;
-    __syncthreads();
-    for (int i = tid; i < kLds; i += kPipeThreads) smem[i] = 0.f;
-    __syncthreads();
-    stage_decoder<kMlpF16x3>(L, smem, p, tid, kPipeThreads);
-    __syncthreads();
-    for (int i = tid; i < kImageFloatsF16; i += kPipeThreads) pack[kPackImageF16 + i] = smem[i];
-    __syncthreads();
-    for (int i = tid; i < kLds; i += kPipeThreads) smem[i] = 0.f;
-    __syncthreads();
-    stage_decoder<kMlpF32>(L, smem, p, tid, kPipeThreads);
-    __syncthreads();
-    for (int i = tid; i < kImageFloatsF32; i += kPipeThreads) pack[kPackImageF32 + i] = smem[i];
-}
-
 // First pass of the staged backward: the forward pipeline in its BWD form (see render_pipe_body).  General sample counts (FULL = false:
 // any S, F the pipelined kernels cover, disparity sampling, per-ray limits), decoder arithmetic chosen on the device as in the forward.
 template <int TP>
@@ -962,3 +853,5 @@ __global__ __launch_bounds__(kPipeThreads, TP == 1 ? GNERF_PIPE_WAVES_PER_SIMD :
     if (mlp == kMlpF32) render_pipe_body<TP, kMlpF32, false, false, true>(P, smem, &Gr, stage);
     else                render_pipe_body<TP, kMlpF16x3, false, false, true>(P, smem, &Gr, stage, sp_direct);
 }
+
+}  // namespace

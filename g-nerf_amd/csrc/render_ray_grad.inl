@@ -1,5 +1,5 @@
 // Ray gradient of the fused renderer: dL/d(ray origins) and dL/d(ray directions) from the staged backward's per-ray blocks.  Included by
-// render.hip after query_grad.inl, whose derivative taps (plane_taps_grad) it shares.
+// render_backward.hip alone (it holds a kernel); the derivative taps (plane_taps_grad.inl) are shared with the point queries.
 //
 // With numeric ray limits the coarse depths do not depend on the rays, the importance depths are constants (renderer.py:198-211) and the
 // decoder ignores directions, so the rays reach the outputs only through the sample positions p_k = o + t_k d:
@@ -16,6 +16,11 @@
 //     slot past n_all adds zeros;
 //   * one butterfly over the 64 lanes per ray at the end, six plain stores.
 // No atomics, no LDS, and an order of additions fixed by n_all alone: the same bits on every run.
+#pragma once
+#include "render_bwd_tile.inl"
+#include "plane_taps_grad.inl"
+
+namespace {
 
 struct RayGradArgs {
     const float* planes; const float* origins; const float* dirs;
@@ -87,3 +92,5 @@ __global__ __launch_bounds__(kRayGradThreads) void render_ray_grad_kernel(RayGra
         }
     }
 }
+
+}  // namespace

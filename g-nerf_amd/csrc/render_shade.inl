@@ -1,5 +1,5 @@
 // The 16-sample shade tile of the pipelined forward kernel (render_pipe.inl), with the decoder staging and plane taps it shares with
-// the backward (render_bwd.inl).  Included by render.hip (inside its anonymous namespace).
+// the backward (render_bwd.inl) and the point queries.  No kernel is defined here: any unit may include it.
 //
 // The one-wave-per-ray kernel (render_kernel_generic) is limited by what one wave must keep: ~100 VGPRs of
 // decoder weights plus 12 KiB of LDS for the colours of the 96 samples of its ray, which caps a CU at 8 waves,
@@ -11,6 +11,11 @@
 //   * bilinear tap addresses and weights are computed ONCE per (sample, plane) -- 48 lanes of a wave do the
 //     3 planes of 16 samples -- and handed to the 8 lanes that read a texel through a 96-byte LDS record;
 //   * plane texels are addressed as SGPR base + 32-bit VGPR offset (no 64-bit address arithmetic).
+#pragma once
+#include "decoder_choice.inl"
+
+namespace {
+
 
 constexpr int kW1Pitch = 36;        // floats per LDS row of W1 [64 x 32]
 constexpr int kW2Pitch = 68;        // floats per LDS row of W2 [33 x 64]
@@ -32,14 +37,14 @@ static_assert(kFwdTapStride >= 24 && kFwdTapStride <= kStagePitch && kFwdTapStri
 __device__ __forceinline__ int stage_swz(int row) { return (row >> 1) & 5; }
 
 // Decoder weights in LDS.  Two formats, BOTH shipped (template parameter MLP of the kernels; chosen per call, see
-// choose_mlp in render.hip):
+// choose_mlp in decoder_choice.inl):
 //  * kMlpF16x3: every fp32 weight w is stored as two halves (hi = f16(w), lo = f16(w - hi)) in MFMA fragment
 //    order, and each product of the MLP is evaluated as hi*hi + hi*lo + lo*hi on v_mfma_f32_16x16x32_f16 with fp32
 //    accumulation (the dropped lo*lo term and the split's own rounding are ~2^-21 relative, i.e. fp32-grade: the
 //    renderer's pixel MSE against the reference stays ~1e-13).  24 matrix instructions x 16 cycles per 16-sample tile
 //    instead of 64 x 32 cycles of v_mfma_f32_16x16x4_f32.  Only valid while features, weights and hidden activations
 //    stay inside f16's range and the absolute error of the low halves (2^-25 per operand) stays negligible after the
-//    decoder's own amplification -- which is what choose_mlp (render.hip) decides on the device, per call.
+//    decoder's own amplification -- which is what choose_mlp (decoder_choice.inl) decides on the device, per call.
 //  * kMlpF32: plain fp32 rows (exact fp32 products on the fp32-input MFMA): any finite input.
 constexpr int kMlpAuto = 0, kMlpF16x3 = 1, kMlpF32 = 2;          // = GNERF_MLP_AUTO / GNERF_MLP_F16X3 / GNERF_MLP_F32
 typedef _Float16 h8 __attribute__((ext_vector_type(8)));
@@ -202,7 +207,7 @@ __device__ __forceinline__ void decoder_lds(ShadeLds& L, float* base) {
 }
 
 // The decoder pack (gnerf_render_pack_decoder): what the head of a pipelined workgroup computes from the decoder alone, made once per
-// decoder by one small kernel.  Floats: [0, kStatFloats) the range statistics (choose_mlp, render.hip); then the two LDS IMAGES, byte for
+// decoder by one small kernel.  Floats: [0, kStatFloats) the range statistics (choose_mlp, decoder_choice.inl); then the two LDS IMAGES, byte for
 // byte what stage_decoder<kMlpF16x3> and stage_decoder<kMlpF32> leave in the weight area (bytes they do not write are zero).  An image is
 // a whole number of 16-byte chunks at a 16-byte offset: a workgroup copies it with thread t taking chunks t, t + 256, ... -- consecutive
 // lanes, consecutive chunks, on both sides (global_load_dwordx4, conflict-free ds_write_b128) -- all loads in flight before the first store.
@@ -637,3 +642,5 @@ __device__ __forceinline__ void shade_tile(const Params& P, const ShadeLds& L, c
 #endif
     GNERF_STAMP(st, 4);         // activations + layer 2
 }
+
+}  // namespace

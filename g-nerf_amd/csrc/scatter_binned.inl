@@ -1,4 +1,4 @@
-// Plane-gradient scatter WITHOUT global float atomics (round 5).  Included by render.hip after render_bwd.inl.
+// Plane-gradient scatter WITHOUT global float atomics (round 5).  Included by render_backward.hip alone (it holds kernels).
 //
 // The reference's plane gradient is F.grid_sample's backward (renderer.py:55-65 through autograd; grid_sample_gradfix.py:57-77 is the
 // same operator): one float atomic per tap and channel.  plane_scatter_kernel (render_bwd.inl) cut the atomics 3.8x by merging a ray
@@ -28,6 +28,10 @@
 // Why integers and not ds_add_f32: tools/probes/lds_atomic_probe.hip (profiles/r05_lds_atomic_probe.json) -- a wave64 ds_add_f32
 // takes 192 CU cycles whatever its addresses (three per lane: the float LDS atomic is serialised), ds_add_u64 takes 6, ds_add_u32 4.
 // Not covered (the caller falls back to plane_scatter_kernel): staging buffers of 2^32 floats or more, ray tiles that straddle items.
+#pragma once
+#include "render_core.inl"
+
+namespace {
 
 #ifndef GNERF_BIN_TILE
 #define GNERF_BIN_TILE 16
@@ -564,3 +568,5 @@ static int launch_binned_scatter(const Params& P, float* stage, char* ws, float*
     hipLaunchKernelGGL(bin_halo_kernel, dim3(A.n_ptiles), dim3(1024), 0, s, P, A);
     return gnerf::check_launch("binned plane scatter");
 }
+
+}  // namespace

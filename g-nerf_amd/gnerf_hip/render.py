@@ -1,4 +1,4 @@
-"""The fused volume renderer and the point queries (csrc/render.hip and the .inl files it includes): the one builder of gnerf_render_params and the calls."""
+"""The fused volume renderer and the point queries (csrc/render.hip, render_pipe.hip, render_backward.hip, render_query.hip and the .inl files they include): the one builder of gnerf_render_params and the calls."""
 
 import ctypes
 import os

@@ -1,5 +1,5 @@
 """What gnerf_render_pack_decoder writes at the head of a decoder pack, restated in numpy float32 in the kernel's summation order
-(csrc/render.hip: decoder_stats).  Shared by tests/test_render_decoder_pack_cpu.py and tests/test_render_decoder_pack_gpu.py."""
+(csrc/decoder_choice.inl: decoder_stats).  Shared by tests/test_render_decoder_pack_cpu.py and tests/test_render_decoder_pack_gpu.py."""
 
 import numpy as np
 
@@ -30,7 +30,7 @@ def _fma32(a, b, c):
 
 def row_statistics(w, scale):
     """Per row of w, one lane each, columns in order, every operation one float32 rounding as the kernel pins them (w1_row_stats /
-    w2_row_stats, csrc/render.hip): |w| s a multiply of its own, its sum plain adds, the sum of squares fused multiply-adds, the maximum."""
+    w2_row_stats, csrc/decoder_choice.inl): |w| s a multiply of its own, its sum plain adds, the sum of squares fused multiply-adds, the maximum."""
     w = np.abs(np.asarray(w, np.float32)) * np.float32(scale)
     l1, sq, mx = (np.zeros(w.shape[0], np.float32) for _ in range(3))
     for c in range(w.shape[1]):
@@ -56,7 +56,7 @@ RANGE_LIMIT, ERR_LIMIT, SOFTPLUS_DIRECT_LIMIT = 30000.0, 2.0 ** -12, 100.0
 
 
 def decision(w1, b1, w2, b2, absmax):
-    """choose_mlp's inequalities (csrc/render.hip) in float64 on the restated statistics: (arithmetic 'f16x3' | 'f32', short softplus,
+    """choose_mlp's inequalities (csrc/decoder_choice.inl) in float64 on the restated statistics: (arithmetic 'f16x3' | 'f32', short softplus,
     e_o, h_hard).  A test that expects a choice keeps e_o and h_hard a few per cent away from their limits: the kernel evaluates the
     same expressions in float32."""
     s, bad = statistics(w1, b1, w2, b2)

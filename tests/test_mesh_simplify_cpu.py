@@ -319,8 +319,9 @@ def test_mesh_simplify_declarations():
         assert callable(getattr(gnerf_hip, name))
     for name in ('mesh_simplify', 'mesh_simplify_count'):
         assert re.search(r'm\.def\("%s"' % name, binding)
-    src = open(os.path.join(ROOT, 'g-nerf_amd', 'csrc', 'build.sh')).read()
-    assert re.search(r'for src in [^;]*\bmesh_simplify\b', src)
+    csrc = os.path.join(ROOT, 'g-nerf_amd', 'csrc')             # build.sh builds the units that compile_unit.sh lists
+    assert re.search(r'^for src in \$UNITS;', open(os.path.join(csrc, 'build.sh')).read(), flags=re.M)
+    assert re.search(r'^UNITS="[^"]*\bmesh_simplify\b', open(os.path.join(csrc, 'compile_unit.sh')).read(), flags=re.M)
 
 
 def test_c_entry_points_refuse_bad_arguments_without_a_gpu():

@@ -1,5 +1,5 @@
-"""GPU tests of the three point-query kernels past one 16-point tile per wave: gnerf_query_points (csrc/render.hip, query_kernel),
-gnerf_query_points_backward (csrc/render_bwd.inl, query_bwd_kernel) and gnerf_query_points_grad (csrc/query_grad.inl, query_grad_kernel)
+"""GPU tests of the three point-query kernels past one 16-point tile per wave: gnerf_query_points (csrc/render_query.hip, query_kernel),
+gnerf_query_points_backward (csrc/query_bwd.inl, query_bwd_kernel) and gnerf_query_points_grad (csrc/query_grad.inl, query_grad_kernel)
 against the float64 oracle (oracle/render_ref.py:query_points, autograd for the gradients) on one scene in which every kernel takes at least
 two trips of its grid-stride loop, a wave's loop crosses from one item into the next, and the tile whose plane scatter is deferred into
 another item's gather is a partial one.  The backward is probed one tile at a time: its outputs are linear in the incoming gradients, so
@@ -69,8 +69,8 @@ def kernel_strides():
     csrc = os.path.join(PKG, 'csrc')
     read = lambda name: open(os.path.join(csrc, name)).read()
     num_cu = int(re.search(r'constexpr int kNumCU = (\d+);', read('common.h')).group(1))
-    waves = int(re.search(r'constexpr int kBwdWaves = (\d+);', read('render_bwd.inl')).group(1))
-    text = read('render.hip')
+    waves = int(re.search(r'constexpr int kBwdWaves = (\d+);', read('render_bwd_tile.inl')).group(1))
+    text = read('render_query.hip')
 
     def body(name):
         start = text.index(f'extern "C" int gnerf_{name}(')

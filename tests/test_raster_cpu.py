@@ -379,8 +379,9 @@ def test_raster_declarations():
     for name in ('rasterize', 'resolve', 'raster_available', 'raster_workspace_bytes'):
         assert callable(getattr(gnerf_hip, name))
     assert re.search(r'm\.def\("raster_visibility"', binding) and re.search(r'm\.def\("raster_resolve"', binding)
-    src = open(os.path.join(ROOT, 'g-nerf_amd', 'csrc', 'build.sh')).read()
-    assert re.search(r'for src in [^;]*\braster\b', src)
+    csrc = os.path.join(ROOT, 'g-nerf_amd', 'csrc')             # build.sh builds the units that compile_unit.sh lists
+    assert re.search(r'^for src in \$UNITS;', open(os.path.join(csrc, 'build.sh')).read(), flags=re.M)
+    assert re.search(r'^UNITS="[^"]*\braster\b', open(os.path.join(csrc, 'compile_unit.sh')).read(), flags=re.M)
 
 
 def test_c_entry_points_refuse_without_a_gpu():

@@ -110,8 +110,9 @@ def test_resize_declarations():
     assert gnerf_hip.resize_aa_available()
     for name in ('resize_aa_forward', 'resize_aa_backward', 'resize_aa_supported'):
         assert callable(getattr(gnerf_hip, name))
-    src = open(os.path.join(ROOT, 'g-nerf_amd', 'csrc', 'build.sh')).read()
-    assert re.search(r'for src in [^;]*\bresize\b', src)
+    csrc = os.path.join(ROOT, 'g-nerf_amd', 'csrc')             # build.sh builds the units that compile_unit.sh lists
+    assert re.search(r'^for src in \$UNITS;', open(os.path.join(csrc, 'build.sh')).read(), flags=re.M)
+    assert re.search(r'^UNITS="[^"]*\bresize\b', open(os.path.join(csrc, 'compile_unit.sh')).read(), flags=re.M)
 
 
 def test_c_entry_points_refuse_without_a_gpu():

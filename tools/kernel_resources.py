@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Per-kernel register / spill / LDS / scratch figures of a gfx950 object or library, from its AMDGPU metadata note
-(llvm-readelf --notes).  usage: tools/kernel_resources.py g-nerf_amd/csrc/render.o [name-substring]"""
+(llvm-readelf --notes).  usage: tools/kernel_resources.py g-nerf_amd/csrc/render_pipe.o [name-substring]"""
 import os, re, subprocess, sys, tempfile
 obj = sys.argv[1]
 flt = sys.argv[2] if len(sys.argv) > 2 else ''

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Every route of the render launchers (csrc/render.hip, host half) on the smallest call that reaches it: one process walks the table
+"""Every route of the render launchers (csrc/render.hip and csrc/render_backward.hip, host halves) on the smallest call that reaches it: one process walks the table
 below and prints one JSON line per case -- name, return code (and the library's error text when the call is refused), a hash of every
 output tensor.  Run it under `rocprofv3 --kernel-trace -f csv -d DIR -- python3 tools/render_routes.py` and reduce the trace with
 `tools/render_routes.py --reduce DIR`: the dispatch-ordered list of (kernel, grid, workgroup, LDS bytes) of the library's kernels.
