@@ -1,5 +1,6 @@
-// The derivative taps of a plane lookup, shared by the position gradient of the point queries (query_grad.inl, project_level.inl) and the
-// ray gradient (render_ray_grad.inl).  No kernel is defined here.
+// The derivative side of a plane lookup: the taps with their derivative weights (plane_taps_grad: the point queries' tile stages in
+// query_grad.inl, and the ray gradient, render_ray_grad.inl) and one plane's share of dL/dposition (plane_position_grad: the zero-padding
+// rule lives in the former, the plane routing in the latter; the tile stages call it, the ray kernel holds a timed copy).  No kernel is defined here.
 #pragma once
 #include "render_core.inl"
 
@@ -32,6 +33,23 @@ __device__ __forceinline__ void plane_taps_grad(int H, int W, float u, float v, 
     wgt = (v4f){wx0 * wy0, wx1 * wy0, wx0 * wy1, wx1 * wy1};
     du = (v4f){dx0 * wy0, dx1 * wy0, dx0 * wy1, dx1 * wy1};
     dv = (v4f){wx0 * dy0, wx1 * dy0, wx0 * dy1, wx1 * dy1};
+}
+
+// One plane's share of dL/dposition over this lane's four channels (cq16 = the lane's byte offset inside a texel, dxv = its four channels
+// of dL/d(mean feature)): the four texels against the derivative weights, summed pairwise, and routed by what plane pl reads --
+// (x,y), (x,z), (z,x).  The callers sum the result over the 8 lanes of a texel.
+__device__ __forceinline__ void plane_position_grad(const char* planes, int pl, const uint4& off, const v4f& du, const v4f& dv, const v4f& dxv, int cq16,
+                                                    float& gx, float& gy, float& gz) {
+    const v4f t00 = *reinterpret_cast<const v4f*>(planes + off.x + cq16);
+    const v4f t10 = *reinterpret_cast<const v4f*>(planes + off.y + cq16);
+    const v4f t01 = *reinterpret_cast<const v4f*>(planes + off.z + cq16);
+    const v4f t11 = *reinterpret_cast<const v4f*>(planes + off.w + cq16);
+    const v4f fu = (t00 * du[0] + t10 * du[1] + t01 * du[2] + t11 * du[3]) * dxv;
+    const v4f fv = (t00 * dv[0] + t10 * dv[1] + t01 * dv[2] + t11 * dv[3]) * dxv;
+    const float su = (fu[0] + fu[1]) + (fu[2] + fu[3]), sv = (fv[0] + fv[1]) + (fv[2] + fv[3]);
+    if (pl == 0) { gx += su; gy += sv; }
+    else if (pl == 1) { gx += su; gz += sv; }
+    else { gz += su; gx += sv; }
 }
 
 }  // namespace

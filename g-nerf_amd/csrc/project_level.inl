@@ -1,6 +1,7 @@
 // Newton projection of points onto the level set sigma = level (gnerf_project_points_to_level; include/gnerf_hip.h states the rules per
-// point).  Included by render_query.hip alone (it holds a kernel).  It is the tile body of query_grad.inl -- tap records, lookup, bwd_mlp_forward, the sigma-only
-// decoder backward on the exact fp32 MFMA, the derivative lookup -- inside a wave-uniform loop over the steps:
+// point).  Included by render_query.hip alone (it holds a kernel).  It calls the tile stages of query_grad.inl -- grad_tap_records, grad_lookup,
+// bwd_mlp_forward, grad_dx_from_dh (the sigma-only decoder backward on the exact fp32 MFMA), grad_point_gradient -- inside a wave-uniform loop
+// over the steps, and owns what is not a stage: the affine, the seed dL/dsigma = 1, the Newton state, the ballots and every lds_wave_sync:
 //   every lane keeps the state of point j = lane & 15 of its tile in registers (start, position, status, residuals; the four lanes of a point
 //   hold the same values, computed from the same operands), so the record lanes (lane < 48) read their point's position without a hand-off;
 //   sigma comes out of bwd_mlp_forward in every lane of its point; the gradient comes out of the derivative lookup in the 8-lane group of point
@@ -31,23 +32,13 @@ __global__ __launch_bounds__(kBwdThreads, 3) void project_level_kernel(Params P,
     extern __shared__ __align__(16) float smem[];
     const gnerf_render_params& p = P.p;
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    float* w1 = smem;
-    float* w2 = w1 + 64 * kW1Pitch;
-    float* b1 = w2 + 33 * kW2Pitch;
-    float* b2 = b1 + 64;
-    for (int i = tid; i < 64 * 32; i += kBwdThreads) w1[(i >> 5) * kW1Pitch + (i & 31)] = p.w1[i];
-    for (int i = tid; i < 33 * 64; i += kBwdThreads) w2[(i >> 6) * kW2Pitch + (i & 63)] = p.w2[i];
-    if (tid < 64) b1[tid] = p.b1[tid];
-    if (tid < 36) b2[tid] = tid < 33 ? p.b2[tid] : 0.f;
-    __syncthreads();
     BwdLds L = {};
-    L.w1 = w1; L.w2 = w2; L.b1 = b1; L.b2 = b2;
+    bwd_stage_decoder_f32<kBwdThreads>(L, smem, p, tid);
     L.stage = smem + kBwdWeightFloats + size_t(wv) * query_grad_wave_floats();
     L.tbuf = L.stage + 16 * kStagePitch;
     float* recs = L.tbuf + 16 * kTPitch;
-    const int j = lane & 15, g = lane >> 4, b = lane >> 3, cq = lane & 7, cq16 = cq * 16;
-    const int H = p.plane_h, W = p.plane_w;
-    const int64_t plane_floats = int64_t(3) * H * W * 32;
+    const int j = lane & 15, g = lane >> 4, b = lane >> 3, cq = lane & 7;
+    const int64_t plane_floats = int64_t(3) * p.plane_h * p.plane_w * 32;
     const float* A = Q.a;
     for (int tile = blockIdx.x * kBwdWaves + wv; tile < Q.n_tiles; tile += gridDim.x * kBwdWaves) {
         const int item = tile / Q.tiles_per_item, t = tile % Q.tiles_per_item;
@@ -68,38 +59,10 @@ __global__ __launch_bounds__(kBwdThreads, 3) void project_level_kernel(Params P,
             }
             const bool finite_pos = isfinite(wx) && isfinite(wy) && isfinite(wz);
             // ---- 1. tap records
-            if (lane < 48) {
-                const int pl = lane >> 4;
-                const float qx = wx * P.box_scale, qy = wy * P.box_scale, qz = wz * P.box_scale;
-                const float u = pl == 2 ? qz : qx;
-                const float v = pl == 0 ? qy : (pl == 1 ? qz : qx);
-                uint4 off; v4f wgt, du, dv;
-                plane_taps_grad(H, W, u, v, P.tex_pitch, P.row_pitch, unsigned(pl) * P.plane_pitch, off, wgt, du, dv);
-                float* rec = recs + (j * 3 + pl) * kGradRecDwords;
-                *reinterpret_cast<uint4*>(rec) = off;
-                *reinterpret_cast<v4f*>(rec + 4) = wgt;
-                *reinterpret_cast<v4f*>(rec + 8) = du;
-                *reinterpret_cast<v4f*>(rec + 12) = dv;
-            }
+            grad_tap_records(P, recs, lane, wx * P.box_scale, wy * P.box_scale, wz * P.box_scale);
             lds_wave_sync();
             // ---- 2. lookup and decoder forward
-#pragma unroll
-            for (int a = 0; a < 2; a++) {
-                const int js = 8 * a + b;
-                v4f acc = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-                for (int pl = 0; pl < 3; pl++) {
-                    const float* rec = recs + (js * 3 + pl) * kGradRecDwords;
-                    const uint4 off = *reinterpret_cast<const uint4*>(rec);
-                    const v4f wgt = *reinterpret_cast<const v4f*>(rec + 4);
-                    const v4f t00 = *reinterpret_cast<const v4f*>(planes + off.x + cq16);
-                    const v4f t10 = *reinterpret_cast<const v4f*>(planes + off.y + cq16);
-                    const v4f t01 = *reinterpret_cast<const v4f*>(planes + off.z + cq16);
-                    const v4f t11 = *reinterpret_cast<const v4f*>(planes + off.w + cq16);
-                    acc += t00 * wgt[0] + t10 * wgt[1] + t01 * wgt[2] + t11 * wgt[3];
-                }
-                *reinterpret_cast<v4f*>(L.stage + js * kStagePitch + 4 * cq) = acc;
-            }
+            grad_lookup(L, recs, planes, b, cq);
             lds_wave_sync();
             v4f h[4], o[2];
             float sig;
@@ -118,17 +81,7 @@ __global__ __launch_bounds__(kBwdThreads, 3) void project_level_kernel(Params P,
 #pragma unroll
             for (int m = 0; m < 4; m++) dh[m] = *reinterpret_cast<const v4f*>(L.w2 + 16 * m + 4 * g);
             v4f dx[2];
-            dx[0] = dx[1] = (v4f){0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int m = 0; m < 4; m++) {
-#pragma unroll
-                for (int r = 0; r < 4; r++) {
-                    const float dpre = dh[m][r] * (1.f - exp_hw(-h[m][r]));
-                    const float* row = L.w1 + (16 * m + 4 * g + r) * kW1Pitch + j;
-                    dx[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(row[0], dpre, dx[0], 0, 0, 0);
-                    dx[1] = __builtin_amdgcn_mfma_f32_16x16x4f32(row[16], dpre, dx[1], 0, 0, 0);
-                }
-            }
+            grad_dx_from_dh(L, h, dh, j, g, dx);
             *reinterpret_cast<v4f*>(L.tbuf + j * kTPitch + 4 * g) = dx[0];           // dX[point][channel]
             *reinterpret_cast<v4f*>(L.tbuf + j * kTPitch + 16 + 4 * g) = dx[1];
             lds_wave_sync();
@@ -136,26 +89,8 @@ __global__ __launch_bounds__(kBwdThreads, 3) void project_level_kernel(Params P,
 #pragma unroll
             for (int a = 0; a < 2; a++) {
                 const int js = 8 * a + b;
-                const v4f dxv = *reinterpret_cast<const v4f*>(L.tbuf + js * kTPitch + 4 * cq);
-                float gx = 0.f, gy = 0.f, gz = 0.f;
-#pragma unroll
-                for (int pl = 0; pl < 3; pl++) {
-                    const float* rec = recs + (js * 3 + pl) * kGradRecDwords;
-                    const uint4 off = *reinterpret_cast<const uint4*>(rec);
-                    const v4f du = *reinterpret_cast<const v4f*>(rec + 8);
-                    const v4f dv = *reinterpret_cast<const v4f*>(rec + 12);
-                    const v4f t00 = *reinterpret_cast<const v4f*>(planes + off.x + cq16);
-                    const v4f t10 = *reinterpret_cast<const v4f*>(planes + off.y + cq16);
-                    const v4f t01 = *reinterpret_cast<const v4f*>(planes + off.z + cq16);
-                    const v4f t11 = *reinterpret_cast<const v4f*>(planes + off.w + cq16);
-                    const v4f fu = (t00 * du[0] + t10 * du[1] + t01 * du[2] + t11 * du[3]) * dxv;
-                    const v4f fv = (t00 * dv[0] + t10 * dv[1] + t01 * dv[2] + t11 * dv[3]) * dxv;
-                    const float su = (fu[0] + fu[1]) + (fu[2] + fu[3]), sv = (fv[0] + fv[1]) + (fv[2] + fv[3]);
-                    if (pl == 0) { gx += su; gy += sv; }
-                    else if (pl == 1) { gx += su; gz += sv; }
-                    else { gz += su; gx += sv; }
-                }
-                gx = group8_total(gx); gy = group8_total(gy); gz = group8_total(gz);
+                float gx, gy, gz;
+                grad_point_gradient(L, recs, planes, js, cq, gx, gy, gz);
                 if (cq < 3) L.stage[js * 4 + cq] = (cq == 0 ? gx : (cq == 1 ? gy : gz)) * P.box_scale;
             }
             lds_wave_sync();                               // also: the records and dX are the next step's to overwrite

@@ -26,6 +26,7 @@ __global__ __launch_bounds__(kBwdThreads, 2) void query_bwd_kernel(Params P, Que
     extern __shared__ __align__(16) float smem[];
     const gnerf_render_params& p = P.p;
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    // ---- decoder into LDS: bwd_stage_decoder_f32 (render_bwd_tile.inl), kept as a copy -- through the helper this kernel's instructions change
     float* w1 = smem;
     float* w2 = w1 + 64 * kW1Pitch;
     float* b1 = w2 + 33 * kW2Pitch;
@@ -62,9 +63,7 @@ __global__ __launch_bounds__(kBwdThreads, 2) void query_bwd_kernel(Params P, Que
             for (int r = 0; r < 4; r++) {
                 const int q = 4 * g + r;
                 const float gc = (Q.grad_rgb && 16 * t + q < Q.n_points) ? Q.grad_rgb[(pt0 + q) * 32 + 16 * n + j] : 0.f;
-                const float e = __builtin_amdgcn_exp2f(o[n][r] * -1.44269504088896341f);
-                const float s = __builtin_amdgcn_rcpf(1.0f + e);
-                const float d = gc * (1.002f * s * (1.f - s));                  // rgb = 1.002 sigmoid(o) - 0.001 (triplane.py:134)
+                const float d = gc * rgb_slope_hw(o[n][r]);
                 L.tbuf[q * kTPitch + 16 * n + j] = d;
                 A.b2[n] += d;
             }

@@ -12,6 +12,11 @@
 //      dots reduced inside the 8-lane group, and
 //        dL/dpoint = (2 / box_warp) * (gu_0 + gu_1 + gv_2,  gv_0,  gv_1 + gu_2)            planes read (x,y), (x,z), (z,x).
 // Every point owns its three outputs: plain stores, no atomics, the same bits on every run.
+//
+// The four stages are functions of this file (grad_tap_records, grad_lookup, grad_dx_from_dh, grad_point_gradient), the one copy that
+// project_level.inl's Newton loop runs too; the decoder staging, the colour slope and the colour half of dH are render_bwd_tile.inl's, the
+// taps and the plane routing plane_taps_grad.inl's.  A kernel owns its tile loop, where the positions come from, what seeds dH, where the
+// three components go, and every lds_wave_sync.
 
 #pragma once
 #include "render_bwd_tile.inl"
@@ -36,73 +41,106 @@ __device__ __forceinline__ float group8_total(float v) {
     return v;
 }
 
+// ---- The four stages of a 16-point tile, shared by query_grad_kernel and project_level_kernel (project_level.inl).  No helper holds an
+// lds_wave_sync: the kernels place them, between the stages.
+
+// 1. the tap records of the tile (lanes 0..47: point j = lane & 15, plane = lane >> 4); (qx, qy, qz) = point j in the planes' [-1, 1] frame
+__device__ __forceinline__ void grad_tap_records(const Params& P, float* recs, int lane, float qx, float qy, float qz) {
+    if (lane < 48) {
+        const int j = lane & 15, pl = lane >> 4;
+        const float u = pl == 2 ? qz : qx;
+        const float v = pl == 0 ? qy : (pl == 1 ? qz : qx);
+        uint4 off; v4f wgt, du, dv;
+        plane_taps_grad(P.p.plane_h, P.p.plane_w, u, v, P.tex_pitch, P.row_pitch, unsigned(pl) * P.plane_pitch, off, wgt, du, dv);
+        float* rec = recs + (j * 3 + pl) * kGradRecDwords;
+        *reinterpret_cast<uint4*>(rec) = off;
+        *reinterpret_cast<v4f*>(rec + 4) = wgt;
+        *reinterpret_cast<v4f*>(rec + 8) = du;
+        *reinterpret_cast<v4f*>(rec + 12) = dv;
+    }
+}
+
+// 2. lookup: 8 points per step (point 8a + b, b = lane >> 3), 8 lanes x 16 bytes per texel (cq = lane & 7); mean features staged as X[point][channel]
+__device__ __forceinline__ void grad_lookup(const BwdLds& L, const float* recs, const char* planes, int b, int cq) {
+#pragma unroll
+    for (int a = 0; a < 2; a++) {
+        const int js = 8 * a + b;
+        v4f acc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int pl = 0; pl < 3; pl++) {
+            const float* rec = recs + (js * 3 + pl) * kGradRecDwords;
+            const uint4 off = *reinterpret_cast<const uint4*>(rec);
+            const v4f wgt = *reinterpret_cast<const v4f*>(rec + 4);
+            const v4f t00 = *reinterpret_cast<const v4f*>(planes + off.x + cq * 16);
+            const v4f t10 = *reinterpret_cast<const v4f*>(planes + off.y + cq * 16);
+            const v4f t01 = *reinterpret_cast<const v4f*>(planes + off.z + cq * 16);
+            const v4f t11 = *reinterpret_cast<const v4f*>(planes + off.w + cq * 16);
+            acc += t00 * wgt[0] + t10 * wgt[1] + t01 * wgt[2] + t11 * wgt[3];
+        }
+        *reinterpret_cast<v4f*>(L.stage + js * kStagePitch + 4 * cq) = acc;
+    }
+}
+
+// 3, second half. dH^T -> through softplus -> dX^T (bwd_tile_core without the weight gradients); h = the hidden activations of bwd_mlp_forward
+__device__ __forceinline__ void grad_dx_from_dh(const BwdLds& L, const v4f (&h)[4], const v4f (&dh)[4], int j, int g, v4f (&dx)[2]) {
+    dx[0] = dx[1] = (v4f){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int m = 0; m < 4; m++) {
+#pragma unroll
+        for (int r = 0; r < 4; r++) {
+            const float dpre = dh[m][r] * (1.f - exp_hw(-h[m][r]));          // d/dpre softplus(pre) = 1 - exp(-softplus(pre))
+            const float* row = L.w1 + (16 * m + 4 * g + r) * kW1Pitch + j;
+            dx[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(row[0], dpre, dx[0], 0, 0, 0);
+            dx[1] = __builtin_amdgcn_mfma_f32_16x16x4f32(row[16], dpre, dx[1], 0, 0, 0);
+        }
+    }
+}
+
+// 4. the texels of point js against the derivative weights and dX[point][channel] (in L.tbuf): the 32-channel dots reduced inside the
+// point's 8-lane group, every lane of which gets dL/d(position in the [-1, 1] frame)
+__device__ __forceinline__ void grad_point_gradient(const BwdLds& L, const float* recs, const char* planes, int js, int cq, float& gx, float& gy, float& gz) {
+    const v4f dxv = *reinterpret_cast<const v4f*>(L.tbuf + js * kTPitch + 4 * cq);
+    gx = gy = gz = 0.f;
+#pragma unroll
+    for (int pl = 0; pl < 3; pl++) {
+        const float* rec = recs + (js * 3 + pl) * kGradRecDwords;
+        const uint4 off = *reinterpret_cast<const uint4*>(rec);
+        const v4f du = *reinterpret_cast<const v4f*>(rec + 8);
+        const v4f dv = *reinterpret_cast<const v4f*>(rec + 12);
+        plane_position_grad(planes, pl, off, du, dv, dxv, cq * 16, gx, gy, gz);
+    }
+    gx = group8_total(gx); gy = group8_total(gy); gz = group8_total(gz);
+}
+
 // RGB: a colour gradient is given.  Without it the colour half of layer 2 is evaluated in neither direction.
 template <bool RGB>
 __global__ __launch_bounds__(kBwdThreads, 3) void query_grad_kernel(Params P, QueryGradArgs Q) {
     extern __shared__ __align__(16) float smem[];
     const gnerf_render_params& p = P.p;
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    float* w1 = smem;
-    float* w2 = w1 + 64 * kW1Pitch;
-    float* b1 = w2 + 33 * kW2Pitch;
-    float* b2 = b1 + 64;
-    for (int i = tid; i < 64 * 32; i += kBwdThreads) w1[(i >> 5) * kW1Pitch + (i & 31)] = p.w1[i];
-    for (int i = tid; i < 33 * 64; i += kBwdThreads) w2[(i >> 6) * kW2Pitch + (i & 63)] = p.w2[i];
-    if (tid < 64) b1[tid] = p.b1[tid];
-    if (tid < 36) b2[tid] = tid < 33 ? p.b2[tid] : 0.f;
-    __syncthreads();
     BwdLds L = {};
-    L.w1 = w1; L.w2 = w2; L.b1 = b1; L.b2 = b2;
+    bwd_stage_decoder_f32<kBwdThreads>(L, smem, p, tid);
     L.stage = smem + kBwdWeightFloats + size_t(wv) * query_grad_wave_floats();
     L.tbuf = L.stage + 16 * kStagePitch;
     float* recs = L.tbuf + 16 * kTPitch;
-    const int j = lane & 15, g = lane >> 4, b = lane >> 3, cq = lane & 7, cq16 = cq * 16;
-    const int H = p.plane_h, W = p.plane_w;
-    const int64_t plane_floats = int64_t(3) * H * W * 32;
+    const int j = lane & 15, g = lane >> 4, b = lane >> 3, cq = lane & 7;
+    const int64_t plane_floats = int64_t(3) * p.plane_h * p.plane_w * 32;
     for (int tile = blockIdx.x * kBwdWaves + wv; tile < Q.n_tiles; tile += gridDim.x * kBwdWaves) {
         const int item = tile / Q.tiles_per_item, t = tile % Q.tiles_per_item;
         const char* planes = reinterpret_cast<const char*>(p.planes_nhwc + int64_t(item) * plane_floats);
         const float* pts = Q.points + int64_t(item) * Q.n_points * 3;
         const int64_t pt0 = int64_t(item) * Q.n_points + 16 * t;
         // ---- 1. tap records (points past the end of a partial last tile repeat the last point; they are never written)
-        if (lane < 48) {
-            const int pl = lane >> 4;
-            const int64_t idx = min(16 * t + j, Q.n_points - 1);
-            const float px = pts[idx * 3 + 0] * P.box_scale, py = pts[idx * 3 + 1] * P.box_scale, pz = pts[idx * 3 + 2] * P.box_scale;
-            const float u = pl == 2 ? pz : px;
-            const float v = pl == 0 ? py : (pl == 1 ? pz : px);
-            uint4 off; v4f wgt, du, dv;
-            plane_taps_grad(H, W, u, v, P.tex_pitch, P.row_pitch, unsigned(pl) * P.plane_pitch, off, wgt, du, dv);
-            float* rec = recs + (j * 3 + pl) * kGradRecDwords;
-            *reinterpret_cast<uint4*>(rec) = off;
-            *reinterpret_cast<v4f*>(rec + 4) = wgt;
-            *reinterpret_cast<v4f*>(rec + 8) = du;
-            *reinterpret_cast<v4f*>(rec + 12) = dv;
-        }
+        const int64_t idx = min(16 * t + j, Q.n_points - 1);
+        grad_tap_records(P, recs, lane, pts[idx * 3 + 0] * P.box_scale, pts[idx * 3 + 1] * P.box_scale, pts[idx * 3 + 2] * P.box_scale);
         lds_wave_sync();
-        // ---- 2. lookup: 8 points per step, 8 lanes x 16 bytes per texel; mean features staged as X[point][channel]
-#pragma unroll
-        for (int a = 0; a < 2; a++) {
-            const int js = 8 * a + b;
-            v4f acc = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int pl = 0; pl < 3; pl++) {
-                const float* rec = recs + (js * 3 + pl) * kGradRecDwords;
-                const uint4 off = *reinterpret_cast<const uint4*>(rec);
-                const v4f wgt = *reinterpret_cast<const v4f*>(rec + 4);
-                const v4f t00 = *reinterpret_cast<const v4f*>(planes + off.x + cq16);
-                const v4f t10 = *reinterpret_cast<const v4f*>(planes + off.y + cq16);
-                const v4f t01 = *reinterpret_cast<const v4f*>(planes + off.z + cq16);
-                const v4f t11 = *reinterpret_cast<const v4f*>(planes + off.w + cq16);
-                acc += t00 * wgt[0] + t10 * wgt[1] + t01 * wgt[2] + t11 * wgt[3];
-            }
-            *reinterpret_cast<v4f*>(L.stage + js * kStagePitch + 4 * cq) = acc;
-        }
+        // ---- 2. lookup and decoder forward
+        grad_lookup(L, recs, planes, b, cq);
         lds_wave_sync();
         v4f h[4], o[2];
         float sig;
         bwd_mlp_forward(L, lane, h, o, sig);
-        // ---- 3. decoder backward: dO -> dH^T -> through softplus -> dX^T (bwd_tile_core without the weight gradients)
+        // ---- 3. decoder backward: dO -> dH^T -> dX^T
         const float dsig = (Q.grad_sigma && 16 * t + j < Q.n_points) ? Q.grad_sigma[pt0 + j] : 0.f;
         v4f dh[4];
 #pragma unroll
@@ -114,32 +152,14 @@ __global__ __launch_bounds__(kBwdThreads, 3) void query_grad_kernel(Params P, Qu
                 for (int r = 0; r < 4; r++) {
                     const int q = 4 * g + r;
                     const float gc = 16 * t + q < Q.n_points ? Q.grad_rgb[(pt0 + q) * 32 + 16 * n + j] : 0.f;
-                    const float e = __builtin_amdgcn_exp2f(o[n][r] * -1.44269504088896341f);
-                    const float s = __builtin_amdgcn_rcpf(1.0f + e);
-                    L.tbuf[q * kTPitch + 16 * n + j] = gc * (1.002f * s * (1.f - s));        // rgb = 1.002 sigmoid(o) - 0.001 (triplane.py:134)
+                    L.tbuf[q * kTPitch + 16 * n + j] = gc * rgb_slope_hw(o[n][r]);
                 }
             }
             lds_wave_sync();
-#pragma unroll
-            for (int s = 0; s < 8; s++) {
-                const float bT = L.tbuf[j * kTPitch + 4 * s + g];
-#pragma unroll
-                for (int m = 0; m < 4; m++)
-                    dh[m] = __builtin_amdgcn_mfma_f32_16x16x4f32(L.w2[(1 + 4 * s + g) * kW2Pitch + 16 * m + j], bT, dh[m], 0, 0, 0);
-            }
+            bwd_dh_add_colour(L, j, g, dh);
         }
         v4f dx[2];
-        dx[0] = dx[1] = (v4f){0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int m = 0; m < 4; m++) {
-#pragma unroll
-            for (int r = 0; r < 4; r++) {
-                const float dpre = dh[m][r] * (1.f - exp_hw(-h[m][r]));          // d/dpre softplus(pre) = 1 - exp(-softplus(pre))
-                const float* row = L.w1 + (16 * m + 4 * g + r) * kW1Pitch + j;
-                dx[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(row[0], dpre, dx[0], 0, 0, 0);
-                dx[1] = __builtin_amdgcn_mfma_f32_16x16x4f32(row[16], dpre, dx[1], 0, 0, 0);
-            }
-        }
+        grad_dx_from_dh(L, h, dh, j, g, dx);
         lds_wave_sync();                                                         // every lane has read dO
         *reinterpret_cast<v4f*>(L.tbuf + j * kTPitch + 4 * g) = dx[0];           // dX[point][channel]
         *reinterpret_cast<v4f*>(L.tbuf + j * kTPitch + 16 + 4 * g) = dx[1];
@@ -148,26 +168,8 @@ __global__ __launch_bounds__(kBwdThreads, 3) void query_grad_kernel(Params P, Qu
 #pragma unroll
         for (int a = 0; a < 2; a++) {
             const int js = 8 * a + b;
-            const v4f dxv = *reinterpret_cast<const v4f*>(L.tbuf + js * kTPitch + 4 * cq);
-            float gx = 0.f, gy = 0.f, gz = 0.f;
-#pragma unroll
-            for (int pl = 0; pl < 3; pl++) {
-                const float* rec = recs + (js * 3 + pl) * kGradRecDwords;
-                const uint4 off = *reinterpret_cast<const uint4*>(rec);
-                const v4f du = *reinterpret_cast<const v4f*>(rec + 8);
-                const v4f dv = *reinterpret_cast<const v4f*>(rec + 12);
-                const v4f t00 = *reinterpret_cast<const v4f*>(planes + off.x + cq16);
-                const v4f t10 = *reinterpret_cast<const v4f*>(planes + off.y + cq16);
-                const v4f t01 = *reinterpret_cast<const v4f*>(planes + off.z + cq16);
-                const v4f t11 = *reinterpret_cast<const v4f*>(planes + off.w + cq16);
-                const v4f fu = (t00 * du[0] + t10 * du[1] + t01 * du[2] + t11 * du[3]) * dxv;
-                const v4f fv = (t00 * dv[0] + t10 * dv[1] + t01 * dv[2] + t11 * dv[3]) * dxv;
-                const float su = (fu[0] + fu[1]) + (fu[2] + fu[3]), sv = (fv[0] + fv[1]) + (fv[2] + fv[3]);
-                if (pl == 0) { gx += su; gy += sv; }
-                else if (pl == 1) { gx += su; gz += sv; }
-                else { gz += su; gx += sv; }
-            }
-            gx = group8_total(gx); gy = group8_total(gy); gz = group8_total(gz);
+            float gx, gy, gz;
+            grad_point_gradient(L, recs, planes, js, cq, gx, gy, gz);
             if (cq < 3 && 16 * t + js < Q.n_points)
                 Q.grad_points[(pt0 + js) * 3 + cq] = (cq == 0 ? gx : (cq == 1 ? gy : gz)) * P.box_scale;
         }

@@ -39,7 +39,7 @@ __global__ __launch_bounds__(kBwdThreads, GNERF_BWD_WAVE_OCC) void render_bwd_ke
     const int n_all = S + F;
     const int fine_e0 = 16 * P.tiles_c;
 
-    // ---- decoder into LDS (plain fp32 rows; every matrix is read in two orientations)
+    // ---- decoder into LDS: bwd_stage_decoder_f32 (render_bwd_tile.inl), kept as a copy -- through the helper this kernel's instructions change
     float* w1 = smem;
     float* w2 = w1 + 64 * kW1Pitch;
     float* b1 = w2 + 33 * kW2Pitch;

@@ -1,5 +1,6 @@
-// The backward's per-tile helpers: LDS carve-up, the lookup with its deferred plane scatter, the decoder forward and backward of one
-// 16-sample tile on the exact fp32 MFMA, the decoder-gradient reduction.  Shared by the renderer's backward (render_bwd.inl,
+// The backward's per-tile helpers: LDS carve-up and the fp32 decoder's staging (bwd_stage_decoder_f32, the one copy of that preamble), the
+// lookup with its deferred plane scatter, the decoder forward and backward of one 16-sample tile on the exact fp32 MFMA (the colour slope
+// rgb_slope_hw and the colour half of dH, bwd_dh_add_colour, are here once for every backward), the decoder-gradient reduction.  Shared by the renderer's backward (render_bwd.inl,
 // render_ray_grad.inl) and the point queries (query_bwd.inl, query_grad.inl, project_level.inl).  No kernel is defined here.
 #pragma once
 #include "render_shade.inl"
@@ -25,6 +26,29 @@ struct BwdLds {
     float* s_t; float* s_sig; float* s_q; float* w_s; float* trans; float* ds;         // sorted order / per interval
     float* stage; float* tbuf; float* hbuf; float* taps;
 };
+
+// The decoder into the first kBwdWeightFloats of a workgroup's LDS as plain fp32 rows (every matrix is read in two orientations), b2 zero
+// padded to 36; sets L.w1 / w2 / b1 / b2 and ends with the workgroup's barrier.  Every thread of the THREADS of the workgroup must call.
+template <int THREADS>
+__device__ __forceinline__ void bwd_stage_decoder_f32(BwdLds& L, float* smem, const gnerf_render_params& p, int tid) {
+    float* w1 = smem;
+    float* w2 = w1 + 64 * kW1Pitch;
+    float* b1 = w2 + 33 * kW2Pitch;
+    float* b2 = b1 + 64;
+    for (int i = tid; i < 64 * 32; i += THREADS) w1[(i >> 5) * kW1Pitch + (i & 31)] = p.w1[i];
+    for (int i = tid; i < 33 * 64; i += THREADS) w2[(i >> 6) * kW2Pitch + (i & 63)] = p.w2[i];
+    if (tid < 64) b1[tid] = p.b1[tid];
+    if (tid < 36) b2[tid] = tid < 33 ? p.b2[tid] : 0.f;
+    __syncthreads();
+    L.w1 = w1; L.w2 = w2; L.b1 = b1; L.b2 = b2;
+}
+
+// d(colour) / d(pre-activation): rgb = 1.002 sigmoid(o) - 0.001 (triplane.py:134; sigmoid_rgb_hw is the forward), from the sigmoid or from o
+__device__ __forceinline__ float rgb_slope_of_sigmoid(float s) { return 1.002f * s * (1.f - s); }
+__device__ __forceinline__ float rgb_slope_hw(float o) {
+    const float e = __builtin_amdgcn_exp2f(o * -1.44269504088896341f);
+    return rgb_slope_of_sigmoid(__builtin_amdgcn_rcpf(1.0f + e));
+}
 
 
 #ifdef GNERF_ABLATE_ATOMIC       // timing-only build: plain stores instead of atomics (wrong results)
@@ -270,6 +294,17 @@ struct BwdAcc {
     float b2s;        // db2[0], partial
 };
 
+// The colour half of dH^T[hidden][sample] = sum_out W2[out][hidden] dO[sample][out], dO[16][32] in `tbuf`, added to dh (the H^T layout)
+__device__ __forceinline__ void bwd_dh_add_colour(const BwdLds& L, int j, int g, v4f (&dh)[4]) {
+#pragma unroll
+    for (int s = 0; s < 8; s++) {
+        const float bT = L.tbuf[j * kTPitch + 4 * s + g];
+#pragma unroll
+        for (int m = 0; m < 4; m++)
+            dh[m] = __builtin_amdgcn_mfma_f32_16x16x4f32(L.w2[(1 + 4 * s + g) * kW2Pitch + 16 * m + j], bT, dh[m], 0, 0, 0);
+    }
+}
+
 // The decoder's backward pass for one staged tile.  On entry: X in `stage`, dO[16][32] (colour pre-activation gradients)
 // in `tbuf`, h = the hidden activations (H^T layout), dsig = dL/dsigma of this lane's sample.  Accumulates the weight
 // gradients into A and leaves dX[16][32] in `tbuf`.
@@ -285,13 +320,7 @@ __device__ __forceinline__ void bwd_tile_core(const BwdLds& L, v4f (&h)[4], floa
         dh[m] = ws * dsig;
         A.w2s[m] += h[m] * dsig;
     }
-#pragma unroll
-    for (int s = 0; s < 8; s++) {
-        const float bT = L.tbuf[j * kTPitch + 4 * s + g];
-#pragma unroll
-        for (int m = 0; m < 4; m++)
-            dh[m] = __builtin_amdgcn_mfma_f32_16x16x4f32(L.w2[(1 + 4 * s + g) * kW2Pitch + 16 * m + j], bT, dh[m], 0, 0, 0);
-    }
+    bwd_dh_add_colour(L, j, g, dh);
     // ---- through softplus: d/dpre softplus(pre) = 1 - exp(-softplus(pre))
 #pragma unroll
     for (int m = 0; m < 4; m++) {
@@ -366,6 +395,7 @@ __device__ __forceinline__ void bwd_backward_tiles(const Params& P, const BwdLds
         for (int n = 0; n < 2; n++) {
 #pragma unroll
             for (int r = 0; r < 4; r++) {
+                // rgb_slope_hw, kept as a copy: through the helper render_bwd_kernel's instructions change
                 const float e = __builtin_amdgcn_exp2f(o[n][r] * -1.44269504088896341f);
                 const float s = __builtin_amdgcn_rcpf(1.0f + e);
                 const float d = G[n] * vs[r] * (1.002f * s * (1.f - s));

@@ -38,18 +38,8 @@ struct BwdTileF32 {
     BwdLds L;
     float inv_scale;
     __device__ __forceinline__ void setup(const Params& P, float* smem, const float*, int tid) {
-        const gnerf_render_params& p = P.p;
-        float* w1 = smem;
-        float* w2 = w1 + 64 * kW1Pitch;
-        float* b1 = w2 + 33 * kW2Pitch;
-        float* b2 = b1 + 64;
-        for (int i = tid; i < 64 * 32; i += kTileThreads) w1[(i >> 5) * kW1Pitch + (i & 31)] = p.w1[i];
-        for (int i = tid; i < 33 * 64; i += kTileThreads) w2[(i >> 6) * kW2Pitch + (i & 63)] = p.w2[i];
-        if (tid < 64) b1[tid] = p.b1[tid];
-        if (tid < 36) b2[tid] = tid < 33 ? p.b2[tid] : 0.f;
-        __syncthreads();
         L = BwdLds{};
-        L.w1 = w1; L.w2 = w2; L.b1 = b1; L.b2 = b2;
+        bwd_stage_decoder_f32<kTileThreads>(L, smem, P.p, tid);
         inv_scale = 1.f;
     }
     // X in L.stage, the tile's colour weights in vw, dL/dsigma in dsg, G = dL/d colour sum of channels 16n + j  ->  dX[16][32] in L.tbuf
@@ -65,9 +55,7 @@ struct BwdTileF32 {
         for (int n = 0; n < 2; n++) {
 #pragma unroll
             for (int r = 0; r < 4; r++) {
-                const float e = __builtin_amdgcn_exp2f(o[n][r] * -1.44269504088896341f);
-                const float s = __builtin_amdgcn_rcpf(1.0f + e);
-                const float d = G[n] * vs[r] * (1.002f * s * (1.f - s));
+                const float d = G[n] * vs[r] * rgb_slope_hw(o[n][r]);
                 L.tbuf[(4 * g + r) * kTPitch + 16 * n + j] = d;
                 A.b2[n] += d;
             }
@@ -210,7 +198,7 @@ struct BwdTileF16 {
 #pragma unroll
             for (int r = 0; r < 4; r++) {
                 const float s = __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(o[n][r]));
-                const float d = G[n] * vs[r] * (1.002f * s * (1.f - s));
+                const float d = G[n] * vs[r] * rgb_slope_of_sigmoid(s);
                 dO[4 * n + r] = d;
                 A.b2[n] += d;
                 big = fmaxf(big, l1_w2c * fabsf(d));
