@@ -13,7 +13,7 @@
 // marching_cubes (gnerf_hip.marching_cubes' count -> read counts -> emit sequence), ssim_forward / ssim_backward (gnerf_hip.ssim_*),
 // modconv_backward (gnerf_hip.scale_channels_backward / modconv_epilogue_backward), query_points_grad (gnerf_hip.query_points_grad),
 // render_backward_rays (gnerf_hip.render_backward with need_rays), resize_aa (gnerf_hip.resize_aa_forward / _backward),
-// raster_visibility / raster_resolve (gnerf_hip.rasterize / resolve), mesh_components / mesh_compact / mesh_smooth /
+// raster_visibility / raster_resolve / mesh_bake_colors (gnerf_hip.rasterize / resolve / bake_colors), mesh_components / mesh_compact / mesh_smooth /
 // mesh_simplify / mesh_simplify_count / project_points_to_level / mesh_flip_guard (gnerf_hip's of those names).
 //
 // Built ahead of time by csrc/build.sh (g++, no hipcc: there is no device code) into g-nerf_amd/gnerf_hip/gnerf_torch_ext.so.
@@ -638,6 +638,36 @@ std::vector<c10::optional<Tensor>> raster_resolve(Tensor vis, Tensor verts, Tens
     return out;
 }
 
+// gnerf_hip.bake_colors has validated the tensors: vis int64 [n, h, w], frames uint8 [n, fh, fw, 3], normals float32 [V, 3], normal_mat
+// float32 [n, 9], fallback uint8 [V, 3], contiguous on verts' GPU.  colors / weight / seen: preallocated outputs or None.
+// -> (colors uint8 [V, 3], weight float32 [V], seen int32 [V]).
+std::tuple<Tensor, Tensor, Tensor> mesh_bake_colors(Tensor verts, Tensor mesh2cam, Tensor intrinsics, Tensor vis, Tensor frames, c10::optional<Tensor> normals,
+                                                    c10::optional<Tensor> normal_mat, double near_z, double depth_tol, int64_t guard, double min_cos, int64_t power,
+                                                    c10::optional<Tensor> fallback, c10::optional<Tensor> colors, c10::optional<Tensor> weight,
+                                                    c10::optional<Tensor> seen) {
+    TORCH_CHECK(verts.is_cuda() && verts.scalar_type() == torch::kFloat32 && verts.is_contiguous() && mesh2cam.scalar_type() == torch::kFloat32 &&
+                mesh2cam.is_contiguous() && intrinsics.scalar_type() == torch::kFloat32 && intrinsics.is_contiguous(), "mesh_bake_colors: unexpected tensor layout");
+    TORCH_CHECK(vis.is_cuda() && vis.scalar_type() == torch::kInt64 && vis.is_contiguous() && vis.dim() == 3, "mesh_bake_colors: vis must be a contiguous int64 [n, h, w] GPU tensor");
+    TORCH_CHECK(frames.is_cuda() && frames.scalar_type() == torch::kUInt8 && frames.is_contiguous() && frames.dim() == 4 && frames.size(0) == vis.size(0) && frames.size(3) == 3,
+                "mesh_bake_colors: frames must be a contiguous uint8 [n, fh, fw, 3] GPU tensor");
+    TORCH_CHECK(verts.size(0) <= INT_MAX && frames.size(1) <= INT_MAX && frames.size(2) <= INT_MAX && guard >= INT_MIN && guard <= INT_MAX && power >= INT_MIN && power <= INT_MAX,
+                "mesh_bake_colors: oversized argument");
+    const c10::hip::OptionalHIPGuardMasqueradingAsCUDA device_guard(at::device_of(verts));
+    const int n_verts = int(verts.size(0)), n = int(vis.size(0));
+    Tensor c = colors.has_value() ? *colors : torch::empty({n_verts, 3}, verts.options().dtype(torch::kUInt8));
+    Tensor wt = weight.has_value() ? *weight : torch::empty({n_verts}, verts.options().dtype(torch::kFloat32));
+    Tensor sn = seen.has_value() ? *seen : torch::empty({n_verts}, verts.options().dtype(torch::kInt32));
+    auto p = [](const c10::optional<Tensor>& t) -> void* { return t.has_value() ? t->data_ptr() : nullptr; };
+    check_rc(gnerf_mesh_bake_colors(n_verts ? verts.data_ptr<float>() : nullptr, n_verts, mesh2cam.data_ptr<float>(), intrinsics.data_ptr<float>(), n,
+                                    reinterpret_cast<const uint64_t*>(vis.data_ptr<int64_t>()), int(vis.size(1)), int(vis.size(2)), frames.data_ptr<uint8_t>(),
+                                    int(frames.size(1)), int(frames.size(2)), static_cast<const float*>(p(normals)), static_cast<const float*>(p(normal_mat)),
+                                    float(near_z), float(depth_tol), int(guard), float(min_cos), int(power), static_cast<const unsigned char*>(p(fallback)),
+                                    n_verts ? c.data_ptr<uint8_t>() : nullptr, n_verts ? wt.data_ptr<float>() : nullptr, n_verts ? sn.data_ptr<int32_t>() : nullptr,
+                                    current_stream()),
+             "gnerf_mesh_bake_colors");
+    return std::make_tuple(c, wt, sn);
+}
+
 // ------------------------------------------------------------------------------------------------ mesh cleaning (csrc/mesh_clean.hip)
 // gnerf_hip.mesh_components / mesh_compact / mesh_smooth have validated the tensors: verts float32 [V, 3], faces int32 [T, 3], label and
 // faces_of int32 [V], keep uint8 [V], all contiguous on one GPU.
@@ -796,6 +826,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("resize_aa", &resize_aa);
     m.def("raster_visibility", &raster_visibility);
     m.def("raster_resolve", &raster_resolve);
+    m.def("mesh_bake_colors", &mesh_bake_colors);
     m.def("mesh_components", &mesh_components);
     m.def("mesh_compact", &mesh_compact);
     m.def("mesh_smooth", &mesh_smooth);

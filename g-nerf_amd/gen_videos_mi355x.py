@@ -30,6 +30,10 @@ uniform grid, placed by the cell's quadric; both 0 by default, which changes not
 density itself by Newton steps along its gradient, at most R voxels per axis from where it stood (csrc/project_level.inl), faces that this
 turns over get their vertices back (the flip guard of csrc/mesh_clean.hip), and the attributes are evaluated at the final positions; 0 by
 default, which changes nothing.
+`--mesh-bake N` (with `--mesh`) colours the final mesh from N of the orbit's own 512^2 frames, evenly spaced (no extra synthesis): the mesh is
+rasterised from their cameras at `--mesh-bake-res`, every vertex takes the frames' colours where the visibility buffers say it is seen
+(csrc/raster.hip, gnerf_mesh_bake_colors; `--mesh-bake-tol`, `--mesh-bake-guard`, `--mesh-bake-power`), blended by how squarely each view faces
+the surface when `--mesh-attrs` made normals; the decoder's colours, when it made them, stay on the vertices no frame sees.
 """
 
 import argparse
@@ -403,8 +407,34 @@ def snap_extracted_mesh(G, planes, verts, faces, resolution, snap, level=10.0):
     return out.cpu().numpy(), report
 
 
+def bake_frames_of_orbit(full, n_frames, n_bake, radius):
+    """--mesh-bake's choice among the orbit's gathered frames `full` [n_frames, H, W, 3]: n_bake of them at indices (j n_frames) // n_bake, with
+    their camera labels -> (indices, frames uint8 [n_bake, H, W, 3], labels [n_bake, 25] on the host)."""
+    idx = [(j * n_frames) // n_bake for j in range(n_bake)]
+    return idx, full[idx].contiguous(), H.orbit_labels(idx, n_frames, radius)
+
+
+def bake_extracted_mesh(verts, faces, normals, fallback, bake, resolution, cube_length):
+    """--mesh-bake on the final mesh (index space; mesh_to_world_matrix puts it into the world): shape_mi355x.bake_mesh_colors from bake['frames']
+    (uint8 [N, H, W, 3]) and their camera labels bake['labels'] [N, 25], rasterised at bake['res'] (None: the frames' size), with bake['rules'].
+    normals / fallback: per-vertex arrays or tensors, or None.  Kernels when the frames are on a GPU, the numpy ports otherwise."""
+    import shape_mi355x
+    frames, labels = bake['frames'], bake['labels']
+    dev = frames.device
+
+    def place(x, dtype=None):
+        if x is None:
+            return None
+        x = x if isinstance(x, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(x))
+        x = x.to(dev) if dtype is None else x.to(dev, dtype)
+        return x if dev.type == 'cuda' else x.numpy()
+    return shape_mi355x.bake_mesh_colors(place(verts, torch.float32), place(faces, torch.int32), place(frames), labels[:, :16].reshape(-1, 4, 4),
+                                         labels[:, 16:25].reshape(-1, 3, 3), mesh2world=mesh_to_world_matrix(resolution, cube_length),
+                                         normals=place(normals, torch.float32), vis_size=bake.get('res'), fallback=place(fallback), **bake.get('rules', {}))
+
+
 def mesh_density_grid(vol, ply_path, level=10.0, attrs=None, G=None, planes=None, clean=None, report=None, simplify=None, simplify_report=None,
-                      snap=None, snap_report=None):
+                      snap=None, snap_report=None, bake=None, bake_report=None):
     """--mesh: the mesh shape_utils.convert_mrc makes of the .mrc of this volume (shape_utils.py:103-105: transpose(2, 1, 0), voxel
     size 1, origin 0), made where the volume lives -- on a GPU the marching-cubes kernel reads it in HBM, only the mesh comes to the host.
     attrs: None / 'none', 'normals', 'colors' or 'all' -- per-vertex attributes (mesh_vertex_attributes) of generator G on `planes`
@@ -415,6 +445,9 @@ def mesh_density_grid(vol, ply_path, level=10.0, attrs=None, G=None, planes=None
     attributes; simplify_report: a dict that then receives simplify_mesh's report.  snap: None or shape_mi355x.snap_options' dict -- the order
     becomes marching cubes, compaction, simplification, smoothing, snap_extracted_mesh (snap_report receives its report), and the attributes
     are evaluated at the snapped positions; with snap None the order and the file's bytes are those of a call without it.
+    bake: None or bake_extracted_mesh's dict (frames, labels, res, rules) -- last of all the final mesh is coloured from those frames, with the
+    normals when attrs made them and the decoder's colours, when it made them, as the fallback; the result becomes the file's colours and
+    bake_report receives it (colors, weight, seen).
     Writes `ply_path`; returns (vertex count, triangle count, seconds spent in marching cubes)."""
     import shape_mi355x
     attrs = 'none' if attrs is None else attrs
@@ -443,6 +476,13 @@ def mesh_density_grid(vol, ply_path, level=10.0, attrs=None, G=None, planes=None
         normals, colors = (None if t is None else t.cpu().numpy() for t in (normals, colors))
     if not snap:
         verts = smooth_extracted_mesh(verts, faces, clean)
+    if bake:
+        if G is None:
+            raise ValueError('mesh_density_grid: the bake needs the generator G (its box)')
+        baked = bake_extracted_mesh(verts, faces, normals, colors, bake, vol.shape[0], G.rendering_kwargs['box_warp'])
+        colors = baked['colors'].cpu().numpy() if isinstance(baked['colors'], torch.Tensor) else baked['colors']
+        if bake_report is not None:
+            bake_report.update(baked)
     if isinstance(verts, torch.Tensor):
         verts, faces = verts.cpu().numpy(), faces.cpu().numpy()
     shape_mi355x.write_ply(ply_path, verts, faces, normals=normals, colors=colors)
@@ -505,6 +545,13 @@ def main():
                          'R voxels per axis from where it stood; faces that this turns over get their vertices back (--mesh and --geometry-out; 0: off)')
     ap.add_argument('--mesh-snap-steps', type=int, default=6, help='Newton steps of --mesh-snap at the most')
     ap.add_argument('--mesh-snap-tol', type=float, default=None, help='|sigma - level| at which a vertex of --mesh-snap is done (default: 2^-10 max(1, |level|))')
+    ap.add_argument('--mesh-bake', type=int, default=0, metavar='N',
+                    help='colour the vertices of --mesh from N of the orbit\'s frames, at indices (j * frames) // N: each vertex takes the frames\' colours where '
+                         'it is visible, blended by how squarely the views face it (with the normals of --mesh-attrs); the decoder\'s colours stay where no frame sees (0: off)')
+    ap.add_argument('--mesh-bake-res', type=int, default=None, help='resolution of the visibility buffers of --mesh-bake (default: the frames\' size)')
+    ap.add_argument('--mesh-bake-tol', type=float, default=2.0 ** -8, help='relative depth tolerance of --mesh-bake\'s occlusion test')
+    ap.add_argument('--mesh-bake-guard', type=int, default=1, help='--mesh-bake tests the (2 GUARD + 1)^2 pixels around a vertex (0..4)')
+    ap.add_argument('--mesh-bake-power', type=int, default=2, help='--mesh-bake weights a view by cos^POWER of the angle between normal and line of sight (0..8)')
     ap.add_argument('--voxel-res', type=int, default=512)
     ap.add_argument('--geometry-out', default=None, help='also draw the mesh of the density volume from every orbit camera (shaded geometry frames, '
                                                          'uint8 [F, H, W, 3]) and write them to this .npy (rank 0); uses --voxel-res, --mesh-level, --mesh-attrs, --frames-per-call')
@@ -515,6 +562,13 @@ def main():
         ap.error('--mesh-keep, --mesh-min-faces and --mesh-smooth must be >= 0')
     if not args.mesh_simplify >= 0 or args.mesh_simplify == float('inf') or args.mesh_target_faces < 0:
         ap.error('--mesh-simplify and --mesh-target-faces must be >= 0')
+    if args.mesh_bake and not args.mesh:
+        ap.error('--mesh-bake requires --mesh')
+    if not 0 <= args.mesh_bake <= args.frames:
+        ap.error('--mesh-bake must be 0 .. --frames')
+    if (not args.mesh_bake_tol >= 0 or not 0 <= args.mesh_bake_guard <= 4 or not 0 <= args.mesh_bake_power <= 8
+            or (args.mesh_bake_res is not None and not 1 <= args.mesh_bake_res <= 4096)):
+        ap.error('--mesh-bake-tol must be >= 0, --mesh-bake-guard 0..4, --mesh-bake-power 0..8, --mesh-bake-res 1..4096')
     import shape_mi355x
     clean = shape_mi355x.clean_options(args.mesh_keep, args.mesh_min_faces, args.mesh_smooth)
     simplify = shape_mi355x.simplify_options(args.mesh_simplify, args.mesh_target_faces)
@@ -579,15 +633,23 @@ def main():
             shape_mi355x.write_mrc(args.shapes_mrc, vol.cpu().numpy())
         if args.mesh:
             t0 = time.perf_counter()
-            report, simplify_report, snap_report = {}, {}, {}
+            report, simplify_report, snap_report, bake_report = {}, {}, {}, {}
+            bake = None
+            if args.mesh_bake:                                           # N of the frames this run has just gathered, and their cameras
+                _, bake_frames, bake_labels = bake_frames_of_orbit(full, args.frames, args.mesh_bake, G.rendering_kwargs['avg_camera_radius'])
+                bake = dict(frames=bake_frames, labels=bake_labels, res=args.mesh_bake_res,
+                            rules=dict(depth_tol=args.mesh_bake_tol, guard=args.mesh_bake_guard, power=args.mesh_bake_power))
             nv, nf, dt = mesh_density_grid(vol, args.mesh, args.mesh_level, attrs=args.mesh_attrs, G=G, planes=planes, clean=clean, report=report,
-                                           simplify=simplify, simplify_report=simplify_report, snap=snap, snap_report=snap_report)
+                                           simplify=simplify, simplify_report=simplify_report, snap=snap, snap_report=snap_report, bake=bake,
+                                           bake_report=bake_report)
             if report:
                 print(shape_mi355x.clean_report_line(report, args.mesh_smooth))
             if simplify_report:
                 print(shape_mi355x.simplify_report_line(simplify_report))
             if snap_report:
                 print(shape_mi355x.snap_report_line(snap_report))
+            if bake_report:
+                print(shape_mi355x.bake_report_line(bake_report, args.mesh_bake))
             print(f'mesh at level {args.mesh_level:g}: {dt * 1e3:.2f} ms, {nv} vertices, {nf} triangles -> {args.mesh}'
                   + (f' (with {args.mesh_attrs}: {(time.perf_counter() - t0) * 1e3:.2f} ms in all, file included)' if args.mesh_attrs != 'none' else ''))
     if args.geometry_out:

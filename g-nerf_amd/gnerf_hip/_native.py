@@ -138,6 +138,8 @@ SIGNATURES = {
     'gnerf_raster_visibility': (_c_i, [_c_p, _c_i, _c_p, _c_i, _c_p, _c_p, _c_i, _c_i, _c_i, _c_f, _c_i, _c_p, _c_p, _c_p, _c_p]),
     'gnerf_raster_resolve': (_c_i, [_c_p, _c_p, _c_i, _c_p, _c_i, _c_p, _c_p, _c_i, _c_i, _c_i, _c_p, _c_p, _c_p, ctypes.POINTER(_c_f),
                                     _c_p, _c_p, _c_p, _c_p, _c_p]),
+    'gnerf_mesh_bake_colors': (_c_i, [_c_p, _c_i, _c_p, _c_p, _c_i, _c_p, _c_i, _c_i, _c_p, _c_i, _c_i, _c_p, _c_p, _c_f, _c_f, _c_i, _c_f, _c_i, _c_p,
+                                      _c_p, _c_p, _c_p, _c_p]),
     'gnerf_mesh_workspace_bytes': (_c_i, [_c_i, _c_i, ctypes.POINTER(ctypes.c_size_t)]),
     'gnerf_mesh_components': (_c_i, [_c_p, _c_i, _c_i, _c_p, _c_p, _c_p, _c_p, _c_p]),
     'gnerf_mesh_compact_count': (_c_i, [_c_p, _c_i, _c_i, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p]),

@@ -1,4 +1,5 @@
-"""The triangle rasteriser for extracted meshes (csrc/raster.hip): a visibility buffer per view, then depth / normal / shaded colour."""
+"""The triangle rasteriser for extracted meshes (csrc/raster.hip): a visibility buffer per view, then depth / normal / shaded colour;
+and its inverse, the multi-view colour bake: frames back onto the vertices."""
 
 import ctypes
 
@@ -182,3 +183,94 @@ def resolve(vis, verts, faces, mesh2cam, intrinsics, normals=None, normal_mat=No
             got = e.raster_resolve(vis, v, f, A, K, normals, normal_mat, colors, sh, [o in want for o in RASTER_OUTPUTS])
         return {o: t for o, t in zip(RASTER_OUTPUTS, got) if o in want}
     return _resolve_ctypes(vis, v, f, A, K, normals, normal_mat, colors, sh, want)
+
+
+# ---------------------------------------------------------------------------------------------------------------- the colour bake
+BAKE_MAX_GUARD = 4                  # GNERF_BAKE_MAX_GUARD
+BAKE_MAX_POWER = 8                  # GNERF_BAKE_MAX_POWER
+BAKE_OUTPUTS = ('colors', 'weight', 'seen')
+# arguments, not measurements (include/gnerf_hip.h, gnerf_mesh_bake_colors, derives depth_tol)
+BAKE_RULES = dict(near=0.01, depth_tol=2.0 ** -8, guard=1, min_cos=0.1, power=2)
+
+
+def bake_available():
+    """Whether the loaded library has the colour bake (a version-15 library built before it does not)."""
+    return hasattr(load(), 'gnerf_mesh_bake_colors')
+
+
+def _bake_rules(near, depth_tol, guard, min_cos, power):
+    """The five rule arguments as the C ABI takes them; ValueError for what gnerf_mesh_bake_colors would refuse."""
+    if not near > 0:
+        raise ValueError('bake: near must be > 0')
+    if not depth_tol >= 0:
+        raise ValueError('bake: depth_tol must be >= 0')
+    if int(guard) != guard or not 0 <= guard <= BAKE_MAX_GUARD:
+        raise ValueError(f'bake: guard must be an integer in 0..{BAKE_MAX_GUARD}')
+    if int(power) != power or not 0 <= power <= BAKE_MAX_POWER:
+        raise ValueError(f'bake: power must be an integer in 0..{BAKE_MAX_POWER}')
+    return float(near), float(depth_tol), int(guard), float(min_cos), int(power)
+
+
+def _bake_colors_ctypes(v, A, K, vis, frames, normals, normal_mat, rules, fallback, colors=None, weight=None, seen=None):
+    """The ctypes route of bake_colors (arguments as bake_colors has validated them; rules: _bake_rules' tuple)."""
+    dev, V = v.device, len(v)
+    colors = torch.empty([V, 3], dtype=torch.uint8, device=dev) if colors is None else colors
+    weight = torch.empty([V], dtype=torch.float32, device=dev) if weight is None else weight
+    seen = torch.empty([V], dtype=torch.int32, device=dev) if seen is None else seen
+    n, h, w = vis.shape
+    near, depth_tol, guard, min_cos, power = rules
+    _launch('gnerf_mesh_bake_colors', vis, _ptr(v) if V else None, V, _ptr(A), _ptr(K), n, _ptr(vis), h, w, _ptr(frames), frames.shape[1],
+            frames.shape[2], _ptr(normals), _ptr(normal_mat), near, depth_tol, guard, min_cos, power, _ptr(fallback), _ptr(colors) if V else None,
+            _ptr(weight) if V else None, _ptr(seen) if V else None)
+    return dict(colors=colors, weight=weight, seen=seen)
+
+
+@profiled('gnerf_hip::bake_colors')
+def bake_colors(verts, mesh2cam, intrinsics, vis, frames, normals=None, normal_mat=None, near=BAKE_RULES['near'], depth_tol=BAKE_RULES['depth_tol'],
+                guard=BAKE_RULES['guard'], min_cos=BAKE_RULES['min_cos'], power=BAKE_RULES['power'], fallback=None, out=None):
+    """Multi-view vertex colours: every vertex (verts float32 [V, 3], CUDA) gathers its colour from `frames` (uint8 [n, fh, fw, 3]) taken by the
+    cameras (mesh2cam [n, 3, 4], intrinsics [n, 3, 3]) whose visibility buffers `vis` (rasterize's int64 [n, h, w], of the same mesh, cameras
+    and near) decide where it is hidden; views are blended by cos^power of the angle between the vertex normal and the line of sight when
+    normals float32 [V, 3] and normal_mat [n, 3, 3] (mesh frame -> camera frame) are given, equally otherwise.  -> dict(colors uint8 [V, 3],
+    weight float32 [V], seen int32 [V]): a vertex no view sees (seen == 0, weight == 0) gets its `fallback` colour (uint8 [V, 3]) or 0.
+    Rules: include/gnerf_hip.h, gnerf_mesh_bake_colors; shape_mi355x.bake_colors_numpy gives the same bits.  One launch, no host read:
+    capturable (float32 contiguous camera tensors, vis and frames are read in place).  out: an optional dict of preallocated outputs."""
+    if not bake_available():
+        raise RuntimeError('gnerf_hip: this libgnerf_hip.so was built without the colour bake (gnerf_mesh_bake_colors): rebuild it (csrc/build.sh)')
+    rules = _bake_rules(near, depth_tol, guard, min_cos, power)
+    _require_cuda(verts, vis, frames)
+    v = _f32(verts, (3,), 'verts')
+    A, K = _cameras(mesh2cam, intrinsics, v.device)
+    if vis.dtype != torch.int64 or vis.ndim != 3 or vis.shape[0] != len(A) or not vis.is_contiguous() or vis.device != v.device:
+        raise ValueError('bake: vis must be rasterize\'s int64 [n_views, h, w] tensor')
+    if (frames.dtype != torch.uint8 or frames.ndim != 4 or frames.shape[0] != len(A) or frames.shape[3] != 3 or frames.device != v.device
+            or not (1 <= frames.shape[1] <= RASTER_MAX_SIZE and 1 <= frames.shape[2] <= RASTER_MAX_SIZE)):
+        raise ValueError(f'bake: frames must be uint8 [n_views, fh, fw, 3] on the mesh\'s device, fh and fw in 1..{RASTER_MAX_SIZE}')
+    frames = frames.detach().contiguous()
+    if normals is not None:
+        if normal_mat is None:
+            raise ValueError('bake: normals need normal_mat')
+        _require_cuda(normals, normal_mat)
+        normals, normal_mat = _f32(normals, (3,), 'normals'), _f32(normal_mat, (9,), 'normal_mat')
+        if len(normals) != len(v) or len(normal_mat) != len(A) or normals.device != v.device or normal_mat.device != v.device:
+            raise ValueError('bake: normals must be [V, 3] and normal_mat [n_views, 3, 3], on the mesh\'s device')
+    else:
+        normal_mat = None
+    if fallback is not None:
+        _require_cuda(fallback)
+        if fallback.dtype != torch.uint8 or tuple(fallback.shape) != (len(v), 3) or fallback.device != v.device:
+            raise ValueError('bake: fallback must be uint8 [V, 3] on the mesh\'s device')
+        fallback = fallback.detach().contiguous()
+    out = dict(out or {})
+    if set(out) - set(BAKE_OUTPUTS):
+        raise ValueError(f'bake: out holds {BAKE_OUTPUTS} at the most')
+    for name, dtype, shape in (('colors', torch.uint8, (len(v), 3)), ('weight', torch.float32, (len(v),)), ('seen', torch.int32, (len(v),))):
+        t = out.get(name)
+        if t is not None and (t.dtype != dtype or tuple(t.shape) != shape or not t.is_contiguous() or t.device != v.device):
+            raise ValueError(f'bake: out[{name!r}] must be a contiguous {dtype} tensor of shape {shape} on the mesh\'s device')
+    e = _native.ext()
+    if e is not None and hasattr(e, 'mesh_bake_colors'):
+        with _on_device(v.device):
+            got = e.mesh_bake_colors(v, A, K, vis, frames, normals, normal_mat, *rules, fallback, out.get('colors'), out.get('weight'), out.get('seen'))
+        return dict(zip(BAKE_OUTPUTS, got))
+    return _bake_colors_ctypes(v, A, K, vis, frames, normals, normal_mat, rules, fallback, out.get('colors'), out.get('weight'), out.get('seen'))

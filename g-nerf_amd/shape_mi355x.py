@@ -21,6 +21,10 @@ render_mesh draws such a mesh from the renderer's cameras on the renderer's pixe
 normals, shaded frames): CUDA tensors go to the rasteriser kernels (csrc/raster.hip through gnerf_hip.rasterize / resolve), numpy arrays to
 rasterize_numpy / resolve_numpy below, which state the arithmetic (include/gnerf_hip.h, gnerf_raster_*) and give the same bits.
 
+bake_mesh_colors goes the other way: it colours such a mesh's vertices from frames of it (the orbit's) and their cameras, through render_mesh's
+visibility buffers.  CUDA tensors go to gnerf_hip.rasterize / bake_colors (csrc/raster.hip), numpy arrays to rasterize_numpy /
+bake_colors_numpy below (include/gnerf_hip.h, gnerf_mesh_bake_colors): the same bits.
+
 clean_mesh edits such a mesh between extraction and its consumers: connected components, the selection of the large ones, compaction and
 Taubin smoothing.  CUDA tensors go to csrc/mesh_clean.hip (gnerf_hip.mesh_components / mesh_compact / mesh_smooth), numpy arrays to
 mesh_components_numpy / mesh_select / mesh_compact_numpy / mesh_smooth_numpy below (include/gnerf_hip.h, gnerf_mesh_*): the same bits.
@@ -293,8 +297,9 @@ def _raster_size(size):
     return h, w
 
 
-def _raster_project(v, A, K, h, w, near):
-    """The vertex stage for one view: (cam float32 [V, 3], iz float32 [V], X int64 [V], Y int64 [V], bad uint8 [V]: 1 near, 2 guard)."""
+def _raster_point(v, A, K, near):
+    """The first half of the vertex stage for one view, which the rasteriser and the colour bake share: (cam float32 [V, 3], near_bad [V]:
+    non-finite or not in front of near, iz float32 [V], xc, yc float32 [V]: the normalised image coordinates; iz is 0 where near_bad)."""
     x, y, z = v[:, 0], v[:, 1], v[:, 2]
     with np.errstate(all='ignore'):
         cam = np.stack([((A[4 * r] * x + A[4 * r + 1] * y) + A[4 * r + 2] * z) + A[4 * r + 3] for r in range(3)], axis=1)
@@ -304,6 +309,13 @@ def _raster_project(v, A, K, h, w, near):
         fx, sk, cx, fy, cy = K[0], K[1], K[2], K[4], K[5]
         xc = (fx * xn + sk * yn) + cx
         yc = fy * yn + cy
+    return cam.astype(np.float32), near_bad, iz, xc, yc
+
+
+def _raster_project(v, A, K, h, w, near):
+    """The vertex stage for one view: (cam float32 [V, 3], iz float32 [V], X int64 [V], Y int64 [V], bad uint8 [V]: 1 near, 2 guard)."""
+    cam, near_bad, iz, xc, yc = _raster_point(v, A, K, near)
+    with np.errstate(all='ignore'):
         fX = np.rint((xc * _F(w)) * _F(256))
         fY = np.rint((yc * _F(h)) * _F(256))
         guard_bad = ~near_bad & (~(np.abs(fX) <= _F(2097152)) | ~(np.abs(fY) <= _F(2097152)))
@@ -552,6 +564,163 @@ def render_mesh(verts, faces, cam2world, intrinsics, size, mesh2world=None, norm
                         shading=shading, outputs=outputs)
     out['counts'] = counts
     return out
+
+
+# ---------------------------------------------------------------------------------------------------------------- colour bake
+# The numpy port of gnerf_mesh_bake_colors (csrc/raster.hip; include/gnerf_hip.h states the rules): the rasteriser's inverse.  Every vertex
+# gathers its colour from the views' frames: projected with the rasteriser's vertex stage, rejected where the view's visibility buffer holds
+# nothing or a nearer surface anywhere in the (2 guard + 1)^2 window around its pixel, sampled bilinearly, blended by cos^power of the angle
+# between its normal and the line of sight.  float32, one rounding per operation in the kernel's order: the same bits.
+BAKE_RULES = dict(near=0.01, depth_tol=2.0 ** -8, guard=1, min_cos=0.1, power=2)       # arguments, not measurements (the header derives depth_tol)
+
+
+def _dot3_f32(a0, a1, a2, b0, b1, b2):
+    return (a0 * b0 + a1 * b1) + a2 * b2
+
+
+def bake_colors_numpy(verts, mesh2cam, intrinsics, vis, frames, normals=None, normal_mat=None, near=0.01, depth_tol=2.0 ** -8, guard=1, min_cos=0.1,
+                      power=2, fallback=None):
+    """The numpy port of gnerf_mesh_bake_colors: dict(colors uint8 [V, 3], weight float32 [V], seen int32 [V]).  vis: rasterize_numpy's
+    uint64 [n_views, h, w] (or the kernel's int64 bits); frames uint8 [n_views, fh, fw, 3]; normals [V, 3] need normal_mat [n_views, 3, 3]."""
+    v = np.ascontiguousarray(np.asarray(verts), dtype=np.float32).reshape(-1, 3)
+    A, K = _raster_cameras(mesh2cam, intrinsics)
+    vis = np.ascontiguousarray(np.asarray(vis))
+    frames = np.asarray(frames)
+    n_views = len(A)
+    if vis.ndim != 3 or vis.dtype.itemsize != 8 or vis.dtype.kind not in 'iu' or vis.shape[0] != n_views:
+        raise ValueError('bake: vis must be the 64-bit [n_views, h, w] visibility buffer of the same cameras')
+    vis = vis.view(np.uint64)
+    h, w = _raster_size(vis.shape[1:])
+    if frames.dtype != np.uint8 or frames.ndim != 4 or frames.shape[0] != n_views or frames.shape[3] != 3:
+        raise ValueError('bake: frames must be uint8 [n_views, fh, fw, 3]')
+    fh, fw = _raster_size(frames.shape[1:3])
+    if not near > 0:
+        raise ValueError('bake: near must be > 0')
+    if not depth_tol >= 0:
+        raise ValueError('bake: depth_tol must be >= 0')
+    if int(guard) != guard or not 0 <= guard <= 4:
+        raise ValueError('bake: guard must be an integer in 0..4')
+    if int(power) != power or not 0 <= power <= 8:
+        raise ValueError('bake: power must be an integer in 0..8')
+    guard, power, tol, min_cos = int(guard), int(power), _F(depth_tol), _F(min_cos)
+    V = len(v)
+    if normals is not None:
+        if normal_mat is None:
+            raise ValueError('bake: normals need normal_mat')
+        normals = np.ascontiguousarray(np.asarray(normals), dtype=np.float32).reshape(-1, 3)
+        N = np.ascontiguousarray(np.asarray(normal_mat), dtype=np.float32).reshape(-1, 9)
+        if len(normals) != V or len(N) != n_views:
+            raise ValueError('bake: normals must be [V, 3] and normal_mat [n_views, 3, 3]')
+    if fallback is not None:
+        fallback = np.asarray(fallback)
+        if fallback.dtype != np.uint8 or fallback.shape != (V, 3):
+            raise ValueError('bake: fallback must be uint8 [V, 3]')
+    acc = np.zeros((V, 3), dtype=np.float32)
+    accw = np.zeros(V, dtype=np.float32)
+    seen = np.zeros(V, dtype=np.int32)
+    for view in range(n_views if V else 0):
+        with np.errstate(all='ignore'):
+            cam, near_bad, _, xc, yc = _raster_point(v, A[view], K[view], near)         # the rasteriser's vertex stage, before it snaps
+            sx, sy = xc * _F(w), yc * _F(h)
+            idx = np.nonzero(~near_bad & (sx >= 0) & (sx < _F(w)) & (sy >= 0) & (sy < _F(h)))[0]
+            p, xc, yc, sx, sy = cam[idx], xc[idx], yc[idx], sx[idx], sy[idx]
+            col, row = np.floor(sx).astype(np.int64), np.floor(sy).astype(np.int64)
+            # occlusion: the whole window, clipped to the image
+            open_ = np.ones(len(idx), dtype=bool)
+            for dr in range(-guard, guard + 1):
+                for dc in range(-guard, guard + 1):
+                    r, c = row + dr, col + dc
+                    inside = (r >= 0) & (r < h) & (c >= 0) & (c < w)
+                    key = vis[view][np.clip(r, 0, h - 1), np.clip(c, 0, w - 1)]
+                    z_pix = np.ascontiguousarray((key >> np.uint64(32)).astype(np.uint32)).view(np.float32)
+                    passes = (key != RASTER_EMPTY) & (p[:, 2] <= z_pix + tol * z_pix)
+                    open_ &= passes | ~inside
+            idx, p, xc, yc = idx[open_], p[open_], xc[open_], yc[open_]
+            wgt = np.ones(len(idx), dtype=np.float32)
+            if normals is not None:
+                n, Nv = normals[idx], N[view]
+                nc = [_dot3_f32(Nv[3 * r], Nv[3 * r + 1], Nv[3 * r + 2], n[:, 0], n[:, 1], n[:, 2]) for r in range(3)]
+                n_p = _dot3_f32(nc[0], nc[1], nc[2], p[:, 0], p[:, 1], p[:, 2])
+                nn = _dot3_f32(nc[0], nc[1], nc[2], nc[0], nc[1], nc[2])
+                pp = _dot3_f32(p[:, 0], p[:, 1], p[:, 2], p[:, 0], p[:, 1], p[:, 2])
+                cosine = (-n_p) / np.sqrt(nn * pp)
+                facing = cosine > min_cos
+                idx, p, xc, yc, cosine = idx[facing], p[facing], xc[facing], yc[facing], cosine[facing]
+                wgt = np.ones(len(idx), dtype=np.float32)
+                if power > 0:
+                    wgt = cosine
+                    for _ in range(1, power):
+                        wgt = wgt * cosine
+            # bilinear sample at the vertex's own position, the taps clamped into the frame
+            u, t = xc * _F(fw) - _F(0.5), yc * _F(fh) - _F(0.5)
+            x0f, y0f = np.floor(u), np.floor(t)
+            tx, ty = u - x0f, t - y0f
+            ux, uy = _F(1) - tx, _F(1) - ty
+            x0, y0 = x0f.astype(np.int64), y0f.astype(np.int64)
+            x1, y1 = np.clip(x0 + 1, 0, fw - 1), np.clip(y0 + 1, 0, fh - 1)
+            x0, y0 = np.clip(x0, 0, fw - 1), np.clip(y0, 0, fh - 1)
+            f = frames[view]
+            c00, c01, c10, c11 = (f[y, x].astype(np.float32) for y, x in ((y0, x0), (y0, x1), (y1, x0), (y1, x1)))
+            top = ux[:, None] * c00 + tx[:, None] * c01
+            bot = ux[:, None] * c10 + tx[:, None] * c11
+            s = uy[:, None] * top + ty[:, None] * bot
+            acc[idx] = acc[idx] + wgt[:, None] * s
+            accw[idx] = accw[idx] + wgt
+            seen[idx] += 1
+    colors = np.zeros((V, 3), dtype=np.uint8) if fallback is None else fallback.copy()
+    hit = accw > 0
+    with np.errstate(all='ignore'):
+        mean = acc[hit] / accw[hit][:, None]
+        colors[hit] = np.rint(np.fmin(np.fmax(mean, _F(0)), _F(255))).astype(np.int32).astype(np.uint8)
+    return dict(colors=colors, weight=accw, seen=seen)
+
+
+def bake_mesh_colors(verts, faces, frames, cam2world, intrinsics, mesh2world=None, normals=None, vis_size=None, **rules):
+    """Colour a mesh's vertices from frames of it: rasterise it from the frames' cameras (cam2world [n, 4, 4] and normalised intrinsics
+    [n, 3, 3], as render_mesh takes them) at vis_size (default: the frames' size), then bake (BAKE_RULES' keys and `fallback` pass through
+    `rules`) -> dict(colors uint8 [V, 3], weight float32 [V], seen int32 [V]).  CUDA tensors run the gfx950 kernels (gnerf_hip.rasterize /
+    bake_colors) and return tensors on their device; numpy arrays run the ports -- the same bits either way.  normals [V, 3] are in the mesh's
+    frame; with them the views are weighted by how squarely they face the surface."""
+    unknown = set(rules) - set(BAKE_RULES) - {'fallback'}
+    if unknown:
+        raise ValueError(f'bake: unknown rule(s) {sorted(unknown)}')
+    try:
+        import torch
+    except ImportError:                                                  # pragma: no cover - torch is part of the stack
+        torch = None
+    on_gpu = torch is not None and isinstance(verts, torch.Tensor) and verts.is_cuda
+
+    def host(x):
+        return x.detach().cpu().numpy() if torch is not None and isinstance(x, torch.Tensor) else np.asarray(x)
+    mesh2cam, normal_mat = mesh_to_camera(host(cam2world), None if mesh2world is None else host(mesh2world))
+    K = np.ascontiguousarray(host(intrinsics), dtype=np.float32).reshape(-1, 9)
+    size = tuple(frames.shape[1:3]) if vis_size is None else vis_size
+    near = rules.get('near', BAKE_RULES['near'])
+    fallback = rules.get('fallback')
+    if on_gpu:
+        import gnerf_hip
+        dev = verts.device
+        A, Kd, Nd = (torch.from_numpy(np.ascontiguousarray(x)).to(dev) for x in (mesh2cam.reshape(-1, 12), K, normal_mat.reshape(-1, 9)))
+        vis, _ = gnerf_hip.rasterize(verts, faces, A, Kd, size, near=near)
+        frames, normals, fallback = (x if x is None or isinstance(x, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(x)) for x in (frames, normals, fallback))
+        frames, normals, fallback = (None if x is None else x.to(dev) for x in (frames, normals, fallback))
+        return gnerf_hip.bake_colors(verts, A, Kd, vis, frames, normals=normals, normal_mat=Nd if normals is not None else None,
+                                     **dict(rules, fallback=fallback))
+    verts, faces, frames, normals, fallback = (None if x is None else host(x) for x in (verts, faces, frames, normals, fallback))
+    vis, _ = rasterize_numpy(verts, faces, mesh2cam, K, size, near=near)
+    return bake_colors_numpy(verts, mesh2cam, K, vis, frames, normals=normals, normal_mat=normal_mat if normals is not None else None,
+                             **dict(rules, fallback=fallback))
+
+
+def bake_report_line(baked, n_views):
+    """One line about a bake_colors / bake_mesh_colors result (tensors or arrays) from n_views frames: the number of views, the share of
+    vertices at least one of them sees, and the median number of views per seen vertex."""
+    seen = baked['seen']
+    seen = seen.detach().cpu().numpy() if hasattr(seen, 'detach') else np.asarray(seen)
+    n_seen = int((seen > 0).sum())
+    share = n_seen / len(seen) if len(seen) else 0.0
+    median = float(np.median(seen[seen > 0])) if n_seen else 0.0
+    return f'mesh bake: {int(n_views)} views, {n_seen} of {len(seen)} vertices seen ({100 * share:.1f} %), median {median:g} views per seen vertex'
 
 
 # ---------------------------------------------------------------------------------------------------------------- mesh cleaning

@@ -745,6 +745,42 @@ int gnerf_raster_resolve(const uint64_t* vis, const float* verts, int n_verts, c
                          gnerf_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * (ABI 15, added without a new version) Multi-view colour bake, the rasteriser's inverse (csrc/raster.hip): every vertex of a mesh gathers
+ * its colour from n_views frames taken by the cameras whose visibility buffers gnerf_raster_visibility made of that mesh.  Gather-only: one
+ * thread per vertex, no atomics, no workspace, one launch, no host read, capturable.  Float32, every operation rounded on its own in the order
+ * written here (no fused multiply-add); a dot product a . b is (a0 b0 + a1 b1) + a2 b2.  g-nerf_amd/shape_mi355x.py's bake_colors_numpy
+ * restates it and gives the same bits.  No UV atlas, no gradients, no filling of unseen vertices from their neighbours.
+ *   inputs: verts, mesh2cam, intrinsics, n_views, vis [n_views, h, w] and near as gnerf_raster_visibility takes and makes them; frames uint8
+ *     [n_views, fh, fw, 3] (fh, fw in 1..GNERF_RASTER_MAX_SIZE, need not equal h, w; n_views * fh * fw < 2^31); optional normals float32
+ *     [n_verts, 3] with the per-view 3x3 normal_mat [n_views, 9] of gnerf_raster_resolve; optional fallback uint8 [n_verts, 3].
+ *   per vertex, the views in ascending order; a view is SKIPPED at the first of these tests that fails:
+ *     vertex: p, iz, xn, yn, xc, yc as the rasteriser's vertex stage forms them (the same bits); p finite and p.z > near.
+ *     pixel: sx = xc w, sy = yc h; 0 <= sx < w and 0 <= sy < h, tested on the floats; col = (int)floorf(sx), row = (int)floorf(sy).
+ *     occlusion: every pixel of the (2 guard + 1)^2 window around (row, col), clipped to the image, holds a non-empty key, and with z_pix =
+ *       uint_as_float(key >> 32): p.z <= z_pix + depth_tol z_pix.  guard = 0 tests the one pixel.  An empty neighbour rejects ON PURPOSE: at a
+ *       silhouette a frame blends the surface with its background.
+ *     facing (only with normals): n_c = normal_mat n per row; c = -(n_c . p) / sqrtf((n_c . n_c)(p . p)); c > min_cos (a NaN fails).
+ *   weight: wgt = 1 without normals or with power == 0, else c multiplied by itself power - 1 times (((c c) c) ...).
+ *   sample: u = xc fw - 0.5, v = yc fh - 0.5 (texel centres at integer + 0.5); x0 = floorf(u), tx = u - x0, y0 = floorf(v), ty = v - y0; the taps
+ *     x0, x0 + 1, y0, y0 + 1 are clamped into the frame; per channel, with the uint8 texels as floats: top = (1 - tx) c00 + tx c01,
+ *     bot = (1 - tx) c10 + tx c11, s = (1 - ty) top + ty bot.
+ *   accumulate: acc[k] += wgt s[k]; accw += wgt; seen += 1.
+ *   outputs: colors uint8 [n_verts, 3] = (uint8)rintf(min(max(acc[k] / accw, 0), 255)) where accw > 0, else the vertex's fallback colour (0
+ *     without one); weight float32 [n_verts] = accw and seen int32 [n_verts] = the number of views that counted (each optional, NULL = not wanted).
+ *   The defaults of the Python layer are arguments, not measurements: depth_tol = 2^-8, guard = 1, min_cos = 0.1, power = 2.  Across one pixel of
+ *     an h-row image a surface whose normal makes the angle t with the line of sight changes its depth by z tan(t) / (fy h), relatively
+ *     tan(t) / (fy h): at the shipped camera (fy = 4.2647) and 512 rows, t = 75 degrees gives 3.73 / 2183 = 1.7e-3, and 2^-8 = 3.9e-3 is about
+ *     twice that -- a vertex anywhere inside its pixel passes on slopes up to there, a surface further behind than that is hidden.
+ * GNERF_E_ARG for null required pointers, sizes out of the rasteriser's ranges, near <= 0, depth_tol < 0, guard outside
+ * 0..GNERF_BAKE_MAX_GUARD, power outside 0..GNERF_BAKE_MAX_POWER, normals without normal_mat.  n_verts == 0 is valid: nothing is launched. */
+#define GNERF_BAKE_MAX_GUARD 4
+#define GNERF_BAKE_MAX_POWER 8
+int gnerf_mesh_bake_colors(const float* verts, int n_verts, const float* mesh2cam, const float* intrinsics, int n_views, const uint64_t* vis,
+                           int h, int w, const unsigned char* frames, int fh, int fw, const float* normals, const float* normal_mat,
+                           float near_z, float depth_tol, int guard, float min_cos, int power, const unsigned char* fallback,
+                           unsigned char* colors, float* weight, int32_t* seen, gnerf_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * (ABI 15, added without a new version) Cleaning the meshes gnerf_marching_cubes_* extracts: connected components, compaction to the kept
  * components, Taubin smoothing (csrc/mesh_clean.hip).  g-nerf_amd/shape_mi355x.py restates the rules and holds numpy ports
  * (mesh_components_numpy, mesh_select, mesh_compact_numpy, mesh_smooth_numpy) that give the same bits.
