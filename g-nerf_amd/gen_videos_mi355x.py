@@ -44,6 +44,7 @@ import numpy as np
 import torch
 
 import gnerf_harness as H
+import shape_mi355x
 
 
 def ffhq_generator_kwargs(depth_resolution=48, depth_resolution_importance=48):
@@ -324,41 +325,6 @@ def mesh_vertex_attributes(G, planes, verts, resolution, want_normals=True, want
     return (torch.cat(normals or [empty]) if want_normals else None), (torch.cat(colors or [empty.to(torch.uint8)]) if want_colors else None)
 
 
-def clean_extracted_mesh(verts, faces, clean):
-    """The first half of the --mesh-keep / --mesh-min-faces / --mesh-smooth flags on a mesh marching cubes just made: components, selection
-    and compaction (shape_mi355x.clean_mesh without smoothing), so that vertex attributes are queried at the kept vertices only, at their
-    extracted positions.  clean: shape_mi355x.clean_options' dict or None (nothing runs) -> (verts, faces, report or None)."""
-    if not clean:
-        return verts, faces, None
-    import shape_mi355x
-    cleaned = shape_mi355x.clean_mesh(verts, faces, keep_largest=clean['keep_largest'], min_faces=clean['min_faces'])
-    return cleaned.verts, cleaned.faces, cleaned.report
-
-
-def simplify_extracted_mesh(verts, faces, simplify):
-    """--mesh-simplify / --mesh-target-faces on the mesh the compaction left (shape_mi355x.simplify_mesh), before the vertex attributes are
-    queried -- at the simplified vertices -- and before the smoothing.  simplify: shape_mi355x.simplify_options' dict or None (nothing runs)
-    -> (verts, faces, report or None)."""
-    if not simplify:
-        return verts, faces, None
-    import shape_mi355x
-    simplified = shape_mi355x.simplify_mesh(verts, faces, **simplify)
-    return simplified.verts, simplified.faces, simplified.report
-
-
-def smooth_extracted_mesh(verts, faces, clean):
-    """The second half: the Taubin iterations, which move positions last (normals and colours stay those of the extracted surface)."""
-    if not clean or not clean['smooth']:
-        return verts
-    import shape_mi355x
-    if isinstance(verts, torch.Tensor) and verts.is_cuda:
-        import gnerf_hip
-        return gnerf_hip.mesh_smooth(verts, faces, clean['smooth'])
-    smoothed = shape_mi355x.mesh_smooth_numpy(verts.numpy() if isinstance(verts, torch.Tensor) else verts, faces.numpy() if isinstance(faces, torch.Tensor) else faces,
-                                              clean['smooth'])
-    return torch.from_numpy(smoothed) if isinstance(verts, torch.Tensor) else smoothed
-
-
 @torch.no_grad()
 def snap_extracted_mesh(G, planes, verts, faces, resolution, snap, level=10.0):
     """--mesh-snap: the last stage, after the smoothing.  Every vertex (index space) goes back onto the level set sigma = level of generator
@@ -371,7 +337,6 @@ def snap_extracted_mesh(G, planes, verts, faces, resolution, snap, level=10.0):
     flips (per guard round), flips_left, tol."""
     if not snap:
         return verts, None
-    import shape_mi355x
     kw = G.rendering_kwargs
     dev = planes.device
     v = (verts if isinstance(verts, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(verts))).to(dev).float().reshape(-1, 3)
@@ -418,7 +383,6 @@ def bake_extracted_mesh(verts, faces, normals, fallback, bake, resolution, cube_
     """--mesh-bake on the final mesh (index space; mesh_to_world_matrix puts it into the world): shape_mi355x.bake_mesh_colors from bake['frames']
     (uint8 [N, H, W, 3]) and their camera labels bake['labels'] [N, 25], rasterised at bake['res'] (None: the frames' size), with bake['rules'].
     normals / fallback: per-vertex arrays or tensors, or None.  Kernels when the frames are on a GPU, the numpy ports otherwise."""
-    import shape_mi355x
     frames, labels = bake['frames'], bake['labels']
     dev = frames.device
 
@@ -433,60 +397,45 @@ def bake_extracted_mesh(verts, faces, normals, fallback, bake, resolution, cube_
                                          normals=place(normals, torch.float32), vis_size=bake.get('res'), fallback=place(fallback), **bake.get('rules', {}))
 
 
-def mesh_density_grid(vol, ply_path, level=10.0, attrs=None, G=None, planes=None, clean=None, report=None, simplify=None, simplify_report=None,
-                      snap=None, snap_report=None, bake=None, bake_report=None):
-    """--mesh: the mesh shape_utils.convert_mrc makes of the .mrc of this volume (shape_utils.py:103-105: transpose(2, 1, 0), voxel
-    size 1, origin 0), made where the volume lives -- on a GPU the marching-cubes kernel reads it in HBM, only the mesh comes to the host.
+def mesh_of_density_grid(vol, level=10.0, attrs=None, G=None, planes=None, clean=None, simplify=None, snap=None, bake=None):
+    """The mesh shape_utils.convert_mrc makes of the .mrc of this volume (shape_utils.py:103-105: transpose(2, 1, 0), voxel size 1, origin 0),
+    made where the volume lives -- on a GPU the marching-cubes kernel reads it in HBM -- and taken through shape_mi355x.finish_mesh, which
+    states the order of the stages -> (its FinishedMesh, on the volume's route and in index space, as the reference's; seconds spent in
+    marching cubes).
     attrs: None / 'none', 'normals', 'colors' or 'all' -- per-vertex attributes (mesh_vertex_attributes) of generator G on `planes`
-    (extract_density_grid(..., return_planes=True)), evaluated on the device too; the vertices stay in index space, as the reference's.
-    clean: None or shape_mi355x.clean_options' dict -- marching cubes, then components and compaction, then the attributes (at the kept
-    vertices' extracted positions), then smoothing.  report: a dict that receives clean_mesh's report when the mesh was cleaned (left as
-    it is otherwise).  simplify: None or shape_mi355x.simplify_options' dict -- the mesh is simplified between the compaction and the
-    attributes; simplify_report: a dict that then receives simplify_mesh's report.  snap: None or shape_mi355x.snap_options' dict -- the order
-    becomes marching cubes, compaction, simplification, smoothing, snap_extracted_mesh (snap_report receives its report), and the attributes
-    are evaluated at the snapped positions; with snap None the order and the file's bytes are those of a call without it.
-    bake: None or bake_extracted_mesh's dict (frames, labels, res, rules) -- last of all the final mesh is coloured from those frames, with the
-    normals when attrs made them and the decoder's colours, when it made them, as the fallback; the result becomes the file's colours and
-    bake_report receives it (colors, weight, seen).
-    Writes `ply_path`; returns (vertex count, triangle count, seconds spent in marching cubes)."""
-    import shape_mi355x
+    (extract_density_grid(..., return_planes=True)).  clean, simplify, snap: None or shape_mi355x.clean_options' / simplify_options' /
+    snap_options' dict (snap_extracted_mesh on G and `planes`).  bake: None or bake_extracted_mesh's dict (frames, labels, res, rules) -- the
+    final mesh is coloured from those frames, with the normals when attrs made them and the decoder's colours, when it made them, as the fallback.
+    With every option None nothing but marching cubes runs."""
     attrs = 'none' if attrs is None else attrs
     if attrs not in MESH_ATTRS:
         raise ValueError(f'mesh_density_grid: attrs must be one of {MESH_ATTRS}')
     if (attrs != 'none' or snap) and (G is None or planes is None):
         raise ValueError('mesh_density_grid: vertex attributes and the snap need the generator G and the planes the volume was made from')
+    if bake and G is None:
+        raise ValueError('mesh_density_grid: the bake needs the generator G (its box)')
+    res = vol.shape[0]
     t0 = time.perf_counter()
     verts, faces = shape_mi355x.marching_cubes(vol.permute(2, 1, 0).contiguous(), level)     # (reads its counts: synchronised)
     dt = time.perf_counter() - t0
-    verts, faces, cleaned = clean_extracted_mesh(verts, faces, clean)
-    if report is not None and cleaned is not None:
-        report.update(cleaned)
-    verts, faces, simplified = simplify_extracted_mesh(verts, faces, simplify)
-    if simplify_report is not None and simplified is not None:
-        simplify_report.update(simplified)
-    normals = colors = None
-    if snap:                                                 # smoothing, then the snap, then the attributes: at the final positions
-        verts = smooth_extracted_mesh(verts, faces, clean)
-        verts, snapped = snap_extracted_mesh(G, planes, verts, faces, vol.shape[0], snap, level=level)
-        if snap_report is not None and snapped is not None:
-            snap_report.update(snapped)
+    stages = {}
+    if snap:
+        stages['snap'] = lambda v, f: snap_extracted_mesh(G, planes, v, f, res, snap, level=level)
     if attrs != 'none':
-        v = verts if isinstance(verts, torch.Tensor) else torch.from_numpy(verts).to(vol.device)
-        normals, colors = mesh_vertex_attributes(G, planes, v, vol.shape[0], attrs in ('normals', 'all'), attrs in ('colors', 'all'))
-        normals, colors = (None if t is None else t.cpu().numpy() for t in (normals, colors))
-    if not snap:
-        verts = smooth_extracted_mesh(verts, faces, clean)
+        stages['attributes'] = lambda v: mesh_vertex_attributes(G, planes, torch.as_tensor(v).to(vol.device), res, attrs in ('normals', 'all'),
+                                                                attrs in ('colors', 'all'))
     if bake:
-        if G is None:
-            raise ValueError('mesh_density_grid: the bake needs the generator G (its box)')
-        baked = bake_extracted_mesh(verts, faces, normals, colors, bake, vol.shape[0], G.rendering_kwargs['box_warp'])
-        colors = baked['colors'].cpu().numpy() if isinstance(baked['colors'], torch.Tensor) else baked['colors']
-        if bake_report is not None:
-            bake_report.update(baked)
-    if isinstance(verts, torch.Tensor):
-        verts, faces = verts.cpu().numpy(), faces.cpu().numpy()
+        stages['bake'] = lambda v, f, normals, colors: bake_extracted_mesh(v, f, normals, colors, bake, res, G.rendering_kwargs['box_warp'])
+    return shape_mi355x.finish_mesh(verts, faces, clean=clean, simplify=simplify, **stages), dt
+
+
+def mesh_density_grid(vol, ply_path, level=10.0, **options):
+    """--mesh: write mesh_of_density_grid(vol, level, **options) to `ply_path`, with its normals and its colours -- the baked ones when it baked.
+    Returns (vertex count, triangle count, seconds spent in marching cubes), with the FinishedMesh (the reports) as its attribute `mesh`."""
+    mesh, dt = mesh_of_density_grid(vol, level, **options)
+    verts, faces, normals, colors = (shape_mi355x.to_host(x) for x in (mesh.verts, mesh.faces, mesh.normals, mesh.baked['colors'] if mesh.baked else mesh.colors))
     shape_mi355x.write_ply(ply_path, verts, faces, normals=normals, colors=colors)
-    return len(verts), len(faces), dt
+    return shape_mi355x.Written((len(verts), len(faces), dt), mesh)
 
 
 @torch.no_grad()
@@ -495,26 +444,23 @@ def render_geometry_orbit(verts, faces, n_frames, res, voxel_res, cube_length, r
     """This rank's shaded geometry frames of the orbit, uint8 [n_local, res, res, 3] on verts' device (None for an empty share): the mesh of a
     voxel_res^3 density volume (index space; mesh_to_world_matrix puts it into the world) drawn from the orbit's cameras, frames_per_call
     views per rasteriser call, on the pixel grid of image_raw / image_depth at that resolution.  CUDA tensors take the kernels, CPU tensors
-    the numpy port (shape_mi355x.render_mesh)."""
-    import shape_mi355x
+    and numpy arrays the numpy port (shape_mi355x.render_mesh)."""
     lo, hi = H.shard_range(n_frames, rank, world)
     if hi == lo:
         return None, (lo, hi)
     labels = H.orbit_labels(range(lo, hi), n_frames, radius)
     mesh2world = mesh_to_world_matrix(voxel_res, cube_length)
     k = max(int(frames_per_call), 1)
-    on_gpu = verts.is_cuda
-    mesh = [t if (t is None or on_gpu) else t.numpy() for t in (verts, faces, normals, colors)]
     frames = []
     for j in range(0, hi - lo, k):
         c = labels[j:j + k]
-        out = shape_mi355x.render_mesh(mesh[0], mesh[1], c[:, :16].reshape(-1, 4, 4), c[:, 16:25].reshape(-1, 3, 3), res, mesh2world=mesh2world,
-                                       normals=mesh[2], colors=mesh[3], shading=shading, outputs=('frame',))
-        frames.append(out['frame'] if on_gpu else torch.from_numpy(out['frame']))
+        out = shape_mi355x.render_mesh(verts, faces, c[:, :16].reshape(-1, 4, 4), c[:, 16:25].reshape(-1, 3, 3), res, mesh2world=mesh2world,
+                                       normals=normals, colors=colors, shading=shading, outputs=('frame',))
+        frames.append(torch.as_tensor(out['frame']))
     return torch.cat(frames), (lo, hi)
 
 
-def main():
+def arg_parser():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument('--network', help='generator pickle (G_ema)')
     ap.add_argument('--encoder', help='identity encoder pickle (E)')
@@ -533,13 +479,7 @@ def main():
     ap.add_argument('--mesh', default=None, help='also mesh the density volume on the device and write this .ply (shape_utils.py; rank 0)')
     ap.add_argument('--mesh-level', type=float, default=10, help='isosurface level of --mesh (shape_utils.py:111)')
     ap.add_argument('--mesh-attrs', choices=MESH_ATTRS, default='none', help='per-vertex attributes of --mesh: normals of the density field and / or the decoder\'s colours')
-    ap.add_argument('--mesh-keep', type=int, default=0, help='keep only this many of the largest connected components of the mesh (--mesh and --geometry-out; 0: all)')
-    ap.add_argument('--mesh-min-faces', type=int, default=0, help='drop connected components with fewer triangles than this (0: none)')
-    ap.add_argument('--mesh-smooth', type=int, default=0, help='Taubin smoothing iterations of the mesh, applied last (lambda 0.5, mu -0.53, boundaries pinned; 0: none)')
-    ap.add_argument('--mesh-simplify', type=float, default=0, metavar='CELL',
-                    help='simplify the mesh by vertex clustering on a grid of cells this many voxels wide, after the components, before the attributes and the smoothing (0: off)')
-    ap.add_argument('--mesh-target-faces', type=int, default=0, metavar='N',
-                    help='pick the cell instead: the smallest of CELL (or one voxel) * 2^(j / 4), j = 0 .. 40, that leaves at most N triangles (0: off)')
+    shape_mi355x.add_mesh_arguments(ap, attributes=True)
     ap.add_argument('--mesh-snap', type=float, default=0, metavar='R',
                     help='last, after the smoothing: move every vertex onto the level set of the density itself (Newton steps along its gradient), at most '
                          'R voxels per axis from where it stood; faces that this turns over get their vertices back (--mesh and --geometry-out; 0: off)')
@@ -557,11 +497,13 @@ def main():
                                                          'uint8 [F, H, W, 3]) and write them to this .npy (rank 0); uses --voxel-res, --mesh-level, --mesh-attrs, --frames-per-call')
     ap.add_argument('--geometry-res', type=int, default=512, help='resolution of the geometry frames')
     ap.add_argument('--no-solver-search', action='store_true', help='leave torch.backends.cudnn.benchmark off (MIOpen takes its first heuristic pick per shape)')
+    return ap
+
+
+def main():
+    ap = arg_parser()
     args = ap.parse_args()
-    if min(args.mesh_keep, args.mesh_min_faces, args.mesh_smooth) < 0:
-        ap.error('--mesh-keep, --mesh-min-faces and --mesh-smooth must be >= 0')
-    if not args.mesh_simplify >= 0 or args.mesh_simplify == float('inf') or args.mesh_target_faces < 0:
-        ap.error('--mesh-simplify and --mesh-target-faces must be >= 0')
+    clean, simplify, snap = shape_mi355x.mesh_options_from_args(args, ap)
     if args.mesh_bake and not args.mesh:
         ap.error('--mesh-bake requires --mesh')
     if not 0 <= args.mesh_bake <= args.frames:
@@ -569,13 +511,6 @@ def main():
     if (not args.mesh_bake_tol >= 0 or not 0 <= args.mesh_bake_guard <= 4 or not 0 <= args.mesh_bake_power <= 8
             or (args.mesh_bake_res is not None and not 1 <= args.mesh_bake_res <= 4096)):
         ap.error('--mesh-bake-tol must be >= 0, --mesh-bake-guard 0..4, --mesh-bake-power 0..8, --mesh-bake-res 1..4096')
-    import shape_mi355x
-    clean = shape_mi355x.clean_options(args.mesh_keep, args.mesh_min_faces, args.mesh_smooth)
-    simplify = shape_mi355x.simplify_options(args.mesh_simplify, args.mesh_target_faces)
-    try:
-        snap = shape_mi355x.snap_options(args.mesh_snap, args.mesh_snap_steps, args.mesh_snap_tol)
-    except ValueError as err:
-        ap.error(str(err))
     H.configure_backend(False if args.no_solver_search else None)
 
     rank, world, local_rank = H.init_from_env()
@@ -611,6 +546,7 @@ def main():
         if args.out:
             np.save(args.out, full.cpu().numpy())
     made = {}
+    stages = dict(attrs=args.mesh_attrs, G=G, clean=clean, simplify=simplify, snap=snap)         # of the mesh, for --mesh and --geometry-out alike
 
     def volume_and_planes():                                             # made once per process, whichever option asks first
         if 'vol' not in made:
@@ -633,56 +569,34 @@ def main():
             shape_mi355x.write_mrc(args.shapes_mrc, vol.cpu().numpy())
         if args.mesh:
             t0 = time.perf_counter()
-            report, simplify_report, snap_report, bake_report = {}, {}, {}, {}
             bake = None
             if args.mesh_bake:                                           # N of the frames this run has just gathered, and their cameras
                 _, bake_frames, bake_labels = bake_frames_of_orbit(full, args.frames, args.mesh_bake, G.rendering_kwargs['avg_camera_radius'])
                 bake = dict(frames=bake_frames, labels=bake_labels, res=args.mesh_bake_res,
                             rules=dict(depth_tol=args.mesh_bake_tol, guard=args.mesh_bake_guard, power=args.mesh_bake_power))
-            nv, nf, dt = mesh_density_grid(vol, args.mesh, args.mesh_level, attrs=args.mesh_attrs, G=G, planes=planes, clean=clean, report=report,
-                                           simplify=simplify, simplify_report=simplify_report, snap=snap, snap_report=snap_report, bake=bake,
-                                           bake_report=bake_report)
-            if report:
-                print(shape_mi355x.clean_report_line(report, args.mesh_smooth))
-            if simplify_report:
-                print(shape_mi355x.simplify_report_line(simplify_report))
-            if snap_report:
-                print(shape_mi355x.snap_report_line(snap_report))
-            if bake_report:
-                print(shape_mi355x.bake_report_line(bake_report, args.mesh_bake))
+            nv, nf, dt = written = mesh_density_grid(vol, args.mesh, args.mesh_level, planes=planes, bake=bake, **stages)
+            made['mesh'] = written.mesh
+            for line in shape_mi355x.report_lines(written.mesh.reports, smooth=args.mesh_smooth, bake_views=args.mesh_bake):
+                print(line)
             print(f'mesh at level {args.mesh_level:g}: {dt * 1e3:.2f} ms, {nv} vertices, {nf} triangles -> {args.mesh}'
                   + (f' (with {args.mesh_attrs}: {(time.perf_counter() - t0) * 1e3:.2f} ms in all, file included)' if args.mesh_attrs != 'none' else ''))
     if args.geometry_out:
-        # every rank meshes the volume itself (the same bits everywhere: no mesh travels between ranks), then draws its share of the cameras
+        # every rank meshes the volume itself (the same bits everywhere: no mesh travels between ranks), then draws its share of the cameras;
+        # rank 0 draws the mesh --mesh has just made and reported, when it has
         vol, planes = volume_and_planes()
-        verts, faces = shape_mi355x.marching_cubes(vol.permute(2, 1, 0).contiguous(), args.mesh_level)
-        verts, faces, report = clean_extracted_mesh(verts, faces, clean)
-        if report is not None and rank == 0 and not args.mesh:           # (--mesh has printed the same line)
-            print(shape_mi355x.clean_report_line(report, args.mesh_smooth))
-        verts, faces, report = simplify_extracted_mesh(verts, faces, simplify)
-        if report is not None and rank == 0 and not args.mesh:
-            print(shape_mi355x.simplify_report_line(report))
-        if not isinstance(verts, torch.Tensor):
-            verts, faces = torch.from_numpy(verts), torch.from_numpy(faces)
-        normals = colors = None
-        if snap:                                                         # smoothing, then the snap, then the attributes: at the final positions
-            verts = smooth_extracted_mesh(verts, faces, clean)
-            verts, report = snap_extracted_mesh(G, planes, verts, faces, args.voxel_res, snap, level=args.mesh_level)
-            if report is not None and rank == 0 and not args.mesh:
-                print(shape_mi355x.snap_report_line(report))
-        if args.mesh_attrs != 'none':
-            normals, colors = mesh_vertex_attributes(G, planes, verts.to(device), args.voxel_res, args.mesh_attrs in ('normals', 'all'), args.mesh_attrs in ('colors', 'all'))
-            if not verts.is_cuda:
-                normals, colors = (None if t is None else t.cpu() for t in (normals, colors))
-        if not snap:
-            verts = smooth_extracted_mesh(verts, faces, clean)
+        if 'mesh' not in made:
+            made['mesh'], _ = mesh_of_density_grid(vol, args.mesh_level, planes=planes, **stages)
+            if rank == 0:
+                for line in shape_mi355x.report_lines(made['mesh'].reports, smooth=args.mesh_smooth):
+                    print(line)
+        verts, faces, normals, colors = made['mesh'][:4]                 # (the decoder's colours, also after a bake)
         if device.type == 'cuda':
             torch.cuda.synchronize()
         t0 = time.perf_counter()
         geo, _ = render_geometry_orbit(verts, faces, args.frames, args.geometry_res, args.voxel_res, G.rendering_kwargs['box_warp'],
                                        G.rendering_kwargs['avg_camera_radius'], rank, world, args.frames_per_call, normals=normals, colors=colors)
         if geo is None:
-            geo = torch.zeros([0, args.geometry_res, args.geometry_res, 3], dtype=torch.uint8, device=verts.device)
+            geo = torch.zeros([0, args.geometry_res, args.geometry_res, 3], dtype=torch.uint8)
         full_geo = H.gather_frames(geo.to(device), args.frames)
         if device.type == 'cuda':
             torch.cuda.synchronize()
@@ -691,6 +605,7 @@ def main():
             print(f'geometry frames: {args.frames} at {args.geometry_res}x{args.geometry_res} of {len(faces)} triangles in {dt:.3f} s = {args.frames / dt:.2f} frames/s '
                   f'-> {args.geometry_out}')
             np.save(args.geometry_out, full_geo.cpu().numpy())
+
 
 if __name__ == '__main__':
     main()

@@ -33,6 +33,8 @@ simplify_mesh shrinks such a mesh: vertex clustering on a uniform grid with a qu
 target face count.  CUDA tensors go to csrc/mesh_simplify.hip (gnerf_hip.mesh_simplify / mesh_simplify_count), numpy arrays to
 mesh_simplify_numpy below (include/gnerf_hip.h, gnerf_mesh_simplify_*): the same bits.
 
+finish_mesh walks these stages, and those that need a generator (given as callables), in the one order both CLIs use.
+
 CLI, as shape_utils.py's (:102-123):  python shape_mi355x.py INPUT [--level 10]   (INPUT: a .mrc / .npy file or a directory of them)
   [--mesh-keep K] [--mesh-min-faces N] [--mesh-smooth ITERS] clean the mesh first (all 0 by default: the file is the uncleaned one, byte for byte)
   [--mesh-simplify CELL] [--mesh-target-faces N] simplify it between the compaction and the smoothing (both 0 by default: nothing runs)
@@ -47,6 +49,55 @@ import sys
 import time
 
 import numpy as np
+
+
+# ---------------------------------------------------------------------------------------------------------------- the two routes
+# Every function below that names two implementations chooses between them here: a CUDA tensor takes the gfx950 kernels (gnerf_hip) and
+# stays on its device, anything else -- a numpy array, a list, a CPU tensor -- is brought to the host as numpy and takes the ports.
+def _torch():
+    """torch, or None where it is not installed (the numpy route needs none)."""
+    try:
+        import torch
+    except ImportError:                                                  # pragma: no cover - torch is part of the stack
+        return None
+    return torch
+
+
+def is_gpu(x):
+    """Whether x takes the GPU route: it is a CUDA tensor."""
+    torch = sys.modules.get('torch')                                     # (a tensor in hand means torch is loaded)
+    return torch is not None and isinstance(x, torch.Tensor) and x.is_cuda
+
+
+def to_host(x):
+    """x on the host as numpy: a tensor of any device is copied over, None stays None, anything else goes through np.asarray."""
+    if x is None:
+        return None
+    return x.detach().cpu().numpy() if hasattr(x, 'detach') else np.asarray(x)
+
+
+_MeshRoute = collections.namedtuple('_MeshRoute', 'xp rasterize resolve bake_colors components compact smooth simplify simplify_count')
+
+
+def _mesh_route(verts, faces):
+    """The route a mesh takes, chosen once per call of render_mesh, bake_mesh_colors, clean_mesh, simplify_mesh and finish_mesh -> (route, verts,
+    faces): the kernels and torch for CUDA tensors, left where they are; the numpy ports and numpy for anything else, brought to the host.
+    route.xp is the array module: what the callers do to the arrays themselves is spelled alike in both."""
+    if is_gpu(verts):
+        import gnerf_hip as g
+        return (_MeshRoute(_torch(), g.rasterize, g.resolve, g.bake_colors, g.mesh_components, g.mesh_compact, g.mesh_smooth, g.mesh_simplify,
+                           g.mesh_simplify_count), verts.detach().reshape(-1, 3).float(), faces)
+    return (_MeshRoute(np, rasterize_numpy, resolve_numpy, bake_colors_numpy, mesh_components_numpy, mesh_compact_numpy, mesh_smooth_numpy, mesh_simplify_numpy,
+                       lambda *mesh: mesh_simplify_numpy(*mesh, count_only=True)), np.asarray(to_host(verts), dtype=np.float32).reshape(-1, 3), to_host(faces))
+
+
+def _on_route(x, like):
+    """x (an array, a tensor or None) where `like` lives: a tensor on its device when `like` takes the GPU route, numpy on the host otherwise."""
+    if x is None or not is_gpu(like):
+        return to_host(x)
+    torch = _torch()
+    return (x if isinstance(x, torch.Tensor) else torch.from_numpy(np.array(x))).to(like.device)      # (a copy: x may be a read-only view)
+
 
 # ---------------------------------------------------------------------------------------------------------------- the case table
 # Corner c of a cell sits at offset (c >> 2 & 1, c >> 1 & 1, c & 1) along axes (0, 1, 2) from the cell's lower corner, so corners are
@@ -247,21 +298,13 @@ def marching_cubes(volume, level, spacing=1.0, origin=(0.0, 0.0, 0.0)):
     `spacing` (a scalar or one per axis) plus `origin`; with the defaults nothing is applied."""
     s, o = _spacing_origin(spacing, origin)
     identity = bool(np.all(s == 1) and np.all(o == 0))
-    try:
-        import torch
-    except ImportError:                                                  # pragma: no cover - torch is part of the stack
-        torch = None
-    if torch is not None and isinstance(volume, torch.Tensor):
-        if volume.is_cuda:
-            import gnerf_hip
-            verts, faces = gnerf_hip.marching_cubes(volume, level)
-            if not identity:
-                verts = verts * torch.from_numpy(s.copy()).to(verts.device) + torch.from_numpy(o.copy()).to(verts.device)
-            return verts, faces
-        volume = volume.detach().numpy()
-    verts, faces = marching_cubes_numpy(volume, level)
+    if is_gpu(volume):
+        import gnerf_hip
+        verts, faces = gnerf_hip.marching_cubes(volume, level)
+    else:
+        verts, faces = marching_cubes_numpy(to_host(volume), level)
     if not identity:
-        verts = verts * s + o
+        verts = verts * _on_route(s, verts) + _on_route(o, verts)
     return verts, faces
 
 
@@ -532,35 +575,25 @@ def mesh_to_camera(cam2world, mesh2world=None):
     return full[:, :3, :].astype(np.float32), np.linalg.inv(lin).transpose(0, 2, 1).astype(np.float32)
 
 
+def _cameras_on_route(verts, cam2world, intrinsics, mesh2world):
+    """render_mesh's and bake_mesh_colors' cameras, made on the host (mesh_to_camera) and put where verts live -> (mesh2cam [n, 12],
+    intrinsics [n, 9], normal_mat [n, 9]), float32."""
+    mesh2cam, normal_mat = mesh_to_camera(to_host(cam2world), to_host(mesh2world))
+    K = np.ascontiguousarray(to_host(intrinsics), dtype=np.float32).reshape(-1, 9)
+    return tuple(_on_route(x, verts) for x in (mesh2cam.reshape(-1, 12), K, normal_mat.reshape(-1, 9)))
+
+
 def render_mesh(verts, faces, cam2world, intrinsics, size, mesh2world=None, normals=None, colors=None, near=0.01, cull='none', shading=None,
                 outputs=('tri_id', 'depth', 'normal', 'frame')):
     """Draw a triangle mesh from n cameras (cam2world [n, 4, 4] and normalised intrinsics [n, 3, 3]: what a camera label holds) on the
     renderer's pixel grid -> dict of `outputs` (tri_id, depth as image_depth measures it, camera-frame normal, shaded uint8 frame) plus
     'counts'.  CUDA tensors run the gfx950 kernels (gnerf_hip.rasterize / resolve) and return tensors on their device; numpy arrays run
     the numpy port -- the same bits either way.  normals [V, 3] are in the mesh's frame (mesh_vertex_attributes'), colors uint8 [V, 3]."""
-    try:
-        import torch
-    except ImportError:                                                  # pragma: no cover - torch is part of the stack
-        torch = None
-    on_gpu = torch is not None and isinstance(verts, torch.Tensor) and verts.is_cuda
-
-    def host(x):
-        return x.detach().cpu().numpy() if torch is not None and isinstance(x, torch.Tensor) else np.asarray(x)
-    mesh2cam, normal_mat = mesh_to_camera(host(cam2world), None if mesh2world is None else host(mesh2world))
-    K = np.ascontiguousarray(host(intrinsics), dtype=np.float32).reshape(-1, 9)
-    if on_gpu:
-        import gnerf_hip
-        dev = verts.device
-        A, Kd, Nd = (torch.from_numpy(np.ascontiguousarray(x)).to(dev) for x in (mesh2cam.reshape(-1, 12), K, normal_mat.reshape(-1, 9)))
-        vis, counts = gnerf_hip.rasterize(verts, faces, A, Kd, size, near=near, cull=cull)
-        out = gnerf_hip.resolve(vis, verts, faces, A, Kd, normals=normals, normal_mat=Nd if normals is not None else None, colors=colors,
-                                shading=shading, outputs=outputs)
-        out['counts'] = counts
-        return out
-    if torch is not None:
-        verts, faces, normals, colors = (None if x is None else host(x) for x in (verts, faces, normals, colors))
-    vis, counts = rasterize_numpy(verts, faces, mesh2cam, K, size, near=near, cull=cull)
-    out = resolve_numpy(vis, verts, faces, mesh2cam, K, normals=normals, normal_mat=normal_mat if normals is not None else None, colors=colors,
+    route, verts, faces = _mesh_route(verts, faces)
+    mesh2cam, K, normal_mat = _cameras_on_route(verts, cam2world, intrinsics, mesh2world)
+    normals, colors = _on_route(normals, verts), _on_route(colors, verts)
+    vis, counts = route.rasterize(verts, faces, mesh2cam, K, size, near=near, cull=cull)
+    out = route.resolve(vis, verts, faces, mesh2cam, K, normals=normals, normal_mat=normal_mat if normals is not None else None, colors=colors,
                         shading=shading, outputs=outputs)
     out['counts'] = counts
     return out
@@ -684,39 +717,19 @@ def bake_mesh_colors(verts, faces, frames, cam2world, intrinsics, mesh2world=Non
     unknown = set(rules) - set(BAKE_RULES) - {'fallback'}
     if unknown:
         raise ValueError(f'bake: unknown rule(s) {sorted(unknown)}')
-    try:
-        import torch
-    except ImportError:                                                  # pragma: no cover - torch is part of the stack
-        torch = None
-    on_gpu = torch is not None and isinstance(verts, torch.Tensor) and verts.is_cuda
-
-    def host(x):
-        return x.detach().cpu().numpy() if torch is not None and isinstance(x, torch.Tensor) else np.asarray(x)
-    mesh2cam, normal_mat = mesh_to_camera(host(cam2world), None if mesh2world is None else host(mesh2world))
-    K = np.ascontiguousarray(host(intrinsics), dtype=np.float32).reshape(-1, 9)
     size = tuple(frames.shape[1:3]) if vis_size is None else vis_size
-    near = rules.get('near', BAKE_RULES['near'])
-    fallback = rules.get('fallback')
-    if on_gpu:
-        import gnerf_hip
-        dev = verts.device
-        A, Kd, Nd = (torch.from_numpy(np.ascontiguousarray(x)).to(dev) for x in (mesh2cam.reshape(-1, 12), K, normal_mat.reshape(-1, 9)))
-        vis, _ = gnerf_hip.rasterize(verts, faces, A, Kd, size, near=near)
-        frames, normals, fallback = (x if x is None or isinstance(x, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(x)) for x in (frames, normals, fallback))
-        frames, normals, fallback = (None if x is None else x.to(dev) for x in (frames, normals, fallback))
-        return gnerf_hip.bake_colors(verts, A, Kd, vis, frames, normals=normals, normal_mat=Nd if normals is not None else None,
-                                     **dict(rules, fallback=fallback))
-    verts, faces, frames, normals, fallback = (None if x is None else host(x) for x in (verts, faces, frames, normals, fallback))
-    vis, _ = rasterize_numpy(verts, faces, mesh2cam, K, size, near=near)
-    return bake_colors_numpy(verts, mesh2cam, K, vis, frames, normals=normals, normal_mat=normal_mat if normals is not None else None,
+    route, verts, faces = _mesh_route(verts, faces)
+    mesh2cam, K, normal_mat = _cameras_on_route(verts, cam2world, intrinsics, mesh2world)
+    frames, normals, fallback = (_on_route(x, verts) for x in (frames, normals, rules.get('fallback')))
+    vis, _ = route.rasterize(verts, faces, mesh2cam, K, size, near=rules.get('near', BAKE_RULES['near']))
+    return route.bake_colors(verts, mesh2cam, K, vis, frames, normals=normals, normal_mat=normal_mat if normals is not None else None,
                              **dict(rules, fallback=fallback))
 
 
 def bake_report_line(baked, n_views):
     """One line about a bake_colors / bake_mesh_colors result (tensors or arrays) from n_views frames: the number of views, the share of
     vertices at least one of them sees, and the median number of views per seen vertex."""
-    seen = baked['seen']
-    seen = seen.detach().cpu().numpy() if hasattr(seen, 'detach') else np.asarray(seen)
+    seen = to_host(baked['seen'])
     n_seen = int((seen > 0).sum())
     share = n_seen / len(seen) if len(seen) else 0.0
     median = float(np.median(seen[seen > 0])) if n_seen else 0.0
@@ -864,6 +877,13 @@ def mesh_smooth_numpy(verts, faces, iterations, lam=0.5, mu=-0.53, pin_boundary=
     return cur
 
 
+def _gather(attribute, src_vertex):
+    """A per-vertex attribute (or None) at the vertices src_vertex names: with a device index on the GPU route, on the host otherwise."""
+    if attribute is None:
+        return None
+    return _on_route(attribute, src_vertex)[src_vertex.long() if is_gpu(src_vertex) else src_vertex]
+
+
 def clean_mesh(verts, faces, keep_largest=0, min_faces=0, smooth=0, lam=0.5, mu=-0.53, pin_boundary=True, normals=None, colors=None):
     """Keep the large pieces of a mesh, drop the rest, fair the surface: components -> selection (keep_largest: at most that many components,
     0 = no limit; min_faces: only components with at least that many faces) -> compaction -> `smooth` Taubin iterations.  CUDA tensors run the
@@ -871,39 +891,19 @@ def clean_mesh(verts, faces, keep_largest=0, min_faces=0, smooth=0, lam=0.5, mu=
     run the numpy ports and return numpy arrays -- the same bits either way.  -> CleanedMesh(verts, faces, normals, colors, src_vertex, report):
     normals / colors are the given per-vertex arrays gathered at the kept vertices (None when not given; smoothing does not touch them), src_vertex
     the old index of every new vertex, report a dict: components, kept, faces, kept_faces, share (kept_faces / faces), vertices, kept_vertices."""
-    try:
-        import torch
-    except ImportError:                                                  # pragma: no cover - torch is part of the stack
-        torch = None
-    on_gpu = torch is not None and isinstance(verts, torch.Tensor) and verts.is_cuda
-    if on_gpu:
-        import gnerf_hip
-        dev = verts.device
-        label, faces_of, counts = gnerf_hip.mesh_components(faces, len(verts))
-        roots = torch.nonzero(faces_of).reshape(-1)                      # only the labels and their face counts travel to the host
-        sizes = faces_of[roots].cpu().numpy()
-        kept = mesh_select(sizes, keep_largest, min_faces, labels=roots.cpu().numpy())
-        keep = torch.zeros(len(verts), dtype=torch.uint8, device=dev)
-        keep[torch.from_numpy(kept).to(dev)] = 1
-        v, f, src = gnerf_hip.mesh_compact(verts, faces, label, faces_of, keep)
-        index = src.long()
-        normals, colors = (None if t is None else t.to(dev)[index] for t in (normals, colors))
-        if smooth:
-            v = gnerf_hip.mesh_smooth(v, f, smooth, lam, mu, pin_boundary)
-        kept_faces, n_faces = int(sizes[np.isin(roots.cpu().numpy(), kept)].sum()), int(sizes.sum())
-    else:
-        if torch is not None:
-            verts, faces, normals, colors = (t.detach().cpu().numpy() if isinstance(t, torch.Tensor) else t for t in (verts, faces, normals, colors))
-        verts = np.asarray(verts, dtype=np.float32).reshape(-1, 3)
-        label, faces_of, counts = mesh_components_numpy(faces, len(verts))
-        kept = mesh_select(faces_of, keep_largest, min_faces)
-        keep = np.zeros(len(verts), dtype=np.uint8)
-        keep[kept] = 1
-        v, f, src = mesh_compact_numpy(verts, faces, label, faces_of, keep)
-        normals, colors = (None if t is None else np.asarray(t)[src] for t in (normals, colors))
-        if smooth:
-            v = mesh_smooth_numpy(v, f, smooth, lam, mu, pin_boundary)
-        kept_faces, n_faces = int(faces_of[kept].sum()), int(faces_of.sum(dtype=np.int64))
+    route, verts, faces = _mesh_route(verts, faces)
+    xp = route.xp
+    label, faces_of, counts = route.components(faces, len(verts))
+    roots = xp.where(faces_of > 0)[0]                                    # of the GPU route's arrays only the labels with faces and
+    roots, sizes = to_host(roots), to_host(faces_of[roots])             # their face counts travel to the host, for the selection
+    kept = mesh_select(sizes, keep_largest, min_faces, labels=roots)
+    keep = xp.zeros_like(faces_of, dtype=xp.uint8)
+    keep[_on_route(kept, keep)] = 1
+    v, f, src = route.compact(verts, faces, label, faces_of, keep)
+    normals, colors = _gather(normals, src), _gather(colors, src)
+    if smooth:
+        v = route.smooth(v, f, smooth, lam, mu, pin_boundary)
+    kept_faces, n_faces = int(sizes[np.isin(roots, kept)].sum(dtype=np.int64)), int(sizes.sum(dtype=np.int64))
     report = dict(components=int(counts[0]), kept=int(len(kept)), faces=n_faces, kept_faces=kept_faces, share=kept_faces / n_faces if n_faces else 1.0,
                   vertices=int(len(verts)), kept_vertices=int(len(v)))
     return CleanedMesh(v, f, normals, colors, src, report)
@@ -1106,30 +1106,15 @@ def simplify_mesh(verts, faces, cell=None, target_faces=0, origin=None, normals=
     return numpy arrays -- the same bits either way.  -> SimplifiedMesh(verts, faces, normals, colors, src_vertex, vertex_map, report): normals /
     colors are the given per-vertex arrays gathered at src_vertex (None when not given), report a dict: cell, origin, target_faces, j and
     count_calls (None / 0 without a target), met, vertices, faces, new_vertices, new_faces, invalid, collapsed, absorbed, multi."""
-    try:
-        import torch
-    except ImportError:                                                  # pragma: no cover - torch is part of the stack
-        torch = None
     target_faces = int(target_faces)
     if target_faces < 0:
         raise ValueError(f'simplify_mesh: target_faces must be >= 0, got {target_faces}')
     if cell is None and target_faces == 0:
         raise ValueError('simplify_mesh: give a cell, a target_faces > 0, or both')
-    on_gpu = torch is not None and isinstance(verts, torch.Tensor) and verts.is_cuda
-    if on_gpu:
-        import gnerf_hip
-        dev = verts.device
-        verts = verts.detach().reshape(-1, 3).to(torch.float32)
-        finite = verts[torch.isfinite(verts).all(dim=1)]
-        lo_hi = torch.stack([finite.min(dim=0).values, finite.max(dim=0).values]).cpu().numpy() if len(finite) else np.zeros((2, 3), np.float32)
-        count = lambda c, o: gnerf_hip.mesh_simplify_count(verts, faces, c, o).numpy()
-    else:
-        if torch is not None:
-            verts, faces, normals, colors = (t.detach().cpu().numpy() if isinstance(t, torch.Tensor) else t for t in (verts, faces, normals, colors))
-        verts = np.asarray(verts, dtype=np.float32).reshape(-1, 3)
-        finite = verts[np.all(np.isfinite(verts), axis=1)]
-        lo_hi = np.stack([finite.min(axis=0), finite.max(axis=0)]) if len(finite) else np.zeros((2, 3), np.float32)
-        count = lambda c, o: mesh_simplify_numpy(verts, faces, c, o, count_only=True)
+    route, verts, faces = _mesh_route(verts, faces)
+    xp = route.xp
+    finite = verts[xp.isfinite(verts).all(1)]
+    lo_hi = to_host(xp.stack([xp.amin(finite, 0), xp.amax(finite, 0)])) if len(finite) else np.zeros((2, 3), np.float32)
     origin = lo_hi[0] if origin is None else origin
     base, origin = _simplify_params(1.0 if cell is None else cell, origin)
     if np.any((lo_hi[1].astype(np.float64) - origin.astype(np.float64)) / np.float64(base) >= MESH_SIMPLIFY_GRID):
@@ -1137,15 +1122,10 @@ def simplify_mesh(verts, faces, cell=None, target_faces=0, origin=None, normals=
     j, calls, met = None, 0, True
     if target_faces:
         cells = simplify_candidates(base)
-        j, calls, met = simplify_search(lambda i: int(count(cells[i], origin)[1]), target_faces)
+        j, calls, met = simplify_search(lambda i: int(route.simplify_count(verts, faces, cells[i], origin)[1]), target_faces)
         base = np.float32(cells[j])
-    if on_gpu:
-        v, f, src, vmap, counts = gnerf_hip.mesh_simplify(verts, faces, float(base), origin)
-        index = src.long()
-        normals, colors = (None if t is None else t.to(dev)[index] for t in (normals, colors))
-    else:
-        v, f, src, vmap, counts = mesh_simplify_numpy(verts, faces, base, origin)
-        normals, colors = (None if t is None else np.asarray(t)[src] for t in (normals, colors))
+    v, f, src, vmap, counts = route.simplify(verts, faces, float(base), origin)
+    normals, colors = _gather(normals, src), _gather(colors, src)
     c = [int(x) for x in counts]
     report = dict(cell=float(base), origin=tuple(float(x) for x in origin), target_faces=target_faces, j=j, count_calls=calls, met=bool(met),
                   vertices=int(len(verts)), faces=int(c[1] + c[2] + c[3] + c[4]), new_vertices=c[0], new_faces=c[1], invalid=c[2], collapsed=c[3], absorbed=c[4],
@@ -1165,7 +1145,7 @@ def simplify_options(cell=0.0, target_faces=0, voxel=1.0):
     """The CLIs' two flags (--mesh-simplify CELL, in voxels of edge `voxel`, and --mesh-target-faces N) as simplify_mesh keywords, or None when
     both are 0 (nothing runs)."""
     cell, target_faces = float(cell), int(target_faces)
-    if cell < 0 or target_faces < 0 or cell != cell:
+    if not 0 <= cell < float('inf') or target_faces < 0:
         raise ValueError('--mesh-simplify and --mesh-target-faces must be >= 0')
     if not cell and not target_faces:
         return None
@@ -1257,34 +1237,85 @@ def snap_report_line(report):
             f'max {report["max_before"]:.3g} -> {report["max_after"]:.3g}')
 
 
-def process_mesh(verts, faces, clean=None, simplify=None):
-    """What the CLIs do to a mesh marching cubes just made, up to the smoothing: components and compaction (clean: clean_options' dict or
-    None), then simplification (simplify: simplify_options' dict or None).  -> (verts, faces, clean report or None, simplify report or None);
-    smoothing (smooth_mesh) comes after the vertex attributes have been evaluated, at the final vertices."""
-    clean_report = simplify_report = None
-    if clean:
+# ---------------------------------------------------------------------------------------------------------------- the pipeline
+# What both CLIs do to a mesh marching cubes just made, in the one order there is.  The stages that need the generator (the snap, the vertex
+# attributes, the bake) come in as callables, so that this module works from a volume alone.
+MESH_STAGES = ('clean', 'simplify', 'snap', 'bake')                      # the stages that report, in the order they run
+FinishedMesh = collections.namedtuple('FinishedMesh', 'verts faces normals colors baked reports')
+
+
+class Written(tuple):
+    """What a function that writes a mesh file returns: the plain tuple of counts its callers unpack, with the FinishedMesh it wrote (reports
+    included) as the attribute `mesh`."""
+    def __new__(cls, counts, mesh):
+        self = super().__new__(cls, counts)
+        self.mesh = mesh
+        return self
+
+
+def finish_mesh(verts, faces, clean=None, simplify=None, snap=None, attributes=None, bake=None):
+    """Every stage between marching cubes and the consumers of its mesh (verts [V, 3], faces [T, 3]: CUDA tensors take the kernels and stay
+    on their device, numpy arrays take the ports, a CPU tensor becomes numpy here) -> FinishedMesh(verts, faces, normals, colors, baked, reports).
+      clean, simplify: clean_options' / simplify_options' dict, or None (the stage does not run);
+      snap(verts, faces) -> (verts, report); attributes(verts) -> (normals or None, colors or None);
+      bake(verts, faces, normals, colors) -> bake_mesh_colors' dict: callables on this route's arrays, or None.
+    normals and colors are the attributes' (the decoder's colours; the baked ones are baked['colors']), baked is the bake's dict or None, and
+    reports holds the report of every stage of MESH_STAGES that ran, in that order (the bake's is its dict)."""
+    route, verts, faces = _mesh_route(verts, faces)
+    reports = {}
+    if clean:                                                            # components, selection, compaction
         cleaned = clean_mesh(verts, faces, keep_largest=clean['keep_largest'], min_faces=clean['min_faces'])
-        verts, faces, clean_report = cleaned.verts, cleaned.faces, cleaned.report
+        verts, faces, reports['clean'] = cleaned.verts, cleaned.faces, cleaned.report
     if simplify:
         simplified = simplify_mesh(verts, faces, **simplify)
-        verts, faces, simplify_report = simplified.verts, simplified.faces, simplified.report
-    return verts, faces, clean_report, simplify_report
+        verts, faces, reports['simplify'] = simplified.verts, simplified.faces, simplified.report
+    # Normally the attributes are those of the extracted surface: they are evaluated at the kept (or simplified) vertices where marching
+    # cubes put them, and only then does the smoothing move the positions.  A snap puts the vertices where they stay, on the level set, so
+    # with one the smoothing comes first, then the snap, and the attributes are evaluated at the final positions.
+    smooth = clean['smooth'] if clean else 0
+    normals = colors = baked = None
+    if snap:
+        if smooth:
+            verts = route.smooth(verts, faces, smooth)
+        verts, reports['snap'] = snap(verts, faces)
+    if attributes:
+        normals, colors = (_on_route(x, verts) for x in attributes(verts))
+    if smooth and not snap:
+        verts = route.smooth(verts, faces, smooth)
+    if bake:                                                             # the final mesh; the attributes' colours stay where no frame sees
+        baked = reports['bake'] = bake(verts, faces, normals, colors)
+    return FinishedMesh(verts, faces, normals, colors, baked, reports)
 
 
-def smooth_mesh(verts, faces, clean=None):
-    """The Taubin iterations of clean_options' dict (None or smooth == 0: nothing) on a mesh of either route; positions only."""
-    if not clean or not clean['smooth']:
-        return verts
+def report_lines(reports, smooth=0, bake_views=0):
+    """The CLIs' stdout lines about finish_mesh's reports, one per stage that ran, in stage order (smooth: the Taubin iterations the cleaning
+    line names; bake_views: the number of frames the bake took)."""
+    line = dict(clean=lambda r: clean_report_line(r, smooth), simplify=simplify_report_line, snap=snap_report_line,
+                bake=lambda r: bake_report_line(r, bake_views))
+    return [line[stage](reports[stage]) for stage in MESH_STAGES if stage in reports]
+
+
+def add_mesh_arguments(parser, attributes=False):
+    """Declare the flags of clean_options and simplify_options on a CLI's parser.  attributes: the CLI evaluates vertex attributes (the
+    help says where in the order)."""
+    parser.add_argument('--mesh-keep', type=int, default=0, help='keep only this many of the largest connected components of the mesh (0: all)')
+    parser.add_argument('--mesh-min-faces', type=int, default=0, help='drop connected components with fewer triangles than this (0: none)')
+    parser.add_argument('--mesh-smooth', type=int, default=0, help='Taubin smoothing iterations of the mesh (lambda 0.5, mu -0.53, boundaries pinned; 0: none)')
+    parser.add_argument('--mesh-simplify', type=float, default=0, metavar='CELL',
+                        help='simplify the mesh by vertex clustering on a grid of cells this many voxels wide, after the components, before '
+                             + ('the attributes and ' if attributes else '') + 'the smoothing (0: off)')
+    parser.add_argument('--mesh-target-faces', type=int, default=0, metavar='N',
+                        help='pick the cell instead: the smallest of CELL (or one voxel) * 2^(j / 4), j = 0 .. 40, that leaves at most N triangles (0: off)')
+
+
+def mesh_options_from_args(args, parser):
+    """(clean, simplify, snap): the option dicts of the parsed flags (None: the stage does not run; snap is None on a parser without
+    --mesh-snap).  A value out of range ends the program through parser.error."""
     try:
-        import torch
-    except ImportError:                                                  # pragma: no cover - torch is part of the stack
-        torch = None
-    if torch is not None and isinstance(verts, torch.Tensor):
-        if verts.is_cuda:
-            import gnerf_hip
-            return gnerf_hip.mesh_smooth(verts, faces, clean['smooth'])
-        return torch.from_numpy(mesh_smooth_numpy(verts.numpy(), faces.numpy() if isinstance(faces, torch.Tensor) else faces, clean['smooth']))
-    return mesh_smooth_numpy(verts, faces, clean['smooth'])
+        return (clean_options(args.mesh_keep, args.mesh_min_faces, args.mesh_smooth), simplify_options(args.mesh_simplify, args.mesh_target_faces),
+                snap_options(args.mesh_snap, args.mesh_snap_steps, args.mesh_snap_tol) if hasattr(args, 'mesh_snap') else None)
+    except ValueError as err:
+        parser.error(str(err))
 
 
 # ---------------------------------------------------------------------------------------------------------------- PLY
@@ -1385,29 +1416,13 @@ def read_ply_attrs(path):
     return {k: v for k, v in found.items() if v is not None}
 
 
-def convert_sdf_samples_to_ply(volume, voxel_grid_origin, voxel_size, ply_filename_out, offset=None, scale=None, level=0.0, clean=None, report=None,
-                               simplify=None, simplify_report=None):
+def convert_sdf_samples_to_ply(volume, voxel_grid_origin, voxel_size, ply_filename_out, offset=None, scale=None, level=0.0, clean=None, simplify=None):
     """shape_utils.py:40-100: mesh `volume` at `level` with spacing voxel_size, move the vertices by voxel_grid_origin, then
     / scale and - offset when given, and write the .ply.  `volume` may be a CUDA tensor (the kernel) or a CPU array (the numpy port).
-    clean: None, or clean_mesh's keywords (clean_options) -- the mesh is cleaned where it was extracted, before it is moved; report: a dict
-    that then receives clean_mesh's report.  simplify: None, or simplify_mesh's keywords (simplify_options; the cell in the mesh's units) --
-    the mesh is simplified between the compaction and the smoothing; simplify_report: a dict that then receives simplify_mesh's report.
-    Returns (vertex count, face count)."""
-    verts, faces = marching_cubes(volume, level, spacing=voxel_size)
-    if simplify:
-        verts, faces, cleaned, simplified = process_mesh(verts, faces, clean, simplify)
-        verts = smooth_mesh(verts, faces, clean)
-        if report is not None and cleaned is not None:
-            report.update(cleaned)
-        if simplify_report is not None:
-            simplify_report.update(simplified)
-    elif clean:
-        cleaned = clean_mesh(verts, faces, **clean)
-        verts, faces = cleaned.verts, cleaned.faces
-        if report is not None:
-            report.update(cleaned.report)
-    if not isinstance(verts, np.ndarray):
-        verts, faces = verts.cpu().numpy(), faces.cpu().numpy()
+    clean, simplify: None, or clean_options' / simplify_options' dict (the cell in the mesh's units) -- finish_mesh's stages, run where the mesh
+    was extracted, before it is moved.  Returns (vertex count, face count), with finish_mesh's record (the reports) as its attribute `mesh`."""
+    mesh = finish_mesh(*marching_cubes(volume, level, spacing=voxel_size), clean=clean, simplify=simplify)
+    verts, faces = to_host(mesh.verts), to_host(mesh.faces)
     mesh_points = np.zeros_like(verts)
     mesh_points[:, 0] = voxel_grid_origin[0] + verts[:, 0]
     mesh_points[:, 1] = voxel_grid_origin[1] + verts[:, 1]
@@ -1417,7 +1432,7 @@ def convert_sdf_samples_to_ply(volume, voxel_grid_origin, voxel_size, ply_filena
     if offset is not None:
         mesh_points = mesh_points - offset
     write_ply(ply_filename_out, mesh_points, faces)
-    return len(verts), len(faces)
+    return Written((len(verts), len(faces)), mesh)
 
 
 # ---------------------------------------------------------------------------------------------------------------- MRC
@@ -1483,46 +1498,33 @@ def load_volume(path):
     return read_mrc(path) if path.lower().endswith('.mrc') else np.load(path).astype(np.float32, copy=False)
 
 
-def convert_mrc(input_filename, output_filename, level=10.0, device=None, clean=None, report=None, simplify=None, simplify_report=None):
+def convert_mrc(input_filename, output_filename, level=10.0, device=None, clean=None, simplify=None):
     """shape_utils.py:103-105: mesh transpose(2, 1, 0) of the file's data (.mrc or .npy), voxel size 1, origin 0.  `device`: a torch
-    device to run the kernel on (None: the numpy port).  clean, report, simplify, simplify_report: as convert_sdf_samples_to_ply's.  Returns
-    (vertex count, face count)."""
+    device to run the kernel on (None: the numpy port).  clean, simplify and the return: as convert_sdf_samples_to_ply's."""
     vol = np.ascontiguousarray(np.transpose(load_volume(input_filename), (2, 1, 0)))
     if device is not None:
-        import torch
-        vol = torch.from_numpy(vol).to(device)
-    return convert_sdf_samples_to_ply(vol, [0, 0, 0], 1, output_filename, level=level, clean=clean, report=report, simplify=simplify,
-                                      simplify_report=simplify_report)
+        vol = _torch().from_numpy(vol).to(device)
+    return convert_sdf_samples_to_ply(vol, [0, 0, 0], 1, output_filename, level=level, clean=clean, simplify=simplify)
 
 
-def main(argv=None):
+def arg_parser():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter,
                                  epilog='Snapping the vertices onto the density\'s level set (--mesh-snap of gen_videos_mi355x.py) needs the generator the '
                                         'volume came from: this tool works from the volume alone and has no such flag.')
     ap.add_argument('input', help='a .mrc / .npy volume, or a directory of them (each gets a .ply next to it)')
     ap.add_argument('--level', type=float, default=10, help='the isosurface level (shape_utils.py:111)')
     ap.add_argument('--device', default=None, help="'cuda' runs the gfx950 kernel (default: cuda when available, else the numpy port)")
-    ap.add_argument('--mesh-keep', type=int, default=0, help='keep only this many of the largest connected components (0: all)')
-    ap.add_argument('--mesh-min-faces', type=int, default=0, help='drop connected components with fewer triangles than this (0: none)')
-    ap.add_argument('--mesh-smooth', type=int, default=0, help='Taubin smoothing iterations (lambda 0.5, mu -0.53, boundaries pinned; 0: none)')
-    ap.add_argument('--mesh-simplify', type=float, default=0, metavar='CELL',
-                    help='simplify the mesh by vertex clustering on a grid of cells this many voxels wide, after the components, before the smoothing (0: off)')
-    ap.add_argument('--mesh-target-faces', type=int, default=0, metavar='N',
-                    help='pick the cell instead: the smallest of CELL (or one voxel) * 2^(j / 4), j = 0 .. 40, that leaves at most N triangles (0: off)')
+    add_mesh_arguments(ap)
+    return ap
+
+
+def main(argv=None):
+    ap = arg_parser()
     args = ap.parse_args(argv)
-    if min(args.mesh_keep, args.mesh_min_faces, args.mesh_smooth) < 0:
-        ap.error('--mesh-keep, --mesh-min-faces and --mesh-smooth must be >= 0')
-    if not args.mesh_simplify >= 0 or args.mesh_simplify == float('inf') or args.mesh_target_faces < 0:
-        ap.error('--mesh-simplify and --mesh-target-faces must be >= 0')
-    clean = clean_options(args.mesh_keep, args.mesh_min_faces, args.mesh_smooth)
-    simplify = simplify_options(args.mesh_simplify, args.mesh_target_faces)
+    clean, simplify, _ = mesh_options_from_args(args, ap)
     device = args.device
     if device is None:
-        try:
-            import torch
-            device = 'cuda' if torch.cuda.is_available() else None
-        except ImportError:                                              # pragma: no cover
-            device = None
+        device = 'cuda' if _torch() is not None and _torch().cuda.is_available() else None
     if device == 'cpu':
         device = None
     if os.path.isfile(args.input):
@@ -1534,12 +1536,9 @@ def main(argv=None):
     for path in paths:                                                   # --level is honoured for a single file too (the reference's
         t0 = time.perf_counter()                                         # single-file branch ignores it, shape_utils.py:114-116)
         out = os.path.splitext(path)[0] + '.ply'
-        report, simplify_report = {}, {}
-        nv, nf = convert_mrc(path, out, level=args.level, device=device, clean=clean, report=report, simplify=simplify, simplify_report=simplify_report)
-        if report:
-            print(clean_report_line(report, args.mesh_smooth))
-        if simplify_report:
-            print(simplify_report_line(simplify_report))
+        nv, nf = written = convert_mrc(path, out, level=args.level, device=device, clean=clean, simplify=simplify)
+        for line in report_lines(written.mesh.reports, smooth=args.mesh_smooth):
+            print(line)
         print(f'wrote {out}: {nv} vertices, {nf} triangles ({time.perf_counter() - t0:.3f} s)')
     return 0
 

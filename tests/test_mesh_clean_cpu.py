@@ -365,21 +365,105 @@ def test_gen_videos_cli_on_the_cpu_device(tmp_path):
 
 
 def test_mesh_density_grid_hands_the_report_out(tmp_path):
-    """--mesh's call on a CPU volume: the report comes back through a dict, the return value keeps its three entries."""
+    """--mesh's call on a CPU volume: the report comes back on the returned record, the return value keeps its three entries."""
     import gen_videos_mi355x as gv
     vol = torch.from_numpy(four_balls_field())
     plain, cleaned = str(tmp_path / 'a.ply'), str(tmp_path / 'b.ply')
-    report = {}
-    assert len(gv.mesh_density_grid(vol, plain, 0.0, report=report)) == 3 and report == {}
-    assert len(gv.mesh_density_grid(vol, cleaned, 0.0, clean=S.clean_options(0, 0, 0), report=report)) == 3 and report == {}
+    written = gv.mesh_density_grid(vol, plain, 0.0)
+    assert len(written) == 3 and 'clean' not in written.mesh.reports
+    written = gv.mesh_density_grid(vol, cleaned, 0.0, clean=S.clean_options(0, 0, 0))
+    assert len(written) == 3 and 'clean' not in written.mesh.reports
     assert open(plain, 'rb').read() == open(cleaned, 'rb').read()
-    nv, nf, dt = gv.mesh_density_grid(vol, cleaned, 0.0, clean=S.clean_options(2, 0, 3), report=report)
+    nv, nf, dt = written = gv.mesh_density_grid(vol, cleaned, 0.0, clean=S.clean_options(2, 0, 3))
+    report = written.mesh.reports['clean']
     assert report['components'] == 4 and report['kept'] == 2 and report['kept_faces'] == nf == 7304 + 620 and report['kept_vertices'] == nv
     mv, mf = S.marching_cubes_numpy(vol.permute(2, 1, 0).contiguous().numpy(), 0.0)
     want = S.clean_mesh(mv, mf, keep_largest=2, smooth=3)
     verts, faces = S.read_ply(cleaned)
     assert same_bits(verts, want.verts) and np.array_equal(faces, want.faces) and report == want.report
     assert gv.mesh_density_grid(vol, cleaned, 0.0, clean=S.clean_options(1, 0, 0))[:2] == (len(S.clean_mesh(mv, mf, keep_largest=1).verts), 7304)
+
+
+# ---------------------------------------------------------------------------------------------------------------- the pipeline
+def stand_in_stages(calls):
+    """Stand-ins for the stages that need a generator: each records its name and the arrays it was handed."""
+    def snap(verts, faces):
+        calls.append(('snap', verts.copy(), faces.copy()))
+        return verts + np.float32(0.25), dict(vertices=len(verts))
+
+    def attributes(verts):
+        calls.append(('attributes', verts.copy()))
+        return verts * np.float32(2), verts.astype(np.int64).astype(np.uint8)
+
+    def bake(verts, faces, normals, colors):
+        calls.append(('bake', verts.copy(), faces.copy(), normals, colors))
+        return dict(colors=255 - colors, weight=np.ones(len(verts), np.float32), seen=np.ones(len(verts), np.int32))
+    return snap, attributes, bake
+
+
+@pytest.mark.parametrize('with_snap', [False, True])
+def test_finish_mesh_runs_the_stages_in_the_one_order(meshes, with_snap):
+    """The pipeline against the primitives composed by hand, without a generator: where the attributes are evaluated with and without a snap,
+    the bake last with the attributes' colours, the reports of the stages that ran."""
+    mv, mf = meshes['balls']
+    calls = []
+    snap, attributes, bake = stand_in_stages(calls)
+    got = S.finish_mesh(mv, mf, clean=S.clean_options(2, 0, 3), simplify=S.simplify_options(3.0, 0), snap=snap if with_snap else None,
+                        attributes=attributes, bake=bake)
+    label, faces_of, _ = S.mesh_components_numpy(mf, len(mv))
+    keep = np.zeros(len(mv), np.uint8)
+    keep[S.mesh_select(faces_of, keep_largest=2)] = 1
+    cv, cf, _ = S.mesh_compact_numpy(mv, mf, label, faces_of, keep)
+    sv, sf = S.mesh_simplify_numpy(cv, cf, 3.0, cv.min(axis=0))[:2]
+    smoothed = S.mesh_smooth_numpy(sv, sf, 3)
+    assert 0 < len(sf) < len(cf) < len(mf) and not same_bits(smoothed, sv)
+    if with_snap:
+        assert [c[0] for c in calls] == ['snap', 'attributes', 'bake']
+        assert same_bits(calls[0][1], smoothed) and same_bits(calls[0][2], sf)
+        final = smoothed + np.float32(0.25)
+        seen_by_attributes = final                                       # the smoothed, then snapped positions
+        assert list(got.reports) == ['clean', 'simplify', 'snap', 'bake'] and got.reports['snap'] == dict(vertices=len(sv))
+    else:
+        assert [c[0] for c in calls] == ['attributes', 'bake']
+        final, seen_by_attributes = smoothed, sv                         # the unsmoothed simplified positions
+        assert list(got.reports) == ['clean', 'simplify', 'bake']
+    assert same_bits(calls[-2][1], seen_by_attributes)
+    assert same_bits(got.verts, final) and same_bits(got.faces, sf)
+    assert same_bits(got.normals, seen_by_attributes * np.float32(2)) and same_bits(got.colors, seen_by_attributes.astype(np.int64).astype(np.uint8))
+    _, baked_verts, baked_faces, baked_normals, baked_colors = calls[-1]
+    assert same_bits(baked_verts, final) and same_bits(baked_faces, sf) and baked_normals is got.normals and baked_colors is got.colors
+    assert got.baked is got.reports['bake'] and same_bits(got.baked['colors'], 255 - got.colors)
+    kept = S.clean_mesh(mv, mf, keep_largest=2)
+    assert got.reports['clean'] == kept.report and got.reports['simplify'] == S.simplify_mesh(kept.verts, kept.faces, cell=3.0).report
+    lines = S.report_lines({k: got.reports[k] for k in ('bake', 'simplify', 'clean')}, smooth=3, bake_views=4)       # in stage order, whatever the dict's
+    assert lines == [S.clean_report_line(kept.report, 3), S.simplify_report_line(got.reports['simplify']), S.bake_report_line(got.baked, 4)]
+
+
+def test_finish_mesh_runs_only_what_is_asked(meshes):
+    mv, mf = meshes['balls']
+    plain = S.finish_mesh(mv, mf)
+    assert same_bits(plain.verts, mv) and same_bits(plain.faces, mf) and plain[2:] == (None, None, None, {}) and S.report_lines(plain.reports) == []
+    smoothed = S.finish_mesh(torch.from_numpy(mv.copy()), torch.from_numpy(mf.copy()), clean=S.clean_options(0, 0, 2))     # CPU tensors: numpy out
+    assert isinstance(smoothed.verts, np.ndarray) and same_bits(smoothed.verts, S.mesh_smooth_numpy(mv, mf, 2)) and list(smoothed.reports) == ['clean']
+    simplified = S.finish_mesh(mv, mf, simplify=S.simplify_options(0, 500))
+    assert list(simplified.reports) == ['simplify'] and 0 < len(simplified.faces) <= 500
+
+
+def test_both_clis_take_the_shared_flags_from_one_declaration(monkeypatch, capsys):
+    import gen_videos_mi355x as gv
+    flags = ['--mesh-keep', '2', '--mesh-min-faces', '5', '--mesh-smooth', '3', '--mesh-simplify', '1.5', '--mesh-target-faces', '700']
+    shape, videos = S.arg_parser(), gv.arg_parser()
+    from_shape = S.mesh_options_from_args(shape.parse_args(['volume.mrc', *flags]), shape)
+    from_videos = S.mesh_options_from_args(videos.parse_args([*flags, '--mesh-snap', '1.5']), videos)
+    assert from_shape[:2] == from_videos[:2] == (S.clean_options(2, 5, 3), S.simplify_options(1.5, 700))
+    assert from_shape[2] is None and from_videos[2] == S.snap_options(1.5)               # the shape tool has no generator to snap to
+    assert S.mesh_options_from_args(videos.parse_args([]), videos) == (None, None, None)
+    for bad in (['--mesh-smooth', '-1'], ['--mesh-keep', '-2'], ['--mesh-simplify', '-0.5'], ['--mesh-simplify', 'inf'], ['--mesh-target-faces', '-1']):
+        for run in (lambda: S.main(['volume.mrc', *bad]), gv.main):
+            monkeypatch.setattr(sys, 'argv', ['gen_videos_mi355x.py', '--random-init', *bad])
+            with pytest.raises(SystemExit) as exit_:
+                run()
+            assert exit_.value.code == 2 and 'must be >= 0' in capsys.readouterr().err
 
 
 # ---------------------------------------------------------------------------------------------------------------- interface

@@ -273,8 +273,8 @@ def test_gen_videos_clean_mesh_end_to_end(dev, tmp_path):
     vol, planes = gv.extract_density_grid(G, gv.orbit_latents(G, z, dev), 128, return_planes=True)
     plain, cleaned = str(tmp_path / 'plain.ply'), str(tmp_path / 'cleaned.ply')
     gv.mesh_density_grid(vol, plain, 0.0, attrs='all', G=G, planes=planes)
-    report = {}
-    nv, nf, _ = gv.mesh_density_grid(vol, cleaned, 0.0, attrs='all', G=G, planes=planes, clean=S.clean_options(1, 0, 2), report=report)
+    nv, nf, _ = written = gv.mesh_density_grid(vol, cleaned, 0.0, attrs='all', G=G, planes=planes, clean=S.clean_options(1, 0, 2))
+    report = written.mesh.reports['clean']
     want = S.clean_mesh(*S.read_ply(plain), keep_largest=1, smooth=2)
     got_v, got_f = S.read_ply(cleaned)
     assert report == want.report and report['components'] > 1 and 0 < nv < report['vertices']

@@ -281,12 +281,12 @@ def test_mesh_density_grid_simplifies_between_compaction_and_smoothing(tmp_path)
     import gen_videos_mi355x as gv
     vol = torch.from_numpy(four_balls_field())
     plain, other = str(tmp_path / 'a.ply'), str(tmp_path / 'b.ply')
-    report, simplify_report = {}, {}
     assert len(gv.mesh_density_grid(vol, plain, 0.0)) == 3
-    assert len(gv.mesh_density_grid(vol, other, 0.0, simplify=S.simplify_options(0, 0), report=report, simplify_report=simplify_report)) == 3
-    assert open(plain, 'rb').read() == open(other, 'rb').read() and report == {} and simplify_report == {}
-    nv, nf, _ = gv.mesh_density_grid(vol, other, 0.0, clean=S.clean_options(2, 0, 3), simplify=S.simplify_options(3.0, 0), report=report,
-                                     simplify_report=simplify_report)
+    written = gv.mesh_density_grid(vol, other, 0.0, simplify=S.simplify_options(0, 0))
+    assert len(written) == 3 and open(plain, 'rb').read() == open(other, 'rb').read() and written.mesh.reports == {}
+    nv, nf, _ = written = gv.mesh_density_grid(vol, other, 0.0, clean=S.clean_options(2, 0, 3), simplify=S.simplify_options(3.0, 0))
+    assert list(written.mesh.reports) == ['clean', 'simplify']
+    report, simplify_report = written.mesh.reports['clean'], written.mesh.reports['simplify']
     mv, mf = S.marching_cubes_numpy(vol.permute(2, 1, 0).contiguous().numpy(), 0.0)
     kept = S.clean_mesh(mv, mf, keep_largest=2)
     want = S.simplify_mesh(kept.verts, kept.faces, cell=3.0)

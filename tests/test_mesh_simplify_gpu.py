@@ -137,3 +137,13 @@ def test_simplify_mesh_end_to_end_and_the_rasteriser_on_its_result(dev, meshes):
     drawn, ref = S.render_mesh(got.verts, got.faces, *cams, 48, **kw), S.render_mesh(want.verts, want.faces, *cams, 48, **kw)
     assert same_bits(host(drawn['tri_id']), ref['tri_id']) and same_bits(host(drawn['depth']), ref['depth'])
     assert (ref['tri_id'] >= 0).mean() > 0.02 and drawn['counts'].tolist() == ref['counts'].tolist()
+
+
+def test_finish_mesh_on_the_device_gives_the_numpy_routes_bits(dev, meshes):
+    """The pipeline's stages that need no generator, on CUDA tensors: verts, faces and reports of the numpy route."""
+    verts, faces = meshes['balls']
+    clean, simplify = S.clean_options(2, 0, 3), S.simplify_options(3.0, 0)
+    want = S.finish_mesh(verts, faces, clean=clean, simplify=simplify)
+    got = S.finish_mesh(*on(dev, verts, faces), clean=clean, simplify=simplify)
+    assert got.verts.is_cuda and got.faces.is_cuda and same_bits(host(got.verts), want.verts) and same_bits(host(got.faces), want.faces)
+    assert list(got.reports) == ['clean', 'simplify'] and got.reports == want.reports and 0 < len(want.faces) < len(faces)

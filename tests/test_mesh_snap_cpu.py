@@ -216,12 +216,11 @@ def test_harness_snaps_a_cpu_generator_mesh(tmp_path):
     plain, same, snapped = (str(tmp_path / n) for n in ('plain.ply', 'same.ply', 'snapped.ply'))
     # snap off: the bytes of a call that does not know the option
     gv.mesh_density_grid(vol, plain, level, attrs='all', G=G, planes=planes, clean=S.clean_options(0, 0, 2))
-    snap_report = {}
-    gv.mesh_density_grid(vol, same, level, attrs='all', G=G, planes=planes, clean=S.clean_options(0, 0, 2), snap=S.snap_options(0), snap_report=snap_report)
-    assert open(plain, 'rb').read() == open(same, 'rb').read() and snap_report == {}
+    written = gv.mesh_density_grid(vol, same, level, attrs='all', G=G, planes=planes, clean=S.clean_options(0, 0, 2), snap=S.snap_options(0))
+    assert open(plain, 'rb').read() == open(same, 'rb').read() and 'snap' not in written.mesh.reports
     # snap on
-    nv, nf, _ = gv.mesh_density_grid(vol, snapped, level, attrs='normals', G=G, planes=planes, snap=S.snap_options(1.0), snap_report=snap_report)
-    r = snap_report
+    nv, nf, _ = written = gv.mesh_density_grid(vol, snapped, level, attrs='normals', G=G, planes=planes, snap=S.snap_options(1.0))
+    r = written.mesh.reports['snap']
     print(S.snap_report_line(r))
     assert r['vertices'] == nv and r['converged'] + r['not_converged'] + r['flat'] + r['reverted'] == nv and r['converged'] > 0
     assert len(r['flips']) == 4 and r['flips_left'] == 0

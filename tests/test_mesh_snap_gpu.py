@@ -319,9 +319,9 @@ def test_snap_end_to_end(dev, tmp_path):
     assert float((sigma[moved] - level).abs().max()) <= 2 * r['tol']                        # tol is the kernel's own criterion; as much again for
                                                                                             # the world position rounded along another route
     # the file route, with attributes at the snapped positions, and the rasteriser draws the result
-    path, report = str(tmp_path / 'snapped.ply'), {}
-    nv, nf, _ = gv.mesh_density_grid(vol, path, level, attrs='normals', G=G, planes=planes, snap=S.snap_options(1.0), snap_report=report)
-    assert report == r and (nv, nf) == (len(verts), len(faces))
+    path = str(tmp_path / 'snapped.ply')
+    nv, nf, _ = written = gv.mesh_density_grid(vol, path, level, attrs='normals', G=G, planes=planes, snap=S.snap_options(1.0))
+    assert written.mesh.reports['snap'] == r and (nv, nf) == (len(verts), len(faces))
     file_verts, _ = S.read_ply(path)
     assert np.array_equal(file_verts.view(np.uint32), snapped.cpu().numpy().view(np.uint32))
     normals, _ = gv.mesh_vertex_attributes(G, planes, snapped, res, True, False)
