@@ -23,6 +23,24 @@ static void pad_ray_sequence(Params& P) {
     P.n_tiles = P.p.n_items * (P.tiles_y / kBwdRaysPerWave);
 }
 
+// The second pass: the staged dX rows (ray stride 33 n_all) -> the plane gradient, binned or sorted.  P: the call's Params, its ray sequence
+// padded where the route says so.
+static int launch_scatter(const Params& P, bool binned, float* stage, float* grad_planes, hipStream_t s) {
+    using namespace gnerf;
+    const int n_all = P.p.depth_resolution + P.p.depth_resolution_importance;
+    Params KS = P;
+    KS.bwd_ray_stride = int64_t(n_all) * 33;
+    if (binned) {
+        char* ws = reinterpret_cast<char*>(stage) + bin_workspace_offset(P.total_rays, n_all);
+        return launch_binned_scatter(KS, stage, ws, grad_planes, s);
+    }
+    static PerDeviceOnce once_scatter;
+    if (int e = once_scatter.raise_lds(plane_scatter_kernel, "render_backward")) return e;
+    hipLaunchKernelGGL(plane_scatter_kernel, dim3(KS.n_tiles), dim3(kScatterThreads), scatter_lds_floats() * sizeof(float), s,
+                       KS, static_cast<const float*>(stage), grad_planes);
+    return check_launch("plane_scatter_kernel");
+}
+
 // What one backward call launches: decided once in render_backward_impl, then only read (DESIGN.md 3.2 has the table of routes).
 struct BwdRoute {
     // first pass.  Wave: render_bwd_kernel<false / true>, one wave per ray, float atomics into the plane gradient / dX rows into the staging buffer.
@@ -155,16 +173,7 @@ static int render_backward_impl(const gnerf_render_params* p, const gnerf_render
     if (route.second == BwdRoute::kNoScatter) return GNERF_OK;
     Params KS = K;                                           // the scatter's
     if (route.scatter_padded) pad_ray_sequence(KS);
-    KS.bwd_ray_stride = int64_t(n_all) * 33;
-    if (route.second == BwdRoute::kBinned) {
-        char* ws = reinterpret_cast<char*>(g->scatter_stage) + bin_workspace_offset(P.total_rays, n_all);
-        return launch_binned_scatter(KS, g->scatter_stage, ws, g->grad_planes_nhwc, s);
-    }
-    static PerDeviceOnce once_scatter;
-    if (int e = once_scatter.raise_lds(plane_scatter_kernel, "render_backward")) return e;
-    hipLaunchKernelGGL(plane_scatter_kernel, dim3(KS.n_tiles), dim3(kScatterThreads), scatter_lds_floats() * sizeof(float), s,
-                       KS, static_cast<const float*>(g->scatter_stage), g->grad_planes_nhwc);
-    return check_launch("plane_scatter_kernel");
+    return launch_scatter(KS, route.second == BwdRoute::kBinned, g->scatter_stage, g->grad_planes_nhwc, s);
 }
 
 extern "C" int gnerf_render_backward(const gnerf_render_params* p, const gnerf_render_grads* g, gnerf_stream_t stream) {
@@ -174,6 +183,29 @@ extern "C" int gnerf_render_backward(const gnerf_render_params* p, const gnerf_r
 extern "C" int gnerf_render_backward_rays(const gnerf_render_params* p, const gnerf_render_grads* g, float* grad_origins, float* grad_dirs, gnerf_stream_t stream) {
     if (!grad_origins && !grad_dirs) return gnerf::fail(GNERF_E_ARG, "render_backward_rays: grad_origins and grad_dirs are both null (gnerf_render_backward is that call)");
     return render_backward_impl(p, g, grad_origins, grad_dirs, stream);
+}
+
+// The second pass alone, on rows and depths the caller wrote (include/gnerf_hip.h): the refusals and the choice of scatter are those of
+// render_backward_impl for a staged plane gradient, the launches are launch_scatter's.
+extern "C" int gnerf_render_scatter_rows(const gnerf_render_params* p, float* stage, float* grad_planes_nhwc, gnerf_stream_t stream) {
+    using namespace gnerf;
+    Params P;
+    if (int e = fill_params(p, P)) return e;
+    if (!stage || !grad_planes_nhwc) return fail(GNERF_E_ARG, "render_scatter_rows: stage and grad_planes_nhwc must not be null");
+    if (p->planes_shared) return fail(GNERF_E_UNSUPPORTED, "render_scatter_rows: planes_shared is a forward-only option");
+    if (!p->ray_origins || p->rng_mode != GNERF_RNG_TENSORS) return fail(GNERF_E_UNSUPPORTED, "render_scatter_rows: in-kernel rays / draws are forward-only options");
+    if (p->sigma_noise_coarse || p->sigma_noise_fine) return fail(GNERF_E_UNSUPPORTED, "render_scatter_rows: density noise is a forward-only option");
+    if (!planes_fit_32bit_taps(p)) return fail(GNERF_E_UNSUPPORTED, "render_scatter_rows: planes too large for 32-bit tap offsets");
+    const char* scatter = getenv("GNERF_BWD_SCATTER");
+    const bool force_direct = scatter && !strcmp(scatter, "direct"), force_sorted = scatter && !strcmp(scatter, "sorted");
+    if (force_direct) return fail(GNERF_E_UNSUPPORTED, "render_scatter_rows: GNERF_BWD_SCATTER=direct stages no dX rows");
+    const bool whole_tiles = P.tiles_per_item > 0 || p->n_items == 1 || p->rays_per_item % kBwdRaysPerWave == 0;
+    const bool binned = binned_scatter_covers(P);
+    const bool can_pad = binned && int64_t(p->n_items) * padded_rays_per_item(*p) < INT32_MAX;
+    const bool padded = !whole_tiles && pipe_tiles_per_wave(P) != 0 && !force_sorted && can_pad;        // (route.padded of the whole call)
+    if (!whole_tiles && !padded) return fail(GNERF_E_UNSUPPORTED, "render_scatter_rows: ray tiles straddle items and the binned scatter does not cover this call");
+    if (padded) pad_ray_sequence(P);
+    return launch_scatter(P, binned && !force_sorted, stage, grad_planes_nhwc, as_stream(stream));
 }
 
 extern "C" size_t gnerf_render_backward_stage_bytes(const gnerf_render_params* p) {

@@ -24,7 +24,11 @@
 // from the tile's record count n_t and bound B_t >= |dx| (so that n_t contributions cannot overflow 63 bits).  Integer addition is
 // associative: the sum does not depend on the order in which records arrive, i.e. plane gradients are BIT-REPRODUCIBLE from run to
 // run -- which neither the float-atomic forms nor the reference's grid_sampler_2d_backward are -- and each texel is rounded to fp32
-// once, from 49 or more significant bits below the tile's bound, instead of once per addition.
+// once instead of once per addition.  What the sum carries below the tile's bound: a unit 2^-s is at most 2^(nbits - 60) of the bound
+// (nbits = ceil(log2 n_t)), and one contribution's conversion is off c 2^s by up to 129 units (bin_to_fixed below: 128 for a negative
+// contribution of less than 2^32 units, plus the floor), so a texel of n contributions is within n 129 2^(nbits - 60) of the bound of
+// its exact sum: 2^-29 of the bound at 4096 records in a tile, all on one texel.  Contributions that are multiples of 256 units
+// (at least 2^(nbits - 27) of the bound) convert exactly.  tests/test_plane_scatter_gpu.py holds the scatter to both statements.
 // Why integers and not ds_add_f32: tools/probes/lds_atomic_probe.hip (profiles/r05_lds_atomic_probe.json) -- a wave64 ds_add_f32
 // takes 192 CU cycles whatever its addresses (three per lane: the float LDS atomic is serialised), ds_add_u64 takes 6, ds_add_u32 4.
 // Not covered (the caller falls back to plane_scatter_kernel): staging buffers of 2^32 floats or more, ray tiles that straddle items.
@@ -367,12 +371,17 @@ __global__ __launch_bounds__(1024) void bin_scan_kernel(BinArgs A) {
     }
 }
 
-// fp32 -> 64-bit fixed point: floor of t (|t| < 2^61) as {low word, high word}.
+// fp32 -> 64-bit fixed point: t (|t| < 2^61) as {low word, high word}.  EXACTLY floor(t) for t >= 0 and for t <= -2^32; for
+// -2^32 < t < 0 within 128 units of floor(t), in either direction (tests/test_plane_scatter_cpu.py tabulates a float32 model of this
+// function against floor(t); test_plane_scatter_gpu.py's sign case measures it on the device).
 // Two things this leans on, both properties of the conversion instructions and both deterministic:
-//  * lo = t - hi 2^32 lies in [0, 2^32] -- CLOSED at the top: for a small negative t (t = -1.5: hi = -1) the exact difference 2^32 - 1.5
-//    is not a float and rounds up to 2^32.  v_cvt_u32_f32 saturates, so the low word becomes 0xFFFFFFFF and the sum is one unit of
-//    2^-s (<= 2^-49 of the tile's bound) above floor(t); an explicit clamp to 4294967040.f would cost a half-rate instruction per
-//    record and lane in the kernel's inner loop and give the same word.
+//  * lo = t - hi 2^32 lies in [0, 2^32] and is ROUNDED to 24 bits by the fma.  For t >= 0 and for t <= -2^32 it is a part of t's own 24
+//    bits and exact.  For -2^32 < t < 0 (hi = -1) it is 2^32 - |t|, which needs up to 32 bits: in [2^31, 2^32) a float's spacing is
+//    256, so the low word is 2^32 - |t| rounded to a multiple of 256 (t = -129 -> -256, t = -12345 -> -12288), and what rounds up to
+//    2^32 itself (|t| <= 128: t = -5) saturates in v_cvt_u32_f32 to 0xFFFFFFFF, i.e. the sum gets -1.  The error is small against the
+//    tile's bound (128 units <= 2^(nbits - 53) of it) but it is the whole result of a texel that only receives small negative
+//    contributions in a tile whose bound another row sets.  A signed path for hi = -1 would make it exact at the cost of vector
+//    instructions in the kernel's inner loop, whose time is its vector instructions.
 //  * the conversions send NaN to 0.  The padding records of a segment (bin_scan_kernel) carry weight zero and point at row 0 of the
 //    staging buffer -- the first ray's depths, not a row known to be finite; a non-finite depth there gives 0 * inf = NaN as the
 //    contribution, which this conversion turns into the zero a padding record must add (such a ray's own records go down the fp32

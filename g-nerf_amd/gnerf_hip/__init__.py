@@ -31,7 +31,8 @@ from .conv3x3 import (conv3x3_epilogue, conv3x3_epilogue_supported, conv3x3_epil
                       pack_conv_transpose3x3_weights, pack_conv_transpose3x3_weights_f32x3, split_f16x3, split_overflow_flag)
 from .render import (decoder_pack_available, last_mlp_choice, pack_decoder, planes_layout, query_points, query_points_backward, query_points_grad, render_backward,  # noqa: F401
                      render_forward, render_generated_supported, render_ray_grad_available, render_ray_grad_refusal, render_ray_grad_supported, _render_params,
-                     project_points_to_level, project_to_level_available, _project_points_to_level_ctypes)
+                     project_points_to_level, project_to_level_available, _project_points_to_level_ctypes,
+                     scatter_plane_rows, scatter_plane_rows_available)
 from .mesh import (MESH_SMOOTH_MAX_FACES, marching_cubes, mesh_clean_available, mesh_compact, mesh_components, mesh_smooth, mesh_workspace_bytes,  # noqa: F401
                    mesh_simplify, mesh_simplify_available, mesh_simplify_count, mesh_simplify_workspace_bytes,
                    mesh_flip_guard, mesh_flip_guard_available, _mesh_flip_guard_ctypes,

@@ -88,6 +88,7 @@ SIGNATURES = {
     'gnerf_render_forward': (_c_i, [ctypes.POINTER(RenderParams), _c_p]),
     'gnerf_render_backward': (_c_i, [ctypes.POINTER(RenderParams), ctypes.POINTER(RenderGrads), _c_p]),
     'gnerf_render_backward_rays': (_c_i, [ctypes.POINTER(RenderParams), ctypes.POINTER(RenderGrads), _c_p, _c_p, _c_p]),
+    'gnerf_render_scatter_rows': (_c_i, [ctypes.POINTER(RenderParams), _c_p, _c_p, _c_p]),
     'gnerf_render_decoder_pack_bytes': (ctypes.c_size_t, []),
     'gnerf_render_pack_decoder': (_c_i, [_c_p, _c_p, _c_p, _c_p, _c_p, _c_p]),
     'gnerf_render_forward_packed': (_c_i, [ctypes.POINTER(RenderParams), _c_p, _c_p]),
@@ -152,9 +153,10 @@ SIGNATURES = {
 }
 # exports added WITHOUT a new ABI version: a library of the same version built before them (a variant build behind GNERF_HIP_LIB) loads, and
 # what needs them asks modconv_backward_available() / render_ray_grad_available() / decoder_pack_available() / resize_aa_available() /
-# raster_available() / mesh_clean_available() / mesh_simplify_available() / project_to_level_available() / mesh_flip_guard_available()
+# raster_available() / mesh_clean_available() / mesh_simplify_available() / project_to_level_available() / mesh_flip_guard_available() /
+# scatter_plane_rows_available()
 OPTIONAL_SYMBOLS = frozenset(n for n in SIGNATURES if n.startswith(('gnerf_project_points_to_level', 'gnerf_modconv_backward_','gnerf_scale_channels_backward', 'gnerf_modconv_epilogue_backward',
-                                                                    'gnerf_render_backward_rays', 'gnerf_render_decoder_pack_bytes',
+                                                                    'gnerf_render_backward_rays', 'gnerf_render_scatter_rows', 'gnerf_render_decoder_pack_bytes',
                                                                     'gnerf_render_pack_decoder', 'gnerf_render_forward_packed', 'gnerf_resize_aa_', 'gnerf_raster_', 'gnerf_mesh_')))
 
 

@@ -432,6 +432,43 @@ def render_backward(planes_nhwc, n_items, decoder, ray_origins, ray_dirs, noise_
     return g_planes, g_dec
 
 
+def scatter_plane_rows_available():
+    """Does the loaded library export gnerf_render_scatter_rows?  (Added without a new ABI version: a variant build of the same version
+    made before it loads and answers False.)"""
+    return hasattr(load(), 'gnerf_render_scatter_rows')
+
+
+def scatter_plane_rows(planes_like, n_items, origins, dirs, depths, rows, *, box_warp, image_width=0, out=None):
+    """The second pass of the staged backward alone (gnerf_render_scatter_rows): the plane gradient of rows the caller wrote.
+    planes_like: a float32 GPU tensor laid out as the planes, [3N,H,W,32] or interleaved [N,H,W,96] (only shape and layout are read);
+    origins, dirs [N,M,3]; depths [N,M,K] (any order: the scatter sums); rows [N,M,K,32], dL/d(mean feature) of the sample at that depth.
+    The call fills a staging buffer as the staged first pass would and runs the scatter gnerf_render_backward would pick
+    (GNERF_BWD_SCATTER=sorted: the LDS-merged atomic form).  out: a gradient tensor like planes_like to ADD into; a zeroed one otherwise.
+    Returns the gradient, laid out like planes_like."""
+    what = 'scatter_plane_rows'
+    _require_cuda(planes_like, origins, dirs, depths, rows, out)
+    o, d, t, r = _f32c(origins), _f32c(dirs), _f32c(depths), _f32c(rows)
+    if t.ndim != 3 or tuple(t.shape[:2]) != tuple(o.shape[:2]) or tuple(r.shape) != (*t.shape, 32):
+        raise RuntimeError(f'{what}: depths must be [N,M,K] and rows [N,M,K,32]')
+    dev, n_all = planes_like.device, int(t.shape[2])
+    # the scatter dereferences neither planes, decoder nor draws: the params carry them because the whole call's validation asks for them
+    spare = torch.zeros([64 * 33], dtype=torch.float32, device=dev)
+    p, keep, m = _render_params(planes_like, n_items, (spare[:64 * 32].view(64, 32), spare[:64], spare.view(33, 64), spare[:33]), o, d, t, None,
+                                n_all, 0, 1.0, 2.0, box_warp, False, False, image_width, what)
+    if out is None:
+        out = torch.zeros_like(planes_like)
+    elif out.dtype != torch.float32 or out.shape != planes_like.shape or not out.is_contiguous() or out.device != dev:
+        raise RuntimeError(f'{what}: out must be a contiguous float32 tensor like planes_like')
+    stage = torch.empty([int(load().gnerf_render_backward_stage_bytes(ctypes.byref(p)))], dtype=torch.uint8, device=dev)
+    rays = n_items * m
+    front = stage[:rays * 33 * n_all * 4].view(torch.float32).view(rays, 33 * n_all)
+    front[:, :n_all] = t.reshape(rays, n_all)
+    front[:, n_all:] = r.reshape(rays, n_all * 32)
+    _launch('gnerf_render_scatter_rows', planes_like, ctypes.byref(p), stage.data_ptr(), out.data_ptr())
+    del keep, stage
+    return out
+
+
 @profiled('gnerf_hip::query_points')
 def query_points(planes_nhwc, n_items, decoder, points, box_warp, want_rgb=True):
     """run_model for arbitrary points [N,P,3] -> sigma [N,P,1], rgb [N,P,32] (rgb None when want_rgb is False)."""

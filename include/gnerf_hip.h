@@ -493,7 +493,11 @@ typedef struct gnerf_render_grads {
            scatter's workspace: per-plane-tile counts / starts / scales / order, the record arrays (8 + 16 bytes per (sample, plane)
            record) and the tile halos.  The second pass sums every 16 x 16-texel plane tile in LDS in 64-bit fixed point and writes it
            with plain stores -- no float atomics, bit-identical gradients from run to run (GNERF_BWD_SCATTER=sorted selects round 4's
-           LDS-merged atomic pass instead, which uses only the rows);
+           LDS-merged atomic pass instead, which uses only the rows).  Precision of the fixed-point sum: with n_t records in a tile
+           (nbits = ceil(log2 n_t)) and B the largest |row value| among them, a texel that n records reach is within
+           n * 129 * 2^(nbits - 60) * B of the exact sum of its float32 products before its one rounding to float32 (129: the conversion
+           of a negative product of less than 2^32 units is off by up to 128 units, the floor adds one); products of at least
+           2^(nbits - 27) * B convert exactly;
          * without grad_planes_nhwc (decoder gradients only): gnerf_render_backward_exchange_bytes(p) bytes suffice (below): per sample
            depth, colour weight, dL/dsigma.
        NULL: single pass (one float atomic per tap and channel). */
@@ -525,6 +529,20 @@ int gnerf_render_backward(const gnerf_render_params* p, const gnerf_render_grads
  * noise, in-kernel rays / draws, planes_shared).  The call cannot tell a buffer of exchange size from one of stage size: the caller
  * sizes it. */
 int gnerf_render_backward_rays(const gnerf_render_params* p, const gnerf_render_grads* g, float* grad_origins, float* grad_dirs, gnerf_stream_t stream);
+
+/* The SECOND pass of the staged backward alone (added without a new ABI version, like gnerf_render_backward_rays): the plane gradient
+ * of rows and depths the caller wrote, for tests and tools that hold the scatter to a reference of its own.
+ * p: params as for gnerf_render_backward; the scatter reads the rays, the sample counts (n_all = depth_resolution +
+ * depth_resolution_importance), the plane shape and layout, box_warp and image_width, and dereferences nothing else of it.
+ * stage: gnerf_render_backward_stage_bytes(p) bytes, 256-byte aligned.  Its front holds, per ray, n_all depths and then n_all rows of 32
+ * floats (dL/d(mean feature) of the sample at that depth) -- what the staged first pass leaves, ray stride 33 n_all floats; the rest is
+ * the call's workspace.  Sample k of ray r adds w_tap * row to the four texels of its bilinear footprint (zero padding, align_corners =
+ * false, w_tap with the 1/3 of the plane mean) in each of the three planes, at p = (o + t d) * 2 / box_warp.
+ * grad_planes_nhwc is ACCUMULATED into, laid out as p's planes.
+ * The scatter is chosen as gnerf_render_backward chooses it: the binned fixed-point form where it covers the call, GNERF_BWD_SCATTER=sorted
+ * the LDS-merged atomic form; a ragged call of several items walks the padded ray sequence.  GNERF_E_UNSUPPORTED, before any launch:
+ * what gnerf_render_backward refuses, GNERF_BWD_SCATTER=direct, and ragged calls the padded binned form does not cover. */
+int gnerf_render_scatter_rows(const gnerf_render_params* p, float* stage, float* grad_planes_nhwc, gnerf_stream_t stream);
 
 /* The decoder pack (added without a new ABI version, like gnerf_render_backward_rays).
  * Before its first ray every workgroup of the pipelined render kernels reduces the decoder's range statistics (which pick the decoder
