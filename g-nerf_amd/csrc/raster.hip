@@ -17,6 +17,8 @@
 //
 // Below resolve: the colour bake, gnerf_mesh_bake_colors -- the inverse operation, frames back onto the vertices through the same vertex
 // stage and the visibility buffers made above (one thread per vertex, gather-only; shape_mi355x.bake_colors_numpy: the same bits).
+// Below that: the texture bake, gnerf_mesh_bake_texture -- the same stage function per texel of the atlas the header lays out -- and the
+// textured resolve, gnerf_raster_resolve_textured (shape_mi355x.bake_texture_numpy / resolve_textured_numpy: the same bits).
 #include "common.h"
 
 #include <algorithm>
@@ -383,6 +385,83 @@ struct BakeRules {
     int power;
 };
 
+// One view of one point: the bake's rules from the vertex stage to the accumulation, the stage the vertex bake and the texture bake are both
+// built from (the same bits in both).  v: the point in the mesh frame; n: its normal there, read only when normal_mat is given.  A view that
+// fails a test leaves the sums as they are.
+struct BakeSums {
+    float acc0, acc1, acc2, accw;
+    int count;
+};
+
+template <int GUARD>
+__device__ __forceinline__ void bake_view(const float (&v)[3], const float (&n)[3], int view, const float* __restrict__ mesh2cam,
+                                          const float* __restrict__ intrinsics, const u64* __restrict__ vis, int h, int w,
+                                          const unsigned char* __restrict__ frames, int fh, int fw, const float* __restrict__ normal_mat,
+                                          const BakeRules& rules, BakeSums& sums) {
+    const float fwf = float(fw), fhf = float(fh);
+    const Camera cam = load_camera(mesh2cam, intrinsics, view, h, w);
+    const Point q = to_image(cam, v, rules.near_z);
+    if (!q.ok) return;
+    const float sx = mul_rn(q.xc, cam.wf), sy = mul_rn(q.yc, cam.hf);
+    if (!(sx >= 0.0f && sx < cam.wf && sy >= 0.0f && sy < cam.hf)) return;
+    const int col = int(floorf(sx)), row = int(floorf(sy));
+    // occlusion: every pixel of the window holds a surface, and none of them lies in front of the point by more than the tolerance.
+    // Coordinates held inside the image visit exactly the pixels of the clipped window (some of them twice).
+    const u64* __restrict__ vis_view = vis + int64_t(view) * h * w;
+    bool open = true;
+#pragma unroll
+    for (int dr = -GUARD; dr <= GUARD; dr++)
+#pragma unroll
+        for (int dc = -GUARD; dc <= GUARD; dc++) {
+            const int r = min(max(row + dr, 0), h - 1), c = min(max(col + dc, 0), w - 1);
+            const u64 key = vis_view[int64_t(r) * w + c];
+            const float z_pix = __uint_as_float(uint32_t(key >> 32));
+            open &= key != kEmpty && q.p[2] <= add_rn(z_pix, mul_rn(rules.depth_tol, z_pix));
+        }
+    if (!open) return;
+    float wgt = 1.0f;
+    if (normal_mat) {
+        const float* N = normal_mat + int64_t(view) * 9;
+        float nc[3];
+#pragma unroll
+        for (int r = 0; r < 3; r++) nc[r] = dot3(N[r * 3 + 0], N[r * 3 + 1], N[r * 3 + 2], n[0], n[1], n[2]);
+        const float np_ = dot3(nc[0], nc[1], nc[2], q.p[0], q.p[1], q.p[2]);
+        const float nn = dot3(nc[0], nc[1], nc[2], nc[0], nc[1], nc[2]), pp = dot3(q.p[0], q.p[1], q.p[2], q.p[0], q.p[1], q.p[2]);
+        const float cosine = div_rn(-np_, sqrtf(mul_rn(nn, pp)));
+        if (!(cosine > rules.min_cos)) return;
+        if (rules.power > 0) {
+            wgt = cosine;
+            for (int k = 1; k < rules.power; k++) wgt = mul_rn(wgt, cosine);
+        }
+    }
+    // bilinear sample of the frame at the point's own position (texel centres at integer + 0.5), the taps clamped into the frame
+    const float u = sub_rn(mul_rn(q.xc, fwf), 0.5f), t = sub_rn(mul_rn(q.yc, fhf), 0.5f);
+    const float x0f = floorf(u), y0f = floorf(t);
+    const float tx = sub_rn(u, x0f), ty = sub_rn(t, y0f);
+    const float ux = sub_rn(1.0f, tx), uy = sub_rn(1.0f, ty);
+    const int x0 = min(max(int(x0f), 0), fw - 1), x1 = min(max(int(x0f) + 1, 0), fw - 1);
+    const int y0 = min(max(int(y0f), 0), fh - 1), y1 = min(max(int(y0f) + 1, 0), fh - 1);
+    const unsigned char* __restrict__ frame = frames + int64_t(view) * fh * fw * 3;
+    const unsigned char* p00 = frame + (int64_t(y0) * fw + x0) * 3;
+    const unsigned char* p01 = frame + (int64_t(y0) * fw + x1) * 3;
+    const unsigned char* p10 = frame + (int64_t(y1) * fw + x0) * 3;
+    const unsigned char* p11 = frame + (int64_t(y1) * fw + x1) * 3;
+    float s[3];
+#pragma unroll
+    for (int k = 0; k < 3; k++) {
+        const float top = add_rn(mul_rn(ux, float(p00[k])), mul_rn(tx, float(p01[k])));
+        const float bot = add_rn(mul_rn(ux, float(p10[k])), mul_rn(tx, float(p11[k])));
+        s[k] = add_rn(mul_rn(uy, top), mul_rn(ty, bot));
+    }
+    sums.acc0 = add_rn(sums.acc0, mul_rn(wgt, s[0]));
+    sums.acc1 = add_rn(sums.acc1, mul_rn(wgt, s[1]));
+    sums.acc2 = add_rn(sums.acc2, mul_rn(wgt, s[2]));
+    sums.accw = add_rn(sums.accw, wgt);
+    sums.count++;
+}
+
+__device__ __forceinline__ unsigned char level_u8(float v) { return (unsigned char)(int)rintf(fminf(fmaxf(v, 0.0f), 255.0f)); }
+
 // GUARD is a template parameter so that the window's loads have no branch between them and are all in flight together: a loop that left at
 // the first failing pixel waited for every key in turn (guard = 1, 32 views of 512^2: 0.154 -> 0.071 ms for 78 k vertices, 0.163 -> 0.149 ms
 // for 352 k).
@@ -397,81 +476,156 @@ __global__ __launch_bounds__(kThreads) void mesh_bake_kernel(const float* __rest
     const float v[3] = {verts[int64_t(i) * 3 + 0], verts[int64_t(i) * 3 + 1], verts[int64_t(i) * 3 + 2]};
     float n[3] = {0.f, 0.f, 0.f};
     if (normals) { n[0] = normals[int64_t(i) * 3 + 0]; n[1] = normals[int64_t(i) * 3 + 1]; n[2] = normals[int64_t(i) * 3 + 2]; }
-    const float fwf = float(fw), fhf = float(fh);
-    float acc0 = 0.f, acc1 = 0.f, acc2 = 0.f, accw = 0.f;
-    int count = 0;
-    for (int view = 0; view < n_views; view++) {
-        const Camera cam = load_camera(mesh2cam, intrinsics, view, h, w);
-        const Point q = to_image(cam, v, rules.near_z);
-        if (!q.ok) continue;
-        const float sx = mul_rn(q.xc, cam.wf), sy = mul_rn(q.yc, cam.hf);
-        if (!(sx >= 0.0f && sx < cam.wf && sy >= 0.0f && sy < cam.hf)) continue;
-        const int col = int(floorf(sx)), row = int(floorf(sy));
-        // occlusion: every pixel of the window holds a surface, and none of them lies in front of the vertex by more than the tolerance.
-        // Coordinates held inside the image visit exactly the pixels of the clipped window (some of them twice).
-        const u64* __restrict__ vis_view = vis + int64_t(view) * h * w;
-        bool open = true;
-#pragma unroll
-        for (int dr = -GUARD; dr <= GUARD; dr++)
-#pragma unroll
-            for (int dc = -GUARD; dc <= GUARD; dc++) {
-                const int r = min(max(row + dr, 0), h - 1), c = min(max(col + dc, 0), w - 1);
-                const u64 key = vis_view[int64_t(r) * w + c];
-                const float z_pix = __uint_as_float(uint32_t(key >> 32));
-                open &= key != kEmpty && q.p[2] <= add_rn(z_pix, mul_rn(rules.depth_tol, z_pix));
-            }
-        if (!open) continue;
-        float wgt = 1.0f;
-        if (normals) {
-            const float* N = normal_mat + int64_t(view) * 9;
-            float nc[3];
-#pragma unroll
-            for (int r = 0; r < 3; r++) nc[r] = dot3(N[r * 3 + 0], N[r * 3 + 1], N[r * 3 + 2], n[0], n[1], n[2]);
-            const float np_ = dot3(nc[0], nc[1], nc[2], q.p[0], q.p[1], q.p[2]);
-            const float nn = dot3(nc[0], nc[1], nc[2], nc[0], nc[1], nc[2]), pp = dot3(q.p[0], q.p[1], q.p[2], q.p[0], q.p[1], q.p[2]);
-            const float cosine = div_rn(-np_, sqrtf(mul_rn(nn, pp)));
-            if (!(cosine > rules.min_cos)) continue;
-            if (rules.power > 0) {
-                wgt = cosine;
-                for (int k = 1; k < rules.power; k++) wgt = mul_rn(wgt, cosine);
-            }
-        }
-        // bilinear sample of the frame at the vertex's own position (texel centres at integer + 0.5), the taps clamped into the frame
-        const float u = sub_rn(mul_rn(q.xc, fwf), 0.5f), t = sub_rn(mul_rn(q.yc, fhf), 0.5f);
-        const float x0f = floorf(u), y0f = floorf(t);
-        const float tx = sub_rn(u, x0f), ty = sub_rn(t, y0f);
-        const float ux = sub_rn(1.0f, tx), uy = sub_rn(1.0f, ty);
-        const int x0 = min(max(int(x0f), 0), fw - 1), x1 = min(max(int(x0f) + 1, 0), fw - 1);
-        const int y0 = min(max(int(y0f), 0), fh - 1), y1 = min(max(int(y0f) + 1, 0), fh - 1);
-        const unsigned char* __restrict__ frame = frames + int64_t(view) * fh * fw * 3;
-        const unsigned char* p00 = frame + (int64_t(y0) * fw + x0) * 3;
-        const unsigned char* p01 = frame + (int64_t(y0) * fw + x1) * 3;
-        const unsigned char* p10 = frame + (int64_t(y1) * fw + x0) * 3;
-        const unsigned char* p11 = frame + (int64_t(y1) * fw + x1) * 3;
-        float s[3];
-#pragma unroll
-        for (int k = 0; k < 3; k++) {
-            const float top = add_rn(mul_rn(ux, float(p00[k])), mul_rn(tx, float(p01[k])));
-            const float bot = add_rn(mul_rn(ux, float(p10[k])), mul_rn(tx, float(p11[k])));
-            s[k] = add_rn(mul_rn(uy, top), mul_rn(ty, bot));
-        }
-        acc0 = add_rn(acc0, mul_rn(wgt, s[0]));
-        acc1 = add_rn(acc1, mul_rn(wgt, s[1]));
-        acc2 = add_rn(acc2, mul_rn(wgt, s[2]));
-        accw = add_rn(accw, wgt);
-        count++;
-    }
+    BakeSums sums = {0.f, 0.f, 0.f, 0.f, 0};
+    for (int view = 0; view < n_views; view++)
+        bake_view<GUARD>(v, n, view, mesh2cam, intrinsics, vis, h, w, frames, fh, fw, normals ? normal_mat : nullptr, rules, sums);
     unsigned char out[3] = {0, 0, 0};
-    if (accw > 0.0f) {
-        out[0] = (unsigned char)(int)rintf(fminf(fmaxf(div_rn(acc0, accw), 0.0f), 255.0f));
-        out[1] = (unsigned char)(int)rintf(fminf(fmaxf(div_rn(acc1, accw), 0.0f), 255.0f));
-        out[2] = (unsigned char)(int)rintf(fminf(fmaxf(div_rn(acc2, accw), 0.0f), 255.0f));
+    if (sums.accw > 0.0f) {
+        out[0] = level_u8(div_rn(sums.acc0, sums.accw));
+        out[1] = level_u8(div_rn(sums.acc1, sums.accw));
+        out[2] = level_u8(div_rn(sums.acc2, sums.accw));
     } else if (fallback) {
         out[0] = fallback[int64_t(i) * 3 + 0]; out[1] = fallback[int64_t(i) * 3 + 1]; out[2] = fallback[int64_t(i) * 3 + 2];
     }
     colors[int64_t(i) * 3 + 0] = out[0]; colors[int64_t(i) * 3 + 1] = out[1]; colors[int64_t(i) * 3 + 2] = out[2];
-    if (weight) weight[i] = accw;
-    if (seen) seen[i] = count;
+    if (weight) weight[i] = sums.accw;
+    if (seen) seen[i] = sums.count;
+}
+
+// ------------------------------------------------------------------------------------------------ texture bake (gnerf_mesh_bake_texture)
+// The same gather per TEXEL of the atlas include/gnerf_hip.h lays out (two triangles to a P x P cell): thread g is texel g % P^2 of cell
+// g / P^2, so the texels of a cell are consecutive threads -- at P = 8 a wave is one cell, its lanes read two face records and six vertices
+// between them (one request each), and what they gather from a view are neighbouring pixels.  The loop over the views is wave-uniform, the
+// cameras sit in scalar registers as in the vertex bake.  The grid covers every cell of the texture, the empty ones of the last row too:
+// every texel is written.
+struct Atlas {
+    int patch, cells_per_row, tw, n_pairs;
+};
+
+template <int GUARD>
+__global__ __launch_bounds__(kThreads) void mesh_bake_texture_kernel(const float* __restrict__ verts, int n_verts, const int32_t* __restrict__ faces,
+                                                                     int n_tris, Atlas atlas, int n_texels, const float* __restrict__ mesh2cam,
+                                                                     const float* __restrict__ intrinsics, int n_views, const u64* __restrict__ vis,
+                                                                     int h, int w, const unsigned char* __restrict__ frames, int fh, int fw,
+                                                                     const float* __restrict__ normals, const float* __restrict__ normal_mat,
+                                                                     BakeRules rules, const unsigned char* __restrict__ fallback, uchar3 background,
+                                                                     unsigned char* __restrict__ texture, float* __restrict__ weight,
+                                                                     int32_t* __restrict__ seen) {
+    const int g = int(blockIdx.x) * kThreads + int(threadIdx.x);
+    if (g >= n_texels) return;
+    const int P = atlas.patch, pp = P * P;
+    const int pair = g / pp, local = g - pair * pp, j = local / P, i = local - j * P;
+    const int crow = pair / atlas.cells_per_row, ccol = pair - crow * atlas.cells_per_row;
+    const int64_t texel = int64_t(crow * P + j) * atlas.tw + (ccol * P + i);
+    const int half = i + j >= P ? 1 : 0;
+    const int64_t t = int64_t(pair) * 2 + half;
+    int id[3] = {0, 0, 0};
+    bool owned = t < n_tris;
+    if (owned) {
+        id[0] = faces[t * 3 + 0]; id[1] = faces[t * 3 + 1]; id[2] = faces[t * 3 + 2];
+        owned = uint32_t(id[0]) < uint32_t(n_verts) && uint32_t(id[1]) < uint32_t(n_verts) && uint32_t(id[2]) < uint32_t(n_verts);
+    }
+    if (!owned) {
+        texture[texel * 3 + 0] = background.x; texture[texel * 3 + 1] = background.y; texture[texel * 3 + 2] = background.z;
+        if (weight) weight[texel] = 0.0f;
+        if (seen) seen[texel] = -1;
+        return;
+    }
+    const float L = float(P - 3);
+    const float b1 = div_rn(float(half ? P - 1 - i : i), L), b2 = div_rn(float(half ? P - 1 - j : j), L);
+    const float b0 = sub_rn(sub_rn(1.0f, b1), b2);
+    const float* v0 = verts + int64_t(id[0]) * 3;
+    const float* v1 = verts + int64_t(id[1]) * 3;
+    const float* v2 = verts + int64_t(id[2]) * 3;
+    float x[3], n[3] = {0.f, 0.f, 0.f};
+#pragma unroll
+    for (int k = 0; k < 3; k++) x[k] = add_rn(add_rn(mul_rn(b0, v0[k]), mul_rn(b1, v1[k])), mul_rn(b2, v2[k]));
+    if (normals) {
+        const float* n0 = normals + int64_t(id[0]) * 3;
+        const float* n1 = normals + int64_t(id[1]) * 3;
+        const float* n2 = normals + int64_t(id[2]) * 3;
+#pragma unroll
+        for (int k = 0; k < 3; k++) n[k] = add_rn(add_rn(mul_rn(b0, n0[k]), mul_rn(b1, n1[k])), mul_rn(b2, n2[k]));
+    }
+    // what an unseen texel holds, made before the loop over the views: the fallback's pointer, the corner ids and the barycentrics need not
+    // live through it (the guard = 4 instantiation has no scalar register to spare)
+    unsigned char unseen[3] = {background.x, background.y, background.z};
+    if (fallback) {
+        const unsigned char* c0 = fallback + int64_t(id[0]) * 3;
+        const unsigned char* c1 = fallback + int64_t(id[1]) * 3;
+        const unsigned char* c2 = fallback + int64_t(id[2]) * 3;
+#pragma unroll
+        for (int k = 0; k < 3; k++) unseen[k] = level_u8(add_rn(add_rn(mul_rn(b0, float(c0[k])), mul_rn(b1, float(c1[k]))), mul_rn(b2, float(c2[k]))));
+    }
+    unsigned char* __restrict__ out = texture + texel * 3;
+    BakeSums sums = {0.f, 0.f, 0.f, 0.f, 0};
+    for (int view = 0; view < n_views; view++)
+        bake_view<GUARD>(x, n, view, mesh2cam, intrinsics, vis, h, w, frames, fh, fw, normals ? normal_mat : nullptr, rules, sums);
+    const bool hit = sums.accw > 0.0f;
+    out[0] = hit ? level_u8(div_rn(sums.acc0, sums.accw)) : unseen[0];
+    out[1] = hit ? level_u8(div_rn(sums.acc1, sums.accw)) : unseen[1];
+    out[2] = hit ? level_u8(div_rn(sums.acc2, sums.accw)) : unseen[2];
+    if (weight) weight[texel] = sums.accw;
+    if (seen) seen[texel] = sums.count;
+}
+
+// ------------------------------------------------------------------------------------------------ textured resolve
+// raster_resolve_kernel's sibling: one thread per pixel, the winning triangle set up again (the same bits), its perspective-correct weights
+// taken back from the drawn order to the face's own corners, and the atlas sampled bilinearly at the point they name in the triangle's patch.
+__global__ __launch_bounds__(kThreads) void raster_resolve_textured_kernel(const u64* __restrict__ vis, const float* __restrict__ verts, int n_verts,
+                                                                           const int32_t* __restrict__ faces, int n_tris, const float* __restrict__ mesh2cam,
+                                                                           const float* __restrict__ intrinsics, int n_pixels, int h, int w,
+                                                                           const unsigned char* __restrict__ texture, Atlas atlas, int th, uchar3 background,
+                                                                           unsigned char* __restrict__ out_frame) {
+    const int p = int(blockIdx.x) * kThreads + int(threadIdx.x);
+    if (p >= n_pixels) return;
+    const int view = p / (h * w), rem = p - view * (h * w), row = rem / w, col = rem - row * w;
+    const u64 key = vis[p];
+    const uint32_t tri = uint32_t(key);
+    bool hit = key != kEmpty && tri < uint32_t(n_tris);
+    Vtx v0, v1, v2;
+    int id[3];
+    if (hit) {
+        const Camera cam = load_camera(mesh2cam, intrinsics, view, h, w);
+        hit = fetch(verts, n_verts, faces, tri, cam, 0.0f, v0, v1, v2, id);
+    }
+    Tri t = {};
+    if (hit) {
+        t = setup(v0, v1, v2, GNERF_RASTER_CULL_NONE, h, w);
+        hit = t.status == 0;
+    }
+    if (!hit) {
+        out_frame[int64_t(p) * 3 + 0] = background.x; out_frame[int64_t(p) * 3 + 1] = background.y; out_frame[int64_t(p) * 3 + 2] = background.z;
+        return;
+    }
+    int64_t wa, wb, wc;
+    (void)cover(t, row, col, wa, wb, wc);
+    float ba, bb, bc;
+    const float iz = interp_iz(t, wa, wb, wc, ba, bb, bc);
+    const float qb = div_rn(mul_rn(bb, t.izb), iz), qc = div_rn(mul_rn(bc, t.izc), iz);
+    const float q1 = t.flipped ? qc : qb, q2 = t.flipped ? qb : qc;      // drawn as (0, 2, 1) when flipped: back to the face's corners 1 and 2
+    const int P = atlas.patch, pair = int(tri >> 1);
+    const int crow = pair / atlas.cells_per_row, ccol = pair - crow * atlas.cells_per_row;
+    const float L = float(P - 3), far = float(P - 1);
+    float lx = mul_rn(q1, L), ly = mul_rn(q2, L);
+    if (tri & 1u) { lx = sub_rn(far, lx); ly = sub_rn(far, ly); }
+    const float u = add_rn(float(ccol * P), lx), s = add_rn(float(crow * P), ly);
+    const float x0f = floorf(u), y0f = floorf(s);
+    const float tx = sub_rn(u, x0f), ty = sub_rn(s, y0f);
+    const float ux = sub_rn(1.0f, tx), uy = sub_rn(1.0f, ty);
+    const int tw = atlas.tw;
+    const int x0 = min(max(int(x0f), 0), tw - 1), x1 = min(max(int(x0f) + 1, 0), tw - 1);
+    const int y0 = min(max(int(y0f), 0), th - 1), y1 = min(max(int(y0f) + 1, 0), th - 1);
+    const unsigned char* p00 = texture + (int64_t(y0) * tw + x0) * 3;
+    const unsigned char* p01 = texture + (int64_t(y0) * tw + x1) * 3;
+    const unsigned char* p10 = texture + (int64_t(y1) * tw + x0) * 3;
+    const unsigned char* p11 = texture + (int64_t(y1) * tw + x1) * 3;
+#pragma unroll
+    for (int k = 0; k < 3; k++) {
+        const float top = add_rn(mul_rn(ux, float(p00[k])), mul_rn(tx, float(p01[k])));
+        const float bot = add_rn(mul_rn(ux, float(p10[k])), mul_rn(tx, float(p11[k])));
+        out_frame[int64_t(p) * 3 + k] = level_u8(add_rn(mul_rn(uy, top), mul_rn(ty, bot)));
+    }
 }
 
 int check_geometry(const char* what, int n_verts, int n_tris, int n_views, int h, int w, int64_t* total) {
@@ -576,4 +730,86 @@ extern "C" int gnerf_mesh_bake_colors(const float* verts, int n_verts, const flo
     hipLaunchKernelGGL(kernel, dim3((n_verts + kThreads - 1) / kThreads), dim3(kThreads), 0, as_stream(stream), verts, n_verts, mesh2cam, intrinsics,
                        n_views, reinterpret_cast<const u64*>(vis), h, w, frames, fh, fw, normals, normal_mat, rules, fallback, colors, weight, seen);
     return check_launch("mesh_bake_colors");
+}
+
+namespace {
+
+// The atlas rule of include/gnerf_hip.h, in integers.  rc != 0: the error is set.
+int atlas_layout(const char* what, int n_tris, int patch, int* cells_per_row, int* th, int* tw) {
+    using namespace gnerf;
+    if (n_tris < 0) return fail(GNERF_E_ARG, "%s: negative triangle count", what);
+    if (patch < GNERF_ATLAS_MIN_PATCH || patch > GNERF_ATLAS_MAX_PATCH)
+        return fail(GNERF_E_ARG, "%s: patch must be %d..%d (got %d)", what, GNERF_ATLAS_MIN_PATCH, GNERF_ATLAS_MAX_PATCH, patch);
+    const int64_t n_pairs = (int64_t(n_tris) + 1) / 2;
+    int64_t c = 0;
+    while (c * c < n_pairs) c++;                     // (at most 32768 steps, on the host)
+    const int64_t rows = c ? (n_pairs + c - 1) / c : 0;
+    if (c * patch > GNERF_ATLAS_MAX_SIZE || rows * patch > GNERF_ATLAS_MAX_SIZE)
+        return fail(GNERF_E_UNSUPPORTED, "%s: %d triangles at patch %d need an atlas of %lld x %lld texels, more than %d a side", what, n_tris, patch,
+                    (long long)(rows * patch), (long long)(c * patch), GNERF_ATLAS_MAX_SIZE);
+    *cells_per_row = int(c);
+    *th = int(rows * patch);
+    *tw = int(c * patch);
+    return GNERF_OK;
+}
+
+}  // namespace
+
+extern "C" int gnerf_mesh_atlas_layout(int n_tris, int patch, int* cells_per_row, int* th, int* tw) {
+    using namespace gnerf;
+    if (!cells_per_row || !th || !tw) return fail(GNERF_E_ARG, "mesh_atlas_layout: null pointer");
+    return atlas_layout("mesh_atlas_layout", n_tris, patch, cells_per_row, th, tw);
+}
+
+extern "C" int gnerf_mesh_bake_texture(const float* verts, int n_verts, const int32_t* faces, int n_tris, int patch, const float* mesh2cam,
+                                       const float* intrinsics, int n_views, const uint64_t* vis, int h, int w, const unsigned char* frames, int fh, int fw,
+                                       const float* normals, const float* normal_mat, float near_z, float depth_tol, int guard, float min_cos, int power,
+                                       const unsigned char* fallback, const unsigned char* background, unsigned char* texture, float* weight, int32_t* seen,
+                                       gnerf_stream_t stream) {
+    using namespace gnerf;
+    const char* what = "mesh_bake_texture";
+    int64_t total;
+    if (int rc = check_geometry(what, n_verts, n_tris, n_views, h, w, &total)) return rc;
+    if (int rc = check_geometry("mesh_bake_texture (frames)", n_verts, n_tris, n_views, fh, fw, &total)) return rc;
+    if (!mesh2cam || !intrinsics || !vis || !frames || !background) return fail(GNERF_E_ARG, "%s: null pointer", what);
+    if (n_tris > 0 && (!faces || !texture || (n_verts > 0 && !verts))) return fail(GNERF_E_ARG, "%s: null pointer (verts / faces / texture of a non-empty mesh)", what);
+    if (!(near_z > 0.0f)) return fail(GNERF_E_ARG, "%s: near must be > 0", what);
+    if (!(depth_tol >= 0.0f)) return fail(GNERF_E_ARG, "%s: depth_tol must be >= 0", what);
+    if (guard < 0 || guard > GNERF_BAKE_MAX_GUARD) return fail(GNERF_E_ARG, "%s: guard must be 0..%d (got %d)", what, GNERF_BAKE_MAX_GUARD, guard);
+    if (power < 0 || power > GNERF_BAKE_MAX_POWER) return fail(GNERF_E_ARG, "%s: power must be 0..%d (got %d)", what, GNERF_BAKE_MAX_POWER, power);
+    if (normals && !normal_mat) return fail(GNERF_E_ARG, "%s: normals need normal_mat", what);
+    int cells, th, tw;
+    if (int rc = atlas_layout(what, n_tris, patch, &cells, &th, &tw)) return rc;
+    if (n_tris == 0) return GNERF_OK;
+    const int n_texels = th * tw;                                          // at most 2^28
+    const Atlas atlas = {patch, cells, tw, (n_tris + 1) / 2};
+    const BakeRules rules = {near_z, depth_tol, min_cos, power};
+    const uchar3 bg = {background[0], background[1], background[2]};
+    static_assert(GNERF_BAKE_MAX_GUARD == 4, "one instantiation per guard");
+    const auto kernel = guard == 0 ? mesh_bake_texture_kernel<0> : guard == 1 ? mesh_bake_texture_kernel<1> : guard == 2 ? mesh_bake_texture_kernel<2>
+                      : guard == 3 ? mesh_bake_texture_kernel<3> : mesh_bake_texture_kernel<4>;
+    hipLaunchKernelGGL(kernel, dim3((n_texels + kThreads - 1) / kThreads), dim3(kThreads), 0, as_stream(stream), verts, n_verts, faces, n_tris, atlas, n_texels,
+                       mesh2cam, intrinsics, n_views, reinterpret_cast<const u64*>(vis), h, w, frames, fh, fw, normals, normal_mat, rules, fallback, bg, texture,
+                       weight, seen);
+    return check_launch("mesh_bake_texture");
+}
+
+extern "C" int gnerf_raster_resolve_textured(const uint64_t* vis, const float* verts, int n_verts, const int32_t* faces, int n_tris, const float* mesh2cam,
+                                             const float* intrinsics, int n_views, int h, int w, const unsigned char* texture, int patch,
+                                             const unsigned char* background, unsigned char* frame, gnerf_stream_t stream) {
+    using namespace gnerf;
+    const char* what = "raster_resolve_textured";
+    int64_t total;
+    if (int rc = check_geometry(what, n_verts, n_tris, n_views, h, w, &total)) return rc;
+    if (!vis || !mesh2cam || !intrinsics || !background || !frame) return fail(GNERF_E_ARG, "%s: null pointer", what);
+    if (total > 0 && (!verts || !faces || !texture)) return fail(GNERF_E_ARG, "%s: null pointer (verts / faces / texture of a non-empty mesh)", what);
+    int cells, th, tw;
+    if (int rc = atlas_layout(what, n_tris, patch, &cells, &th, &tw)) return rc;
+    const Atlas atlas = {patch, cells, tw, (n_tris + 1) / 2};
+    const uchar3 bg = {background[0], background[1], background[2]};
+    const int n_pixels = n_views * h * w;
+    hipLaunchKernelGGL(raster_resolve_textured_kernel, dim3((n_pixels + kThreads - 1) / kThreads), dim3(kThreads), 0, as_stream(stream),
+                       reinterpret_cast<const u64*>(vis), verts, n_verts, faces, total == 0 ? 0 : n_tris, mesh2cam, intrinsics, n_pixels, h, w, texture, atlas,
+                       th, bg, frame);
+    return check_launch("raster_resolve_textured");
 }

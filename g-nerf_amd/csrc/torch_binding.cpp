@@ -13,7 +13,8 @@
 // marching_cubes (gnerf_hip.marching_cubes' count -> read counts -> emit sequence), ssim_forward / ssim_backward (gnerf_hip.ssim_*),
 // modconv_backward (gnerf_hip.scale_channels_backward / modconv_epilogue_backward), query_points_grad (gnerf_hip.query_points_grad),
 // render_backward_rays (gnerf_hip.render_backward with need_rays), resize_aa (gnerf_hip.resize_aa_forward / _backward),
-// raster_visibility / raster_resolve / mesh_bake_colors (gnerf_hip.rasterize / resolve / bake_colors), mesh_components / mesh_compact / mesh_smooth /
+// raster_visibility / raster_resolve / mesh_bake_colors (gnerf_hip.rasterize / resolve / bake_colors), mesh_atlas_layout / mesh_bake_texture /
+// raster_resolve_textured (gnerf_hip.atlas_layout / bake_texture / resolve_textured), mesh_components / mesh_compact / mesh_smooth /
 // mesh_simplify / mesh_simplify_count / project_points_to_level / mesh_flip_guard (gnerf_hip's of those names).
 //
 // Built ahead of time by csrc/build.sh (g++, no hipcc: there is no device code) into g-nerf_amd/gnerf_hip/gnerf_torch_ext.so.
@@ -668,6 +669,71 @@ std::tuple<Tensor, Tensor, Tensor> mesh_bake_colors(Tensor verts, Tensor mesh2ca
     return std::make_tuple(c, wt, sn);
 }
 
+// The atlas of (n_tris, patch) -> (cells per row, th, tw); the library's error (patch out of range, an atlas past the cap) is raised.
+std::tuple<int64_t, int64_t, int64_t> mesh_atlas_layout(int64_t n_tris, int64_t patch) {
+    TORCH_CHECK(n_tris >= 0 && n_tris <= INT_MAX && patch >= INT_MIN && patch <= INT_MAX, "mesh_atlas_layout: oversized argument");
+    int cells = 0, th = 0, tw = 0;
+    check_rc(gnerf_mesh_atlas_layout(int(n_tris), int(patch), &cells, &th, &tw), "gnerf_mesh_atlas_layout");
+    return std::make_tuple(int64_t(cells), int64_t(th), int64_t(tw));
+}
+
+// gnerf_hip.bake_texture has validated the tensors as mesh_bake_colors' are, plus faces int32 [T, 3].  texture / weight / seen: preallocated
+// outputs or None.  -> (texture uint8 [th, tw, 3], weight float32 [th, tw], seen int32 [th, tw]).
+std::tuple<Tensor, Tensor, Tensor> mesh_bake_texture(Tensor verts, Tensor faces, int64_t patch, Tensor mesh2cam, Tensor intrinsics, Tensor vis, Tensor frames,
+                                                     c10::optional<Tensor> normals, c10::optional<Tensor> normal_mat, double near_z, double depth_tol,
+                                                     int64_t guard, double min_cos, int64_t power, c10::optional<Tensor> fallback, std::vector<int64_t> background,
+                                                     c10::optional<Tensor> texture, c10::optional<Tensor> weight, c10::optional<Tensor> seen) {
+    TORCH_CHECK(verts.is_cuda() && verts.scalar_type() == torch::kFloat32 && verts.is_contiguous() && faces.scalar_type() == torch::kInt32 && faces.is_contiguous() &&
+                mesh2cam.scalar_type() == torch::kFloat32 && mesh2cam.is_contiguous() && intrinsics.scalar_type() == torch::kFloat32 && intrinsics.is_contiguous(),
+                "mesh_bake_texture: unexpected tensor layout");
+    TORCH_CHECK(vis.is_cuda() && vis.scalar_type() == torch::kInt64 && vis.is_contiguous() && vis.dim() == 3, "mesh_bake_texture: vis must be a contiguous int64 [n, h, w] GPU tensor");
+    TORCH_CHECK(frames.is_cuda() && frames.scalar_type() == torch::kUInt8 && frames.is_contiguous() && frames.dim() == 4 && frames.size(0) == vis.size(0) && frames.size(3) == 3,
+                "mesh_bake_texture: frames must be a contiguous uint8 [n, fh, fw, 3] GPU tensor");
+    TORCH_CHECK(verts.size(0) <= INT_MAX && faces.size(0) <= INT_MAX && frames.size(1) <= INT_MAX && frames.size(2) <= INT_MAX && guard >= INT_MIN && guard <= INT_MAX &&
+                power >= INT_MIN && power <= INT_MAX && patch >= INT_MIN && patch <= INT_MAX, "mesh_bake_texture: oversized argument");
+    TORCH_CHECK(background.size() == 3, "mesh_bake_texture: background holds 3 values");
+    const c10::hip::OptionalHIPGuardMasqueradingAsCUDA device_guard(at::device_of(verts));
+    const int n_verts = int(verts.size(0)), n_tris = int(faces.size(0)), n = int(vis.size(0));
+    int cells = 0, th = 0, tw = 0;
+    check_rc(gnerf_mesh_atlas_layout(n_tris, int(patch), &cells, &th, &tw), "gnerf_mesh_atlas_layout");
+    Tensor tex = texture.has_value() ? *texture : torch::empty({th, tw, 3}, verts.options().dtype(torch::kUInt8));
+    Tensor wt = weight.has_value() ? *weight : torch::empty({th, tw}, verts.options().dtype(torch::kFloat32));
+    Tensor sn = seen.has_value() ? *seen : torch::empty({th, tw}, verts.options().dtype(torch::kInt32));
+    TORCH_CHECK(tex.numel() == int64_t(th) * tw * 3 && wt.numel() == int64_t(th) * tw && sn.numel() == int64_t(th) * tw, "mesh_bake_texture: an output of the wrong size");
+    unsigned char bg[3];
+    for (int k = 0; k < 3; k++) bg[k] = (unsigned char)std::min<int64_t>(std::max<int64_t>(background[k], 0), 255);
+    auto p = [](const c10::optional<Tensor>& t) -> void* { return t.has_value() ? t->data_ptr() : nullptr; };
+    check_rc(gnerf_mesh_bake_texture(n_verts ? verts.data_ptr<float>() : nullptr, n_verts, n_tris ? faces.data_ptr<int32_t>() : nullptr, n_tris, int(patch),
+                                     mesh2cam.data_ptr<float>(), intrinsics.data_ptr<float>(), n, reinterpret_cast<const uint64_t*>(vis.data_ptr<int64_t>()),
+                                     int(vis.size(1)), int(vis.size(2)), frames.data_ptr<uint8_t>(), int(frames.size(1)), int(frames.size(2)),
+                                     static_cast<const float*>(p(normals)), static_cast<const float*>(p(normal_mat)), float(near_z), float(depth_tol), int(guard),
+                                     float(min_cos), int(power), static_cast<const unsigned char*>(p(fallback)), bg, n_tris ? tex.data_ptr<uint8_t>() : nullptr,
+                                     n_tris ? wt.data_ptr<float>() : nullptr, n_tris ? sn.data_ptr<int32_t>() : nullptr, current_stream()),
+             "gnerf_mesh_bake_texture");
+    return std::make_tuple(tex, wt, sn);
+}
+
+// gnerf_hip.resolve_textured has validated the tensors as raster_resolve's are, plus texture uint8 [th, tw, 3] of the atlas of (T, patch).
+Tensor raster_resolve_textured(Tensor vis, Tensor verts, Tensor faces, Tensor mesh2cam, Tensor intrinsics, Tensor texture, int64_t patch,
+                               std::vector<int64_t> background) {
+    TORCH_CHECK(vis.is_cuda() && vis.scalar_type() == torch::kInt64 && vis.is_contiguous() && vis.dim() == 3, "raster_resolve_textured: vis must be a contiguous int64 [n, h, w] GPU tensor");
+    TORCH_CHECK(texture.is_cuda() && texture.scalar_type() == torch::kUInt8 && texture.is_contiguous(), "raster_resolve_textured: texture must be a contiguous uint8 GPU tensor");
+    TORCH_CHECK(verts.size(0) <= INT_MAX && faces.size(0) <= INT_MAX && patch >= INT_MIN && patch <= INT_MAX && background.size() == 3, "raster_resolve_textured: oversized argument");
+    const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(at::device_of(vis));
+    const int n = int(vis.size(0)), h = int(vis.size(1)), w = int(vis.size(2)), n_verts = int(verts.size(0)), n_tris = int(faces.size(0));
+    int cells = 0, th = 0, tw = 0;
+    check_rc(gnerf_mesh_atlas_layout(n_tris, int(patch), &cells, &th, &tw), "gnerf_mesh_atlas_layout");
+    TORCH_CHECK(texture.numel() == int64_t(th) * tw * 3, "raster_resolve_textured: texture is not the atlas of this mesh and patch");
+    Tensor frame = torch::empty({n, h, w, 3}, vis.options().dtype(torch::kUInt8));
+    unsigned char bg[3];
+    for (int k = 0; k < 3; k++) bg[k] = (unsigned char)std::min<int64_t>(std::max<int64_t>(background[k], 0), 255);
+    check_rc(gnerf_raster_resolve_textured(reinterpret_cast<const uint64_t*>(vis.data_ptr<int64_t>()), n_verts ? verts.data_ptr<float>() : nullptr, n_verts,
+                                           n_tris ? faces.data_ptr<int32_t>() : nullptr, n_tris, mesh2cam.data_ptr<float>(), intrinsics.data_ptr<float>(), n, h, w,
+                                           n_tris ? texture.data_ptr<uint8_t>() : nullptr, int(patch), bg, frame.data_ptr<uint8_t>(), current_stream()),
+             "gnerf_raster_resolve_textured");
+    return frame;
+}
+
 // ------------------------------------------------------------------------------------------------ mesh cleaning (csrc/mesh_clean.hip)
 // gnerf_hip.mesh_components / mesh_compact / mesh_smooth have validated the tensors: verts float32 [V, 3], faces int32 [T, 3], label and
 // faces_of int32 [V], keep uint8 [V], all contiguous on one GPU.
@@ -827,6 +893,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("raster_visibility", &raster_visibility);
     m.def("raster_resolve", &raster_resolve);
     m.def("mesh_bake_colors", &mesh_bake_colors);
+    m.def("mesh_atlas_layout", &mesh_atlas_layout);
+    m.def("mesh_bake_texture", &mesh_bake_texture);
+    m.def("raster_resolve_textured", &raster_resolve_textured);
     m.def("mesh_components", &mesh_components);
     m.def("mesh_compact", &mesh_compact);
     m.def("mesh_smooth", &mesh_smooth);

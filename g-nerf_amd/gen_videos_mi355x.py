@@ -34,6 +34,9 @@ default, which changes nothing.
 rasterised from their cameras at `--mesh-bake-res`, every vertex takes the frames' colours where the visibility buffers say it is seen
 (csrc/raster.hip, gnerf_mesh_bake_colors; `--mesh-bake-tol`, `--mesh-bake-guard`, `--mesh-bake-power`), blended by how squarely each view faces
 the surface when `--mesh-attrs` made normals; the decoder's colours, when it made them, stay on the vertices no frame sees.
+`--mesh-texture P --mesh-texture-out PATH.obj` (with `--mesh-bake N`) also bakes those N frames into a texture atlas of the final mesh, two
+triangles to a cell of P x P texels (gnerf_mesh_bake_texture: the vertex bake's rules per texel), and writes the mesh with its UVs as PATH.obj,
+its .mtl and its .png; the .ply of `--mesh` is the same file as without it.
 """
 
 import argparse
@@ -379,10 +382,11 @@ def bake_frames_of_orbit(full, n_frames, n_bake, radius):
     return idx, full[idx].contiguous(), H.orbit_labels(idx, n_frames, radius)
 
 
-def bake_extracted_mesh(verts, faces, normals, fallback, bake, resolution, cube_length):
+def bake_extracted_mesh(verts, faces, normals, fallback, bake, resolution, cube_length, patch=0):
     """--mesh-bake on the final mesh (index space; mesh_to_world_matrix puts it into the world): shape_mi355x.bake_mesh_colors from bake['frames']
     (uint8 [N, H, W, 3]) and their camera labels bake['labels'] [N, 25], rasterised at bake['res'] (None: the frames' size), with bake['rules'].
-    normals / fallback: per-vertex arrays or tensors, or None.  Kernels when the frames are on a GPU, the numpy ports otherwise."""
+    normals / fallback: per-vertex arrays or tensors, or None.  Kernels when the frames are on a GPU, the numpy ports otherwise.
+    patch > 0: --mesh-texture instead, shape_mi355x.bake_mesh_texture of the atlas at that patch size from the same frames, cameras and rules."""
     frames, labels = bake['frames'], bake['labels']
     dev = frames.device
 
@@ -392,9 +396,10 @@ def bake_extracted_mesh(verts, faces, normals, fallback, bake, resolution, cube_
         x = x if isinstance(x, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(x))
         x = x.to(dev) if dtype is None else x.to(dev, dtype)
         return x if dev.type == 'cuda' else x.numpy()
-    return shape_mi355x.bake_mesh_colors(place(verts, torch.float32), place(faces, torch.int32), place(frames), labels[:, :16].reshape(-1, 4, 4),
-                                         labels[:, 16:25].reshape(-1, 3, 3), mesh2world=mesh_to_world_matrix(resolution, cube_length),
-                                         normals=place(normals, torch.float32), vis_size=bake.get('res'), fallback=place(fallback), **bake.get('rules', {}))
+    stage = shape_mi355x.bake_mesh_colors if not patch else lambda *a, **kw: shape_mi355x.bake_mesh_texture(*a, patch=patch, **kw)
+    return stage(place(verts, torch.float32), place(faces, torch.int32), place(frames), labels[:, :16].reshape(-1, 4, 4),
+                 labels[:, 16:25].reshape(-1, 3, 3), mesh2world=mesh_to_world_matrix(resolution, cube_length),
+                 normals=place(normals, torch.float32), vis_size=bake.get('res'), fallback=place(fallback), **bake.get('rules', {}))
 
 
 def mesh_of_density_grid(vol, level=10.0, attrs=None, G=None, planes=None, clean=None, simplify=None, snap=None, bake=None):
@@ -405,7 +410,8 @@ def mesh_of_density_grid(vol, level=10.0, attrs=None, G=None, planes=None, clean
     attrs: None / 'none', 'normals', 'colors' or 'all' -- per-vertex attributes (mesh_vertex_attributes) of generator G on `planes`
     (extract_density_grid(..., return_planes=True)).  clean, simplify, snap: None or shape_mi355x.clean_options' / simplify_options' /
     snap_options' dict (snap_extracted_mesh on G and `planes`).  bake: None or bake_extracted_mesh's dict (frames, labels, res, rules) -- the
-    final mesh is coloured from those frames, with the normals when attrs made them and the decoder's colours, when it made them, as the fallback.
+    final mesh is coloured from those frames, with the normals when attrs made them and the decoder's colours, when it made them, as the fallback;
+    with bake['texture'] = P > 0 its texture atlas at patch P is baked from them too (the FinishedMesh's reports['texture']).
     With every option None nothing but marching cubes runs."""
     attrs = 'none' if attrs is None else attrs
     if attrs not in MESH_ATTRS:
@@ -426,6 +432,9 @@ def mesh_of_density_grid(vol, level=10.0, attrs=None, G=None, planes=None, clean
                                                                 attrs in ('colors', 'all'))
     if bake:
         stages['bake'] = lambda v, f, normals, colors: bake_extracted_mesh(v, f, normals, colors, bake, res, G.rendering_kwargs['box_warp'])
+        if bake.get('texture'):
+            stages['texture'] = lambda v, f, normals, colors: bake_extracted_mesh(v, f, normals, colors, bake, res, G.rendering_kwargs['box_warp'],
+                                                                                  patch=bake['texture'])
     return shape_mi355x.finish_mesh(verts, faces, clean=clean, simplify=simplify, **stages), dt
 
 
@@ -479,7 +488,7 @@ def arg_parser():
     ap.add_argument('--mesh', default=None, help='also mesh the density volume on the device and write this .ply (shape_utils.py; rank 0)')
     ap.add_argument('--mesh-level', type=float, default=10, help='isosurface level of --mesh (shape_utils.py:111)')
     ap.add_argument('--mesh-attrs', choices=MESH_ATTRS, default='none', help='per-vertex attributes of --mesh: normals of the density field and / or the decoder\'s colours')
-    shape_mi355x.add_mesh_arguments(ap, attributes=True)
+    shape_mi355x.add_mesh_arguments(ap, attributes=True, texture=True)
     ap.add_argument('--mesh-snap', type=float, default=0, metavar='R',
                     help='last, after the smoothing: move every vertex onto the level set of the density itself (Newton steps along its gradient), at most '
                          'R voxels per axis from where it stood; faces that this turns over get their vertices back (--mesh and --geometry-out; 0: off)')
@@ -506,6 +515,7 @@ def main():
     clean, simplify, snap = shape_mi355x.mesh_options_from_args(args, ap)
     if args.mesh_bake and not args.mesh:
         ap.error('--mesh-bake requires --mesh')
+    texture_patch = shape_mi355x.texture_from_args(args, ap)
     if not 0 <= args.mesh_bake <= args.frames:
         ap.error('--mesh-bake must be 0 .. --frames')
     if (not args.mesh_bake_tol >= 0 or not 0 <= args.mesh_bake_guard <= 4 or not 0 <= args.mesh_bake_power <= 8
@@ -573,11 +583,17 @@ def main():
             if args.mesh_bake:                                           # N of the frames this run has just gathered, and their cameras
                 _, bake_frames, bake_labels = bake_frames_of_orbit(full, args.frames, args.mesh_bake, G.rendering_kwargs['avg_camera_radius'])
                 bake = dict(frames=bake_frames, labels=bake_labels, res=args.mesh_bake_res,
-                            rules=dict(depth_tol=args.mesh_bake_tol, guard=args.mesh_bake_guard, power=args.mesh_bake_power))
+                            rules=dict(depth_tol=args.mesh_bake_tol, guard=args.mesh_bake_guard, power=args.mesh_bake_power), texture=texture_patch)
             nv, nf, dt = written = mesh_density_grid(vol, args.mesh, args.mesh_level, planes=planes, bake=bake, **stages)
             made['mesh'] = written.mesh
             for line in shape_mi355x.report_lines(written.mesh.reports, smooth=args.mesh_smooth, bake_views=args.mesh_bake):
                 print(line)
+            if texture_patch:                                            # the same mesh again as .obj + .mtl + .png, with the atlas' UVs
+                mesh, textured = written.mesh, written.mesh.reports['texture']
+                shape_mi355x.write_obj(args.mesh_texture_out, shape_mi355x.to_host(mesh.verts), shape_mi355x.to_host(mesh.faces),
+                                       shape_mi355x.atlas_uvs(nf, texture_patch), shape_mi355x.to_host(textured['texture']),
+                                       normals=shape_mi355x.to_host(mesh.normals))
+                print(shape_mi355x.texture_report_line(textured, args.mesh_bake, texture_patch) + f' -> {args.mesh_texture_out}')
             print(f'mesh at level {args.mesh_level:g}: {dt * 1e3:.2f} ms, {nv} vertices, {nf} triangles -> {args.mesh}'
                   + (f' (with {args.mesh_attrs}: {(time.perf_counter() - t0) * 1e3:.2f} ms in all, file included)' if args.mesh_attrs != 'none' else ''))
     if args.geometry_out:

@@ -43,3 +43,5 @@ from .resize import (RESIZE_MAX_TAPS, RESIZE_MODES, resize_aa_available, resize_
 from .raster import (RASTER_CULL, RASTER_MAX_SIZE, RASTER_OUTPUTS, RASTER_SHADING, RASTER_SMALL_PIXELS, raster_available, raster_workspace_bytes, rasterize,  # noqa: F401
                      resolve, shading_vector, _rasterize_ctypes, _resolve_ctypes)
 from .raster import BAKE_MAX_GUARD, BAKE_MAX_POWER, BAKE_OUTPUTS, BAKE_RULES, bake_available, bake_colors, _bake_colors_ctypes  # noqa: F401
+from .raster import (ATLAS_MAX_PATCH, ATLAS_MAX_SIZE, ATLAS_MIN_PATCH, TEXTURE_OUTPUTS, atlas_layout, bake_texture, resolve_textured, texture_available,  # noqa: F401
+                     _bake_texture_ctypes, _resolve_textured_ctypes)

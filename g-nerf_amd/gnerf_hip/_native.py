@@ -141,6 +141,10 @@ SIGNATURES = {
                                     _c_p, _c_p, _c_p, _c_p, _c_p]),
     'gnerf_mesh_bake_colors': (_c_i, [_c_p, _c_i, _c_p, _c_p, _c_i, _c_p, _c_i, _c_i, _c_p, _c_i, _c_i, _c_p, _c_p, _c_f, _c_f, _c_i, _c_f, _c_i, _c_p,
                                       _c_p, _c_p, _c_p, _c_p]),
+    'gnerf_mesh_atlas_layout': (_c_i, [_c_i, _c_i, ctypes.POINTER(_c_i), ctypes.POINTER(_c_i), ctypes.POINTER(_c_i)]),
+    'gnerf_mesh_bake_texture': (_c_i, [_c_p, _c_i, _c_p, _c_i, _c_i, _c_p, _c_p, _c_i, _c_p, _c_i, _c_i, _c_p, _c_i, _c_i, _c_p, _c_p, _c_f, _c_f, _c_i, _c_f, _c_i,
+                                       _c_p, ctypes.POINTER(ctypes.c_ubyte), _c_p, _c_p, _c_p, _c_p]),
+    'gnerf_raster_resolve_textured': (_c_i, [_c_p, _c_p, _c_i, _c_p, _c_i, _c_p, _c_p, _c_i, _c_i, _c_i, _c_p, _c_i, ctypes.POINTER(ctypes.c_ubyte), _c_p, _c_p]),
     'gnerf_mesh_workspace_bytes': (_c_i, [_c_i, _c_i, ctypes.POINTER(ctypes.c_size_t)]),
     'gnerf_mesh_components': (_c_i, [_c_p, _c_i, _c_i, _c_p, _c_p, _c_p, _c_p, _c_p]),
     'gnerf_mesh_compact_count': (_c_i, [_c_p, _c_i, _c_i, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p]),
@@ -154,7 +158,7 @@ SIGNATURES = {
 # exports added WITHOUT a new ABI version: a library of the same version built before them (a variant build behind GNERF_HIP_LIB) loads, and
 # what needs them asks modconv_backward_available() / render_ray_grad_available() / decoder_pack_available() / resize_aa_available() /
 # raster_available() / mesh_clean_available() / mesh_simplify_available() / project_to_level_available() / mesh_flip_guard_available() /
-# scatter_plane_rows_available()
+# scatter_plane_rows_available() / texture_available()
 OPTIONAL_SYMBOLS = frozenset(n for n in SIGNATURES if n.startswith(('gnerf_project_points_to_level', 'gnerf_modconv_backward_','gnerf_scale_channels_backward', 'gnerf_modconv_epilogue_backward',
                                                                     'gnerf_render_backward_rays', 'gnerf_render_scatter_rows', 'gnerf_render_decoder_pack_bytes',
                                                                     'gnerf_render_pack_decoder', 'gnerf_render_forward_packed', 'gnerf_resize_aa_', 'gnerf_raster_', 'gnerf_mesh_')))

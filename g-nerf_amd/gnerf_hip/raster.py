@@ -1,5 +1,5 @@
 """The triangle rasteriser for extracted meshes (csrc/raster.hip): a visibility buffer per view, then depth / normal / shaded colour;
-and its inverse, the multi-view colour bake: frames back onto the vertices."""
+and its inverse, the multi-view colour bake: frames back onto the vertices, or into a texture atlas that a textured resolve draws."""
 
 import ctypes
 
@@ -211,6 +211,32 @@ def _bake_rules(near, depth_tol, guard, min_cos, power):
     return float(near), float(depth_tol), int(guard), float(min_cos), int(power)
 
 
+def _bake_inputs(v, A, vis, frames, normals, normal_mat, fallback):
+    """What bake_colors and bake_texture check alike, for verts v [V, 3] and cameras A [n, 12] -> (frames, normals, normal_mat, fallback) as the
+    C ABI takes them; ValueError for a tensor of the wrong kind."""
+    if vis.dtype != torch.int64 or vis.ndim != 3 or vis.shape[0] != len(A) or not vis.is_contiguous() or vis.device != v.device:
+        raise ValueError('bake: vis must be rasterize\'s int64 [n_views, h, w] tensor')
+    if (frames.dtype != torch.uint8 or frames.ndim != 4 or frames.shape[0] != len(A) or frames.shape[3] != 3 or frames.device != v.device
+            or not (1 <= frames.shape[1] <= RASTER_MAX_SIZE and 1 <= frames.shape[2] <= RASTER_MAX_SIZE)):
+        raise ValueError(f'bake: frames must be uint8 [n_views, fh, fw, 3] on the mesh\'s device, fh and fw in 1..{RASTER_MAX_SIZE}')
+    frames = frames.detach().contiguous()
+    if normals is not None:
+        if normal_mat is None:
+            raise ValueError('bake: normals need normal_mat')
+        _require_cuda(normals, normal_mat)
+        normals, normal_mat = _f32(normals, (3,), 'normals'), _f32(normal_mat, (9,), 'normal_mat')
+        if len(normals) != len(v) or len(normal_mat) != len(A) or normals.device != v.device or normal_mat.device != v.device:
+            raise ValueError('bake: normals must be [V, 3] and normal_mat [n_views, 3, 3], on the mesh\'s device')
+    else:
+        normal_mat = None
+    if fallback is not None:
+        _require_cuda(fallback)
+        if fallback.dtype != torch.uint8 or tuple(fallback.shape) != (len(v), 3) or fallback.device != v.device:
+            raise ValueError('bake: fallback must be uint8 [V, 3] on the mesh\'s device')
+        fallback = fallback.detach().contiguous()
+    return frames, normals, normal_mat, fallback
+
+
 def _bake_colors_ctypes(v, A, K, vis, frames, normals, normal_mat, rules, fallback, colors=None, weight=None, seen=None):
     """The ctypes route of bake_colors (arguments as bake_colors has validated them; rules: _bake_rules' tuple)."""
     dev, V = v.device, len(v)
@@ -241,26 +267,7 @@ def bake_colors(verts, mesh2cam, intrinsics, vis, frames, normals=None, normal_m
     _require_cuda(verts, vis, frames)
     v = _f32(verts, (3,), 'verts')
     A, K = _cameras(mesh2cam, intrinsics, v.device)
-    if vis.dtype != torch.int64 or vis.ndim != 3 or vis.shape[0] != len(A) or not vis.is_contiguous() or vis.device != v.device:
-        raise ValueError('bake: vis must be rasterize\'s int64 [n_views, h, w] tensor')
-    if (frames.dtype != torch.uint8 or frames.ndim != 4 or frames.shape[0] != len(A) or frames.shape[3] != 3 or frames.device != v.device
-            or not (1 <= frames.shape[1] <= RASTER_MAX_SIZE and 1 <= frames.shape[2] <= RASTER_MAX_SIZE)):
-        raise ValueError(f'bake: frames must be uint8 [n_views, fh, fw, 3] on the mesh\'s device, fh and fw in 1..{RASTER_MAX_SIZE}')
-    frames = frames.detach().contiguous()
-    if normals is not None:
-        if normal_mat is None:
-            raise ValueError('bake: normals need normal_mat')
-        _require_cuda(normals, normal_mat)
-        normals, normal_mat = _f32(normals, (3,), 'normals'), _f32(normal_mat, (9,), 'normal_mat')
-        if len(normals) != len(v) or len(normal_mat) != len(A) or normals.device != v.device or normal_mat.device != v.device:
-            raise ValueError('bake: normals must be [V, 3] and normal_mat [n_views, 3, 3], on the mesh\'s device')
-    else:
-        normal_mat = None
-    if fallback is not None:
-        _require_cuda(fallback)
-        if fallback.dtype != torch.uint8 or tuple(fallback.shape) != (len(v), 3) or fallback.device != v.device:
-            raise ValueError('bake: fallback must be uint8 [V, 3] on the mesh\'s device')
-        fallback = fallback.detach().contiguous()
+    frames, normals, normal_mat, fallback = _bake_inputs(v, A, vis, frames, normals, normal_mat, fallback)
     out = dict(out or {})
     if set(out) - set(BAKE_OUTPUTS):
         raise ValueError(f'bake: out holds {BAKE_OUTPUTS} at the most')
@@ -274,3 +281,128 @@ def bake_colors(verts, mesh2cam, intrinsics, vis, frames, normals=None, normal_m
             got = e.mesh_bake_colors(v, A, K, vis, frames, normals, normal_mat, *rules, fallback, out.get('colors'), out.get('weight'), out.get('seen'))
         return dict(zip(BAKE_OUTPUTS, got))
     return _bake_colors_ctypes(v, A, K, vis, frames, normals, normal_mat, rules, fallback, out.get('colors'), out.get('weight'), out.get('seen'))
+
+
+# ---------------------------------------------------------------------------------------------------------------- the texture atlas
+ATLAS_MIN_PATCH = 4                 # GNERF_ATLAS_MIN_PATCH
+ATLAS_MAX_PATCH = 64                # GNERF_ATLAS_MAX_PATCH
+ATLAS_MAX_SIZE = 16384              # GNERF_ATLAS_MAX_SIZE
+TEXTURE_OUTPUTS = ('texture', 'weight', 'seen')
+_TEXTURE_EXPORTS = ('gnerf_mesh_atlas_layout', 'gnerf_mesh_bake_texture', 'gnerf_raster_resolve_textured')
+
+
+def texture_available():
+    """Whether the loaded library has the texture bake and the textured resolve (a version-15 library built before them does not)."""
+    return all(hasattr(load(), name) for name in _TEXTURE_EXPORTS)
+
+
+def _require_texture():
+    if not texture_available():
+        raise RuntimeError('gnerf_hip: this libgnerf_hip.so was built without the texture atlas (gnerf_mesh_bake_texture): rebuild it (csrc/build.sh)')
+
+
+def _patch(patch):
+    if int(patch) != patch or not ATLAS_MIN_PATCH <= patch <= ATLAS_MAX_PATCH:
+        raise ValueError(f'atlas: patch must be an integer in {ATLAS_MIN_PATCH}..{ATLAS_MAX_PATCH}')
+    return int(patch)
+
+
+def _rgb(colour, what):
+    rgb = [int(c) for c in colour]
+    if len(rgb) != 3 or any(not 0 <= c <= 255 for c in rgb):
+        raise ValueError(f'{what}: background must be three values in 0..255')
+    return rgb
+
+
+def atlas_layout(n_tris, patch):
+    """The atlas of a mesh of n_tris triangles at `patch` texels per patch side -> (cells per row, th, tw), from the library's own host
+    function (include/gnerf_hip.h, gnerf_mesh_atlas_layout, states the rule; shape_mi355x.atlas_layout restates it).  ValueError for a patch
+    out of range, NativeError (code E_UNSUPPORTED) for an atlas past ATLAS_MAX_SIZE a side."""
+    _require_texture()
+    cells, th, tw = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+    _check(load().gnerf_mesh_atlas_layout(int(n_tris), _patch(patch), ctypes.byref(cells), ctypes.byref(th), ctypes.byref(tw)), 'gnerf_mesh_atlas_layout')
+    return cells.value, th.value, tw.value
+
+
+def _bake_texture_ctypes(v, f, patch, A, K, vis, frames, normals, normal_mat, rules, fallback, background, texture=None, weight=None, seen=None):
+    """The ctypes route of bake_texture (arguments as bake_texture has validated them; rules: _bake_rules' tuple, background: three ints)."""
+    dev, V, T = v.device, len(v), len(f)
+    _, th, tw = atlas_layout(T, patch)
+    texture = torch.empty([th, tw, 3], dtype=torch.uint8, device=dev) if texture is None else texture
+    weight = torch.empty([th, tw], dtype=torch.float32, device=dev) if weight is None else weight
+    seen = torch.empty([th, tw], dtype=torch.int32, device=dev) if seen is None else seen
+    n, h, w = vis.shape
+    near, depth_tol, guard, min_cos, power = rules
+    bg = (ctypes.c_ubyte * 3)(*background)
+    _launch('gnerf_mesh_bake_texture', vis, _ptr(v) if V else None, V, _ptr(f) if T else None, T, patch, _ptr(A), _ptr(K), n, _ptr(vis), h, w, _ptr(frames),
+            frames.shape[1], frames.shape[2], _ptr(normals), _ptr(normal_mat), near, depth_tol, guard, min_cos, power, _ptr(fallback), bg,
+            _ptr(texture) if T else None, _ptr(weight) if T else None, _ptr(seen) if T else None)
+    return dict(texture=texture, weight=weight, seen=seen)
+
+
+@profiled('gnerf_hip::bake_texture')
+def bake_texture(verts, faces, mesh2cam, intrinsics, vis, frames, patch=8, normals=None, normal_mat=None, near=BAKE_RULES['near'],
+                 depth_tol=BAKE_RULES['depth_tol'], guard=BAKE_RULES['guard'], min_cos=BAKE_RULES['min_cos'], power=BAKE_RULES['power'], fallback=None,
+                 background=(0, 0, 0), out=None):
+    """Multi-view TEXTURE of a mesh: bake_colors' rules for every texel of the atlas of (len(faces), patch) -- two triangles to a patch x patch
+    cell, atlas_layout's size -- instead of every vertex; arguments as bake_colors takes them, plus faces int32 [T, 3]; fallback stays uint8
+    [V, 3] per vertex and is mixed by a texel's barycentrics; background: three values 0..255 for the texels nobody owns (and the owned but
+    unseen ones without a fallback).  -> dict(texture uint8 [th, tw, 3], weight float32 [th, tw], seen int32 [th, tw]: -1 where nobody owns).
+    Rules: include/gnerf_hip.h, gnerf_mesh_bake_texture; shape_mi355x.bake_texture_numpy gives the same bits.  One launch, no host read:
+    capturable, as bake_colors is.  out: an optional dict of preallocated outputs."""
+    _require_texture()
+    rules = _bake_rules(near, depth_tol, guard, min_cos, power)
+    patch, background = _patch(patch), _rgb(background, 'bake')
+    _require_cuda(vis, frames)
+    v, f = _mesh(verts, faces)
+    A, K = _cameras(mesh2cam, intrinsics, v.device)
+    frames, normals, normal_mat, fallback = _bake_inputs(v, A, vis, frames, normals, normal_mat, fallback)
+    _, th, tw = atlas_layout(len(f), patch)
+    out = dict(out or {})
+    if set(out) - set(TEXTURE_OUTPUTS):
+        raise ValueError(f'bake: out holds {TEXTURE_OUTPUTS} at the most')
+    for name, dtype, shape in (('texture', torch.uint8, (th, tw, 3)), ('weight', torch.float32, (th, tw)), ('seen', torch.int32, (th, tw))):
+        t = out.get(name)
+        if t is not None and (t.dtype != dtype or tuple(t.shape) != shape or not t.is_contiguous() or t.device != v.device):
+            raise ValueError(f'bake: out[{name!r}] must be a contiguous {dtype} tensor of shape {shape} on the mesh\'s device')
+    e = _native.ext()
+    if e is not None and hasattr(e, 'mesh_bake_texture'):
+        with _on_device(v.device):
+            got = e.mesh_bake_texture(v, f, patch, A, K, vis, frames, normals, normal_mat, *rules, fallback, background, out.get('texture'), out.get('weight'),
+                                      out.get('seen'))
+        return dict(zip(TEXTURE_OUTPUTS, got))
+    return _bake_texture_ctypes(v, f, patch, A, K, vis, frames, normals, normal_mat, rules, fallback, background, out.get('texture'), out.get('weight'),
+                                out.get('seen'))
+
+
+def _resolve_textured_ctypes(vis, v, f, A, K, texture, patch, background):
+    n, h, w = vis.shape
+    frame = torch.empty([n, h, w, 3], dtype=torch.uint8, device=vis.device)
+    bg = (ctypes.c_ubyte * 3)(*background)
+    _launch('gnerf_raster_resolve_textured', vis, _ptr(vis), _ptr(v) if len(v) else None, len(v), _ptr(f) if len(f) else None, len(f), _ptr(A), _ptr(K), n, h, w,
+            _ptr(texture) if len(f) else None, patch, bg, _ptr(frame))
+    return frame
+
+
+@profiled('gnerf_hip::raster_resolve_textured')
+def resolve_textured(vis, verts, faces, mesh2cam, intrinsics, texture, patch=8, background=(255, 255, 255)):
+    """The frame of rasterize's visibility buffer with the mesh's atlas on it: resolve's sibling -> frame uint8 [n, h, w, 3], every covered
+    pixel a bilinear sample of `texture` (bake_texture's uint8 [th, tw, 3], of the same faces and patch) at the point of its triangle's patch
+    that the pixel's perspective-correct barycentrics name, unlit; background: three values 0..255 for the empty pixels.  Rules:
+    include/gnerf_hip.h, gnerf_raster_resolve_textured; shape_mi355x.resolve_textured_numpy gives the same bits."""
+    _require_texture()
+    patch, background = _patch(patch), _rgb(background, 'raster')
+    v, f = _mesh(verts, faces)
+    A, K = _cameras(mesh2cam, intrinsics, v.device)
+    _require_cuda(vis, texture)
+    if vis.dtype != torch.int64 or vis.ndim != 3 or vis.shape[0] != len(A) or not vis.is_contiguous() or vis.device != v.device:
+        raise ValueError('raster: vis must be rasterize\'s int64 [n_views, h, w] tensor')
+    _, th, tw = atlas_layout(len(f), patch)
+    if texture.dtype != torch.uint8 or tuple(texture.shape) != (th, tw, 3) or texture.device != v.device:
+        raise ValueError(f'raster: texture must be the uint8 [{th}, {tw}, 3] atlas of this mesh and patch, on the mesh\'s device')
+    texture = texture.detach().contiguous()
+    e = _native.ext()
+    if e is not None and hasattr(e, 'raster_resolve_textured'):
+        with _on_device(v.device):
+            return e.raster_resolve_textured(vis, v, f, A, K, texture, patch, background)
+    return _resolve_textured_ctypes(vis, v, f, A, K, texture, patch, background)

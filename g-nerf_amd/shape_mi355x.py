@@ -47,6 +47,7 @@ import os
 import struct
 import sys
 import time
+import zlib
 
 import numpy as np
 
@@ -76,19 +77,19 @@ def to_host(x):
     return x.detach().cpu().numpy() if hasattr(x, 'detach') else np.asarray(x)
 
 
-_MeshRoute = collections.namedtuple('_MeshRoute', 'xp rasterize resolve bake_colors components compact smooth simplify simplify_count')
+_MeshRoute = collections.namedtuple('_MeshRoute', 'xp rasterize resolve bake_colors components compact smooth simplify simplify_count bake_texture resolve_textured')
 
 
 def _mesh_route(verts, faces):
-    """The route a mesh takes, chosen once per call of render_mesh, bake_mesh_colors, clean_mesh, simplify_mesh and finish_mesh -> (route, verts,
+    """The route a mesh takes, chosen once per call of render_mesh, bake_mesh_colors, bake_mesh_texture, clean_mesh, simplify_mesh and finish_mesh -> (route, verts,
     faces): the kernels and torch for CUDA tensors, left where they are; the numpy ports and numpy for anything else, brought to the host.
     route.xp is the array module: what the callers do to the arrays themselves is spelled alike in both."""
     if is_gpu(verts):
         import gnerf_hip as g
         return (_MeshRoute(_torch(), g.rasterize, g.resolve, g.bake_colors, g.mesh_components, g.mesh_compact, g.mesh_smooth, g.mesh_simplify,
-                           g.mesh_simplify_count), verts.detach().reshape(-1, 3).float(), faces)
+                           g.mesh_simplify_count, g.bake_texture, g.resolve_textured), verts.detach().reshape(-1, 3).float(), faces)
     return (_MeshRoute(np, rasterize_numpy, resolve_numpy, bake_colors_numpy, mesh_components_numpy, mesh_compact_numpy, mesh_smooth_numpy, mesh_simplify_numpy,
-                       lambda *mesh: mesh_simplify_numpy(*mesh, count_only=True)), np.asarray(to_host(verts), dtype=np.float32).reshape(-1, 3), to_host(faces))
+                       lambda *mesh: mesh_simplify_numpy(*mesh, count_only=True), bake_texture_numpy, resolve_textured_numpy), np.asarray(to_host(verts), dtype=np.float32).reshape(-1, 3), to_host(faces))
 
 
 def _on_route(x, like):
@@ -584,17 +585,25 @@ def _cameras_on_route(verts, cam2world, intrinsics, mesh2world):
 
 
 def render_mesh(verts, faces, cam2world, intrinsics, size, mesh2world=None, normals=None, colors=None, near=0.01, cull='none', shading=None,
-                outputs=('tri_id', 'depth', 'normal', 'frame')):
+                outputs=('tri_id', 'depth', 'normal', 'frame'), texture=None, patch=8):
     """Draw a triangle mesh from n cameras (cam2world [n, 4, 4] and normalised intrinsics [n, 3, 3]: what a camera label holds) on the
     renderer's pixel grid -> dict of `outputs` (tri_id, depth as image_depth measures it, camera-frame normal, shaded uint8 frame) plus
     'counts'.  CUDA tensors run the gfx950 kernels (gnerf_hip.rasterize / resolve) and return tensors on their device; numpy arrays run
-    the numpy port -- the same bits either way.  normals [V, 3] are in the mesh's frame (mesh_vertex_attributes'), colors uint8 [V, 3]."""
+    the numpy port -- the same bits either way.  normals [V, 3] are in the mesh's frame (mesh_vertex_attributes'), colors uint8 [V, 3].
+    texture: bake_mesh_texture's uint8 [th, tw, 3] atlas at `patch`; with it 'frame' is the textured resolve's (resolve_textured: the
+    texture's own colours, unlit, on the shading's background) and every other output is as without it."""
     route, verts, faces = _mesh_route(verts, faces)
     mesh2cam, K, normal_mat = _cameras_on_route(verts, cam2world, intrinsics, mesh2world)
     normals, colors = _on_route(normals, verts), _on_route(colors, verts)
     vis, counts = route.rasterize(verts, faces, mesh2cam, K, size, near=near, cull=cull)
-    out = route.resolve(vis, verts, faces, mesh2cam, K, normals=normals, normal_mat=normal_mat if normals is not None else None, colors=colors,
-                        shading=shading, outputs=outputs)
+    plain = tuple(o for o in outputs if texture is None or o != 'frame')
+    out = {}
+    if plain:
+        out = route.resolve(vis, verts, faces, mesh2cam, K, normals=normals, normal_mat=normal_mat if normals is not None else None, colors=colors,
+                            shading=shading, outputs=plain)
+    if texture is not None and 'frame' in outputs:
+        background = [int(c) for c in _to_u8(_shading_vector(shading)[8:11])]
+        out['frame'] = route.resolve_textured(vis, verts, faces, mesh2cam, K, _on_route(texture, verts), patch=patch, background=background)
     out['counts'] = counts
     return out
 
@@ -611,11 +620,9 @@ def _dot3_f32(a0, a1, a2, b0, b1, b2):
     return (a0 * b0 + a1 * b1) + a2 * b2
 
 
-def bake_colors_numpy(verts, mesh2cam, intrinsics, vis, frames, normals=None, normal_mat=None, near=0.01, depth_tol=2.0 ** -8, guard=1, min_cos=0.1,
-                      power=2, fallback=None):
-    """The numpy port of gnerf_mesh_bake_colors: dict(colors uint8 [V, 3], weight float32 [V], seen int32 [V]).  vis: rasterize_numpy's
-    uint64 [n_views, h, w] (or the kernel's int64 bits); frames uint8 [n_views, fh, fw, 3]; normals [V, 3] need normal_mat [n_views, 3, 3]."""
-    v = np.ascontiguousarray(np.asarray(verts), dtype=np.float32).reshape(-1, 3)
+def _bake_arguments(n_points, mesh2cam, intrinsics, vis, frames, normals, normal_mat, near, depth_tol, guard, power, fallback):
+    """The checks bake_colors_numpy and bake_texture_numpy share -> (A, K, vis as uint64, frames, normals, N, fallback); n_points: the length
+    normals and fallback must have (the vertices)."""
     A, K = _raster_cameras(mesh2cam, intrinsics)
     vis = np.ascontiguousarray(np.asarray(vis))
     frames = np.asarray(frames)
@@ -623,10 +630,10 @@ def bake_colors_numpy(verts, mesh2cam, intrinsics, vis, frames, normals=None, no
     if vis.ndim != 3 or vis.dtype.itemsize != 8 or vis.dtype.kind not in 'iu' or vis.shape[0] != n_views:
         raise ValueError('bake: vis must be the 64-bit [n_views, h, w] visibility buffer of the same cameras')
     vis = vis.view(np.uint64)
-    h, w = _raster_size(vis.shape[1:])
+    _raster_size(vis.shape[1:])
     if frames.dtype != np.uint8 or frames.ndim != 4 or frames.shape[0] != n_views or frames.shape[3] != 3:
         raise ValueError('bake: frames must be uint8 [n_views, fh, fw, 3]')
-    fh, fw = _raster_size(frames.shape[1:3])
+    _raster_size(frames.shape[1:3])
     if not near > 0:
         raise ValueError('bake: near must be > 0')
     if not depth_tol >= 0:
@@ -635,19 +642,29 @@ def bake_colors_numpy(verts, mesh2cam, intrinsics, vis, frames, normals=None, no
         raise ValueError('bake: guard must be an integer in 0..4')
     if int(power) != power or not 0 <= power <= 8:
         raise ValueError('bake: power must be an integer in 0..8')
-    guard, power, tol, min_cos = int(guard), int(power), _F(depth_tol), _F(min_cos)
-    V = len(v)
+    N = None
     if normals is not None:
         if normal_mat is None:
             raise ValueError('bake: normals need normal_mat')
         normals = np.ascontiguousarray(np.asarray(normals), dtype=np.float32).reshape(-1, 3)
         N = np.ascontiguousarray(np.asarray(normal_mat), dtype=np.float32).reshape(-1, 9)
-        if len(normals) != V or len(N) != n_views:
+        if len(normals) != n_points or len(N) != n_views:
             raise ValueError('bake: normals must be [V, 3] and normal_mat [n_views, 3, 3]')
     if fallback is not None:
         fallback = np.asarray(fallback)
-        if fallback.dtype != np.uint8 or fallback.shape != (V, 3):
+        if fallback.dtype != np.uint8 or fallback.shape != (n_points, 3):
             raise ValueError('bake: fallback must be uint8 [V, 3]')
+    return A, K, vis, frames, normals, N, fallback
+
+
+def _bake_gather(v, A, K, vis, frames, normals, N, near, depth_tol, guard, min_cos, power):
+    """The bake's rules for the points v float32 [M, 3] (normals [M, 3] with N [n_views, 9], or None), view after view: the port of the stage
+    function the vertex bake and the texture bake are built from -> (acc float32 [M, 3], accw float32 [M], seen int32 [M])."""
+    n_views = len(A)
+    h, w = vis.shape[1:]
+    fh, fw = frames.shape[1:3]
+    guard, power, tol, min_cos = int(guard), int(power), _F(depth_tol), _F(min_cos)
+    V = len(v)
     acc = np.zeros((V, 3), dtype=np.float32)
     accw = np.zeros(V, dtype=np.float32)
     seen = np.zeros(V, dtype=np.int32)
@@ -700,11 +717,26 @@ def bake_colors_numpy(verts, mesh2cam, intrinsics, vis, frames, normals=None, no
             acc[idx] = acc[idx] + wgt[:, None] * s
             accw[idx] = accw[idx] + wgt
             seen[idx] += 1
+    return acc, accw, seen
+
+
+def _bake_levels(acc, accw):
+    """rintf(min(max(acc / accw, 0), 255)) as uint8, per row."""
+    with np.errstate(all='ignore'):
+        return np.rint(np.fmin(np.fmax(acc / accw[:, None], _F(0)), _F(255))).astype(np.int32).astype(np.uint8)
+
+
+def bake_colors_numpy(verts, mesh2cam, intrinsics, vis, frames, normals=None, normal_mat=None, near=0.01, depth_tol=2.0 ** -8, guard=1, min_cos=0.1,
+                      power=2, fallback=None):
+    """The numpy port of gnerf_mesh_bake_colors: dict(colors uint8 [V, 3], weight float32 [V], seen int32 [V]).  vis: rasterize_numpy's
+    uint64 [n_views, h, w] (or the kernel's int64 bits); frames uint8 [n_views, fh, fw, 3]; normals [V, 3] need normal_mat [n_views, 3, 3]."""
+    v = np.ascontiguousarray(np.asarray(verts), dtype=np.float32).reshape(-1, 3)
+    V = len(v)
+    A, K, vis, frames, normals, N, fallback = _bake_arguments(V, mesh2cam, intrinsics, vis, frames, normals, normal_mat, near, depth_tol, guard, power, fallback)
+    acc, accw, seen = _bake_gather(v, A, K, vis, frames, normals, N, near, depth_tol, guard, min_cos, power)
     colors = np.zeros((V, 3), dtype=np.uint8) if fallback is None else fallback.copy()
     hit = accw > 0
-    with np.errstate(all='ignore'):
-        mean = acc[hit] / accw[hit][:, None]
-        colors[hit] = np.rint(np.fmin(np.fmax(mean, _F(0)), _F(255))).astype(np.int32).astype(np.uint8)
+    colors[hit] = _bake_levels(acc[hit], accw[hit])
     return dict(colors=colors, weight=accw, seen=seen)
 
 
@@ -734,6 +766,203 @@ def bake_report_line(baked, n_views):
     share = n_seen / len(seen) if len(seen) else 0.0
     median = float(np.median(seen[seen > 0])) if n_seen else 0.0
     return f'mesh bake: {int(n_views)} views, {n_seen} of {len(seen)} vertices seen ({100 * share:.1f} %), median {median:g} views per seen vertex'
+
+
+# ---------------------------------------------------------------------------------------------------------------- texture atlas
+# The numpy ports of gnerf_mesh_atlas_layout, gnerf_mesh_bake_texture and gnerf_raster_resolve_textured (csrc/raster.hip; include/gnerf_hip.h
+# states the rules): the atlas is a function of (n_tris, patch) alone -- two triangles to a P x P cell, C = ceil(sqrt(n_pairs)) cells to a
+# row, corners 0, 1, 2 of half 0 at the texel centres (0, 0), (L, 0), (0, L) of the cell with L = P - 3, half 1 the same rule on
+# (P - 1 - i, P - 1 - j) --, the bake runs the colour bake's rules at every owned texel's point b0 v0 + b1 v1 + b2 v2, and the textured resolve
+# samples the atlas where a pixel's perspective-correct barycentrics point.  float32, one rounding per operation: the same bits.
+ATLAS_MIN_PATCH, ATLAS_MAX_PATCH, ATLAS_MAX_SIZE = 4, 64, 16384
+
+
+def _atlas_patch(patch):
+    if int(patch) != patch or not ATLAS_MIN_PATCH <= patch <= ATLAS_MAX_PATCH:
+        raise ValueError(f'atlas: patch must be an integer in {ATLAS_MIN_PATCH}..{ATLAS_MAX_PATCH}')
+    return int(patch)
+
+
+def _atlas_rgb(colour):
+    rgb = np.asarray(colour)
+    if rgb.shape != (3,) or np.any(rgb < 0) or np.any(rgb > 255) or np.any(rgb != np.floor(rgb)):
+        raise ValueError('atlas: background must be three integers in 0..255')
+    return rgb.astype(np.uint8)
+
+
+def atlas_layout(n_tris, patch):
+    """The atlas of n_tris triangles at `patch` texels per patch side -> (cells per row C, th, tw): C the smallest integer with C C >= n_pairs,
+    n_pairs = (n_tris + 1) // 2, ceil(n_pairs / C) rows of cells; (0, 0, 0) for no triangle.  ValueError past ATLAS_MAX_SIZE texels a side."""
+    n_tris, patch = int(n_tris), _atlas_patch(patch)
+    if n_tris < 0:
+        raise ValueError('atlas: negative triangle count')
+    n_pairs = (n_tris + 1) // 2
+    cells = 0
+    while cells * cells < n_pairs:
+        cells += 1
+    rows = -(-n_pairs // cells) if cells else 0
+    th, tw = rows * patch, cells * patch
+    if max(th, tw) > ATLAS_MAX_SIZE:
+        raise ValueError(f'atlas: {n_tris} triangles at patch {patch} need {th} x {tw} texels, more than {ATLAS_MAX_SIZE} a side')
+    return cells, th, tw
+
+
+def _atlas_corners(n_tris, patch):
+    """Texel indices (x, y) int64 [n_tris, 3] of the three corners of every triangle."""
+    cells, _, _ = atlas_layout(n_tris, patch)
+    t = np.arange(n_tris, dtype=np.int64)
+    pair, half = t >> 1, t & 1
+    row, col = (pair // cells, pair % cells) if cells else (pair, pair)
+    L = patch - 3
+    i, j = np.array([0, L, 0], dtype=np.int64), np.array([0, 0, L], dtype=np.int64)
+    i = np.where(half[:, None] == 1, patch - 1 - i, i)
+    j = np.where(half[:, None] == 1, patch - 1 - j, j)
+    return col[:, None] * patch + i, row[:, None] * patch + j
+
+
+def atlas_uvs(n_tris, patch):
+    """UVs float32 [n_tris, 3, 2] of every face corner: (u, v) = ((x + 0.5) / tw, (y + 0.5) / th) of the corner's texel (x, y), v from the TOP
+    row (write_obj flips it)."""
+    _, th, tw = atlas_layout(n_tris, patch)
+    x, y = _atlas_corners(n_tris, patch)
+    if n_tris == 0:
+        return np.zeros((0, 3, 2), dtype=np.float32)
+    return np.stack([(x + 0.5) / tw, (y + 0.5) / th], axis=-1).astype(np.float32)
+
+
+def _atlas_texels(n_tris, patch):
+    """Per texel of the atlas: (tri int64 [th, tw]: the triangle that owns it or -1, li, lj int64 [th, tw]: its local indices under that
+    half's rule, the ones the barycentrics are formed from)."""
+    cells, th, tw = atlas_layout(n_tris, patch)
+    y, x = np.meshgrid(np.arange(th, dtype=np.int64), np.arange(tw, dtype=np.int64), indexing='ij')
+    i, j = x % patch, y % patch
+    half = (i + j >= patch).astype(np.int64)
+    tri = ((y // patch) * cells + x // patch) * 2 + half
+    tri = np.where(tri < n_tris, tri, -1)
+    return tri, np.where(half == 1, patch - 1 - i, i), np.where(half == 1, patch - 1 - j, j)
+
+
+def bake_texture_numpy(verts, faces, mesh2cam, intrinsics, vis, frames, patch=8, normals=None, normal_mat=None, near=0.01, depth_tol=2.0 ** -8, guard=1,
+                       min_cos=0.1, power=2, fallback=None, background=(0, 0, 0)):
+    """The numpy port of gnerf_mesh_bake_texture: dict(texture uint8 [th, tw, 3], weight float32 [th, tw], seen int32 [th, tw]) of the atlas of
+    (len(faces), patch); arguments as bake_colors_numpy takes them, plus faces; fallback uint8 [V, 3] per vertex; background: three values
+    0..255.  seen is -1 (and weight 0, the texel the background) where nobody owns the texel or its face names a vertex that is not there."""
+    v, f = _raster_mesh(verts, faces)
+    V, T = len(v), len(f)
+    A, K, vis, frames, normals, N, fallback = _bake_arguments(V, mesh2cam, intrinsics, vis, frames, normals, normal_mat, near, depth_tol, guard, power, fallback)
+    background = _atlas_rgb(background)
+    _, th, tw = atlas_layout(T, patch)
+    texture = np.empty((th, tw, 3), dtype=np.uint8)
+    texture[...] = background
+    weight = np.zeros((th, tw), dtype=np.float32)
+    seen = np.full((th, tw), -1, dtype=np.int32)
+    if T == 0:
+        return dict(texture=texture, weight=weight, seen=seen)
+    tri, li, lj = _atlas_texels(T, patch)
+    valid = ((f >= 0) & (f < V)).all(axis=1)
+    idx = np.nonzero((tri.ravel() >= 0) & valid[np.maximum(tri.ravel(), 0)])[0]
+    g = f[tri.ravel()[idx]].astype(np.int64)
+    L = _F(int(patch) - 3)
+    b1, b2 = li.ravel()[idx].astype(np.float32) / L, lj.ravel()[idx].astype(np.float32) / L
+    b0 = (_F(1) - b1) - b2
+
+    def mix(values):                                                     # (b0 a0 + b1 a1) + b2 a2 of a per-vertex float32 [V, 3]
+        return (b0[:, None] * values[g[:, 0]] + b1[:, None] * values[g[:, 1]]) + b2[:, None] * values[g[:, 2]]
+    with np.errstate(all='ignore'):
+        x = mix(v)
+        n = mix(normals) if normals is not None else None
+        acc, accw, count = _bake_gather(x, A, K, vis, frames, n, N, near, depth_tol, guard, min_cos, power)
+        out = np.broadcast_to(background, (len(idx), 3)).copy()
+        if fallback is not None:
+            out = np.rint(np.fmin(np.fmax(mix(fallback.astype(np.float32)), _F(0)), _F(255))).astype(np.int32).astype(np.uint8)
+    hit = accw > 0
+    out[hit] = _bake_levels(acc[hit], accw[hit])
+    texture.reshape(-1, 3)[idx] = out
+    weight.reshape(-1)[idx] = accw
+    seen.reshape(-1)[idx] = count
+    return dict(texture=texture, weight=weight, seen=seen)
+
+
+def resolve_textured_numpy(vis, verts, faces, mesh2cam, intrinsics, texture, patch=8, background=(255, 255, 255)):
+    """The numpy port of gnerf_raster_resolve_textured: frame uint8 [n_views, h, w, 3], every covered pixel a bilinear sample of `texture`
+    (uint8 [th, tw, 3], the atlas of (len(faces), patch)), unlit; the empty pixels hold `background`."""
+    v, f = _raster_mesh(verts, faces)
+    A, K = _raster_cameras(mesh2cam, intrinsics)
+    vis = np.asarray(vis)
+    n_views, h, w = vis.shape
+    if len(A) != n_views:
+        raise ValueError('raster: vis and the cameras disagree about n_views')
+    patch, background = _atlas_patch(patch), _atlas_rgb(background)
+    cells, th, tw = atlas_layout(len(f), patch)
+    texture = np.asarray(texture)
+    if texture.dtype != np.uint8 or texture.shape != (th, tw, 3):
+        raise ValueError(f'raster: texture must be the uint8 [{th}, {tw}, 3] atlas of this mesh and patch')
+    frame = np.empty((n_views, h, w, 3), dtype=np.uint8)
+    frame[...] = background
+    n_tris = len(f) if len(v) else 0
+    L, far = _F(patch - 3), _F(patch - 1)
+    for view in range(n_views):
+        key = vis[view].reshape(-1).astype(np.uint64)
+        tri = (key & np.uint64(0xFFFFFFFF)).astype(np.int64)
+        pix = np.nonzero((key != RASTER_EMPTY) & (tri < n_tris))[0]
+        if len(pix) == 0:
+            continue
+        _, iz_v, X, Y, bad = _raster_project(v, A[view], K[view], h, w, 0.0)
+        t = _raster_setup(f[tri[pix]], len(v), X, Y, iz_v, bad, 0, h, w)
+        keep = t['status'] == 0
+        pix = pix[keep]
+        t = {k: x[keep] for k, x in t.items()}
+        tri = tri[pix]
+        _, wa, wb, wc = _raster_cover(t, pix // w, pix % w)
+        with np.errstate(all='ignore'):
+            iz, _, bb, bc = _raster_iz(t, wa, wb, wc)
+            qb, qc = (bb * t['izb']) / iz, (bc * t['izc']) / iz
+            q1, q2 = np.where(t['flipped'], qc, qb), np.where(t['flipped'], qb, qc)      # drawn as (0, 2, 1) when flipped
+            pair, odd = tri >> 1, (tri & 1) == 1
+            lx, ly = q1 * L, q2 * L
+            lx, ly = np.where(odd, far - lx, lx), np.where(odd, far - ly, ly)
+            u, s = ((pair % cells) * patch).astype(np.float32) + lx, ((pair // cells) * patch).astype(np.float32) + ly
+            x0f, y0f = np.floor(u), np.floor(s)
+            tx, ty = u - x0f, s - y0f
+            ux, uy = _F(1) - tx, _F(1) - ty
+            x0, y0 = x0f.astype(np.int64), y0f.astype(np.int64)
+            x1, y1 = np.clip(x0 + 1, 0, tw - 1), np.clip(y0 + 1, 0, th - 1)
+            x0, y0 = np.clip(x0, 0, tw - 1), np.clip(y0, 0, th - 1)
+            c00, c01, c10, c11 = (texture[y, x].astype(np.float32) for y, x in ((y0, x0), (y0, x1), (y1, x0), (y1, x1)))
+            top = ux[:, None] * c00 + tx[:, None] * c01
+            bot = ux[:, None] * c10 + tx[:, None] * c11
+            sample = uy[:, None] * top + ty[:, None] * bot
+            frame[view].reshape(-1, 3)[pix] = np.rint(np.fmin(np.fmax(sample, _F(0)), _F(255))).astype(np.int32).astype(np.uint8)
+    return frame
+
+
+def bake_mesh_texture(verts, faces, frames, cam2world, intrinsics, patch=8, mesh2world=None, normals=None, vis_size=None, **rules):
+    """Texture a mesh from frames of it, as bake_mesh_colors colours its vertices: rasterise it from the frames' cameras at vis_size (default:
+    the frames' size), then bake the atlas of (len(faces), patch) (BAKE_RULES' keys, `fallback` and `background` pass through `rules`) ->
+    dict(texture uint8 [th, tw, 3], weight float32 [th, tw], seen int32 [th, tw]); atlas_uvs(len(faces), patch) are its UVs.  CUDA tensors run the
+    gfx950 kernels (gnerf_hip.rasterize / bake_texture) and return tensors on their device; numpy arrays run the ports -- the same bits."""
+    unknown = set(rules) - set(BAKE_RULES) - {'fallback', 'background'}
+    if unknown:
+        raise ValueError(f'bake: unknown rule(s) {sorted(unknown)}')
+    size = tuple(frames.shape[1:3]) if vis_size is None else vis_size
+    route, verts, faces = _mesh_route(verts, faces)
+    mesh2cam, K, normal_mat = _cameras_on_route(verts, cam2world, intrinsics, mesh2world)
+    frames, normals, fallback = (_on_route(x, verts) for x in (frames, normals, rules.get('fallback')))
+    vis, _ = route.rasterize(verts, faces, mesh2cam, K, size, near=rules.get('near', BAKE_RULES['near']))
+    return route.bake_texture(verts, faces, mesh2cam, K, vis, frames, patch=patch, normals=normals, normal_mat=normal_mat if normals is not None else None,
+                              **dict(rules, fallback=fallback))
+
+
+def texture_report_line(baked, n_views, patch):
+    """One line about a bake_texture / bake_mesh_texture result from n_views frames: the atlas' size, the texels some triangle owns, the share
+    of them at least one view sees, and the median number of views per seen texel."""
+    seen = to_host(baked['seen'])
+    th, tw = seen.shape
+    owned, n_seen = int((seen >= 0).sum()), int((seen > 0).sum())
+    share = n_seen / owned if owned else 0.0
+    median = float(np.median(seen[seen > 0])) if n_seen else 0.0
+    return (f'mesh texture: {tw} x {th} atlas (patch {int(patch)}), {int(n_views)} views, {n_seen} of {owned} owned texels seen ({100 * share:.1f} %), '
+            f'median {median:g} views per seen texel')
 
 
 # ---------------------------------------------------------------------------------------------------------------- mesh cleaning
@@ -1253,12 +1482,14 @@ class Written(tuple):
         return self
 
 
-def finish_mesh(verts, faces, clean=None, simplify=None, snap=None, attributes=None, bake=None):
+def finish_mesh(verts, faces, clean=None, simplify=None, snap=None, attributes=None, bake=None, texture=None):
     """Every stage between marching cubes and the consumers of its mesh (verts [V, 3], faces [T, 3]: CUDA tensors take the kernels and stay
     on their device, numpy arrays take the ports, a CPU tensor becomes numpy here) -> FinishedMesh(verts, faces, normals, colors, baked, reports).
       clean, simplify: clean_options' / simplify_options' dict, or None (the stage does not run);
       snap(verts, faces) -> (verts, report); attributes(verts) -> (normals or None, colors or None);
-      bake(verts, faces, normals, colors) -> bake_mesh_colors' dict: callables on this route's arrays, or None.
+      bake(verts, faces, normals, colors) -> bake_mesh_colors' dict: callables on this route's arrays, or None;
+      texture(verts, faces, normals, colors) -> bake_mesh_texture's dict, run after the bake on the same final mesh: its result is
+      reports['texture'] (the record keeps its six fields; MESH_STAGES and report_lines leave it to the caller, who knows the patch).
     normals and colors are the attributes' (the decoder's colours; the baked ones are baked['colors']), baked is the bake's dict or None, and
     reports holds the report of every stage of MESH_STAGES that ran, in that order (the bake's is its dict)."""
     route, verts, faces = _mesh_route(verts, faces)
@@ -1284,6 +1515,8 @@ def finish_mesh(verts, faces, clean=None, simplify=None, snap=None, attributes=N
         verts = route.smooth(verts, faces, smooth)
     if bake:                                                             # the final mesh; the attributes' colours stay where no frame sees
         baked = reports['bake'] = bake(verts, faces, normals, colors)
+    if texture:
+        reports['texture'] = texture(verts, faces, normals, colors)
     return FinishedMesh(verts, faces, normals, colors, baked, reports)
 
 
@@ -1295,9 +1528,10 @@ def report_lines(reports, smooth=0, bake_views=0):
     return [line[stage](reports[stage]) for stage in MESH_STAGES if stage in reports]
 
 
-def add_mesh_arguments(parser, attributes=False):
+def add_mesh_arguments(parser, attributes=False, texture=False):
     """Declare the flags of clean_options and simplify_options on a CLI's parser.  attributes: the CLI evaluates vertex attributes (the
-    help says where in the order)."""
+    help says where in the order).  texture: the CLI has frames to bake, and gets --mesh-texture / --mesh-texture-out (texture_from_args
+    checks them)."""
     parser.add_argument('--mesh-keep', type=int, default=0, help='keep only this many of the largest connected components of the mesh (0: all)')
     parser.add_argument('--mesh-min-faces', type=int, default=0, help='drop connected components with fewer triangles than this (0: none)')
     parser.add_argument('--mesh-smooth', type=int, default=0, help='Taubin smoothing iterations of the mesh (lambda 0.5, mu -0.53, boundaries pinned; 0: none)')
@@ -1306,6 +1540,12 @@ def add_mesh_arguments(parser, attributes=False):
                              + ('the attributes and ' if attributes else '') + 'the smoothing (0: off)')
     parser.add_argument('--mesh-target-faces', type=int, default=0, metavar='N',
                         help='pick the cell instead: the smallest of CELL (or one voxel) * 2^(j / 4), j = 0 .. 40, that leaves at most N triangles (0: off)')
+    if texture:
+        parser.add_argument('--mesh-texture', type=int, default=0, metavar='P',
+                            help=f'also bake a texture atlas of the final mesh from the frames of --mesh-bake, two triangles to a cell of P x P texels '
+                                 f'({ATLAS_MIN_PATCH}..{ATLAS_MAX_PATCH}; 0: off); needs --mesh-bake and --mesh-texture-out')
+        parser.add_argument('--mesh-texture-out', default=None, metavar='PATH.obj',
+                            help='where --mesh-texture writes the textured mesh: this .obj, its .mtl and its .png beside it')
 
 
 def mesh_options_from_args(args, parser):
@@ -1316,6 +1556,82 @@ def mesh_options_from_args(args, parser):
                 snap_options(args.mesh_snap, args.mesh_snap_steps, args.mesh_snap_tol) if hasattr(args, 'mesh_snap') else None)
     except ValueError as err:
         parser.error(str(err))
+
+
+def texture_from_args(args, parser):
+    """The patch size of --mesh-texture (0: off) once the flags add_mesh_arguments(texture=True) declared are in range and have what they
+    need; anything else ends the program through parser.error."""
+    patch, out = args.mesh_texture, args.mesh_texture_out
+    if patch == 0:
+        if out:
+            parser.error('--mesh-texture-out requires --mesh-texture')
+        return 0
+    if not ATLAS_MIN_PATCH <= patch <= ATLAS_MAX_PATCH:
+        parser.error(f'--mesh-texture must be 0 or {ATLAS_MIN_PATCH}..{ATLAS_MAX_PATCH}')
+    if not getattr(args, 'mesh_bake', 0):
+        parser.error('--mesh-texture requires --mesh-bake')
+    if not out or not out.lower().endswith('.obj'):
+        parser.error('--mesh-texture requires --mesh-texture-out PATH.obj')
+    return patch
+
+
+# ---------------------------------------------------------------------------------------------------------------- OBJ and PNG
+def _png_chunk(kind, data):
+    return struct.pack('>I', len(data)) + kind + data + struct.pack('>I', zlib.crc32(kind + data) & 0xFFFFFFFF)
+
+
+def write_png(path, rgb):
+    """8-bit RGB PNG of rgb uint8 [h, w, 3] (h, w >= 1), written with zlib and struct alone: IHDR, one IDAT of rows with filter type 0, IEND."""
+    rgb = np.asarray(rgb)
+    if rgb.dtype != np.uint8 or rgb.ndim != 3 or rgb.shape[2] != 3 or rgb.shape[0] < 1 or rgb.shape[1] < 1:
+        raise ValueError('write_png: rgb must be uint8 [h, w, 3] with h, w >= 1')
+    h, w = rgb.shape[:2]
+    rows = np.zeros((h, 1 + 3 * w), dtype=np.uint8)                      # (filter byte 0 in front of every row)
+    rows[:, 1:] = rgb.reshape(h, 3 * w)
+    with open(path, 'wb') as f:
+        f.write(b'\x89PNG\r\n\x1a\n')
+        f.write(_png_chunk(b'IHDR', struct.pack('>IIBBBBB', w, h, 8, 2, 0, 0, 0)))
+        f.write(_png_chunk(b'IDAT', zlib.compress(rows.tobytes(), 6)))
+        f.write(_png_chunk(b'IEND', b''))
+
+
+def write_obj(path, verts, faces, uvs, texture_png, normals=None):
+    """Wavefront OBJ of a textured mesh: `path`, the material library <stem>.mtl beside it, and the texture.  uvs float [T, 3, 2] (atlas_uvs:
+    one per face corner, v from the top row) become one `vt u 1-v` each, in OBJ's bottom-left origin; faces are `f a/ta b/tb c/tc`
+    (`a/ta/a` with normals [V, 3]), 1-based.  texture_png: the texture itself, uint8 [th, tw, 3], written to <stem>.png -- or the path of a
+    PNG that exists already; the .mtl's map_Kd names it by its base name.  -> the PNG's path."""
+    verts = np.asarray(verts, dtype=np.float64).reshape(-1, 3)
+    faces = np.asarray(faces, dtype=np.int64).reshape(-1, 3)
+    uvs = np.asarray(uvs, dtype=np.float64)
+    if uvs.shape != (len(faces), 3, 2):
+        raise ValueError('write_obj: uvs must be [T, 3, 2], one per face corner')
+    if normals is not None:
+        normals = np.asarray(normals, dtype=np.float64)
+        if normals.shape != verts.shape:
+            raise ValueError('write_obj: normals must be [V, 3]')
+    stem = os.path.splitext(path)[0]
+    if isinstance(texture_png, (str, os.PathLike)):
+        png = os.fspath(texture_png)
+    else:
+        png = stem + '.png'
+        write_png(png, texture_png)
+    name = os.path.basename(stem)
+    with open(stem + '.mtl', 'w') as f:
+        f.write(f'newmtl {name}\nKa 1 1 1\nKd 1 1 1\nKs 0 0 0\nillum 0\nmap_Kd {os.path.basename(png)}\n')
+    vt = uvs.reshape(-1, 2).copy()
+    vt[:, 1] = 1.0 - vt[:, 1]
+    ta = np.arange(1, 3 * len(faces) + 1, dtype=np.int64).reshape(-1, 3)
+    with open(path, 'w') as f:
+        f.write(f'mtllib {name}.mtl\nusemtl {name}\n')
+        np.savetxt(f, verts, fmt='v %.9g %.9g %.9g')
+        if normals is not None:
+            np.savetxt(f, normals, fmt='vn %.9g %.9g %.9g')
+        np.savetxt(f, vt, fmt='vt %.9g %.9g')
+        if normals is not None:
+            np.savetxt(f, np.stack([faces + 1, ta, faces + 1], axis=2).reshape(-1, 9), fmt='f %d/%d/%d %d/%d/%d %d/%d/%d')
+        else:
+            np.savetxt(f, np.stack([faces + 1, ta], axis=2).reshape(-1, 6), fmt='f %d/%d %d/%d %d/%d')
+    return png
 
 
 # ---------------------------------------------------------------------------------------------------------------- PLY

@@ -708,7 +708,7 @@ int gnerf_resize_aa_backward(const void* dy, void* dx, int dtype, int n, int c, 
 
 /* ------------------------------------------------------------------------------------------
  * (ABI 15, added without a new version) Triangle rasteriser for the meshes gnerf_marching_cubes_* extracts: a visibility buffer per view,
- * then depth / normal / shaded colour per pixel.  No gradients, no antialiasing, no textures, no transparency, and NO NEAR-PLANE CLIPPING:
+ * then depth / normal / shaded colour per pixel.  No gradients, no antialiasing, no transparency (textures: gnerf_raster_resolve_textured, below), and NO NEAR-PLANE CLIPPING:
  * a triangle with a vertex at or behind `near` is dropped whole (the shipped cameras sit 2.7 from a unit box).  Everything is float32 with
  * every operation rounded on its own, in the order written here (no fused multiply-add); g-nerf_amd/shape_mi355x.py's rasterize_numpy /
  * resolve_numpy restate it and give the same bits.
@@ -767,7 +767,7 @@ int gnerf_raster_resolve(const uint64_t* vis, const float* verts, int n_verts, c
  * its colour from n_views frames taken by the cameras whose visibility buffers gnerf_raster_visibility made of that mesh.  Gather-only: one
  * thread per vertex, no atomics, no workspace, one launch, no host read, capturable.  Float32, every operation rounded on its own in the order
  * written here (no fused multiply-add); a dot product a . b is (a0 b0 + a1 b1) + a2 b2.  g-nerf_amd/shape_mi355x.py's bake_colors_numpy
- * restates it and gives the same bits.  No UV atlas, no gradients, no filling of unseen vertices from their neighbours.
+ * restates it and gives the same bits.  No gradients, no filling of unseen vertices from their neighbours (the texture atlas: below).
  *   inputs: verts, mesh2cam, intrinsics, n_views, vis [n_views, h, w] and near as gnerf_raster_visibility takes and makes them; frames uint8
  *     [n_views, fh, fw, 3] (fh, fw in 1..GNERF_RASTER_MAX_SIZE, need not equal h, w; n_views * fh * fw < 2^31); optional normals float32
  *     [n_verts, 3] with the per-view 3x3 normal_mat [n_views, 9] of gnerf_raster_resolve; optional fallback uint8 [n_verts, 3].
@@ -797,6 +797,59 @@ int gnerf_mesh_bake_colors(const float* verts, int n_verts, const float* mesh2ca
                            int h, int w, const unsigned char* frames, int fh, int fw, const float* normals, const float* normal_mat,
                            float near_z, float depth_tol, int guard, float min_cos, int power, const unsigned char* fallback,
                            unsigned char* colors, float* weight, int32_t* seen, gnerf_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
+ * (ABI 15, added without a new version) Texture atlas of a mesh, baked from the same frames (csrc/raster.hip): the colour bake's rules per
+ * TEXEL instead of per vertex, and a textured resolve to look at the result.  g-nerf_amd/shape_mi355x.py's atlas_layout / atlas_uvs /
+ * bake_texture_numpy / resolve_textured_numpy restate all of it and give the same bits.  No mip-maps, no chart-based atlas, no filling of
+ * unseen texels from their neighbours.
+ * THE ATLAS is a function of (n_tris, patch) alone; no kernel takes a UV buffer.  P = patch texels per patch side, GNERF_ATLAS_MIN_PATCH <= P
+ *   <= GNERF_ATLAS_MAX_PATCH; two triangles share one P x P cell: pair = t >> 1, half = t & 1, n_pairs = (n_tris + 1) / 2.  C = the smallest
+ *   integer with C C >= n_pairs (in integers), rows = ceil(n_pairs / C); the texture is tw = C P wide and th = rows P high, cell
+ *   (pair / C, pair % C) starts at texel (row P, col P).  tw and th are at most GNERF_ATLAS_MAX_SIZE each, GNERF_E_UNSUPPORTED otherwise,
+ *   before any launch; n_tris == 0 gives a 0 x 0 atlas and no launch.
+ *   Inside a cell, with local texel indices (i = column, j = row) in 0 .. P - 1 and L = P - 3: half 0 owns the texels with i + j <= P - 1,
+ *   its corners 0, 1, 2 lie at the texel centres (0, 0), (L, 0), (0, L); half 1 owns i + j >= P and is the same rule on (P - 1 - i, P - 1 - j).
+ *   The texels of half 1 in the last cell of an odd n_tris, and whole cells past n_pairs, are owned by nobody.  A texel's barycentrics, formed
+ *   in this order, may be negative (an owned texel outside its triangle is extrapolated on the triangle's plane):
+ *     b1 = float(i) / float(L), b2 = float(j) / float(L), b0 = (1 - b1) - b2.
+ *   Why L = P - 3: a bilinear sample at a point (x, y) inside the triangle, x, y >= 0 and x + y <= L, has non-zero weight only on the taps
+ *   (floor x + {0, 1}, floor y + {0, 1}), a tap + 1 only where that fractional part is positive, and floor x + floor y <= L - 1 whenever a
+ *   fractional part is positive: every such tap has i + j <= L + 1 = P - 2 (half 0; i + j >= P + 1 for half 1).  So a triangle never reads its
+ *   neighbour's texels and no dilation pass is needed; the spare diagonal i + j = P - 1 goes to half 0 (with L = P - 2 the halves would
+ *   collide on it).  UV of corner k of triangle t, with (x, y) its texel index: u = (x + 0.5) / tw, v = (y + 0.5) / th from the top row.
+ * gnerf_mesh_atlas_layout: host only; *cells_per_row = C, *th, *tw.
+ * gnerf_mesh_bake_texture: one thread per texel, gather-only: one launch, no atomics, no LDS, no workspace, no host read, capturable.  Inputs
+ *   as gnerf_mesh_bake_colors takes them, plus faces int32 [n_tris, 3] and patch; fallback uint8 [n_verts, 3] per VERTEX; background: three
+ *   HOST uint8 values.  Per owned texel: x = (b0 v0 + b1 v1) + b2 v2 per component, and with normals n = (b0 n0 + b1 n1) + b2 n2 (left
+ *   unnormalised: the cosine normalises); then per view, in ascending order, exactly the vertex bake's rules with x in place of the vertex
+ *   (vertex, pixel, occlusion, facing, weight, sample, accumulate): both kernels are built from one stage function.
+ *   outputs: texture uint8 [th, tw, 3]; optional weight float32 [th, tw] and seen int32 [th, tw].  accw > 0: rintf(min(max(acc[k] / accw, 0),
+ *     255)); owned with accw == 0: with a fallback the mix (b0 c0 + b1 c1) + b2 c2 of the corners' fallback colours, clamped to 0 .. 255 and
+ *     rounded with rintf, else background; weight = accw, seen = the views that counted.  A texel nobody owns, and every texel of a face that
+ *     names a vertex outside [0, n_verts): background, weight = 0, seen = -1.  Every texel of the texture is written.
+ * gnerf_raster_resolve_textured: gnerf_raster_resolve's sibling, one thread per pixel -> frame uint8 [n_views, h, w, 3] from vis, the same
+ *   mesh and cameras, and texture uint8 [th, tw, 3] of gnerf_mesh_atlas_layout(n_tris, patch).  The winning triangle's barycentrics are those
+ *   of the depth step (the same bits as resolve); they are taken back from the drawn order to the face's own corners (a triangle with
+ *   area < 0 is drawn as (0, 2, 1)), q_i = (b_i iz_i) / iz; local position x = q1 L, y = q2 L (half 0) or x = (P - 1) - q1 L, y = (P - 1) - q2 L
+ *   (half 1); u = float(col P) + x, v = float(row P) + y; x0 = floorf(u), tx = u - x0, y0 = floorf(v), ty = v - y0, taps x0, x0 + 1, y0, y0 + 1
+ *   clamped into the texture, top / bot / s as the frame sampler of gnerf_mesh_bake_colors; frame = rintf(min(max(s, 0), 255)), UNLIT (the
+ *   texture holds the frames' lit colours); empty pixels: background (three HOST uint8 values).
+ *   KNOWN LIMIT: float rounding can put x + y a few ulp past L; the over-run tap then carries a weight of that size and lands on the spare
+ *   diagonal.  That is part of the rule and of the port, not an error.
+ * GNERF_E_ARG as gnerf_mesh_bake_colors / gnerf_raster_resolve, and for patch out of range. */
+#define GNERF_ATLAS_MIN_PATCH 4
+#define GNERF_ATLAS_MAX_PATCH 64
+#define GNERF_ATLAS_MAX_SIZE 16384
+int gnerf_mesh_atlas_layout(int n_tris, int patch, int* cells_per_row, int* th, int* tw);
+int gnerf_mesh_bake_texture(const float* verts, int n_verts, const int32_t* faces, int n_tris, int patch, const float* mesh2cam,
+                            const float* intrinsics, int n_views, const uint64_t* vis, int h, int w, const unsigned char* frames, int fh, int fw,
+                            const float* normals, const float* normal_mat, float near_z, float depth_tol, int guard, float min_cos, int power,
+                            const unsigned char* fallback, const unsigned char* background, unsigned char* texture, float* weight, int32_t* seen,
+                            gnerf_stream_t stream);
+int gnerf_raster_resolve_textured(const uint64_t* vis, const float* verts, int n_verts, const int32_t* faces, int n_tris, const float* mesh2cam,
+                                  const float* intrinsics, int n_views, int h, int w, const unsigned char* texture, int patch,
+                                  const unsigned char* background, unsigned char* frame, gnerf_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
  * (ABI 15, added without a new version) Cleaning the meshes gnerf_marching_cubes_* extracts: connected components, compaction to the kept
