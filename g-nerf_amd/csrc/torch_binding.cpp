@@ -15,7 +15,7 @@
 // render_backward_rays (gnerf_hip.render_backward with need_rays), resize_aa (gnerf_hip.resize_aa_forward / _backward),
 // raster_visibility / raster_resolve / mesh_bake_colors (gnerf_hip.rasterize / resolve / bake_colors), mesh_atlas_layout / mesh_bake_texture /
 // raster_resolve_textured (gnerf_hip.atlas_layout / bake_texture / resolve_textured), mesh_components / mesh_compact / mesh_smooth /
-// mesh_simplify / mesh_simplify_count / project_points_to_level / mesh_flip_guard (gnerf_hip's of those names).
+// mesh_simplify / mesh_simplify_count / project_points_to_level / mesh_flip_guard / query_lattice / band_* (gnerf_hip's of those names).
 //
 // Built ahead of time by csrc/build.sh (g++, no hipcc: there is no device code) into g-nerf_amd/gnerf_hip/gnerf_torch_ext.so.
 
@@ -873,6 +873,87 @@ std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor> mesh_simplify(Tensor verts, T
     return std::make_tuple(out_v, out_f, src, vmap, host);
 }
 
+// ------------------------------------------------------------------------------------------------ narrow band (csrc/query_lattice.inl, csrc/mesh_band.hip)
+// gnerf_hip.query_lattice has converted the tensors (contiguous float32 on one GPU; planes [3,H,W,32] or [1,H,W,96]; index int32 [m], m >= 1;
+// out float32 [n^3]).  Writes out[index].
+void query_lattice(Tensor planes_nhwc, Tensor w1, Tensor b1, Tensor w2, Tensor b2, Tensor index, int64_t n, double cube_length, double box_warp, Tensor out) {
+    auto f32c = [](const Tensor& t, const char* name) {
+        TORCH_CHECK(t.is_cuda() && t.scalar_type() == torch::kFloat32 && t.is_contiguous(), "query_lattice: ", name, " must be a contiguous float32 GPU tensor");
+    };
+    f32c(planes_nhwc, "planes_nhwc"); f32c(w1, "w1"); f32c(b1, "b1"); f32c(w2, "w2"); f32c(b2, "b2"); f32c(out, "out");
+    const bool separate = planes_nhwc.dim() == 4 && planes_nhwc.size(3) == 32 && planes_nhwc.size(0) == 3;
+    const bool interleaved = planes_nhwc.dim() == 4 && planes_nhwc.size(3) == 96 && planes_nhwc.size(0) == 1;
+    TORCH_CHECK(separate || interleaved, "query_lattice: planes_nhwc must be [3,H,W,32] or [1,H,W,96]");
+    TORCH_CHECK(w1.numel() == 64 * 32 && b1.numel() == 64 && w2.numel() == 33 * 64 && b2.numel() == 33, "query_lattice: decoder must be the 32->64->33 MLP");
+    TORCH_CHECK(index.is_cuda() && index.scalar_type() == torch::kInt32 && index.is_contiguous() && index.dim() == 1 && index.numel() >= 1 &&
+                index.numel() <= INT_MAX && index.device() == out.device(), "query_lattice: index must be a contiguous int32 [m] on out's device");
+    TORCH_CHECK(n >= 2 && n * n * n < (int64_t(1) << 31) && out.numel() == n * n * n, "query_lattice: out must hold n^3 < 2^31 values");
+    const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(at::device_of(out));
+    check_rc(gnerf_query_lattice(planes_nhwc.data_ptr<float>(), int(planes_nhwc.size(1)), int(planes_nhwc.size(2)), index.data_ptr<int32_t>(),
+                                 int(index.numel()), int(n), cube_length, float(box_warp), w1.data_ptr<float>(), b1.data_ptr<float>(),
+                                 w2.data_ptr<float>(), b2.data_ptr<float>(), out.data_ptr<float>(), interleaved ? 1 : 0, current_stream()),
+             "gnerf_query_lattice");
+}
+
+// gnerf_hip.BandVolume owns the tensors: volume float32 [n^3], state uint8 [nb^3], workspace uint8 [gnerf_band_workspace_bytes], count int64
+// [1] (a slice of its counts), all contiguous on one GPU; keep: six ints.
+struct BandCall {
+    int n, s;
+    int keep[6];
+};
+
+BandCall band_call(int64_t n, int64_t s, const std::vector<int64_t>& keep, std::initializer_list<const Tensor*> tensors, const char* what) {
+    TORCH_CHECK(n >= 2 && n <= INT_MAX && s >= 1 && s <= 16 && keep.size() == 6, what, ": argument out of range");
+    const Tensor* first = *tensors.begin();
+    for (const Tensor* t : tensors) TORCH_CHECK(t->is_cuda() && t->is_contiguous() && t->device() == first->device(), what, ": unexpected tensor layout");
+    BandCall c;
+    c.n = int(n);
+    c.s = int(s);
+    for (int a = 0; a < 6; a++) c.keep[a] = int(std::min<int64_t>(std::max<int64_t>(keep[a], 0), n));
+    return c;
+}
+
+void band_seed(Tensor volume, int64_t n, int64_t s, double level, std::vector<int64_t> keep, Tensor state, Tensor workspace, Tensor count) {
+    const BandCall c = band_call(n, s, keep, {&volume, &state, &workspace, &count}, "band_seed");
+    TORCH_CHECK(volume.scalar_type() == torch::kFloat32 && state.scalar_type() == torch::kUInt8 && count.scalar_type() == torch::kInt64 && count.numel() >= 1,
+                "band_seed: unexpected tensor type");
+    const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(at::device_of(volume));
+    check_rc(gnerf_band_seed(volume.data_ptr<float>(), c.n, c.s, float(level), c.keep, state.data_ptr<uint8_t>(), workspace.data_ptr(),
+                             count.data_ptr<int64_t>(), current_stream()), "gnerf_band_seed");
+}
+
+void band_points_count(Tensor state, int64_t n, int64_t s, Tensor workspace, Tensor count) {
+    const BandCall c = band_call(n, s, {0, 0, 0, 0, 0, 0}, {&state, &workspace, &count}, "band_points_count");
+    TORCH_CHECK(state.scalar_type() == torch::kUInt8 && count.scalar_type() == torch::kInt64 && count.numel() >= 1, "band_points_count: unexpected tensor type");
+    const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(at::device_of(state));
+    check_rc(gnerf_band_points_count(state.data_ptr<uint8_t>(), c.n, c.s, workspace.data_ptr(), count.data_ptr<int64_t>(), current_stream()),
+             "gnerf_band_points_count");
+}
+
+void band_points_emit(Tensor state, int64_t n, int64_t s, Tensor workspace, Tensor index) {
+    const BandCall c = band_call(n, s, {0, 0, 0, 0, 0, 0}, {&state, &workspace, &index}, "band_points_emit");
+    TORCH_CHECK(state.scalar_type() == torch::kUInt8 && index.scalar_type() == torch::kInt32, "band_points_emit: unexpected tensor type");
+    const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(at::device_of(state));
+    check_rc(gnerf_band_points_emit(state.data_ptr<uint8_t>(), c.n, c.s, workspace.data_ptr(), index.numel() ? index.data_ptr<int32_t>() : nullptr,
+                                    index.numel(), current_stream()), "gnerf_band_points_emit");
+}
+
+void band_grow(Tensor volume, int64_t n, int64_t s, double level, std::vector<int64_t> keep, Tensor state, Tensor workspace, Tensor count) {
+    const BandCall c = band_call(n, s, keep, {&volume, &state, &workspace, &count}, "band_grow");
+    TORCH_CHECK(volume.scalar_type() == torch::kFloat32 && state.scalar_type() == torch::kUInt8 && count.scalar_type() == torch::kInt64 && count.numel() >= 1,
+                "band_grow: unexpected tensor type");
+    const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(at::device_of(volume));
+    check_rc(gnerf_band_grow(volume.data_ptr<float>(), c.n, c.s, float(level), c.keep, state.data_ptr<uint8_t>(), workspace.data_ptr(),
+                             count.data_ptr<int64_t>(), current_stream()), "gnerf_band_grow");
+}
+
+void band_fill(Tensor volume, int64_t n, int64_t s, std::vector<int64_t> keep, Tensor state) {
+    const BandCall c = band_call(n, s, keep, {&volume, &state}, "band_fill");
+    TORCH_CHECK(volume.scalar_type() == torch::kFloat32 && state.scalar_type() == torch::kUInt8, "band_fill: unexpected tensor type");
+    const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(at::device_of(volume));
+    check_rc(gnerf_band_fill(volume.data_ptr<float>(), c.n, c.s, c.keep, state.data_ptr<uint8_t>(), current_stream()), "gnerf_band_fill");
+}
+
 }  // namespace
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -903,6 +984,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("mesh_simplify_count", &mesh_simplify_count);
     m.def("project_points_to_level", &project_points_to_level);
     m.def("mesh_flip_guard", &mesh_flip_guard);
+    m.def("query_lattice", &query_lattice);
+    m.def("band_seed", &band_seed);
+    m.def("band_points_count", &band_points_count);
+    m.def("band_points_emit", &band_points_emit);
+    m.def("band_grow", &band_grow);
+    m.def("band_fill", &band_fill);
     // the header version THIS extension was compiled against (a compile-time constant: gnerf_abi_version() would resolve in
     // libgnerf_hip.so at run time and compare the library with itself); gnerf_hip.ext() checks both against its own
     m.def("abi_version", []() { return int(GNERF_ABI_VERSION); });

@@ -22,6 +22,8 @@ HIP graph captured once (FrameProgram); `--shapes out.npy` also extracts the 512
 is still on the device; `--mesh-attrs normals|colors|all` adds the density field's normals and the decoder's colours per vertex.
 `--geometry-out geo.npy` draws that mesh from every orbit camera with the triangle rasteriser (csrc/raster.hip): shaded geometry frames on
 the renderer's pixel grid, uint8 [F, H, W, 3] at `--geometry-res`, smooth-shaded / coloured with `--mesh-attrs`.
+`--mesh-band S` (2, 4, 8 or 16; 0: off) evaluates the volume of both only in a narrow band of bricks of S^3 cells that follows the level set of
+`--mesh-level` (csrc/mesh_band.hip, csrc/query_lattice.inl): the same mesh in the same order, minus detached components thinner than a brick.
 `--mesh-keep K`, `--mesh-min-faces N` and `--mesh-smooth ITERS` clean the mesh of both first (csrc/mesh_clean.hip): only the K largest connected
 components / those with at least N triangles stay, then ITERS Taubin iterations fair the surface; all 0 by default, which changes nothing.
 `--mesh-simplify CELL` (voxels) and `--mesh-target-faces N` simplify it in between (csrc/mesh_simplify.hip): one vertex per occupied cell of a
@@ -48,6 +50,7 @@ import torch
 
 import gnerf_harness as H
 import shape_mi355x
+from gnerf_lattice import voxel_samples  # noqa: F401  (gv.voxel_samples stays)
 
 
 def ffhq_generator_kwargs(depth_resolution=48, depth_resolution_importance=48):
@@ -206,20 +209,6 @@ def render_orbit(G, z, n_frames, res, device, rank=0, world=1, double_depth=True
     return torch.cat(frames), torch.cat(raws), (lo, hi)
 
 
-def voxel_samples(lo, hi, n, cube_length, device):
-    """Points lo..hi-1 of gen_videos.py's create_samples(N=n, voxel_origin=[0,0,0], cube_length) (gen_videos.py:33-56), made on
-    the device chunk by chunk instead of as one [n^3, 3] host tensor (1.6 GB at n = 512).  The arithmetic is the reference's,
-    quirks included: the y and x indices come from FLOAT divisions of the linear index without a floor (a sheared lattice), in
-    fp32 (indices above 2^24 are rounded)."""
-    idx = torch.arange(lo, hi, dtype=torch.int64, device=device)
-    origin, size = -cube_length / 2, cube_length / (n - 1)
-    f = idx.float()
-    s2 = (idx % n).float()
-    s1 = (f / n) % n
-    s0 = ((f / n) / n) % n
-    return torch.stack([s0 * size + origin, s1 * size + origin, s2 * size + origin], dim=-1).unsqueeze(0)
-
-
 def _stack3(a, b, c):
     return torch.stack([a, b, c], dim=-1) if isinstance(a, torch.Tensor) else np.stack([a, b, c], axis=-1)
 
@@ -267,18 +256,16 @@ def normals_to_mesh_frame(normals_world, resolution, cube_length):
     return np.where(length > 0, m / np.where(length > 0, length, 1), 0).astype(m.dtype)
 
 
+def crop_ranges(resolution):
+    """extract_density_grid's crop (gen_videos.py:213-220) as (zeroed at the front, zeroed at the back) per axis of the flipped volume."""
+    pad, pad_top = int(30 * resolution / 256), int(38 * resolution / 256)
+    return [(pad, pad), (pad, pad_top), (pad, pad)]
+
+
 @torch.no_grad()
-def extract_density_grid(G, ws, resolution=512, max_batch=10000000, crop=True, planes=None, return_planes=False):
-    """The density volume gen_videos.py --shapes writes to .mrc (gen_videos.py:189-224): sigma at resolution^3 lattice points of
-    the box, flipped along the first axis, borders zeroed.  The reference calls G.sample_mixed per chunk of 10^7 points, which
-    re-runs the StyleGAN2 backbone for every chunk (14 passes at 512^3); here the planes are made once and every chunk goes
-    through ImportanceRenderer.run_model (the fused point-query kernel on a GPU).  Returns a float32 tensor [r, r, r] on ws' device.
-    planes / return_planes: take the tri-planes [N,3,32,H,W] instead of running the backbone, and hand them back as (vol, planes) --
-    mesh_density_grid evaluates vertex attributes on the same planes."""
-    device = ws.device
-    if planes is None:
-        planes = G.backbone.synthesis(ws, noise_mode='const')
-        planes = planes.view(len(planes), 3, 32, planes.shape[-2], planes.shape[-1])
+def _dense_density(G, planes, resolution, max_batch):
+    """extract_density_grid's sigmas [resolution^3]: every lattice point, chunk by chunk."""
+    device = planes.device
     total = resolution ** 3
     sigmas = torch.empty(total, dtype=torch.float32, device=device)
     for head in range(0, total, max_batch):
@@ -290,16 +277,62 @@ def extract_density_grid(G, ws, resolution=512, max_batch=10000000, crop=True, p
             dirs = torch.zeros_like(pts)
             dirs[..., -1] = -1
             sigmas[head:hi] = G.renderer.run_model(planes, G.decoder, pts, dirs, G.rendering_kwargs)['sigma'].reshape(-1)
+    return sigmas
+
+
+@torch.no_grad()
+def _band_density(G, planes, resolution, crop, band, level):
+    """extract_density_grid's sigmas [resolution^3] through shape_mi355x.band_volume: densities where the level set runs, the coarse corners'
+    values elsewhere -> (sigmas, report).  The crop is handed over as the kept index range per axis of the UNFLIPPED lattice: flip(0)
+    mirrors axis 0, so its front and back exchange."""
+    if level is None:
+        raise ValueError('extract_density_grid: band needs the isosurface level the volume will be meshed at')
+    keep = None
+    if crop:
+        (a0, b0), r1, r2 = crop_ranges(resolution)
+        keep = shape_mi355x.band_keep_of_crop(resolution, [(b0, a0), r1, r2])
+    kw = G.rendering_kwargs
+
+    def field(index, out):
+        out = out if isinstance(out, torch.Tensor) else torch.from_numpy(out)           # (the numpy port's array: shares its memory)
+        G.renderer.query_sigma_lattice(planes, G.decoder, torch.as_tensor(index), resolution, kw, out)
+
+    vol, report = shape_mi355x.band_volume(field, resolution, level, band, keep, device=planes.device)
+    return torch.as_tensor(vol).reshape(-1).to(planes.device), report
+
+
+@torch.no_grad()
+def extract_density_grid(G, ws, resolution=512, max_batch=10000000, crop=True, planes=None, return_planes=False, band=None, level=None, report=None):
+    """The density volume gen_videos.py --shapes writes to .mrc (gen_videos.py:189-224): sigma at resolution^3 lattice points of
+    the box, flipped along the first axis, borders zeroed.  The reference calls G.sample_mixed per chunk of 10^7 points, which
+    re-runs the StyleGAN2 backbone for every chunk (14 passes at 512^3); here the planes are made once and every chunk goes
+    through ImportanceRenderer.run_model (the fused point-query kernel on a GPU).  Returns a float32 tensor [r, r, r] on ws' device.
+    planes / return_planes: take the tri-planes [N,3,32,H,W] instead of running the backbone, and hand them back as (vol, planes) --
+    mesh_density_grid evaluates vertex attributes on the same planes.
+    band=s (2, 4, 8 or 16; None: off) evaluates only a narrow band of bricks of s^3 cells around the level set sigma = `level`
+    (shape_mi355x.band_volume with ImportanceRenderer.query_sigma_lattice as the field; needs this repo's renderer): the mesh of the
+    volume at that level is the dense volume's, minus whole components thinner than a brick that the band never met, but the other
+    values of the volume are NOT densities.  report: a dict that receives the band's report under 'band'."""
+    device = ws.device
+    if planes is None:
+        planes = G.backbone.synthesis(ws, noise_mode='const')
+        planes = planes.view(len(planes), 3, 32, planes.shape[-2], planes.shape[-1])
+    if band:
+        sigmas, band_report = _band_density(G, planes, resolution, crop, band, level)
+        if report is not None:
+            report['band'] = band_report
+    else:
+        sigmas = _dense_density(G, planes, resolution, max_batch)
     vol = sigmas.reshape(resolution, resolution, resolution).flip(0)
     if crop:                                                                                # gen_videos.py:213-220
-        pad, pad_top = int(30 * resolution / 256), int(38 * resolution / 256)
+        (a0, b0), (a1, b1), (a2, b2) = crop_ranges(resolution)
         vol = vol.clone()
-        vol[:pad] = 0
-        vol[-pad:] = 0
-        vol[:, :pad] = 0
-        vol[:, -pad_top:] = 0
-        vol[:, :, :pad] = 0
-        vol[:, :, -pad:] = 0
+        vol[:a0] = 0
+        vol[-b0:] = 0
+        vol[:, :a1] = 0
+        vol[:, -b1:] = 0
+        vol[:, :, :a2] = 0
+        vol[:, :, -b2:] = 0
     return (vol, planes) if return_planes else vol
 
 
@@ -402,7 +435,7 @@ def bake_extracted_mesh(verts, faces, normals, fallback, bake, resolution, cube_
                  normals=place(normals, torch.float32), vis_size=bake.get('res'), fallback=place(fallback), **bake.get('rules', {}))
 
 
-def mesh_of_density_grid(vol, level=10.0, attrs=None, G=None, planes=None, clean=None, simplify=None, snap=None, bake=None):
+def mesh_of_density_grid(vol, level=10.0, attrs=None, G=None, planes=None, clean=None, simplify=None, snap=None, bake=None, band=None):
     """The mesh shape_utils.convert_mrc makes of the .mrc of this volume (shape_utils.py:103-105: transpose(2, 1, 0), voxel size 1, origin 0),
     made where the volume lives -- on a GPU the marching-cubes kernel reads it in HBM -- and taken through shape_mi355x.finish_mesh, which
     states the order of the stages -> (its FinishedMesh, on the volume's route and in index space, as the reference's; seconds spent in
@@ -412,6 +445,8 @@ def mesh_of_density_grid(vol, level=10.0, attrs=None, G=None, planes=None, clean
     snap_options' dict (snap_extracted_mesh on G and `planes`).  bake: None or bake_extracted_mesh's dict (frames, labels, res, rules) -- the
     final mesh is coloured from those frames, with the normals when attrs made them and the decoder's colours, when it made them, as the fallback;
     with bake['texture'] = P > 0 its texture atlas at patch P is baked from them too (the FinishedMesh's reports['texture']).
+    band: None, or the report of the narrow band the volume was made in (extract_density_grid(..., band=s, report=...)['band']), which
+    must have followed this `level`: it becomes the FinishedMesh's reports['band'], ahead of the stages'.
     With every option None nothing but marching cubes runs."""
     attrs = 'none' if attrs is None else attrs
     if attrs not in MESH_ATTRS:
@@ -435,7 +470,10 @@ def mesh_of_density_grid(vol, level=10.0, attrs=None, G=None, planes=None, clean
         if bake.get('texture'):
             stages['texture'] = lambda v, f, normals, colors: bake_extracted_mesh(v, f, normals, colors, bake, res, G.rendering_kwargs['box_warp'],
                                                                                   patch=bake['texture'])
-    return shape_mi355x.finish_mesh(verts, faces, clean=clean, simplify=simplify, **stages), dt
+    mesh = shape_mi355x.finish_mesh(verts, faces, clean=clean, simplify=simplify, **stages)
+    if band is not None:
+        mesh = mesh._replace(reports={'band': band, **mesh.reports})
+    return mesh, dt
 
 
 def mesh_density_grid(vol, ply_path, level=10.0, **options):
@@ -487,6 +525,10 @@ def arg_parser():
     ap.add_argument('--shapes-mrc', default=None, help='also write the density volume as the reference\'s .mrc (gen_videos.py:221-222; rank 0)')
     ap.add_argument('--mesh', default=None, help='also mesh the density volume on the device and write this .ply (shape_utils.py; rank 0)')
     ap.add_argument('--mesh-level', type=float, default=10, help='isosurface level of --mesh (shape_utils.py:111)')
+    ap.add_argument('--mesh-band', type=int, default=0, metavar='S',
+                    help='evaluate the density volume of --mesh / --geometry-out only in a narrow band of bricks of S^3 cells (2, 4, 8 or 16; 8 is a good start) '
+                         'around the level set of --mesh-level: the same mesh, minus detached components thinner than a brick (0: off, every lattice point). '
+                         'With --shapes / --shapes-mrc the dense volume is made once and meshed too: those files hold densities everywhere')
     ap.add_argument('--mesh-attrs', choices=MESH_ATTRS, default='none', help='per-vertex attributes of --mesh: normals of the density field and / or the decoder\'s colours')
     shape_mi355x.add_mesh_arguments(ap, attributes=True, texture=True)
     ap.add_argument('--mesh-snap', type=float, default=0, metavar='R',
@@ -516,6 +558,8 @@ def main():
     if args.mesh_bake and not args.mesh:
         ap.error('--mesh-bake requires --mesh')
     texture_patch = shape_mi355x.texture_from_args(args, ap)
+    if args.mesh_band not in (0,) + shape_mi355x.BAND_BRICKS:
+        ap.error(f'--mesh-band must be 0 or one of {shape_mi355x.BAND_BRICKS}')
     if not 0 <= args.mesh_bake <= args.frames:
         ap.error('--mesh-bake must be 0 .. --frames')
     if (not args.mesh_bake_tol >= 0 or not 0 <= args.mesh_bake_guard <= 4 or not 0 <= args.mesh_bake_power <= 8
@@ -563,12 +607,22 @@ def main():
             if device.type == 'cuda':
                 torch.cuda.synchronize()
             t0 = time.perf_counter()
-            made['vol'], made['planes'] = extract_density_grid(G, orbit_latents(G, z, device), args.voxel_res, return_planes=True)
+            # --shapes / --shapes-mrc write the volume itself, which must hold densities everywhere: with them the dense volume is made
+            # once and meshed too (the same choice on every rank: the geometry frames are drawn from one mesh)
+            band = args.mesh_band if not (args.shapes or args.shapes_mrc) else 0
+            if args.mesh_band and not band and rank == 0:
+                print('--mesh-band: off, --shapes / --shapes-mrc need the dense volume; it is made once and meshed too')
+            reports = {}
+            made['vol'], made['planes'] = extract_density_grid(G, orbit_latents(G, z, device), args.voxel_res, return_planes=True, band=band or None,
+                                                               level=args.mesh_level, report=reports)
+            made['band'] = reports.get('band')
             if device.type == 'cuda':
                 torch.cuda.synchronize()
             dt = time.perf_counter() - t0
             if rank == 0:
                 print(f'density volume {args.voxel_res}^3: {dt:.3f} s = {args.voxel_res ** 3 / dt / 1e9:.2f} G points/s')
+                if made['band']:
+                    print(shape_mi355x.band_report_line(made['band']))
         return made['vol'], made['planes']
 
     if rank == 0 and (args.shapes or args.shapes_mrc or args.mesh):
@@ -584,7 +638,7 @@ def main():
                 _, bake_frames, bake_labels = bake_frames_of_orbit(full, args.frames, args.mesh_bake, G.rendering_kwargs['avg_camera_radius'])
                 bake = dict(frames=bake_frames, labels=bake_labels, res=args.mesh_bake_res,
                             rules=dict(depth_tol=args.mesh_bake_tol, guard=args.mesh_bake_guard, power=args.mesh_bake_power), texture=texture_patch)
-            nv, nf, dt = written = mesh_density_grid(vol, args.mesh, args.mesh_level, planes=planes, bake=bake, **stages)
+            nv, nf, dt = written = mesh_density_grid(vol, args.mesh, args.mesh_level, planes=planes, bake=bake, band=made['band'], **stages)
             made['mesh'] = written.mesh
             for line in shape_mi355x.report_lines(written.mesh.reports, smooth=args.mesh_smooth, bake_views=args.mesh_bake):
                 print(line)
@@ -601,7 +655,7 @@ def main():
         # rank 0 draws the mesh --mesh has just made and reported, when it has
         vol, planes = volume_and_planes()
         if 'mesh' not in made:
-            made['mesh'], _ = mesh_of_density_grid(vol, args.mesh_level, planes=planes, **stages)
+            made['mesh'], _ = mesh_of_density_grid(vol, args.mesh_level, planes=planes, band=made['band'], **stages)
             if rank == 0:
                 for line in shape_mi355x.report_lines(made['mesh'].reports, smooth=args.mesh_smooth):
                     print(line)

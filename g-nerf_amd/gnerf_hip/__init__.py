@@ -32,11 +32,14 @@ from .conv3x3 import (conv3x3_epilogue, conv3x3_epilogue_supported, conv3x3_epil
 from .render import (decoder_pack_available, last_mlp_choice, pack_decoder, planes_layout, query_points, query_points_backward, query_points_grad, render_backward,  # noqa: F401
                      render_forward, render_generated_supported, render_ray_grad_available, render_ray_grad_refusal, render_ray_grad_supported, _render_params,
                      project_points_to_level, project_to_level_available, _project_points_to_level_ctypes,
-                     scatter_plane_rows, scatter_plane_rows_available)
+                     scatter_plane_rows, scatter_plane_rows_available,
+                     query_lattice, query_lattice_available, _query_lattice_ctypes)
 from .mesh import (MESH_SMOOTH_MAX_FACES, marching_cubes, mesh_clean_available, mesh_compact, mesh_components, mesh_smooth, mesh_workspace_bytes,  # noqa: F401
                    mesh_simplify, mesh_simplify_available, mesh_simplify_count, mesh_simplify_workspace_bytes,
                    mesh_flip_guard, mesh_flip_guard_available, _mesh_flip_guard_ctypes,
                    _marching_cubes_ctypes, _mesh_compact_ctypes, _mesh_components_ctypes, _mesh_simplify_ctypes, _mesh_smooth_ctypes)
+from .mesh import (BAND_BRICKS, BandVolume, band_available, band_fill, band_grow, band_points_count, band_points_emit, band_seed,  # noqa: F401
+                   band_workspace_bytes)
 from .ssim import SSIM_MAX_WIN, ssim_backward, ssim_forward  # noqa: F401
 from .resize import (RESIZE_MAX_TAPS, RESIZE_MODES, resize_aa_available, resize_aa_backward, resize_aa_forward, resize_aa_refusal,  # noqa: F401
                      resize_aa_supported)

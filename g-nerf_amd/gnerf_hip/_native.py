@@ -154,14 +154,21 @@ SIGNATURES = {
     'gnerf_mesh_simplify_count': (_c_i, [_c_p, _c_p, _c_i, _c_i, _c_f, ctypes.POINTER(_c_f), _c_p, _c_p, _c_p]),
     'gnerf_mesh_simplify_emit': (_c_i, [_c_p, _c_p, _c_i, _c_i, _c_f, ctypes.POINTER(_c_f), _c_p, _c_p, _c_p, _c_p, _c_p, _c_p]),
     'gnerf_mesh_flip_guard': (_c_i, [_c_p, _c_p, _c_p, _c_i, _c_i, _c_i, _c_p, _c_p, _c_p, _c_p]),
+    'gnerf_query_lattice': (_c_i, [_c_p, _c_i, _c_i, _c_p, _c_i, _c_i, ctypes.c_double, _c_f, _c_p, _c_p, _c_p, _c_p, _c_p, _c_i, _c_p]),
+    'gnerf_band_workspace_bytes': (_c_i, [_c_i, _c_i, ctypes.POINTER(ctypes.c_size_t)]),
+    'gnerf_band_seed': (_c_i, [_c_p, _c_i, _c_i, _c_f, ctypes.POINTER(_c_i), _c_p, _c_p, _c_p, _c_p]),
+    'gnerf_band_points_count': (_c_i, [_c_p, _c_i, _c_i, _c_p, _c_p, _c_p]),
+    'gnerf_band_points_emit': (_c_i, [_c_p, _c_i, _c_i, _c_p, _c_p, _c_i64, _c_p]),
+    'gnerf_band_grow': (_c_i, [_c_p, _c_i, _c_i, _c_f, ctypes.POINTER(_c_i), _c_p, _c_p, _c_p, _c_p]),
+    'gnerf_band_fill': (_c_i, [_c_p, _c_i, _c_i, ctypes.POINTER(_c_i), _c_p, _c_p]),
 }
 # exports added WITHOUT a new ABI version: a library of the same version built before them (a variant build behind GNERF_HIP_LIB) loads, and
 # what needs them asks modconv_backward_available() / render_ray_grad_available() / decoder_pack_available() / resize_aa_available() /
 # raster_available() / mesh_clean_available() / mesh_simplify_available() / project_to_level_available() / mesh_flip_guard_available() /
-# scatter_plane_rows_available() / texture_available()
+# scatter_plane_rows_available() / texture_available() / query_lattice_available() / band_available()
 OPTIONAL_SYMBOLS = frozenset(n for n in SIGNATURES if n.startswith(('gnerf_project_points_to_level', 'gnerf_modconv_backward_','gnerf_scale_channels_backward', 'gnerf_modconv_epilogue_backward',
                                                                     'gnerf_render_backward_rays', 'gnerf_render_scatter_rows', 'gnerf_render_decoder_pack_bytes',
-                                                                    'gnerf_render_pack_decoder', 'gnerf_render_forward_packed', 'gnerf_resize_aa_', 'gnerf_raster_', 'gnerf_mesh_')))
+                                                                    'gnerf_render_pack_decoder', 'gnerf_render_forward_packed', 'gnerf_resize_aa_', 'gnerf_raster_', 'gnerf_mesh_', 'gnerf_query_lattice', 'gnerf_band_')))
 
 
 def profiled(name):

@@ -1,5 +1,5 @@
 """Marching cubes on the density volume (csrc/mesh.hip) the cleaning of its meshes (csrc/mesh_clean.hip): components, compaction, smoothing, and
-their simplification (csrc/mesh_simplify.hip): vertex clustering with quadrics."""
+their simplification (csrc/mesh_simplify.hip): vertex clustering with quadrics, and the bookkeeping of the narrow-band volume (csrc/mesh_band.hip)."""
 
 import ctypes
 
@@ -354,3 +354,137 @@ def mesh_simplify(verts, faces, cell, origin):
         with _on_device(v.device):
             return _mesh_simplify_result(*e.mesh_simplify(v, f, cell, origin))
     return _mesh_simplify_result(*_mesh_simplify_ctypes(v, f, cell, origin))
+
+
+# ---------------------------------------------------------------------------------------------------------------- narrow band (csrc/mesh_band.hip)
+_BAND_SYMBOLS = ('gnerf_band_workspace_bytes', 'gnerf_band_seed', 'gnerf_band_points_count', 'gnerf_band_points_emit', 'gnerf_band_grow', 'gnerf_band_fill')
+BAND_BRICKS = (2, 4, 8, 16)
+
+
+def band_available():
+    """Whether the loaded library has the narrow-band kernels (a version-15 library built before them does not)."""
+    return all(hasattr(load(), name) for name in _BAND_SYMBOLS)
+
+
+def band_workspace_bytes(n, s):
+    nbytes = ctypes.c_size_t()
+    _check(load().gnerf_band_workspace_bytes(int(n), int(s), ctypes.byref(nbytes)), 'gnerf_band_workspace_bytes')
+    return int(nbytes.value)
+
+
+def _band_keep(n, keep):
+    keep = [(0, n)] * 3 if keep is None else [(int(lo), int(hi)) for lo, hi in keep]
+    if len(keep) != 3:
+        raise ValueError('band: keep must be three (lo, hi) index ranges')
+    return [min(max(x, 0), n) for pair in keep for x in pair]
+
+
+def _band_tensor(t, dtype, numel, what, name):
+    _require_cuda(t)
+    if t.dtype != dtype or not t.is_contiguous() or t.numel() != numel:
+        raise ValueError(f'{what}: {name} must be a contiguous {dtype} CUDA tensor of {numel} values')
+    return t
+
+
+def _band_ext(binding):
+    return None if binding == 'ctypes' else _native.ext()
+
+
+@profiled('gnerf_hip::band_seed')
+def band_seed(volume, n, s, level, keep, state, workspace, count, binding=None):
+    """gnerf_band_seed: state (uint8 [nb^3], written) = 2 for the bricks whose corners straddle `level`, count (int64 [1] on the device, written)
+    = their number.  volume float32 [n^3] with the coarse points evaluated; keep: three (lo, hi) or None.  binding='ctypes' forces that route."""
+    e = _band_ext(binding)
+    if e is not None and hasattr(e, 'band_seed'):
+        with _on_device(volume.device):
+            return e.band_seed(volume, n, s, float(level), _band_keep(n, keep), state, workspace, count)
+    _launch('gnerf_band_seed', volume, _ptr(volume), n, s, float(level), (ctypes.c_int * 6)(*_band_keep(n, keep)), _ptr(state), _ptr(workspace), _ptr(count))
+
+
+@profiled('gnerf_hip::band_points_count')
+def band_points_count(state, n, s, workspace, count, binding=None):
+    """gnerf_band_points_count: count (int64 [1] on the device, written) = the length of the index list of the bricks of state 2.  Reads the
+    list of those bricks that band_seed / band_grow left in `workspace`: it follows one of them on the same state."""
+    e = _band_ext(binding)
+    if e is not None and hasattr(e, 'band_points_count'):
+        with _on_device(state.device):
+            return e.band_points_count(state, n, s, workspace, count)
+    _launch('gnerf_band_points_count', state, _ptr(state), n, s, _ptr(workspace), _ptr(count))
+
+
+@profiled('gnerf_hip::band_points_emit')
+def band_points_emit(state, n, s, workspace, m, binding=None):
+    """gnerf_band_points_emit after band_points_count on the same state and workspace, m the count it gave -> the index list int32 [m]."""
+    index = torch.empty(int(m), dtype=torch.int32, device=state.device)
+    e = _band_ext(binding)
+    if e is not None and hasattr(e, 'band_points_emit'):
+        with _on_device(state.device):
+            e.band_points_emit(state, n, s, workspace, index)
+    else:
+        _launch('gnerf_band_points_emit', state, _ptr(state), n, s, _ptr(workspace), _ptr(index) if m else None, int(m))
+    return index
+
+
+@profiled('gnerf_hip::band_grow')
+def band_grow(volume, n, s, level, keep, state, workspace, count, binding=None):
+    """gnerf_band_grow: the bricks of state 2 (their points evaluated in `volume`) name the neighbours their mixed faces lead to, the round
+    closes (2 -> 1, named -> 2) in `state`, count (int64 [1] on the device, written) = the new bricks."""
+    e = _band_ext(binding)
+    if e is not None and hasattr(e, 'band_grow'):
+        with _on_device(volume.device):
+            return e.band_grow(volume, n, s, float(level), _band_keep(n, keep), state, workspace, count)
+    _launch('gnerf_band_grow', volume, _ptr(volume), n, s, float(level), (ctypes.c_int * 6)(*_band_keep(n, keep)), _ptr(state), _ptr(workspace), _ptr(count))
+
+
+@profiled('gnerf_hip::band_fill')
+def band_fill(volume, n, s, keep, state, binding=None):
+    """gnerf_band_fill, in place: every point of `volume` that is neither coarse nor in an active brick takes its coarse corner's effective value."""
+    e = _band_ext(binding)
+    if e is not None and hasattr(e, 'band_fill'):
+        with _on_device(volume.device):
+            return e.band_fill(volume, n, s, _band_keep(n, keep), state)
+    _launch('gnerf_band_fill', volume, _ptr(volume), n, s, (ctypes.c_int * 6)(*_band_keep(n, keep)), _ptr(state))
+
+
+class BandVolume:
+    """The device side of shape_mi355x.band_volume for one volume (float32 [n^3] on a GPU, evaluated in place by the caller): the brick states,
+    the workspace and the two counts, and the stages as the driver calls them.  seed() and grow() also count the next round's points, so the
+    host reads (new bricks, points) together: one read per round."""
+
+    def __init__(self, volume, n, s, level, keep=None, binding=None):
+        if not band_available():
+            raise RuntimeError('gnerf_hip: this libgnerf_hip.so was built without the narrow-band kernels (gnerf_band_*): rebuild it (csrc/build.sh)')
+        self.n, self.s, self.level, self.keep, self.binding = int(n), int(s), float(level), keep, binding
+        if self.s not in BAND_BRICKS:
+            raise ValueError(f'band: the brick edge must be one of {BAND_BRICKS}, got {s}')
+        if self.n < 2 or self.n ** 3 >= 2 ** 31:
+            raise ValueError(f'band: n must be >= 2 with n^3 < 2^31, got {n}')
+        self.volume = _band_tensor(volume, torch.float32, self.n ** 3, 'band', 'volume')
+        dev = volume.device
+        self.nb = -(-(self.n - 1) // self.s)
+        self.state = torch.empty(self.nb ** 3, dtype=torch.uint8, device=dev)
+        self.workspace = torch.empty(band_workspace_bytes(self.n, self.s), dtype=torch.uint8, device=dev)
+        self.counts = torch.empty(2, dtype=torch.int64, device=dev)
+        self.points_next = 0
+
+    def _read(self):
+        band_points_count(self.state, self.n, self.s, self.workspace, self.counts[1:], self.binding)
+        new, self.points_next = (int(c) for c in self.counts.cpu())           # the round's one synchronisation
+        return new
+
+    def seed(self):
+        """-> the seeded bricks."""
+        band_seed(self.volume, self.n, self.s, self.level, self.keep, self.state, self.workspace, self.counts[:1], self.binding)
+        return self._read()
+
+    def points(self):
+        """-> the index list of the bricks that the last seed() / grow() made new."""
+        return band_points_emit(self.state, self.n, self.s, self.workspace, self.points_next, self.binding)
+
+    def grow(self):
+        """-> the bricks this round's growth made new."""
+        band_grow(self.volume, self.n, self.s, self.level, self.keep, self.state, self.workspace, self.counts[:1], self.binding)
+        return self._read()
+
+    def fill(self):
+        band_fill(self.volume, self.n, self.s, self.keep, self.state, self.binding)

@@ -534,6 +534,47 @@ def query_points_grad(planes_nhwc, n_items, decoder, points, box_warp, grad_sigm
     return g_pts
 
 
+def query_lattice_available():
+    """Whether the loaded library has the lattice query (a version-15 library built before it does not)."""
+    return hasattr(load(), 'gnerf_query_lattice')
+
+
+def _query_lattice_ctypes(planes_nhwc, decoder, index, n, cube_length, box_warp, out, interleaved):
+    """The ctypes route of query_lattice (arguments as query_lattice prepares them)."""
+    w1, b1, w2, b2 = decoder
+    _launch('gnerf_query_lattice', out, _ptr(planes_nhwc), planes_nhwc.shape[1], planes_nhwc.shape[2], _ptr(index), index.numel(), n, float(cube_length),
+            float(box_warp), _ptr(w1), _ptr(b1), _ptr(w2), _ptr(b2), _ptr(out), interleaved)
+
+
+@profiled('gnerf_hip::query_lattice')
+def query_lattice(planes_nhwc, decoder, index, n, cube_length, box_warp, out, binding=None):
+    """Densities at lattice points named by their linear index: out[index] = sigma of ONE item's planes at the points
+    voxel_samples(index, ..., n, cube_length) -- the positions are formed in the kernel with that function's fp32 arithmetic, so the bits are
+    those of query_points(..., want_rgb=False) at them (include/gnerf_hip.h, gnerf_query_lattice).  index: CUDA int32 [m] (duplicates allowed; an
+    empty list does nothing); out: a contiguous float32 CUDA tensor of n^3 values, written in place at the listed entries only.  Returns out.
+    binding='ctypes' forces that route."""
+    if not query_lattice_available():
+        raise RuntimeError('gnerf_hip: this libgnerf_hip.so was built without gnerf_query_lattice: rebuild it (csrc/build.sh)')
+    dec = [_f32c(t) for t in decoder]
+    _require_cuda(planes_nhwc, index, out, dec[0])
+    interleaved = planes_layout(planes_nhwc, 1, 'query_lattice')
+    n = int(n)
+    if n < 2 or n ** 3 >= 2 ** 31 or out.dtype != torch.float32 or not out.is_contiguous() or out.numel() != n ** 3:
+        raise RuntimeError('query_lattice: out must be a contiguous float32 tensor of n^3 < 2^31 values')
+    if index.ndim != 1 or index.device != out.device:
+        raise RuntimeError('query_lattice: index must be [m] on out\'s device')
+    idx = index if (index.dtype == torch.int32 and index.is_contiguous()) else index.to(torch.int32).contiguous()
+    if idx.numel() == 0:
+        return out
+    e = None if binding == 'ctypes' else _native.ext()
+    if e is not None and hasattr(e, 'query_lattice'):
+        with _on_device(out.device):
+            e.query_lattice(planes_nhwc, *dec, idx, n, float(cube_length), float(box_warp), out)
+    else:
+        _query_lattice_ctypes(planes_nhwc, dec, idx, n, cube_length, box_warp, out, interleaved)
+    return out
+
+
 def project_to_level_available():
     """Whether the loaded library has the level-set projection kernel (a version-15 library built before it does not)."""
     return hasattr(load(), 'gnerf_project_points_to_level')

@@ -33,6 +33,11 @@ simplify_mesh shrinks such a mesh: vertex clustering on a uniform grid with a qu
 target face count.  CUDA tensors go to csrc/mesh_simplify.hip (gnerf_hip.mesh_simplify / mesh_simplify_count), numpy arrays to
 mesh_simplify_numpy below (include/gnerf_hip.h, gnerf_mesh_simplify_*): the same bits.
 
+band_volume makes the volume itself cheaper: it evaluates the density field only in bricks that the level set runs through (surface following
+from seeded bricks), and the mesh of its volume is the dense volume's in the same order, minus whole components thinner than a brick.  On a
+CUDA device the bookkeeping runs on csrc/mesh_band.hip (gnerf_hip.BandVolume), anywhere else on band_volume_numpy below
+(include/gnerf_hip.h, gnerf_band_*): the same brick states, index lists and volume.
+
 finish_mesh walks these stages, and those that need a generator (given as callables), in the one order both CLIs use.
 
 CLI, as shape_utils.py's (:102-123):  python shape_mi355x.py INPUT [--level 10]   (INPUT: a .mrc / .npy file or a directory of them)
@@ -307,6 +312,236 @@ def marching_cubes(volume, level, spacing=1.0, origin=(0.0, 0.0, 0.0)):
     if not identity:
         verts = verts * _on_route(s, verts) + _on_route(o, verts)
     return verts, faces
+
+
+# ---------------------------------------------------------------------------------------------------------------- narrow band
+# The density volume evaluated only where the surface is, by surface following on bricks (include/gnerf_hip.h, gnerf_band_*, states the rules;
+# DESIGN.md 3.22 the argument): the mesh of the result is the dense volume's mesh in the same vertex and face order, minus whole components
+# that no seeded or grown brick touched.  The lattice is n^3 points in linear order (axis 2 fastest); a brick is s^3 cells, its points the
+# closed ranges, the last brick of an axis partial; the coarse points have every index in {0, s, 2s, ...} + {n - 1}.
+# Brick states (one byte each): 0 inactive, 1 active (its points are evaluated), 2 new (active; its points are evaluated in this round),
+# 3 named by this round's growth (becomes 2 when the round closes).
+BAND_BRICKS = (2, 4, 8, 16)
+
+
+def _band_geometry(n, s, keep):
+    n, s = int(n), int(s)
+    if s not in BAND_BRICKS:
+        raise ValueError(f'band_volume: the brick edge must be one of {BAND_BRICKS}, got {s}')
+    if n < 2 or n ** 3 >= 2 ** 31:
+        raise ValueError(f'band_volume: n must be >= 2 with n^3 < 2^31, got {n}')
+    keep = [(0, n)] * 3 if keep is None else [(min(max(int(lo), 0), n), min(max(int(hi), 0), n)) for lo, hi in keep]
+    if len(keep) != 3:
+        raise ValueError('band_volume: keep must be three (lo, hi) index ranges')
+    return n, s, -(-(n - 1) // s), [(lo, max(hi, lo)) for lo, hi in keep]
+
+
+def band_keep_of_crop(n, ranges):
+    """The kept index range per axis of a crop `vol[:a] = 0; vol[-b:] = 0` per axis (ranges: three (a, b)), python's slices included: b == 0
+    zeroes the whole axis.  For an axis stored flipped, swap a and b first."""
+    return [(a, n - b) if b > 0 else (0, 0) for a, b in ranges]
+
+
+def _band_coarse(n, s, nb):
+    """(bounds [nb + 1]: brick b spans points bounds[b] .. bounds[b + 1]; is_coarse [n])."""
+    bounds = np.minimum(np.arange(nb + 1, dtype=np.int64) * s, n - 1)
+    is_coarse = np.zeros(n, dtype=bool)
+    is_coarse[bounds] = True
+    return bounds, is_coarse
+
+
+def _band_kept(keep, i0, i1, i2):
+    (a0, b0), (a1, b1), (a2, b2) = keep
+    return (i0 >= a0) & (i0 < b0) & (i1 >= a1) & (i1 < b1) & (i2 >= a2) & (i2 < b2)
+
+
+def band_points_numpy(state, n, s):
+    """The index list of a round's new points (gnerf_band_points_*): the points of the bricks of state 2 that are neither coarse nor in a
+    brick of state 1, each once -- a point that several new bricks share goes to the one of the lowest brick index --, brick-major, then
+    row-major within the brick -> int32 [m]."""
+    nb = -(-(n - 1) // s)
+    bounds, is_coarse = _band_coarse(n, s, nb)
+    state = np.asarray(state, dtype=np.uint8).reshape(nb, nb, nb)
+    new = np.flatnonzero(state.reshape(-1) == 2)
+    if not len(new):
+        return np.zeros(0, dtype=np.int32)
+    B = np.stack(np.unravel_index(new, (nb, nb, nb)), axis=1)                                  # [m, 3]
+    lo, hi = bounds[B], bounds[B + 1]
+    off = np.stack(np.meshgrid(*[np.arange(s + 1)] * 3, indexing='ij'), axis=-1).reshape(-1, 3)  # [L, 3], axis 2 fastest
+    P = lo[:, None, :] + off[None]                                                             # [m, L, 3]
+    listed = (P <= hi[:, None, :]).all(-1) & ~is_coarse[np.minimum(P, n - 1)].all(-1)
+    at_lo, at_hi = P == lo[:, None, :], P == hi[:, None, :]
+    for d0 in (-1, 0, 1):
+        for d1 in (-1, 0, 1):
+            for d2 in (-1, 0, 1):
+                d = np.array([d0, d1, d2])
+                if not d.any():
+                    continue
+                O = B + d
+                shares = np.ones(P.shape[:2], dtype=bool)                                      # the point also lies in brick B + d
+                for a in range(3):
+                    if d[a] == -1:
+                        shares &= at_lo[..., a] & (B[:, a] > 0)[:, None]
+                    elif d[a] == 1:
+                        shares &= at_hi[..., a] & (B[:, a] < nb - 1)[:, None]
+                Oc = np.clip(O, 0, nb - 1)
+                st = state[Oc[:, 0], Oc[:, 1], Oc[:, 2]]
+                olin = (O[:, 0] * nb + O[:, 1]) * nb + O[:, 2]
+                first = (st == 1) | ((st == 2) & (olin < new))
+                listed &= ~(shares & first[:, None])
+    idx = (P[..., 0] * n + P[..., 1]) * n + P[..., 2]
+    return idx[listed].astype(np.int32)
+
+
+def band_seed_numpy(vol, n, level, s, keep=None):
+    """gnerf_band_seed: state 2 for every brick whose eight corner points (effective values) are not all on one side of `level`, 0 for
+    the others -> (state uint8 [nb^3], seeds)."""
+    n, s, nb, keep = _band_geometry(n, s, keep)
+    bounds, _ = _band_coarse(n, s, nb)
+    v = np.asarray(vol, dtype=np.float32).reshape(n, n, n)[np.ix_(bounds, bounds, bounds)]
+    g = np.meshgrid(bounds, bounds, bounds, indexing='ij')
+    inside = np.where(_band_kept(keep, *g), v, np.float32(0)) > np.float32(level)
+    corners = [inside[a:nb + a, b:nb + b, c:nb + c] for a in (0, 1) for b in (0, 1) for c in (0, 1)]
+    mixed = np.logical_or.reduce(corners) & ~np.logical_and.reduce(corners)
+    state = np.where(mixed, 2, 0).astype(np.uint8).reshape(-1)
+    return state, int(mixed.sum())
+
+
+def band_grow_numpy(vol, n, level, s, state, keep=None):
+    """gnerf_band_grow: every brick of state 2 tests its six faces whose neighbour has state 0 (or 3); a face whose points (effective values)
+    are not all on one side names the neighbour (3).  Then the round closes: 2 -> 1, 3 -> 2 -> (state', new bricks)."""
+    n, s, nb, keep = _band_geometry(n, s, keep)
+    bounds, _ = _band_coarse(n, s, nb)
+    level = np.float32(level)
+    vol = np.asarray(vol, dtype=np.float32).reshape(-1)
+    state = np.array(state, dtype=np.uint8).reshape(nb, nb, nb)
+    new = np.flatnonzero(state.reshape(-1) == 2)
+    if len(new):
+        B = np.stack(np.unravel_index(new, (nb, nb, nb)), axis=1)
+        lo, hi = bounds[B], bounds[B + 1]
+        u, w = (x.reshape(-1) for x in np.meshgrid(np.arange(s + 1), np.arange(s + 1), indexing='ij'))
+        for a in range(3):
+            b, c = [x for x in range(3) if x != a]
+            for side, d in ((lo, -1), (hi, 1)):
+                O = B.copy()
+                O[:, a] += d
+                exists = (O[:, a] >= 0) & (O[:, a] < nb)
+                Oc = np.clip(O, 0, nb - 1)
+                open_ = exists & np.isin(state[Oc[:, 0], Oc[:, 1], Oc[:, 2]], (0, 3))
+                P = np.empty((len(new), len(u), 3), dtype=np.int64)
+                P[..., a] = side[:, a][:, None]
+                P[..., b] = lo[:, b][:, None] + u[None]
+                P[..., c] = lo[:, c][:, None] + w[None]
+                valid = (P[..., b] <= hi[:, b][:, None]) & (P[..., c] <= hi[:, c][:, None])
+                Pc = np.minimum(P, n - 1)
+                v = vol[(Pc[..., 0] * n + Pc[..., 1]) * n + Pc[..., 2]]
+                inside = np.where(_band_kept(keep, Pc[..., 0], Pc[..., 1], Pc[..., 2]), v, np.float32(0)) > level
+                mixed = open_ & (inside & valid).any(1) & (~inside & valid).any(1)
+                t = Oc[mixed]
+                state[t[:, 0], t[:, 1], t[:, 2]] = 3
+    state = state.reshape(-1)
+    out = np.where(state == 2, 1, np.where(state == 3, 2, state)).astype(np.uint8)
+    return out, int((out == 2).sum())
+
+
+def band_fill_numpy(vol, n, s, state, keep=None):
+    """gnerf_band_fill, in place: every point that is neither coarse nor in a brick of state 1 or 2 takes the effective value of the coarse
+    point at (i // s * s, j // s * s, k // s * s)."""
+    n, s, nb, keep = _band_geometry(n, s, keep)
+    bounds, is_coarse = _band_coarse(n, s, nb)
+    v = vol.reshape(n, n, n)
+    active = np.isin(np.asarray(state).reshape(nb, nb, nb), (1, 2))
+    sizes = np.diff(bounds)
+    cells = np.pad(active.repeat(sizes, 0).repeat(sizes, 1).repeat(sizes, 2), 1)
+    in_active = np.logical_or.reduce([cells[a:n + a, b:n + b, c:n + c] for a in (0, 1) for b in (0, 1) for c in (0, 1)])
+    coarse = is_coarse[:, None, None] & is_coarse[None, :, None] & is_coarse[None, None, :]
+    corner = np.arange(n) // s * s
+    g = np.meshgrid(corner, corner, corner, indexing='ij')
+    value = np.where(_band_kept(keep, *g), v[np.ix_(corner, corner, corner)], np.float32(0))
+    target = ~coarse & ~in_active
+    v[target] = value[target]
+    return vol
+
+
+def _band_driver(n, s, evaluate, coarse_index, band, trace):
+    """The steps of the rules, spelled once for both routes: evaluate(index) writes the densities; band holds the brick states and gives the
+    route's stages -- seed() -> seeds, points() -> the round's index list, grow() -> new bricks, fill(), and state for the trace."""
+    evaluate(coarse_index)
+    evaluated = len(coarse_index)
+    new = seeds = band.seed()
+    per_round = []
+    while new:
+        index = band.points()
+        evaluate(index)
+        evaluated += len(index)
+        new = band.grow()
+        per_round.append(new)
+        if trace is not None:
+            trace.append((to_host(band.state).copy(), to_host(index).copy()))
+    band.fill()
+    return dict(brick=s, bricks=(-(-(n - 1) // s)) ** 3, seeds=seeds, new_bricks=per_round, rounds=len(per_round), host_reads=len(per_round) + 1,
+                points=evaluated, share=evaluated / n ** 3)
+
+
+class _BandNumpy:
+    """The port's side of _band_driver: the brick states of one volume (float32 numpy [n^3], evaluated in place by the caller) and the stages."""
+
+    def __init__(self, vol, n, s, level, keep):
+        self.vol, self.n, self.s, self.level, self.keep, self.state = vol, n, s, level, keep, None
+
+    def seed(self):
+        self.state, seeds = band_seed_numpy(self.vol, self.n, self.level, self.s, self.keep)
+        return seeds
+
+    def points(self):
+        return band_points_numpy(self.state, self.n, self.s)
+
+    def grow(self):
+        self.state, new = band_grow_numpy(self.vol, self.n, self.level, self.s, self.state, self.keep)
+        return new
+
+    def fill(self):
+        band_fill_numpy(self.vol, self.n, self.s, self.state, self.keep)
+
+
+def band_coarse_index(n, s):
+    """The linear indices of the coarse points, ascending -> int32 numpy [(nb + 1)^3]."""
+    bounds, _ = _band_coarse(n, s, -(-(n - 1) // s))
+    return ((bounds[:, None, None] * n + bounds[None, :, None]) * n + bounds[None, None, :]).reshape(-1).astype(np.int32)
+
+
+def band_volume_numpy(field, n, level, s, keep=None, trace=None):
+    """The numpy port of band_volume (the CPU path, and the bits the kernels give): field(index int32 numpy [m], out float32 numpy [n^3])
+    writes the densities at those indices -> (volume float32 [n, n, n] before the crop, report).  trace: a list that receives (state after
+    the round, the round's index list) per round."""
+    n, s, nb, keep = _band_geometry(n, s, keep)
+    vol = np.zeros(n ** 3, dtype=np.float32)
+    report = _band_driver(n, s, lambda index: field(index, vol) if len(index) else None, band_coarse_index(n, s), _BandNumpy(vol, n, s, level, keep), trace)
+    return vol.reshape(n, n, n), report
+
+
+def band_volume(field, n, level, s, keep=None, device=None, trace=None):
+    """The density volume of an n^3 lattice evaluated in a narrow band around the level set (the rules above): field(index, out) writes the
+    densities at the int32 linear indices `index` into the flat float32 `out` [n^3] -- called with every index at most once.  keep: the
+    kept index range (lo, hi) per axis of the crop that follows, None for everything -> (volume [n, n, n] BEFORE the crop, report: brick,
+    bricks, seeds, new_bricks per round, rounds, host_reads, points evaluated and their share of n^3).
+    device: a CUDA device takes the kernels (csrc/mesh_band.hip through gnerf_hip.band_*; index and out are tensors there), anything else the
+    numpy port -- the same brick states, lists and volume either way."""
+    torch = _torch()
+    dev = None if device is None or torch is None else torch.device(device)
+    if dev is None or dev.type != 'cuda':
+        return band_volume_numpy(field, n, level, s, keep, trace)
+    import gnerf_hip
+    n, s, nb, keep = _band_geometry(n, s, keep)
+    vol = torch.empty(n ** 3, dtype=torch.float32, device=dev)
+    report = _band_driver(n, s, lambda index: field(index, vol) if len(index) else None, torch.from_numpy(band_coarse_index(n, s)).to(dev),
+                          gnerf_hip.BandVolume(vol, n, s, level, keep), trace)
+    return vol.reshape(n, n, n), report
+
+
+def band_report_line(report):
+    return (f'band: bricks of {report["brick"]}^3 cells, {report["seeds"]} seeded + {sum(report["new_bricks"])} grown of {report["bricks"]} in '
+            f'{report["rounds"]} round(s), {report["points"]} points evaluated ({100 * report["share"]:.2f} % of the lattice)')
 
 
 # ---------------------------------------------------------------------------------------------------------------- rasteriser

@@ -649,6 +649,25 @@ class ImportanceRenderer(torch.nn.Module):
         dirs[..., -1] = -1
         return self.run_model(planes, decoder, sample_coordinates, dirs, options)['sigma']
 
+    def query_sigma_lattice(self, planes, decoder, index, n, options, out, cube_length=None):
+        """Densities at points of gen_videos.py's n^3 sample lattice named by their linear indices: out[index] = query_sigma at
+        voxel_samples' positions of those indices (cube_length: the lattice's, options['box_warp'] by default), written into the flat float32
+        `out` [n^3] in place; the other entries are left alone.  On CUDA tensors, under query_sigma's conditions, one kernel forms the
+        positions itself and stores straight into `out` (gnerf_hip.query_lattice: the same bits); otherwise voxel_samples at those indices,
+        query_sigma and an indexed store.  Not part of the reference's interface: extract_density_grid's narrow band evaluates through it."""
+        cube_length = options['box_warp'] if cube_length is None else cube_length
+        if len(index) == 0:
+            return out
+        if (planes.device.type == 'cuda' and planes.ndim == 5 and planes.shape[0] == 1 and planes.shape[1] == 3 and planes.shape[2] == 32
+                and not torch.is_grad_enabled() and out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.numel() == n ** 3):
+            fcs = _osg_decoder_weights(decoder)
+            if fcs is not None and options.get('density_noise', 0) == 0:
+                return gnerf_hip.query_lattice(self._planes_nhwc(planes)[0], self._decoder_cache(fcs), index, n, cube_length, options['box_warp'], out)
+        from gnerf_lattice import voxel_samples
+        index = torch.as_tensor(index).to(out.device).long()
+        out.view(-1)[index] = self.query_sigma(planes, decoder, voxel_samples(index, None, n, cube_length, out.device), options).reshape(-1).to(out.dtype)
+        return out
+
     def query_normals(self, planes, decoder, sample_coordinates, options):
         """(sigma [N,P,1], normals [N,P,3]) at arbitrary points: normals = -grad sigma / |grad sigma|, outward for a surface whose inside
         is sigma > level (the mesh's convention); a point where the gradient is zero gets the exact zero vector.  density_noise is not

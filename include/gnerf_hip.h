@@ -971,6 +971,61 @@ int gnerf_mesh_simplify_emit(const float* verts, const int32_t* faces, int n_ver
 int gnerf_mesh_flip_guard(const float* verts_in, const float* verts_moved, const int32_t* faces, int n_verts, int n_tris, int max_rounds,
                           float* verts_out, unsigned char* status, int32_t* counts, gnerf_stream_t stream);
 
+/* (ABI 15, added without a new version) The densities-only point query at LATTICE points named by their linear index (csrc/query_lattice.inl):
+ * what extract_density_grid's narrow band evaluates, gnerf_query_points' kernel with another point source and sink.
+ *   planes_nhwc, plane_h, plane_w, box_warp, w1 .. b2, planes_interleaved: as gnerf_query_points, for ONE item.
+ *   index int32 [m]: linear indices into the n^3 lattice of gen_videos.py's create_samples(N = n, cube_length), duplicates allowed (they write
+ *   the same value); out float32 [n^3]: out[index[i]] = sigma, every other entry is left alone (an index outside [0, n^3) writes nothing).
+ *   The position of index idx is voxel_samples' (gen_videos_mi355x.py) as PyTorch computes it on the device, in fp32, one rounding per
+ *   operation, no contraction: f = float(idx); s2 = float(idx % n) in integers; q1 = f * r, s1 = fmod(q1, n); q0 = q1 * r, s0 = fmod(q0, n)
+ *   with r = 1.0f / float(n) -- a float tensor divided by a Python scalar is multiplied by the scalar's fp32 reciprocal there, which is the
+ *   quotient for a power of two only --; p = (s0, s1, s2) * float(cube_length / (n - 1)) + float(-cube_length / 2), two roundings each.
+ *   So out[idx] holds the bits gnerf_query_points gives at voxel_samples(idx, idx + 1, n, cube_length): a point's result does not depend on the
+ *   other points of its tile.
+ * GNERF_E_ARG for null pointers, m < 1, m beyond gnerf_query_points' cap on n_points, n < 2, n^3 >= 2^31 or a cube_length that is not finite and > 0. */
+int gnerf_query_lattice(const float* planes_nhwc, int plane_h, int plane_w, const int32_t* index, int m, int n, double cube_length, float box_warp,
+                        const float* w1, const float* b1, const float* w2, const float* b2, float* out, int planes_interleaved,
+                        gnerf_stream_t stream);
+
+/* (ABI 15, added without a new version) The narrow band of a density volume: surface following on bricks (csrc/mesh_band.hip; the driver is
+ * shape_mi355x.band_volume, and band_volume_numpy gives the same bits).  Only the lattice points near the level set are evaluated, and the
+ * mesh of the result is the dense volume's in the same vertex and face order, minus whole components that no brick below ever touched.
+ *   SETTING.  The lattice is n^3 points in linear order (axis 2 fastest), volume float32 [n^3].  `level` is the isosurface level, s in
+ *   {2, 4, 8, 16} the brick edge in cells.  A point is INSIDE iff its effective value is > level (ties and NaN are outside: marching cubes'
+ *   rule).  The effective value e(p) is 0 where the caller's crop will zero p and the volume's value elsewhere; keep: six ints on the HOST,
+ *   the kept index range [lo, hi) of axes 0, 1, 2 (null: everything; clamped to [0, n]).
+ *   BRICKS.  nb = ceil((n - 1) / s) bricks per axis; brick b owns the cells [b s, min((b + 1) s, n - 1)) and its points are the closed range
+ *   [b s, min((b + 1) s, n - 1)]: neighbours share their face points, the last brick may be partial.  Brick (b0, b1, b2) has index
+ *   (b0 nb + b1) nb + b2.  The COARSE points have every index in {0, s, 2 s, ...} + {n - 1}: the bricks' corners.
+ *   state: one byte per brick [nb^3]: 0 inactive, 1 active, 2 new (active; its points are evaluated in this round), 3 named by the growth of
+ *   this round (only inside gnerf_band_grow).
+ *   STEPS, as the driver takes them: evaluate the coarse points; gnerf_band_seed; while there are new bricks: gnerf_band_points_count /
+ *   _emit, evaluate the listed points, gnerf_band_grow; gnerf_band_fill; the crop; marching cubes.
+ *   gnerf_band_workspace_bytes: *bytes = the workspace the calls below share (12 bytes per brick + small per-block arrays).  gnerf_band_seed
+ *     and gnerf_band_grow leave the list of the new bricks in it; gnerf_band_points_count / _emit and the next gnerf_band_grow read that list,
+ *     so they follow a seed or grow on the same state and workspace, with the state left as it was.
+ *   gnerf_band_seed: state = 2 for every brick whose eight corner points are not all on one side, 0 for the others; *count = the seeds.
+ *   gnerf_band_points_count: *count = the length of the round's index list: the points of the bricks of state 2 that are not evaluated yet --
+ *     neither coarse nor in a brick of state 1 --, each once: a point that several new bricks share belongs to the one of the lowest index.
+ *   gnerf_band_points_emit: index int32 [m] = that list, m as counted (same state, same workspace, no call between the two): brick-major in
+ *     brick order, then row-major within the brick (axis 2 fastest), so that neighbouring entries share plane texels.
+ *   gnerf_band_grow: every brick of state 2 tests each of its six faces whose neighbour exists and has state 0: if the face's points are
+ *     not all on one side, the neighbour is named (a byte store of 3; every writer stores the same value and a reader takes 0 and 3 alike).
+ *     Then the round closes: 2 -> 1, 3 -> 2; *count = the new bricks.
+ *   gnerf_band_fill: every point that is neither coarse nor in a brick of state 1 or 2 takes the effective value of the coarse point at
+ *     (i0 / s * s, i1 / s * s, i2 / s * s).  It reads coarse points only and writes the others only: in place.
+ *   count: int64 on the DEVICE, written; the driver reads the new bricks and the list's length together, once per round.  Every result is
+ *   placed by index (block prefixes and scans), never by arrival: states, lists and the volume are the same from run to run.
+ * GNERF_E_ARG for null pointers, another s, n < 2, n^3 >= 2^31 or an m that is not a count. */
+int gnerf_band_workspace_bytes(int n, int s, size_t* bytes);
+int gnerf_band_seed(const float* volume, int n, int s, float level, const int* keep, unsigned char* state, void* workspace, int64_t* count,
+                    gnerf_stream_t stream);
+int gnerf_band_points_count(const unsigned char* state, int n, int s, void* workspace, int64_t* count, gnerf_stream_t stream);
+int gnerf_band_points_emit(const unsigned char* state, int n, int s, const void* workspace, int32_t* index, int64_t m, gnerf_stream_t stream);
+int gnerf_band_grow(const float* volume, int n, int s, float level, const int* keep, unsigned char* state, void* workspace, int64_t* count,
+                    gnerf_stream_t stream);
+int gnerf_band_fill(float* volume, int n, int s, const int* keep, const unsigned char* state, gnerf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
