@@ -3,7 +3,7 @@ LLVM="${LLVM_BIN:-/opt/rocm/lib/llvm/bin}"
 # The library's translation units (<name>.hip), listed here and nowhere else.  The render group is the fused renderer: its units share
 # the variant macros (GNERF_STAMPS, GNERF_ABLATE_*, GNERF_PIPE_*, ...), so tools/build_variants.sh recompiles the whole group.
 RENDER_UNITS="render render_pipe render_backward render_query"
-UNITS="capi bias_act upfirdn2d filtered_lrelu filtered_lrelu_fused grid_sample planes modconv conv3x3 $RENDER_UNITS query_lattice mesh ssim resize raster mesh_clean mesh_simplify mesh_band"
+UNITS="capi bias_act upfirdn2d filtered_lrelu filtered_lrelu_fused grid_sample planes modconv conv3x3 $RENDER_UNITS query_lattice mesh ssim resize raster mesh_clean mesh_simplify mesh_band mesh_band_cubes"
 # Every translation unit goes through its device ASSEMBLY: pk_opsel_fixup.py exchanges src0 / src1 of each packed-fp32 instruction
 # that takes the low half of its result from the high register of src1 -- a form that, on MI355X, sometimes reads 0.0 in lanes 48-63
 # while another wave of the SIMD runs v_mfma_f32_16x16x32_f16 (the script's header has the measurements; tools/isa_lint.py checks the

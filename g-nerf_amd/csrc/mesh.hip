@@ -21,12 +21,13 @@
 
 namespace {
 
+#include "mesh_cubes.h"
+
 constexpr int kThreads = 256;
 constexpr int kChunks = 8;
 constexpr int kPoints = kThreads * kChunks;          // points per block
 constexpr int kPointsLog2 = 11;
 static_assert(kPoints == 1 << kPointsLog2, "kPoints must be a power of two");
-static_assert(GNERF_MC_MAX_TRIS < 8, "triangle counts are scanned with three ballots");
 
 struct Geo {
     uint32_t d0, d1, d2, plane, n;                   // plane = d1 * d2, n = d0 * d1 * d2 < 2^31
@@ -57,14 +58,7 @@ inline Workspace carve(void* ws, uint32_t n, uint32_t nb, size_t* total) {
     return w;
 }
 
-// One lattice point: its value, its three forward neighbours' values, its crossed-axis mask (bit a: edge p -> p + e_a exists and is
-// crossed), its cell's case and triangle count (0 unless p is a cell's lower corner).
-struct Point {
-    float v, vn[3];
-    uint32_t mask, cell_case, ntri;
-    bool bad;
-};
-
+// One lattice point (mesh_cubes.h) from the dense volume: its cell's corners are loaded here.
 __device__ __forceinline__ Point classify(const float* __restrict__ vol, const Geo& g, float level, uint32_t idx) {
     const uint32_t r = idx / g.d2, i2 = idx - r * g.d2;
     const uint32_t i0 = r / g.d1, i1 = r - i0 * g.d1;
@@ -77,38 +71,7 @@ __device__ __forceinline__ Point classify(const float* __restrict__ vol, const G
         const uint32_t off = ((c & 4) ? g.plane : 0u) + ((c & 2) ? g.d2 : 0u) + ((c & 1) ? 1u : 0u);
         cv[c] = vol[ok ? idx + off : idx];
     }
-    Point pt;
-    pt.v = cv[0];
-    pt.vn[0] = cv[4];
-    pt.vn[1] = cv[2];
-    pt.vn[2] = cv[1];
-    pt.bad = !__builtin_isfinite(cv[0]);
-    uint32_t cs = 0;
-#pragma unroll
-    for (int c = 0; c < 8; c++) cs |= (cv[c] > level ? 1u : 0u) << c;
-    const uint32_t in0 = cs & 1u;
-    pt.mask = (h0 && ((cs >> 4) & 1u) != in0 ? 1u : 0u) | (h1 && ((cs >> 2) & 1u) != in0 ? 2u : 0u) | (h2 && ((cs >> 1) & 1u) != in0 ? 4u : 0u);
-    pt.cell_case = cs;
-    pt.ntri = (h0 && h1 && h2) ? uint32_t(kMcTriCount[cs]) : 0u;
-    return pt;
-}
-
-__device__ __forceinline__ uint32_t lanes_below(uint64_t m) {
-    return __builtin_amdgcn_mbcnt_hi(uint32_t(m >> 32), __builtin_amdgcn_mbcnt_lo(uint32_t(m), 0u));
-}
-
-// Exclusive prefix of a small per-lane count (< 2^BITS) over the wave, and the wave's total: one ballot per bit.
-template <int BITS>
-__device__ __forceinline__ uint32_t wave_prefix(uint32_t x, uint32_t* total) {
-    uint32_t pre = 0, tot = 0;
-#pragma unroll
-    for (int b = 0; b < BITS; b++) {
-        const uint64_t m = __ballot((x >> b) & 1u);
-        pre += lanes_below(m) << b;
-        tot += uint32_t(__popcll(m)) << b;
-    }
-    *total = tot;
-    return pre;
+    return classify_corners(cv, level, h0, h1, h2);
 }
 
 // Block-exclusive prefix of x over this chunk of kThreads points, carried across chunks in *running (uniform).  wsum: LDS for the four
@@ -157,50 +120,9 @@ __global__ __launch_bounds__(kThreads) void mc_count_kernel(const float* __restr
     }
 }
 
-// One workgroup: exclusive 64-bit offsets of the per-block counts, tile by tile with the carry in registers; totals -> counts[0..2].
-constexpr int kScanThreads = 1024;
-__global__ __launch_bounds__(kScanThreads) void mc_scan_kernel(Workspace ws, uint32_t nb, int64_t* __restrict__ counts) {
-    __shared__ int64_t sv[kScanThreads / 64], st[kScanThreads / 64], sb[kScanThreads / 64];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int64_t carry_v = 0, carry_t = 0, bad = 0;
-    for (uint32_t head = 0; head < nb; head += kScanThreads) {
-        const uint32_t i = head + threadIdx.x;
-        const int64_t v0 = i < nb ? int64_t(ws.blk_v[i]) : 0, t0 = i < nb ? int64_t(ws.blk_t[i]) : 0;
-        bad += i < nb ? int64_t(ws.blk_bad[i]) : 0;
-        int64_t v = v0, t = t0;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const int64_t xv = __shfl_up(v, o, 64), xt = __shfl_up(t, o, 64);
-            if (lane >= o) { v += xv; t += xt; }
-        }
-        if (lane == 63) { sv[wave] = v; st[wave] = t; }
-        __syncthreads();
-        int64_t bv = 0, bt = 0, av = 0, at = 0;
-        for (int w = 0; w < kScanThreads / 64; w++) {
-            bv += w < wave ? sv[w] : 0;
-            bt += w < wave ? st[w] : 0;
-            av += sv[w];
-            at += st[w];
-        }
-        if (i < nb) {
-            ws.voff[i] = carry_v + bv + v - v0;
-            ws.toff[i] = carry_t + bt + t - t0;
-        }
-        carry_v += av;
-        carry_t += at;
-        __syncthreads();                                 // sv / st are rewritten by the next tile
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) bad += __shfl_xor(bad, o, 64);
-    if (lane == 0) sb[wave] = bad;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int64_t b = 0;
-        for (int w = 0; w < kScanThreads / 64; w++) b += sb[w];
-        counts[0] = carry_v;
-        counts[1] = carry_t;
-        counts[2] = b;
-    }
+// One workgroup: exclusive 64-bit offsets of the per-block counts; totals -> counts[0..2] (mesh_cubes.h).
+__global__ __launch_bounds__(kMcScanThreads) void mc_scan_kernel(Workspace ws, uint32_t nb, int64_t* __restrict__ counts) {
+    scan_block_counts(ws.blk_v, ws.blk_t, ws.blk_bad, ws.voff, ws.toff, nb, counts);
 }
 
 __device__ __forceinline__ int32_t vertex_id(const Workspace& ws, uint32_t q, uint32_t axis) {
@@ -279,7 +201,7 @@ extern "C" int gnerf_marching_cubes_count(const float* volume, int d0, int d1, i
     const Workspace ws = carve(workspace, g.n, nb, nullptr);
     hipLaunchKernelGGL(mc_count_kernel, dim3(nb), dim3(kThreads), 0, as_stream(stream), volume, g, level, ws);
     if (int rc = check_launch("marching_cubes_count")) return rc;
-    hipLaunchKernelGGL(mc_scan_kernel, dim3(1), dim3(kScanThreads), 0, as_stream(stream), ws, nb, counts);
+    hipLaunchKernelGGL(mc_scan_kernel, dim3(1), dim3(kMcScanThreads), 0, as_stream(stream), ws, nb, counts);
     return check_launch("marching_cubes_count (scan)");
 }
 

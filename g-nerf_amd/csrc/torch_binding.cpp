@@ -15,7 +15,7 @@
 // render_backward_rays (gnerf_hip.render_backward with need_rays), resize_aa (gnerf_hip.resize_aa_forward / _backward),
 // raster_visibility / raster_resolve / mesh_bake_colors (gnerf_hip.rasterize / resolve / bake_colors), mesh_atlas_layout / mesh_bake_texture /
 // raster_resolve_textured (gnerf_hip.atlas_layout / bake_texture / resolve_textured), mesh_components / mesh_compact / mesh_smooth /
-// mesh_simplify / mesh_simplify_count / project_points_to_level / mesh_flip_guard / query_lattice / band_* (gnerf_hip's of those names).
+// mesh_simplify / mesh_simplify_count / project_points_to_level / mesh_flip_guard / query_lattice / band_* / band_marching_cubes (gnerf_hip's of those names).
 //
 // Built ahead of time by csrc/build.sh (g++, no hipcc: there is no device code) into g-nerf_amd/gnerf_hip/gnerf_torch_ext.so.
 
@@ -954,6 +954,35 @@ void band_fill(Tensor volume, int64_t n, int64_t s, std::vector<int64_t> keep, T
     check_rc(gnerf_band_fill(volume.data_ptr<float>(), c.n, c.s, c.keep, state.data_ptr<uint8_t>(), current_stream()), "gnerf_band_fill");
 }
 
+// gnerf_hip.band_marching_cubes has checked the arguments: volume float32 [n^3] as the band's rounds left it, state uint8 [nb^3] of 0 / 1; keep:
+// six ints, perm and flip: three each; active: the caller's count of active bricks.  Returns (verts [V,3] float32, faces [T,3] int32, counts
+// int64 [4] on the host: V, T, non-finite or a refusal (< 0), visited points).  The emit pass is skipped, and verts / faces are empty, when
+// counts[2] != 0 or V >= 2^31: the Python layer reads the counts and raises.
+std::tuple<Tensor, Tensor, Tensor> band_marching_cubes(Tensor volume, Tensor state, int64_t n, int64_t s, double level, std::vector<int64_t> keep,
+                                                       std::vector<int64_t> perm, std::vector<int64_t> flip, int64_t active) {
+    const BandCall c = band_call(n, s, keep, {&volume, &state}, "band_marching_cubes");
+    TORCH_CHECK(volume.scalar_type() == torch::kFloat32 && state.scalar_type() == torch::kUInt8 && perm.size() == 3 && flip.size() == 3,
+                "band_marching_cubes: unexpected tensor type or view");
+    const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(at::device_of(volume));
+    const int p[3] = {int(perm[0]), int(perm[1]), int(perm[2])}, f[3] = {int(flip[0] != 0), int(flip[1] != 0), int(flip[2] != 0)};
+    size_t bytes = 0;
+    check_rc(gnerf_band_mesh_workspace_bytes(c.n, c.s, active, &bytes), "gnerf_band_mesh_workspace_bytes");
+    Tensor ws = torch::empty({int64_t(bytes)}, volume.options().dtype(torch::kUInt8));
+    Tensor counts = torch::empty({4}, volume.options().dtype(torch::kInt64));
+    check_rc(gnerf_band_mesh_count(volume.data_ptr<float>(), state.data_ptr<uint8_t>(), c.n, c.s, float(level), c.keep, p, f, active, ws.data_ptr(),
+                                   counts.data_ptr<int64_t>(), current_stream()), "gnerf_band_mesh_count");
+    Tensor host = counts.cpu();                                    // the op's one synchronisation
+    const int64_t* k = host.data_ptr<int64_t>();
+    const bool emit = k[2] == 0 && k[0] < (int64_t(1) << 31) && k[0] > 0;
+    Tensor verts = torch::empty({emit ? k[0] : 0, 3}, volume.options());
+    Tensor faces = torch::empty({emit ? k[1] : 0, 3}, volume.options().dtype(torch::kInt32));
+    if (emit)
+        check_rc(gnerf_band_mesh_emit(volume.data_ptr<float>(), state.data_ptr<uint8_t>(), c.n, c.s, float(level), c.keep, p, f, active, ws.data_ptr(),
+                                      verts.data_ptr<float>(), k[1] > 0 ? faces.data_ptr<int32_t>() : nullptr, current_stream()),
+                 "gnerf_band_mesh_emit");
+    return std::make_tuple(verts, faces, host);
+}
+
 }  // namespace
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -990,6 +1019,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("band_points_emit", &band_points_emit);
     m.def("band_grow", &band_grow);
     m.def("band_fill", &band_fill);
+    m.def("band_marching_cubes", &band_marching_cubes);
     // the header version THIS extension was compiled against (a compile-time constant: gnerf_abi_version() would resolve in
     // libgnerf_hip.so at run time and compare the library with itself); gnerf_hip.ext() checks both against its own
     m.def("abi_version", []() { return int(GNERF_ABI_VERSION); });

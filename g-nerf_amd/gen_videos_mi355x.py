@@ -24,6 +24,8 @@ is still on the device; `--mesh-attrs normals|colors|all` adds the density field
 the renderer's pixel grid, uint8 [F, H, W, 3] at `--geometry-res`, smooth-shaded / coloured with `--mesh-attrs`.
 `--mesh-band S` (2, 4, 8 or 16; 0: off) evaluates the volume of both only in a narrow band of bricks of S^3 cells that follows the level set of
 `--mesh-level` (csrc/mesh_band.hip, csrc/query_lattice.inl): the same mesh in the same order, minus detached components thinner than a brick.
+`--mesh-direct` (with `--mesh-band S`) meshes that band brick by brick, on the lattice as the queries left it (csrc/mesh_band_cubes.hip): no fill,
+no flip / crop / transpose copies, the same mesh byte for byte.
 `--mesh-keep K`, `--mesh-min-faces N` and `--mesh-smooth ITERS` clean the mesh of both first (csrc/mesh_clean.hip): only the K largest connected
 components / those with at least N triangles stay, then ITERS Taubin iterations fair the surface; all 0 by default, which changes nothing.
 `--mesh-simplify CELL` (voxels) and `--mesh-target-faces N` simplify it in between (csrc/mesh_simplify.hip): one vertex per occupied cell of a
@@ -42,6 +44,7 @@ its .mtl and its .png; the .ply of `--mesh` is the same file as without it.
 """
 
 import argparse
+import collections
 import sys
 import time
 
@@ -280,13 +283,9 @@ def _dense_density(G, planes, resolution, max_batch):
     return sigmas
 
 
-@torch.no_grad()
-def _band_density(G, planes, resolution, crop, band, level):
-    """extract_density_grid's sigmas [resolution^3] through shape_mi355x.band_volume: densities where the level set runs, the coarse corners'
-    values elsewhere -> (sigmas, report).  The crop is handed over as the kept index range per axis of the UNFLIPPED lattice: flip(0)
-    mirrors axis 0, so its front and back exchange."""
-    if level is None:
-        raise ValueError('extract_density_grid: band needs the isosurface level the volume will be meshed at')
+def _band_field(G, planes, resolution, crop):
+    """What the narrow band is given for extract_density_grid's lattice -> (field(index, out), keep).  The crop is handed over as the kept
+    index range per axis of the UNFLIPPED lattice: flip(0) mirrors axis 0, so its front and back exchange."""
     keep = None
     if crop:
         (a0, b0), r1, r2 = crop_ranges(resolution)
@@ -297,6 +296,16 @@ def _band_density(G, planes, resolution, crop, band, level):
         out = out if isinstance(out, torch.Tensor) else torch.from_numpy(out)           # (the numpy port's array: shares its memory)
         G.renderer.query_sigma_lattice(planes, G.decoder, torch.as_tensor(index), resolution, kw, out)
 
+    return field, keep
+
+
+@torch.no_grad()
+def _band_density(G, planes, resolution, crop, band, level):
+    """extract_density_grid's sigmas [resolution^3] through shape_mi355x.band_volume: densities where the level set runs, the coarse corners'
+    values elsewhere -> (sigmas, report)."""
+    if level is None:
+        raise ValueError('extract_density_grid: band needs the isosurface level the volume will be meshed at')
+    field, keep = _band_field(G, planes, resolution, crop)
     vol, report = shape_mi355x.band_volume(field, resolution, level, band, keep, device=planes.device)
     return torch.as_tensor(vol).reshape(-1).to(planes.device), report
 
@@ -334,6 +343,27 @@ def extract_density_grid(G, ws, resolution=512, max_batch=10000000, crop=True, p
         vol[:, :, :a2] = 0
         vol[:, :, -b2:] = 0
     return (vol, planes) if return_planes else vol
+
+
+DirectMesh = collections.namedtuple('DirectMesh', 'verts faces resolution')     # extract_band_mesh's mesh, for mesh_of_density_grid in place of a volume
+
+
+@torch.no_grad()
+def extract_band_mesh(G, ws, resolution=512, level=10.0, band=8, crop=True, planes=None, return_planes=False, report=None):
+    """The mesh mesh_of_density_grid makes of extract_density_grid(..., band=band, level=level)'s volume at `level`, without that volume's
+    passes: the narrow band's rounds evaluate the densities (no fill), and marching cubes runs over the active bricks alone, reading the
+    lattice as the queries left it -- the flip and the transpose as a view, the crop as the kept range (shape_mi355x.band_mesh) -> (verts
+    float32 [V, 3], faces int32 [T, 3]) on ws' device, in the index space mesh_of_density_grid meshes in, bit for bit and in the same order.
+    planes / return_planes as extract_density_grid's ((verts, faces), planes); report: a dict that receives the band's report under 'band'."""
+    if planes is None:
+        planes = G.backbone.synthesis(ws, noise_mode='const')
+        planes = planes.view(len(planes), 3, 32, planes.shape[-2], planes.shape[-1])
+    field, keep = _band_field(G, planes, resolution, crop)
+    verts, faces, band_report = shape_mi355x.band_mesh(field, resolution, level, band, keep, device=planes.device, **shape_mi355x.BAND_MESH_PIPELINE_VIEW)
+    verts, faces = torch.as_tensor(verts).to(planes.device), torch.as_tensor(faces).to(planes.device)
+    if report is not None:
+        report['band'] = band_report
+    return ((verts, faces), planes) if return_planes else (verts, faces)
 
 
 MESH_ATTRS = ('none', 'normals', 'colors', 'all')
@@ -447,7 +477,8 @@ def mesh_of_density_grid(vol, level=10.0, attrs=None, G=None, planes=None, clean
     with bake['texture'] = P > 0 its texture atlas at patch P is baked from them too (the FinishedMesh's reports['texture']).
     band: None, or the report of the narrow band the volume was made in (extract_density_grid(..., band=s, report=...)['band']), which
     must have followed this `level`: it becomes the FinishedMesh's reports['band'], ahead of the stages'.
-    With every option None nothing but marching cubes runs."""
+    vol may also be a DirectMesh (extract_band_mesh's vertices and faces, and the resolution): marching cubes has run already, the stages follow
+    as on a volume.  With every option None nothing but marching cubes runs."""
     attrs = 'none' if attrs is None else attrs
     if attrs not in MESH_ATTRS:
         raise ValueError(f'mesh_density_grid: attrs must be one of {MESH_ATTRS}')
@@ -455,15 +486,18 @@ def mesh_of_density_grid(vol, level=10.0, attrs=None, G=None, planes=None, clean
         raise ValueError('mesh_density_grid: vertex attributes and the snap need the generator G and the planes the volume was made from')
     if bake and G is None:
         raise ValueError('mesh_density_grid: the bake needs the generator G (its box)')
-    res = vol.shape[0]
-    t0 = time.perf_counter()
-    verts, faces = shape_mi355x.marching_cubes(vol.permute(2, 1, 0).contiguous(), level)     # (reads its counts: synchronised)
-    dt = time.perf_counter() - t0
+    if isinstance(vol, DirectMesh):
+        (verts, faces, res), device, dt = vol, vol.verts.device, 0.0
+    else:
+        res, device = vol.shape[0], vol.device
+        t0 = time.perf_counter()
+        verts, faces = shape_mi355x.marching_cubes(vol.permute(2, 1, 0).contiguous(), level)     # (reads its counts: synchronised)
+        dt = time.perf_counter() - t0
     stages = {}
     if snap:
         stages['snap'] = lambda v, f: snap_extracted_mesh(G, planes, v, f, res, snap, level=level)
     if attrs != 'none':
-        stages['attributes'] = lambda v: mesh_vertex_attributes(G, planes, torch.as_tensor(v).to(vol.device), res, attrs in ('normals', 'all'),
+        stages['attributes'] = lambda v: mesh_vertex_attributes(G, planes, torch.as_tensor(v).to(device), res, attrs in ('normals', 'all'),
                                                                 attrs in ('colors', 'all'))
     if bake:
         stages['bake'] = lambda v, f, normals, colors: bake_extracted_mesh(v, f, normals, colors, bake, res, G.rendering_kwargs['box_warp'])
@@ -529,6 +563,10 @@ def arg_parser():
                     help='evaluate the density volume of --mesh / --geometry-out only in a narrow band of bricks of S^3 cells (2, 4, 8 or 16; 8 is a good start) '
                          'around the level set of --mesh-level: the same mesh, minus detached components thinner than a brick (0: off, every lattice point). '
                          'With --shapes / --shapes-mrc the dense volume is made once and meshed too: those files hold densities everywhere')
+    ap.add_argument('--mesh-direct', action='store_true',
+                    help='with --mesh-band S: mesh the band brick by brick, straight on the lattice as the queries left it (no fill, no crop / flip / '
+                         'transpose passes, no pass over the whole volume): the same mesh, byte for byte (--mesh and --geometry-out; not with --shapes / '
+                         '--shapes-mrc, which need densities everywhere)')
     ap.add_argument('--mesh-attrs', choices=MESH_ATTRS, default='none', help='per-vertex attributes of --mesh: normals of the density field and / or the decoder\'s colours')
     shape_mi355x.add_mesh_arguments(ap, attributes=True, texture=True)
     ap.add_argument('--mesh-snap', type=float, default=0, metavar='R',
@@ -560,6 +598,10 @@ def main():
     texture_patch = shape_mi355x.texture_from_args(args, ap)
     if args.mesh_band not in (0,) + shape_mi355x.BAND_BRICKS:
         ap.error(f'--mesh-band must be 0 or one of {shape_mi355x.BAND_BRICKS}')
+    if args.mesh_direct and not args.mesh_band:
+        ap.error('--mesh-direct requires --mesh-band S')
+    if args.mesh_direct and (args.shapes or args.shapes_mrc):
+        ap.error('--mesh-direct cannot be combined with --shapes / --shapes-mrc: those files need densities everywhere, and the direct route makes no volume')
     if not 0 <= args.mesh_bake <= args.frames:
         ap.error('--mesh-bake must be 0 .. --frames')
     if (not args.mesh_bake_tol >= 0 or not 0 <= args.mesh_bake_guard <= 4 or not 0 <= args.mesh_bake_power <= 8
@@ -613,14 +655,22 @@ def main():
             if args.mesh_band and not band and rank == 0:
                 print('--mesh-band: off, --shapes / --shapes-mrc need the dense volume; it is made once and meshed too')
             reports = {}
-            made['vol'], made['planes'] = extract_density_grid(G, orbit_latents(G, z, device), args.voxel_res, return_planes=True, band=band or None,
-                                                               level=args.mesh_level, report=reports)
+            if args.mesh_direct:                                         # no volume: the band's mesh itself, for mesh_of_density_grid
+                mesh, made['planes'] = extract_band_mesh(G, orbit_latents(G, z, device), args.voxel_res, args.mesh_level, band, return_planes=True,
+                                                         report=reports)
+                made['vol'] = DirectMesh(*mesh, args.voxel_res)
+            else:
+                made['vol'], made['planes'] = extract_density_grid(G, orbit_latents(G, z, device), args.voxel_res, return_planes=True, band=band or None,
+                                                                   level=args.mesh_level, report=reports)
             made['band'] = reports.get('band')
             if device.type == 'cuda':
                 torch.cuda.synchronize()
             dt = time.perf_counter() - t0
             if rank == 0:
-                print(f'density volume {args.voxel_res}^3: {dt:.3f} s = {args.voxel_res ** 3 / dt / 1e9:.2f} G points/s')
+                if args.mesh_direct:
+                    print(f'band mesh of the {args.voxel_res}^3 lattice: {dt:.3f} s, {made["band"]["visited"]} points in {made["band"]["active"]} active bricks')
+                else:
+                    print(f'density volume {args.voxel_res}^3: {dt:.3f} s = {args.voxel_res ** 3 / dt / 1e9:.2f} G points/s')
                 if made['band']:
                     print(shape_mi355x.band_report_line(made['band']))
         return made['vol'], made['planes']

@@ -39,7 +39,7 @@ from .mesh import (MESH_SMOOTH_MAX_FACES, marching_cubes, mesh_clean_available, 
                    mesh_flip_guard, mesh_flip_guard_available, _mesh_flip_guard_ctypes,
                    _marching_cubes_ctypes, _mesh_compact_ctypes, _mesh_components_ctypes, _mesh_simplify_ctypes, _mesh_smooth_ctypes)
 from .mesh import (BAND_BRICKS, BandVolume, band_available, band_fill, band_grow, band_points_count, band_points_emit, band_seed,  # noqa: F401
-                   band_workspace_bytes)
+                   band_workspace_bytes, band_marching_cubes, band_mesh_available, band_mesh_workspace_bytes)
 from .ssim import SSIM_MAX_WIN, ssim_backward, ssim_forward  # noqa: F401
 from .resize import (RESIZE_MAX_TAPS, RESIZE_MODES, resize_aa_available, resize_aa_backward, resize_aa_forward, resize_aa_refusal,  # noqa: F401
                      resize_aa_supported)

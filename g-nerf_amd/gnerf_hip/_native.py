@@ -161,6 +161,9 @@ SIGNATURES = {
     'gnerf_band_points_emit': (_c_i, [_c_p, _c_i, _c_i, _c_p, _c_p, _c_i64, _c_p]),
     'gnerf_band_grow': (_c_i, [_c_p, _c_i, _c_i, _c_f, ctypes.POINTER(_c_i), _c_p, _c_p, _c_p, _c_p]),
     'gnerf_band_fill': (_c_i, [_c_p, _c_i, _c_i, ctypes.POINTER(_c_i), _c_p, _c_p]),
+    'gnerf_band_mesh_workspace_bytes': (_c_i, [_c_i, _c_i, _c_i64, ctypes.POINTER(ctypes.c_size_t)]),
+    'gnerf_band_mesh_count': (_c_i, [_c_p, _c_p, _c_i, _c_i, _c_f, ctypes.POINTER(_c_i), ctypes.POINTER(_c_i), ctypes.POINTER(_c_i), _c_i64, _c_p, _c_p, _c_p]),
+    'gnerf_band_mesh_emit': (_c_i, [_c_p, _c_p, _c_i, _c_i, _c_f, ctypes.POINTER(_c_i), ctypes.POINTER(_c_i), ctypes.POINTER(_c_i), _c_i64, _c_p, _c_p, _c_p, _c_p]),
 }
 # exports added WITHOUT a new ABI version: a library of the same version built before them (a variant build behind GNERF_HIP_LIB) loads, and
 # what needs them asks modconv_backward_available() / render_ray_grad_available() / decoder_pack_available() / resize_aa_available() /

@@ -488,3 +488,86 @@ class BandVolume:
 
     def fill(self):
         band_fill(self.volume, self.n, self.s, self.keep, self.state, self.binding)
+
+
+# ---------------------------------------------------------------------------------------------------------------- band mesh (csrc/mesh_band_cubes.hip)
+_BAND_MESH_SYMBOLS = ('gnerf_band_mesh_workspace_bytes', 'gnerf_band_mesh_count', 'gnerf_band_mesh_emit')
+
+
+def band_mesh_available():
+    """Whether the loaded library has the brick-wise marching cubes of the narrow band (a version-15 library built before it does not)."""
+    return all(hasattr(load(), name) for name in _BAND_MESH_SYMBOLS)
+
+
+def band_mesh_workspace_bytes(n, s, active):
+    nbytes = ctypes.c_size_t()
+    _check(load().gnerf_band_mesh_workspace_bytes(int(n), int(s), int(active), ctypes.byref(nbytes)), 'gnerf_band_mesh_workspace_bytes')
+    return int(nbytes.value)
+
+
+def _band_mesh_ctypes(vol, state, n, s, level, keep, perm, flip, active):
+    """The ctypes route of band_marching_cubes (arguments as it prepares them) -> (verts, faces, counts on the host)."""
+    dev = vol.device
+    ws = torch.empty(band_mesh_workspace_bytes(n, s, active), dtype=torch.uint8, device=dev)
+    counts = torch.empty(4, dtype=torch.int64, device=dev)
+    view = (n, s, float(level), (ctypes.c_int * 6)(*keep), (ctypes.c_int * 3)(*perm), (ctypes.c_int * 3)(*flip), active, _ptr(ws))
+    _launch('gnerf_band_mesh_count', vol, _ptr(vol), _ptr(state), *view, _ptr(counts))
+    host = counts.cpu()                                                      # the op's one synchronisation
+    n_verts, n_faces, n_bad = (int(c) for c in host[:3])
+    emit = n_bad == 0 and 0 < n_verts < 2 ** 31
+    verts = torch.empty([n_verts if emit else 0, 3], dtype=torch.float32, device=dev)
+    faces = torch.empty([n_faces if emit else 0, 3], dtype=torch.int32, device=dev)
+    if emit:
+        _launch('gnerf_band_mesh_emit', vol, _ptr(vol), _ptr(state), *view, _ptr(verts), _ptr(faces) if n_faces else None)
+    return verts, faces, host
+
+
+@profiled('gnerf_hip::band_marching_cubes')
+def band_marching_cubes(volume, state, n, s, level, keep=None, perm=(0, 1, 2), flip=(False, False, False), binding=None, active=None,
+                        return_counts=False):
+    """Triangle mesh of {e > level} over the ACTIVE BRICKS of a narrow band, in a view of the lattice: volume float32 [n^3] (CUDA) as the
+    band's rounds left it -- no band_fill; nothing outside the active bricks' closed point ranges is read --, state uint8 [nb^3] of 0 / 1, keep
+    as band_seed takes it, perm a permutation of (0, 1, 2) and flip a flag per LATTICE axis: mesh coordinate m_k = l_perm[k], mirrored where
+    that axis is flipped -> (verts float32 [V, 3] in mesh coordinates, faces int32 [T, 3]): marching_cubes' of the filled, cropped, flipped and
+    permuted volume, bit for bit and in the same order (include/gnerf_hip.h, gnerf_band_mesh_*; shape_mi355x.band_marching_cubes_numpy gives the
+    same bits).  active: the number of active bricks when the caller knows it (the band driver does); None reads state.sum() to the host first.
+    Reads its counts to the host between its two passes, like marching_cubes.  return_counts: also the counts int64 [4] on the host (V, T,
+    non-finite effective values among the visited points, visited points), and a non-finite value empties the mesh instead of raising.
+    binding='ctypes' forces that route."""
+    if not band_mesh_available():
+        raise RuntimeError('gnerf_hip: this libgnerf_hip.so was built without the band-mesh kernels (gnerf_band_mesh_*): rebuild it (csrc/build.sh)')
+    n, s = int(n), int(s)
+    if s not in BAND_BRICKS:
+        raise ValueError(f'band_marching_cubes: the brick edge must be one of {BAND_BRICKS}, got {s}')
+    if n < 2 or n ** 3 >= 2 ** 31:
+        raise ValueError(f'band_marching_cubes: n must be >= 2 with n^3 < 2^31, got {n}')
+    perm, flip = [int(a) for a in perm], [int(bool(f)) for f in flip]
+    if sorted(perm) != [0, 1, 2] or len(flip) != 3:
+        raise ValueError(f'band_marching_cubes: perm must be a permutation of (0, 1, 2) and flip one flag per lattice axis, got {perm}, {flip}')
+    nb = -(-(n - 1) // s)
+    vol = _band_tensor(volume.detach().reshape(-1), torch.float32, n ** 3, 'band_marching_cubes', 'volume')
+    state = _band_tensor(state.reshape(-1), torch.uint8, nb ** 3, 'band_marching_cubes', 'state')
+    if state.device != vol.device:
+        raise ValueError('band_marching_cubes: volume and state must be on one device')
+    active = int(state.sum()) if active is None else int(active)
+    if not 0 <= active <= nb ** 3:
+        raise ValueError(f'band_marching_cubes: active must be a number of bricks in [0, {nb ** 3}], got {active}')
+    keep = _band_keep(n, keep)
+    e = _band_ext(binding)
+    if e is not None and hasattr(e, 'band_marching_cubes'):
+        with _on_device(vol.device):
+            verts, faces, counts = e.band_marching_cubes(vol, state, n, s, float(level), keep, perm, flip, active)
+    else:
+        verts, faces, counts = _band_mesh_ctypes(vol, state, n, s, level, keep, perm, flip, active)
+    n_verts, _, n_bad, _ = (int(c) for c in counts)
+    if n_bad == -1:
+        raise ValueError(f'band_marching_cubes: state holds more active bricks than active = {active}')
+    if n_bad == -2:
+        raise ValueError('band_marching_cubes: every brick state must be 0 or 1 (the band\'s rounds have not ended)')
+    if n_verts >= 2 ** 31:
+        raise ValueError(f'band_marching_cubes: {n_verts} vertices do not fit int32 face indices')
+    if return_counts:
+        return verts, faces, counts
+    if n_bad:
+        raise ValueError(f'band_marching_cubes: {n_bad} visited point(s) hold a non-finite value')
+    return verts, faces

@@ -38,6 +38,9 @@ from seeded bricks), and the mesh of its volume is the dense volume's in the sam
 CUDA device the bookkeeping runs on csrc/mesh_band.hip (gnerf_hip.BandVolume), anywhere else on band_volume_numpy below
 (include/gnerf_hip.h, gnerf_band_*): the same brick states, index lists and volume.
 
+band_mesh goes on from the band's rounds without the volume's fill: marching cubes over the active bricks alone, in a view of the lattice
+(csrc/mesh_band_cubes.hip through gnerf_hip.band_marching_cubes; band_marching_cubes_numpy below): the mesh of band_volume's volume, bit for bit.
+
 finish_mesh walks these stages, and those that need a generator (given as callables), in the one order both CLIs use.
 
 CLI, as shape_utils.py's (:102-123):  python shape_mi355x.py INPUT [--level 10]   (INPUT: a .mrc / .npy file or a directory of them)
@@ -249,14 +252,27 @@ def marching_cubes_numpy(volume, level):
     bad = int(v.size - np.count_nonzero(np.isfinite(v)))
     if bad:
         raise ValueError(f'marching_cubes: the volume holds {bad} non-finite value(s)')
-    lev = np.float32(level)
+    return _marching_cubes_masked(v, np.float32(level), None)
+
+
+def _marching_cubes_masked(v, lev, seen):
+    """Marching cubes' rules on the float32 volume v, restricted to the points of the mask `seen` (None: every point): an edge is examined iff
+    both endpoints are seen, a cell iff all eight corners are; values at other points are never looked at."""
     d0, d1, d2 = v.shape
     strides = np.array([d1 * d2, d2, 1], dtype=np.int64)
-    inside = v > lev
+    if seen is None:
+        inside = v > lev
+    else:
+        inside = np.zeros(v.shape, dtype=bool)
+        inside[seen] = v[seen] > lev
     cross = np.zeros(v.shape + (3,), dtype=bool)
     cross[:-1, :, :, 0] = inside[:-1] != inside[1:]
     cross[:, :-1, :, 1] = inside[:, :-1] != inside[:, 1:]
     cross[:, :, :-1, 2] = inside[:, :, :-1] != inside[:, :, 1:]
+    if seen is not None:
+        cross[:-1, :, :, 0] &= seen[:-1] & seen[1:]
+        cross[:, :-1, :, 1] &= seen[:, :-1] & seen[:, 1:]
+        cross[:, :, :-1, 2] &= seen[:, :, :-1] & seen[:, :, 1:]
     cross = cross.reshape(-1, 3)
     per_point = cross.sum(axis=1, dtype=np.int64)
     base = np.cumsum(per_point) - per_point                              # first vertex id of each point
@@ -270,11 +286,14 @@ def marching_cubes_numpy(volume, level):
 
     count, table, e_corner, e_axis = _table()
     case = np.zeros((d0 - 1, d1 - 1, d2 - 1), dtype=np.int64)
+    whole = None if seen is None else np.ones(case.shape, dtype=bool)
     for c in range(8):
         o0, o1, o2 = CORNER_OFFSETS[c]
         case |= inside[o0:d0 - 1 + o0, o1:d1 - 1 + o1, o2:d2 - 1 + o2].astype(np.int64) << c
+        if whole is not None:
+            whole &= seen[o0:d0 - 1 + o0, o1:d1 - 1 + o1, o2:d2 - 1 + o2]
     case = case.reshape(-1)
-    ntri = count[case]
+    ntri = count[case] if whole is None else count[case] * whole.reshape(-1)
     cells = np.nonzero(ntri)[0]
     if len(cells) == 0:
         return verts, np.zeros((0, 3), dtype=np.int32)
@@ -463,9 +482,10 @@ def band_fill_numpy(vol, n, s, state, keep=None):
     return vol
 
 
-def _band_driver(n, s, evaluate, coarse_index, band, trace):
+def _band_driver(n, s, evaluate, coarse_index, band, trace, fill=True):
     """The steps of the rules, spelled once for both routes: evaluate(index) writes the densities; band holds the brick states and gives the
-    route's stages -- seed() -> seeds, points() -> the round's index list, grow() -> new bricks, fill(), and state for the trace."""
+    route's stages -- seed() -> seeds, points() -> the round's index list, grow() -> new bricks, fill(), and state for the trace.
+    fill=False leaves the volume as the rounds left it (band_mesh: marching cubes then reads the active bricks only)."""
     evaluate(coarse_index)
     evaluated = len(coarse_index)
     new = seeds = band.seed()
@@ -478,7 +498,8 @@ def _band_driver(n, s, evaluate, coarse_index, band, trace):
         per_round.append(new)
         if trace is not None:
             trace.append((to_host(band.state).copy(), to_host(index).copy()))
-    band.fill()
+    if fill:
+        band.fill()
     return dict(brick=s, bricks=(-(-(n - 1) // s)) ** 3, seeds=seeds, new_bricks=per_round, rounds=len(per_round), host_reads=len(per_round) + 1,
                 points=evaluated, share=evaluated / n ** 3)
 
@@ -542,6 +563,102 @@ def band_volume(field, n, level, s, keep=None, device=None, trace=None):
 def band_report_line(report):
     return (f'band: bricks of {report["brick"]}^3 cells, {report["seeds"]} seeded + {sum(report["new_bricks"])} grown of {report["bricks"]} in '
             f'{report["rounds"]} round(s), {report["points"]} points evaluated ({100 * report["share"]:.2f} % of the lattice)')
+
+
+# The mesh of a band run without the fill (include/gnerf_hip.h, gnerf_band_mesh_*, states the rules; DESIGN.md 3.23 the argument): marching cubes
+# over the points of the active bricks only, in a VIEW of the lattice -- mesh coordinate m_k = l_perm[k], or n - 1 - l_perm[k] where lattice axis
+# perm[k] is flipped, so the mesh volume is vol.reshape(n, n, n).flip(flipped axes).permute(perm) -- with the crop as `keep`.  The result is
+# marching cubes' of the filled, cropped, flipped and permuted volume, bit for bit and in the same order.
+BAND_MESH_PIPELINE_VIEW = dict(perm=(2, 1, 0), flip=(True, False, False))     # extract_density_grid's flip(0) + mesh_of_density_grid's permute
+
+
+def _band_view(perm, flip):
+    perm, flip = tuple(int(a) for a in perm), tuple(bool(f) for f in flip)
+    if sorted(perm) != [0, 1, 2]:
+        raise ValueError(f'band_marching_cubes: perm must be a permutation of (0, 1, 2), got {perm}')
+    if len(flip) != 3:
+        raise ValueError('band_marching_cubes: flip must hold one flag per lattice axis')
+    return perm, flip
+
+
+def band_visited_numpy(state, n, s):
+    """The points in the closed range of at least one active brick -> bool [n, n, n] (state: the final 0 / 1 bytes)."""
+    nb = -(-(n - 1) // s)
+    bounds, _ = _band_coarse(n, s, nb)
+    sizes = np.diff(bounds)
+    active = np.asarray(state).reshape(nb, nb, nb) == 1
+    cells = np.pad(active.repeat(sizes, 0).repeat(sizes, 1).repeat(sizes, 2), 1)
+    return np.logical_or.reduce([cells[a:n + a, b:n + b, c:n + c] for a in (0, 1) for b in (0, 1) for c in (0, 1)])
+
+
+def band_marching_cubes_numpy(volume, state, n, s, level, keep=None, perm=(0, 1, 2), flip=(False, False, False), return_counts=False):
+    """The numpy port of gnerf_hip.band_marching_cubes, written from the rule with plain masks: volume float32 [n^3] as the band's rounds left
+    it (no fill), state uint8 [nb^3] of 0 / 1, keep as band_volume takes it, the view (perm, flip per LATTICE axis) -> (verts float32 [V, 3],
+    faces int32 [T, 3]) in mesh coordinates, the kernels' bits.  Only visited points are read.  Raises ValueError on a non-finite effective value
+    at a visited point; with return_counts nothing is raised and (verts, faces, counts int64 [4]: V, T, non-finite, visited points) comes back,
+    the mesh empty when the third count is not 0."""
+    n, s, nb, keep = _band_geometry(n, s, keep)
+    perm, flip = _band_view(perm, flip)
+    vol = np.asarray(volume)
+    state = np.asarray(state)
+    if vol.size != n ** 3:
+        raise ValueError(f'band_marching_cubes: the volume must hold n^3 = {n ** 3} values, got {vol.size}')
+    if state.size != nb ** 3:
+        raise ValueError(f'band_marching_cubes: state must hold nb^3 = {nb ** 3} bytes, got {state.size}')
+    if state.size and int(state.max()) > 1:
+        raise ValueError('band_marching_cubes: every brick state must be 0 or 1 (the band\'s rounds have not ended)')
+    vol = vol.astype(np.float32, copy=False).reshape(n, n, n)
+    seen = band_visited_numpy(state, n, s)
+    i = np.arange(n)
+    kept = _band_kept(keep, i[:, None, None], i[None, :, None], i[None, None, :])
+    eff = np.zeros((n, n, n), dtype=np.float32)
+    read = seen & kept
+    eff[read] = vol[read]                                                # the only read of the volume
+    axes = [a for a in range(3) if flip[a]]
+    view = lambda x: np.ascontiguousarray(np.transpose(np.flip(x, axes) if axes else x, perm))
+    eff, seen = view(eff), view(seen)
+    bad = int(np.count_nonzero(seen & ~np.isfinite(eff)))
+    if bad and not return_counts:
+        raise ValueError(f'band_marching_cubes: {bad} visited point(s) hold a non-finite value')
+    with np.errstate(all='ignore'):                                     # (a non-finite value is outside or inside by v > level, and counted)
+        verts, faces = _marching_cubes_masked(eff, np.float32(level), seen)
+    if not return_counts:
+        return verts, faces
+    counts = np.array([len(verts), len(faces), bad, int(seen.sum())], dtype=np.int64)
+    if bad:
+        verts, faces = np.zeros((0, 3), dtype=np.float32), np.zeros((0, 3), dtype=np.int32)
+    return verts, faces, counts
+
+
+def band_mesh(field, n, level, s, keep=None, perm=(0, 1, 2), flip=(False, False, False), device=None, trace=None, binding=None):
+    """band_volume's rounds WITHOUT the fill, then marching cubes over the active bricks alone: field(index, out) as band_volume takes it ->
+    (verts float32 [V, 3], faces int32 [T, 3], report) -- the mesh marching cubes makes of band_volume's volume after the crop `keep`, the flips
+    and the permutation, bit for bit and in the same order, with no pass over the n^3 lattice.  report: band_volume's plus active (bricks),
+    visited (points in an active brick's closed range) and mesh (V, T).  Raises ValueError, on either route, when a visited point holds a
+    non-finite effective value, as marching_cubes does on such a volume.  device: a CUDA device takes the kernels (csrc/mesh_band.hip,
+    csrc/mesh_band_cubes.hip; the volume is torch.empty there and nothing initialises it), anything else the numpy ports."""
+    torch = _torch()
+    dev = None if device is None or torch is None else torch.device(device)
+    n, s, nb, keep = _band_geometry(n, s, keep)
+    perm, flip = _band_view(perm, flip)
+    if dev is None or dev.type != 'cuda':
+        vol = np.zeros(n ** 3, dtype=np.float32)
+        band = _BandNumpy(vol, n, s, level, keep)
+        report = _band_driver(n, s, lambda index: field(index, vol) if len(index) else None, band_coarse_index(n, s), band, trace, fill=False)
+        state = band.state if band.state is not None else np.zeros(nb ** 3, dtype=np.uint8)
+        verts, faces, counts = band_marching_cubes_numpy(vol, state, n, s, level, keep, perm, flip, return_counts=True)
+    else:
+        import gnerf_hip
+        vol = torch.empty(n ** 3, dtype=torch.float32, device=dev)
+        band = gnerf_hip.BandVolume(vol, n, s, level, keep, binding=binding)
+        report = _band_driver(n, s, lambda index: field(index, vol) if len(index) else None, torch.from_numpy(band_coarse_index(n, s)).to(dev),
+                              band, trace, fill=False)
+        verts, faces, counts = gnerf_hip.band_marching_cubes(vol, band.state, n, s, level, keep, perm, flip, binding=binding,
+                                                             active=report['seeds'] + sum(report['new_bricks']), return_counts=True)
+    if counts[2]:                                                       # (either route: the route this replaces raises on such a volume too)
+        raise ValueError(f'band_marching_cubes: {int(counts[2])} visited point(s) hold a non-finite value')
+    report.update(active=report['seeds'] + sum(report['new_bricks']), visited=int(counts[3]), mesh=(len(verts), len(faces)))
+    return verts, faces, report
 
 
 # ---------------------------------------------------------------------------------------------------------------- rasteriser

@@ -1026,6 +1026,40 @@ int gnerf_band_grow(const float* volume, int n, int s, float level, const int* k
                     gnerf_stream_t stream);
 int gnerf_band_fill(float* volume, int n, int s, const int* keep, const unsigned char* state, gnerf_stream_t stream);
 
+/* (ABI 15, added without a new version) Marching cubes over the active bricks of a narrow band, brick by brick (csrc/mesh_band_cubes.hip;
+ * shape_mi355x.band_marching_cubes_numpy gives the same bits): no gnerf_band_fill, no crop, flip or transpose pass, nothing proportional to n^3.
+ *   INPUT.  volume float32 [n^3] of a band run BEFORE gnerf_band_fill: true densities at the coarse points and at every point of an active
+ *   brick, unwritten memory elsewhere.  state [nb^3]: the final brick states, every byte 0 or 1 (after the last gnerf_band_grow).  n, s, level
+ *   and keep as gnerf_band_* take them (keep: the kept range of the unflipped lattice).  A VIEW: perm, three ints on the host, a permutation of
+ *   (0, 1, 2) (null: the identity), and flip, three ints on the host, non-zero where that LATTICE axis is flipped (null: none).
+ *   VIEW.  Mesh coordinate m_k = l_perm[k], or n - 1 - l_perm[k] where lattice axis perm[k] is flipped: the mesh volume is
+ *   vol.reshape(n, n, n).flip(flipped axes).permute(perm).
+ *   VALUES.  The effective value e(p) is 0 outside keep and the stored value inside; a point is inside iff e(p) > level (ties and NaN outside).
+ *   VISITED.  A point is visited iff it lies in the closed point range of at least one active brick.  Only visited points are ever read.  An
+ *   edge is examined iff both endpoints are visited, a cell iff all eight corners are.
+ *   OUTPUT.  gnerf_marching_cubes_*'s, in the mesh view: one vertex per examined, crossed edge, owned by the edge's lower endpoint in MESH
+ *   coordinates, ordered by (owner's mesh-linear index with m2 fastest, mesh axis), at the owner's float(m) plus t = (level - v) / (v_next - v)
+ *   on the edge's axis (correctly rounded, not contracted); faces in cell mesh-linear order, then mesh_tables.h's order within the case,
+ *   outward winding, ids into that vertex order.  When state and volume come from one band run this is the mesh gnerf_marching_cubes_* makes of
+ *   the filled, cropped, flipped and permuted volume, bit for bit: once growth has ended a face between an active and an inactive brick lies on
+ *   one side of the level, so every crossed edge and every non-empty cell lies within active bricks, and gnerf_band_fill never writes a point
+ *   of an active brick.
+ *   active: the number of active bricks as the caller knows it (the band driver's seeds + new bricks); it sizes the workspace, which is
+ *   proportional to it (2 bytes per point and 8 bytes per row of s + 1 points of an active brick) plus 4 bytes per brick for a brick -> slot
+ *   map and small per-column arrays -- no 4 bytes per lattice point.
+ *   gnerf_band_mesh_count: counts int64 [4] on the DEVICE = {V, T, non-finite effective values among the visited points, visited points}.
+ *     A refused input gives {0, 0, -1, 0} when the state holds more active bricks than `active`, {0, 0, -2, 0} when a state is neither 0 nor 1.
+ *   gnerf_band_mesh_emit, after a count on the same arguments and workspace: verts float32 [V, 3], faces int32 [T, 3] (null when T = 0).  The
+ *     caller reads the counts between the two and does not emit when counts[2] != 0 or V is 0 or >= 2^31.
+ *   Everything is placed by index: a segment of a brick's row has a closed-form rank in the mesh's point order, and one scan over the segments
+ *   gives every offset.  No float atomics; two runs give the same bytes.
+ * GNERF_E_ARG for null pointers, another s, n < 2, n^3 >= 2^31, a perm that is no permutation or an `active` outside [0, nb^3]. */
+int gnerf_band_mesh_workspace_bytes(int n, int s, int64_t active, size_t* bytes);
+int gnerf_band_mesh_count(const float* volume, const unsigned char* state, int n, int s, float level, const int* keep, const int* perm,
+                          const int* flip, int64_t active, void* workspace, int64_t* counts, gnerf_stream_t stream);
+int gnerf_band_mesh_emit(const float* volume, const unsigned char* state, int n, int s, float level, const int* keep, const int* perm,
+                         const int* flip, int64_t active, const void* workspace, float* verts, int32_t* faces, gnerf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
